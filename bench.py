@@ -2,10 +2,16 @@
 """Headline benchmark: images/sec training SoftNBDT WideResNet-28-10 on CIFAR10-shaped synthetic
 batches (BASELINE.json `metric`, configs[1]: batch 512 per MI355X, fused rules/loss kernel).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N>1 without a torchrun environment: bench.py re-launches itself as
    python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port <free> bench.py ...,
    one rank per GPU over RCCL; launched that way by a driver it just reads RANK/LOCAL_RANK/WORLD_SIZE.)
+
+A plain run does only what the headline needs: set up, W warm-up steps, K timed steps, the JSON line (`value`,
+`ms_per_step` = wall milliseconds of one timed step).  --dump-outputs DIR writes what the last timed step handed its
+caller (dump_outputs).  --full adds everything else the line can carry -- `roofline*`, `agreement`, `other_configs`,
+`cpu_baseline` and, with N ranks, the replica checksums and the step without the gradient exchange (`comm`) -- each
+measured after the timed steps; the --no-* options switch single parts of it off.
 
 A "step" = nbdt.engine.train_step, the engine's default schedule: zero_grad -> backbone forward to the pooled features
 -> classifier + rules + SoftTreeSupLoss forward AND backward in one launch (nbdt_head_soft_tree_loss) -> backbone
@@ -14,15 +20,15 @@ HBM.  In backward the HBM-bound BatchNorm passes run on ~100 CUs BESIDE the MFMA
 ~160 (engine.set_cu_share, on by default; `cu_share` in the JSON line is the calibration made before the first
 backward; --no-cu-share restores the order without it).  Weak scaling: 512 images per GPU.  Prints ONE JSON line on rank 0.
 
-roofline: the dominant kernel is conv_igemm (forward + data-gradient implicit GEMMs; 2/3 of the
+roofline (--full): the dominant kernel is conv_igemm (forward + data-gradient implicit GEMMs; 2/3 of the
 step's flops).  achieved = algorithmic flops of its launches / their HIP-event durations, measured
 live on the launch stream over min(K, 5) further steps of the same loop right after the K timed steps
 (event records between back-to-back kernels would bias `value` by ~5 %), with the engine's second stream
 joined so that no other kernel shares the GPU with the measured launch; peak = 2.5 PFLOP/s dense bf16 MFMA
 (gfx950).
-cpu_baseline: the fp32 CPU oracle port (oracle/torch_models.py WRN + oracle/nbdt_oracle.py loss) on a
+cpu_baseline (--full): the fp32 CPU oracle port (oracle/torch_models.py WRN + oracle/nbdt_oracle.py loss) on a
 bounded sample, all host cores -- test infrastructure used only as the timed baseline here.
-agreement ("top-1 vs ref" half of the metric): after the timed loop the trained weights are copied into the
+agreement (--full; "top-1 vs ref" half of the metric): after the timed loop the trained weights are copied into the
 CPU oracle port and both run an eval-mode forward on the same fixed batch; reported are the fraction of equal
 argmax(logits), of equal HardNBDT predictions (each path's rules on its own logits) and the logit error.
 """
@@ -335,11 +341,43 @@ def other_configs(dev, budget_s=0.6):
     return out
 
 
+DUMP_PARAM_SAMPLE = 1 << 22     # of the ~36.5 M fp32 weights: 16 MB, well inside the 64 MB a dump may take
+DUMP_SEED = 20240
+
+
+def dump_outputs(out_dir, eng, loss):
+    """What a caller of the timed path holds after its last step, as float32 .npy files under `out_dir`: the loss
+    train_step returned (`loss`), a fixed seeded sample of the fp32 weights the step's SGD update left
+    (`params_sample`: DUMP_PARAM_SAMPLE positions, ascending, of all parameters concatenated in name order, the
+    reference's names and shapes) and every BatchNorm running mean and variance (`bn_running_stats`, same order).
+    The positions depend only on the parameter count, so two builds of the same workload compare element for element."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    params = eng.named_params("flat")
+    flat = torch.cat([params[k].detach().reshape(-1).float() for k in sorted(params)])
+    n = min(DUMP_PARAM_SAMPLE, flat.numel())
+    idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:n].sort().values
+    bufs = eng.named_buffers()
+    stats = torch.cat([bufs[k].detach().reshape(-1).float() for k in sorted(bufs)
+                       if not k.endswith("num_batches_tracked")])
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+              "params_sample": flat[idx.to(flat.device)].cpu().numpy(),
+              "bn_running_stats": stats.cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the roofline objects, the agreement with the fp32 CPU port, "
+                         "the other BASELINE.json configurations, the CPU baseline and, with N ranks, the replica "
+                         "checksums and the step without the gradient exchange (off: only the headline)")
     ap.add_argument("--batch", type=int, default=512, help="images per GPU (weak scaling)")
     ap.add_argument("--classes", type=int, default=10)
     ap.add_argument("--cpu-batch", type=int, default=32)
@@ -363,6 +401,8 @@ def main():
     ap.add_argument("--no-other-configs", action="store_true",
                     help="skip the <= 1 s measurements of the other BASELINE.json configurations (`other_configs`)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
 
@@ -414,12 +454,14 @@ def main():
     sync()
     dt = time.perf_counter() - t0
     loss_val = loss.item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, eng, loss)      # before anything below runs further steps
 
-    # Per-kernel durations for the roofline object: the SAME step loop continues for a few more steps
+    # Per-kernel durations for the roofline object (--full): the SAME step loop continues for a few more steps
     # with a HIP event pair around every conv_igemm / conv_wgrad launch on the launch stream.  They are
     # kept out of the K steps that define `value` because 174 event records per step sit between
     # back-to-back kernels and cost ~1.2 ms/step (measured: 21.1 ms -> 22.3 ms), a 5 % bias.
-    timer = None if args.no_kernel_timer else ops.KernelTimer()
+    timer = ops.KernelTimer() if args.full and not args.no_kernel_timer else None
     roof_steps = min(args.steps, 5)
     if timer is not None:
         # The engine normally runs weight gradients on a second stream next to the data-gradient chain; two
@@ -463,24 +505,27 @@ def main():
 
     dt_nocomm = None
     if world > 1:
-        # replicas must still be bit-identical here: same initial weights, every rank applied the SAME all-reduced
-        # gradient in every step so far (timed loop and roofline passes alike); two checksums per rank, gathered
-        flat = eng.store.flat.double()
-        sums = [None] * world
-        torch.distributed.all_gather_object(sums, (float(flat.sum().item()), float((flat * flat).sum().item())))
-        del flat
-        # what the gradient exchange costs a step: the same loop without it (ranks drift apart, nothing after
-        # this point reads the weights except the per-rank roofline pass above, which already ran)
-        nc_steps = min(args.steps, 5)
-        sync()
-        t1 = time.perf_counter()
-        for _ in range(nc_steps):
-            E.train_step(eng, crit, img, y, lr, comm=None)
-        sync()
-        dt_nocomm = (time.perf_counter() - t1) / nc_steps
-        t = torch.tensor([dt, dt_nocomm], dtype=torch.float64, device=dev)
+        if args.full:
+            # replicas must still be bit-identical here: same initial weights, every rank applied the SAME all-reduced
+            # gradient in every step so far (timed loop and roofline passes alike); two checksums per rank, gathered
+            flat = eng.store.flat.double()
+            sums = [None] * world
+            torch.distributed.all_gather_object(sums, (float(flat.sum().item()), float((flat * flat).sum().item())))
+            del flat
+            # what the gradient exchange costs a step: the same loop without it (ranks drift apart, nothing after
+            # this point reads the weights except the per-rank roofline pass above, which already ran)
+            nc_steps = min(args.steps, 5)
+            sync()
+            t1 = time.perf_counter()
+            for _ in range(nc_steps):
+                E.train_step(eng, crit, img, y, lr, comm=None)
+            sync()
+            dt_nocomm = (time.perf_counter() - t1) / nc_steps
+        t = torch.tensor([dt, dt_nocomm or 0.0], dtype=torch.float64, device=dev)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        dt, dt_nocomm = t.tolist()
+        dt = t[0].item()
+        if args.full:
+            dt_nocomm = t[1].item()
         shares = [None] * world          # every rank's schedule (rank 0's calibration decides for all)
         torch.distributed.all_gather_object(shares, bool(eng._cu_share is not None))
     if rank != 0:
@@ -504,10 +549,11 @@ def main():
     if world > 1:
         out["comm"] = {"backend": torch.distributed.get_backend(), "ranks": torch.distributed.get_world_size(),
                        "cu_share_per_rank": shares,
-                       "replica_checksums": sums, "replicas_identical": all(c == sums[0] for c in sums),
-                       "allreduce_bytes_per_rank": int(eng.store.grad.numel()) * 4, "buckets": 3,
-                       "ms_per_step_without_allreduce": round(1e3 * dt_nocomm, 3),
-                       "allreduce_ms_exposed": round(ms - 1e3 * dt_nocomm, 3)}
+                       "allreduce_bytes_per_rank": int(eng.store.grad.numel()) * 4, "buckets": 3}
+        if args.full:
+            out["comm"].update({"replica_checksums": sums, "replicas_identical": all(c == sums[0] for c in sums),
+                                "ms_per_step_without_allreduce": round(1e3 * dt_nocomm, 3),
+                                "allreduce_ms_exposed": round(ms - 1e3 * dt_nocomm, 3)})
         out["comm"].update(comm.describe(int(eng.store.grad.numel()) * 4))
         out["comm"]["grad_buckets_planned"] = [list(r) for r in eng.grad_buckets()]      # [stage 3 .. head], [stage 2], [stem .. stage 1]
     if timer is not None:
@@ -582,12 +628,12 @@ def main():
                                      "share_of_step": round(us * 1e-3 / ms, 5),
                                      "measured": f"HIP events around the launch in {roof_steps} steps continuing the timed loop "
                                                  "(one stream)"}
-    if world == 1 and args.agreement_n > 0:
+    if world == 1 and args.full and args.agreement_n > 0:
         out["agreement"] = agreement(eng, args.classes, args.agreement_n, dev)
-    if world == 1 and not args.no_other_configs:
+    if world == 1 and args.full and not args.no_other_configs:
         del eng      # (its 7 GB of activations; everything that reads it has run)
         out["other_configs"] = other_configs(dev)
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.classes)
     if world == 1 and "agreement" in out and not out["agreement"]["within_tolerance"]:
         print(f"bench.py: logit error {out['agreement']['max_abs_logit_err_over_scale']} of the logit scale exceeds the "

@@ -6,7 +6,7 @@ mkdir -p $OUT
 ( time timeout 1500 python -m pytest tests -m gpu -x -q --durations=5 ) > $OUT/pytest.log 2>&1
 tail -9 $OUT/pytest.log
 timeout 300 python __graft_entry__.py smoke 2>&1 | tail -2 | tee $OUT/smoke.txt
-timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_line.json; cut -c1-200 $OUT/bench_line.json
+timeout 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > $OUT/bench_line.json; cut -c1-200 $OUT/bench_line.json
 timeout 600 python scratch/bench_configs.py 2>/dev/null | grep "^{" > $OUT/configs.jsonl; cat $OUT/configs.jsonl | cut -c1-170
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp
 B="python $R/bench.py --no-cpu-baseline --no-kernel-timer --agreement-n 0"

@@ -4,7 +4,7 @@
 cd $GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/r03_run1
 mkdir -p $OUT
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 2>/dev/null | tail -1 > $OUT/bench_line.json
+timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>/dev/null | tail -1 > $OUT/bench_line.json
 cut -c1-600 $OUT/bench_line.json
 timeout 200 python scratch/cu_share_ab.py --steps 30 --rounds 2 off 47:200:16:96 47:200:16:128:split190 2>&1 | grep -v amdgpu.ids | tee $OUT/cu_share_ab.txt
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT; cd /tmp

@@ -9,7 +9,7 @@ if [ "$1" != "noprof" ]; then
 tail -9 $OUT/pytest.log
 timeout 300 python __graft_entry__.py smoke 2>&1 | tail -2 | tee $OUT/smoke.txt
 fi
-timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 2>$OUT/bench_err.txt | tail -1 > $OUT/bench_line.json; cut -c1-200 $OUT/bench_line.json
+timeout 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full 2>$OUT/bench_err.txt | tail -1 > $OUT/bench_line.json; cut -c1-200 $OUT/bench_line.json
 export TMPDIR=/tmp; R=$GRAFT_REPO_ROOT
 bash $R/scratch/prof_bench.sh r06 > $OUT/prof_bench.log 2>&1
 P=$R/gpurun_out/prof_bench_r06

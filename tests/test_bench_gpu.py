@@ -1,5 +1,5 @@
-"""bench.py end to end on the MI355X with a tiny setting: the JSON contract (keys, units, roofline and cpu_baseline
-objects) is what the driver parses."""
+"""bench.py end to end on the MI355X with a tiny setting: the JSON contract (keys, units, and with --full the roofline and
+cpu_baseline objects) is what the driver parses."""
 import json
 import os
 import subprocess
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--batch", "64", "--cpu-batch", "4"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--batch", "64", "--cpu-batch", "4", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -58,6 +58,34 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
         assert os.path.exists(os.path.join(ROOT, o["profile"])), o["profile"]
 
 
+def test_plain_bench_times_only_the_steps_and_dumps_the_last_step(tmp_path):
+    """Without --full the line carries the headline alone (nothing measured after the timed steps), and --dump-outputs
+    writes the last timed step's loss, weight sample and running statistics as float32 .npy files, 64 MB at most."""
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--batch", "64", "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "images/sec" and d["higher_is_better"] is True
+    assert abs(d["value"] - 64 * 3 / (d["ms_per_step"] * 3e-3)) < 0.02 * d["value"]
+    for key in ("roofline", "roofline_wgrad", "roofline_rules", "agreement", "other_configs", "cpu_baseline"):
+        assert key not in d, key
+    files = sorted(os.listdir(tmp_path / "dump"))
+    assert files == ["bn_running_stats.npy", "loss.npy", "params_sample.npy"]
+    total = 0
+    for f in files:
+        a = np.load(tmp_path / "dump" / f)
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), f
+        total += a.nbytes
+    assert total <= 64 << 20
+    assert abs(float(np.load(tmp_path / "dump" / "loss.npy")[0]) - d["config"]["final_loss"]) < 1e-4
+
+
 def test_bench_two_rank_branch_runs_on_one_gpu_over_gloo():
     """`bench.py --gpus 2` re-launches itself through torch.distributed.run (one rank per GPU over RCCL on a
     multi-GPU node).  On a 1-GPU box the same branch -- self-launch, per-rank shard, GradComm buckets reduced during
@@ -68,7 +96,7 @@ def test_bench_two_rank_branch_runs_on_one_gpu_over_gloo():
     multi = torch.cuda.device_count() >= 2
     extra = [] if multi else ["--backend", "gloo", "--share-gpu"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-                          "--batch", "64", "--no-cpu-baseline", "--agreement-n", "0"] + extra,
+                          "--batch", "64", "--full", "--no-cpu-baseline", "--agreement-n", "0"] + extra,
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -93,7 +121,7 @@ def test_bench_n_rank_branch_at_the_driver_rank_counts(ranks):
     multi = torch.cuda.device_count() >= ranks
     extra = [] if multi else ["--backend", "gloo", "--share-gpu"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "3",
-                          "--warmup", "1", "--batch", "64", "--no-cpu-baseline", "--agreement-n", "0",
+                          "--warmup", "1", "--batch", "64", "--full", "--no-cpu-baseline", "--agreement-n", "0",
                           "--no-kernel-timer", "--no-other-configs"] + extra,
                          capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -117,3 +145,22 @@ def test_bench_n_rank_branch_at_the_driver_rank_counts(ranks):
     assert sum(c["bucket_bytes_last_step"]) == c["allreduce_bytes_per_rank"]
     assert c["reserved_cus_while_buckets_in_flight"] == (c["rccl_max_nchannels"] if multi else 0)
     assert abs(d["value"] - 64 * ranks * 3 / (d["ms_per_step"] * 3e-3)) < 0.02 * d["value"]
+
+
+def test_plain_two_rank_run_reports_the_slowest_rank_and_nothing_after_the_steps():
+    """The driver's scaling command without --full: max-over-ranks timing and the cheap half of `comm`, no extra loops."""
+    import torch
+    multi = torch.cuda.device_count() >= 2
+    extra = [] if multi else ["--backend", "gloo", "--share-gpu"]
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                          "--batch", "64"] + extra, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, out.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 2 and d["config"]["global_batch"] == 128
+    assert abs(d["value"] - 128 * 2 / (d["ms_per_step"] * 2e-3)) < 0.02 * d["value"]
+    c = d["comm"]
+    assert c["ranks"] == 2 and c["buckets"] == 3 and len(c["cu_share_per_rank"]) == 2
+    assert "replica_checksums" not in c and "allreduce_ms_exposed" not in c
+    assert "roofline" not in d and "cpu_baseline" not in d

@@ -98,3 +98,61 @@ def test_committed_bench_line_is_consistent_with_its_committed_evidence(bench, m
         assert os.path.exists(os.path.join(ROOT, o["profile"])), o["profile"]
         assert abs(o["frac"] - o["achieved"] / o["peak"]) < 1e-3
         assert abs(o["value"] * o["ms_per_step"] / 1e3 - o["batch_per_gpu"]) < 0.01 * o["batch_per_gpu"]
+
+
+class _FakeEngine:
+    """named_params / named_buffers like the engines': reference names, logical (possibly strided) fp32 views."""
+
+    def __init__(self, seed):
+        import torch
+        g = torch.Generator().manual_seed(seed)
+        self.params = {"conv1.weight": torch.randn(16, 3, 3, 3, generator=g),
+                       "block.conv.weight": torch.randn(64, 32, 3, 3, generator=g)[:, :16],
+                       "bn1.weight": torch.randn(16, generator=g), "linear.bias": torch.randn(10, generator=g)}
+        self.buffers = {"bn1.running_mean": torch.randn(16, generator=g), "bn1.running_var": torch.rand(16, generator=g),
+                        "bn1.num_batches_tracked": torch.tensor(3)}
+
+    def named_params(self, which="flat"):
+        assert which == "flat"
+        return dict(self.params)
+
+    def named_buffers(self):
+        return dict(self.buffers)
+
+
+def test_dump_outputs_writes_a_fixed_float32_sample_of_what_the_step_left(bench, tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_PARAM_SAMPLE", 1000)
+    eng = _FakeEngine(0)
+    bench.dump_outputs(str(tmp_path / "a"), eng, torch.tensor(2.5))
+    assert sorted(os.listdir(tmp_path / "a")) == ["bn_running_stats.npy", "loss.npy", "params_sample.npy"]
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert got["loss"].tolist() == [2.5]
+    flat = torch.cat([eng.params[k].reshape(-1) for k in sorted(eng.params)]).numpy()
+    assert got["params_sample"].shape == (1000,) and np.isin(got["params_sample"], flat).all()
+    stats = np.concatenate([eng.buffers["bn1.running_mean"].numpy(), eng.buffers["bn1.running_var"].numpy()])
+    np.testing.assert_array_equal(got["bn_running_stats"], stats)
+    # the same positions in every run: another engine's values, the same sample indices
+    eng2 = _FakeEngine(1)
+    bench.dump_outputs(str(tmp_path / "b"), eng2, torch.tensor(1.0))
+    flat2 = torch.cat([eng2.params[k].reshape(-1) for k in sorted(eng2.params)]).numpy()
+    pos = np.searchsorted(np.sort(flat), got["params_sample"])
+    order = np.argsort(flat)
+    np.testing.assert_array_equal(np.load(tmp_path / "b" / "params_sample.npy"), flat2[order[pos]])
+    # a model smaller than the sample is dumped whole, in order
+    monkeypatch.setattr(bench, "DUMP_PARAM_SAMPLE", 10 ** 6)
+    bench.dump_outputs(str(tmp_path / "c"), eng, torch.tensor(2.5))
+    np.testing.assert_array_equal(np.load(tmp_path / "c" / "params_sample.npy"), flat)
+
+
+def test_command_line_has_full_and_dump_outputs_and_refuses_zero_steps():
+    import subprocess
+    import sys
+    h = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True,
+                       timeout=120)
+    assert h.returncode == 0 and "--full" in h.stdout and "--dump-outputs" in h.stdout
+    z = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                       timeout=120)
+    assert z.returncode == 2 and "--steps" in z.stderr
