@@ -20,8 +20,6 @@ import torch
 
 from nbdt import _C, ops
 
-SIDE_STREAM_PRIORITY = 0       # HIP stream priority of the weight-gradient stream (A/B: scratch/ab_stream_priority.py)
-
 ALIGN = 8  # elements: keeps every parameter 16-byte aligned in the bf16 mirror
 
 _SIDE_STREAMS = {}
@@ -36,7 +34,7 @@ def side_stream(device):
     dev = torch.device(device)
     key = (dev.type, dev.index if dev.index is not None else torch.cuda.current_device())
     if key not in _SIDE_STREAMS:
-        _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev, priority=SIDE_STREAM_PRIORITY)
+        _SIDE_STREAMS[key] = torch.cuda.Stream(device=dev)
     return _SIDE_STREAMS[key]
 
 
@@ -53,6 +51,7 @@ class ParamStore:
         self.inits = []     # (name, fn(view))
         self.n = 0
         self.flat = self.grad = self.mom = self.bf16 = None
+        self._views = {}    # (which buffer, name) -> (view, the buffer it was made of)
 
     def add(self, name, shape, init):
         assert self.flat is None and name not in self.entries
@@ -82,12 +81,11 @@ class ParamStore:
     def _cached(self, which, buf, name):
         # the flat buffers are allocated once (finalize) and only ever written in place: a named view is made once.  (ResNet18
         # on CIFAR10 at 128 images is bound by the host's launch path: 9,000 slice + view calls per 50 steps were 10 % of it.)
-        cache = self.__dict__.setdefault("_views", {})
-        hit = cache.get((which, name))
+        hit = self._views.get((which, name))
         if hit is not None and hit[1] is buf:          # (a replaced flat buffer -- nobody does that today -- is a miss)
             return hit[0]
         v = self._view(buf, name)
-        cache[(which, name)] = (v, buf)
+        self._views[(which, name)] = (v, buf)
         return v
 
     def p(self, name):
@@ -127,7 +125,8 @@ class Conv:
         store.add(name, (self.cout, self.taps, self.cin), init)
         self._plans = {}
         self.wd = None
-        self.merge_parity_classes = True   # (A/B: False launches the parity classes of a strided data gradient one by one)
+        self.wt_fwd = self.wt_dgrad = None   # DMA-ordered weight tiles (dense 3x3 / stride 1: _Engine.finalize)
+        self.side_stream = None              # the engine's second stream for weight gradients, or None: the caller's
 
     def logical(self, buf):
         """[cout_real, cin_real, k, k] view (OIHW semantics, channels_last memory) of a flat buffer."""
@@ -142,7 +141,7 @@ class Conv:
 
     def _make_plan(self, B, Hi, Wi):
         p = self._raw_plan(B, Hi, Wi)
-        if getattr(self, "wt_fwd", None) is not None:      # dense 3x3 / stride 1: DMA-ordered weight tiles
+        if self.wt_fwd is not None:      # dense 3x3 / stride 1: DMA-ordered weight tiles
             p[0].w_tiled = self.wt_fwd.data_ptr()
             for descs in (p[1], p[2]):
                 if descs is not None and len(descs) == 1:
@@ -199,7 +198,7 @@ class Conv:
             assert len(descs) == 1 and not accumulate
             ops.conv_igemm_bnbwd(descs[0], gout, self.wd, gin, bn_x, bn.mean, bn.rstd, bn.gamma, bn.beta, partials)
             return
-        if len(descs) > 1 and self.merge_parity_classes:      # strided 3x3: four parity classes, one grid
+        if len(descs) > 1:      # strided 3x3: four parity classes, one grid
             ops.conv_igemm_multi(descs, gout, self._wd_for(gout), gin)
             return
         for d in descs:
@@ -222,7 +221,7 @@ class Conv:
 
     def backward_weight_s2d(self, xs, gout, Hi, Wi, cu_budget=0):
         desc = self.s2d_plan(xs.shape[0], Hi, Wi)[1]
-        side = getattr(self, "side_stream", None)
+        side = self.side_stream
         if side is None:
             ops.conv_wgrad(desc, xs, gout, self.store.g(self.name), cu_budget)
             return
@@ -235,7 +234,7 @@ class Conv:
         """cu_budget: CUs this launch is sized for when it runs on the second stream (0 = all of them): the caller
         is about to launch an HBM-bound pass on the main stream that should get the remaining CUs."""
         B, Hp, Wp, _ = x.shape
-        side = getattr(self, "side_stream", None)
+        side = self.side_stream
         if side is None:
             ops.conv_wgrad(self.plan(B, Hp - 2, Wp - 2)[3], x, gout, self.store.g(self.name), cu_budget)
             return
@@ -326,9 +325,8 @@ class BatchNorm:
 
     def backward_cus(self, gy, x, gx, cus, gx_add=None):
         """Backward of relu(bn(x)) entirely on `cus` CUs: sums and elementwise pass, the fold of the sums in the latter's
-        prologue (no dgrad-epilogue partials; owner.fuse_bn_fold = False: the three-launch form, A/B and tests)."""
-        scratch = self.owner.slot_pair(self.C) if self.owner.fuse_bn_fold else self.owner.scratch(self.C)
-        ops.bn_bwd_cus(gy, x, self.mean, self.rstd, self.gamma, self.beta, scratch, self.dsum,
+        prologue (no dgrad-epilogue partials), summed into the owner's slot pair of this channel count."""
+        ops.bn_bwd_cus(gy, x, self.mean, self.rstd, self.gamma, self.beta, self.owner.slot_pair(self.C), self.dsum,
                        self.store.g(self.name + ".weight"), self.store.g(self.name + ".bias"), gx, cus, gx_add=gx_add)
 
     def backward(self, gy, y, x, gx, relu=True, gx_add=None, g_resid=None):
@@ -354,12 +352,9 @@ class _Engine:
         self.act_dtype = torch.bfloat16   # storage of activations / activation gradients (fp32: set_reference_fp32)
         self.debug_keep = False   # tests: give every unit its own gradient buffers (no reuse)
         self.debug_share_serial = False   # tests: the CU-sharing schedule's exact launches (CU counts, budgets) on ONE stream
-        self.debug_join_each_unit = False # A/B: join the side stream at the top of every unit (the schedule before round 3)
         self.fuse_stats = True    # BN sums come out of the producing conv's epilogue (no stats pass)
         self.fuse_eval = True     # inference: eval-mode BN + activation folded into the conv epilogue
         self.share_bn2_tensors, self.share_bn1_tensors = 5, 6   # tensor passes of the confined BatchNorm backward (CU plan)
-        self.fuse_bn_fold = True  # CU-confined BatchNorm backward: fold of the sums inside the elementwise pass (2 launches)
-        self.fuse_dw_bn_bwd = True  # MBConv: BatchNorm-backward sums in the depthwise data gradient's epilogue (A/B)
         self.fuse_bn1_bwd = True  # ResNet basic block: bn1's backward sums in conv2's data-gradient epilogue (A/B)
         self._side = None         # second stream for weight gradients (WRNEngine turns it on)
         self._cu_share = None     # set_cu_share(): BatchNorm-backward passes beside weight gradients on disjoint CUs
@@ -368,18 +363,15 @@ class _Engine:
         self._share_calibrated = True
         self.cu_share_report = None
         self._overlap = True
-        self.use_seg = True       # shape-changing units on the slice-list kernel (conv_seg.hip); False: rounds 1-5's launches
-        self._seg_ops = {}
-        self.seg_share = True     # ... with bn1's backward beside conv1's weight gradient on disjoint CUs (strided units; "all": every one; False: none)
-        self.seg_join = None      # wait for conv2's weight gradient before the slice-list data gradient: "small" (8x8 grids), "all", None
-        # CU sharing, per stage: dense units whose output grid has at least this many pixels take their BatchNorm-backward
-        # sums from the data gradient's epilogue again (the round-1 fused form) and confine only the elementwise pass
-        # (0 = every stage uses the split form).  Where the confined reduce + apply outlast the weight gradient beside them
-        # (32x32: 290-310 us against 250-300), the sums cost less at MFMA price than on the critical chain.
-        self.share_fused_hw = 0
+        self._seg_ops = {}        # slice-list launches (SegOp) by (unit, role, geometry)
+        self._seg_skip = set()    # ... and the keys whose fused conv2 + shortcut launch is not taken (_seg_conv2_sc)
         self.share_stage_us = {}  # output-grid pixels (ho * wo) -> split_target_us of that stage (absent: set_cu_share's)
-        self.share_scale_batch = True   # ... scaled by batch / 512 (False: rounds 3-5, the same microseconds at every batch)
-        self.share_fused_target_us = 200.0
+        self._slot_pairs = {}     # channel count -> [buffer 0, buffer 1, dirty index] (slot_pair)
+        self._slot_arena, self._slot_arena_pairs = None, 0    # the one buffer every slot pair lives in (reset_slot_pairs)
+        self._partials = None     # conv-epilogue BatchNorm partial sums (partials)
+        self._reserved_now = 0    # CUs the MFMA launches currently leave to in-flight all-reduces (_reserve_for)
+        self._grad_is_zero = False   # the flat gradient buffer is known to be zero (sgd_step(zero_grad=True))
+        self._B = None            # batch of the last forward()
 
     def seg_op(self, key, build, sources, sources32, on_side=False):
         """The SegOp `key` (created, and its weights tiled, at first use: a new batch size or image size)."""
@@ -424,7 +416,7 @@ class _Engine:
         "`slots` is zero on entry": a step makes an ODD number of calls per channel count (2n-1 for a WRN stage), so the
         pair does not return to its starting state by itself -- backward() calls reset_slot_pairs() first, which makes
         every step (and every captured graph of one) start from (zero, zero) whatever ran before it."""
-        pairs = self.__dict__.setdefault("_slot_pairs", {})
+        pairs = self._slot_pairs
         if C not in pairs:
             n = ops.BN_SLOTS * 2 * C
             # [buffer 0, buffer 1, index of the buffer the LAST call summed into (dirty), or -1: both are zero]
@@ -438,10 +430,10 @@ class _Engine:
         """Zero the one dirty buffer of every slot pair (a stream-ordered fill on the caller's stream) so that the next
         slot_pair() call finds (zero, zero).  Called at the top of backward(): a hipGraph of a step bakes the pointers
         in, and without this replay k+1's first call per channel count summed into what replay k's last call left."""
-        pairs = self.__dict__.get("_slot_pairs", {})
+        pairs = self._slot_pairs
         if not pairs:
             return
-        if self.__dict__.get("_slot_arena_pairs") != len(pairs):
+        if self._slot_arena_pairs != len(pairs):
             # (re)pack every pair into ONE zeroed arena, so that a step pays one fill launch for all channel counts instead of
             # one each (three per WRN-28-10 step: 15 us + their launch gaps between forward and backward).  Only when a new
             # channel count appeared -- the first backward of a shape; GraphedStep's warm-up steps come before its capture.
@@ -462,7 +454,7 @@ class _Engine:
         """Workspace for the conv-epilogue BN partial sums of a padded [B,H+2,W+2,C] output."""
         B, Hp, Wp, C = out.shape
         need = ((B * (Hp - 2) * (Wp - 2) + 255) // 256) * 2 * C
-        if getattr(self, "_partials", None) is None or self._partials.numel() < need:
+        if self._partials is None or self._partials.numel() < need:
             self._partials = torch.empty(need, device=self.device)
         return self._partials
 
@@ -494,7 +486,7 @@ class _Engine:
         self.fuse_eval = not on
         self._bufs = {}
         self._seg_ops = {}
-        self.__dict__.pop("_seg_skip", None)
+        self._seg_skip = set()
         for c in self.convs:
             c._plans = {}
         self._share_calibrated = True        # (a timing decision between two schedules of the SLOW kernels means nothing)
@@ -551,12 +543,13 @@ class _Engine:
                                                            max(8, int(min_cus)), int(max_cus))
         self._share_calibrated = not calibrate
 
-    def _split_us(self, grid_pixels, B):
-        """Time budget of the confined reduce + apply of a stage whose output grid has `grid_pixels` pixels: share_stage_us
-        (or set_cu_share's split_target_us), quoted at 512 images -- the weight gradient beside the pass lasts in proportion
+    def _split_us(self, out):
+        """Time budget of the confined reduce + apply of a stage, from a padded [B, H+2, W+2, C] tensor on its output grid:
+        share_stage_us[H * W] (or set_cu_share's split_target_us), quoted at 512 images -- the weight gradient beside the pass lasts in proportion
         to the batch, so the pass's budget does too and the CU split does not depend on the batch (a 256-image shard with
         512-image microseconds gave its passes half the CUs: 10.6 instead of 9.3 ms per step)."""
-        return self.share_stage_us.get(grid_pixels, self._share_split[1]) * (B / 512.0 if self.share_scale_batch else 1.0)
+        B, Hp, Wp, _ = out.shape
+        return self.share_stage_us.get((Hp - 2) * (Wp - 2), self._share_split[1]) * (B / 512.0)
 
     def _share_plan(self, conv, x, elements, tensors, us=None):
         """(weight-gradient descriptor, its CU budget, CUs for the elementwise pass of `tensors` tensors of `elements`
@@ -601,7 +594,7 @@ class _Engine:
             raise RuntimeError("calibrate_cu_share() synchronises with the host: call it (or run one eager step) "
                                "before capturing the step in a hipGraph")
         u = self._calibration_unit()
-        if u is None or self._side is None or getattr(self, "_B", None) is None:
+        if u is None or self._side is None or self._B is None:
             self._cu_share = None
             self.cu_share_report = {"enabled": False, "reason": "no unit / second stream / forward to calibrate on"}
             return self.cu_share_report
@@ -616,14 +609,14 @@ class _Engine:
         # (plumbing: a one-off fill so the MFMAs see real data -- from a private generator: the caller's global
         # RNG stream is not advanced by a calibration)
         ops.interior(g).normal_(0.0, 1e-3, generator=torch.Generator(device=self.device).manual_seed(0x5eed))
-        split, split_us = self._share_split[0], self._split_us(h * w, B)
+        split, split_us = self._share_split[0], self._split_us(t)
         elements = B * h * w * cout
         desc, budget, n = self._share_plan(conv, a2, elements, 5 if split else 3, split_us if split else None)
         main = torch.cuda.current_stream(self.device)
         dw = torch.zeros_like(self.store.g(conv.name))
         dsum = torch.empty(2 * bn.C, device=self.device)
         dg, db = torch.zeros(bn.C, device=self.device), torch.zeros(bn.C, device=self.device)
-        partials, scratch = self.partials(t), self.scratch(bn.C)
+        partials = self.partials(t)
         plan = conv.plan(B, h, w)
         d_plain = plan[1][0]
 
@@ -648,8 +641,7 @@ class _Engine:
             dgrad(not split)
             wgrad_side(budget)
             if split:
-                ops.bn_bwd_cus(ga2, t, bn.mean, bn.rstd, bn.gamma, bn.beta,
-                               self.slot_pair(bn.C) if self.fuse_bn_fold else scratch, dsum, dg, db, gt, n)
+                ops.bn_bwd_cus(ga2, t, bn.mean, bn.rstd, bn.gamma, bn.beta, self.slot_pair(bn.C), dsum, dg, db, gt, n)
             else:
                 ops.bn_bwd_fused(ga2, t, bn.mean, bn.rstd, bn.gamma, bn.beta, partials, dsum, dg, db, gt, cus=n)
             main.wait_stream(self._side)
@@ -692,7 +684,7 @@ class _Engine:
         per channel): the one-block-per-CU MFMA launches that follow are sized for the rest (ops.set_reserved_cus), so
         none of their persistent blocks waits for a CU an all-reduce block holds.  comm=None: back to the whole chip."""
         n = int(getattr(comm, "reserved_cus", 0) or 0) if comm is not None else 0
-        if n != getattr(self, "_reserved_now", 0):
+        if n != self._reserved_now:
             ops.set_reserved_cus(n)
             self._reserved_now = n
 
@@ -700,6 +692,82 @@ class _Engine:
         """Order every weight-gradient launch issued on the side stream before what follows on the main one."""
         if self._side is not None:
             torch.cuda.current_stream(self.device).wait_stream(self._side)
+
+    # ---- what every engine's forward() / backward() does around its own launches
+    bucket_units = ()   # keys of the units after whose backward grad_buckets()[0] and [1] are complete
+
+    def _input(self, img):
+        """The image as contiguous fp32, remembered with its batch size for backward()."""
+        if img.dtype != torch.float32 or not img.is_contiguous():
+            img = img.float().contiguous()
+        self._img, self._B = img, img.shape[0]
+        return img
+
+    def _pool_head(self, x, mean, rstd, gamma, beta, head):
+        """Global pooling of relu(bn(x)) into [B, feat_c], then the classifier (head=False: the pooled features)."""
+        B = self._B
+        self._pooled = self._tensor("pooled", (B, self.feat_c))
+        ops.bn_relu_pool(x, mean, rstd, gamma, beta, self._pooled)
+        if not head:
+            return self._pooled
+        z = self._tensor("z", (B, self.num_classes))
+        w, b = self.classifier_names
+        ops.linear_fwd(self._pooled, self.store.p(w), self.store.p(b), z)
+        return z
+
+    def _head_backward(self, gz, gpooled):
+        """dL/dpooled: `gpooled` after forward(head=False) (the fused head kernel already accumulated the classifier's
+        gradients), else the classifier's backward from gz = dL/dz."""
+        if gpooled is not None:
+            return gpooled
+        gz = gz.contiguous()
+        gpool = self._tensor("gpool", (self._B, self.feat_c))
+        w, b = self.classifier_names
+        ops.linear_bwd(self._pooled, self.store.p(w), gz, gpool, self.store.g(w), self.store.g(b))
+        return gpool
+
+    def _begin_backward(self, comm):
+        self._grad_is_zero = False   # this call accumulates into the gradient buffer
+        self.join_side_stream()      # dgrad weight copies (built on the second stream after the last update)
+        if self._cu_share is not None and not self._share_calibrated:
+            self.calibrate_cu_share(comm)      # once per set_cu_share(): keep the sharing only if it is faster here
+        self.reset_slot_pairs()      # the confined BatchNorm backward's slot buffers start every step from (zero, zero)
+
+    def _units_backward(self, units, comm):
+        """(i, unit) for `units` in reverse order, with the cross-stream protocol around each unit's launches.
+
+        Gradient buffers are shared between units, and a weight gradient still running on the side stream may be reading
+        what a later unit is about to overwrite.  Joining the side stream at the top of every unit would order that, but
+        it makes the main stream wait for the weight gradient issued LAST (~70 us of a 1 ms WRN unit with 96 CUs idle:
+        0.95 ms of launch gaps per backward in profiles/r03_split_*two_streams*).  Instead the main stream waits for
+        everything the side stream had been given ONE UNIT AGO (an event recorded at the top of the previous unit), and
+        each engine rotates the buffers a weight gradient reads so that unit i never writes what unit i - 1's may still
+        be reading (i is the unit's position in this order).  After each unit named in `bucket_units` the side stream is
+        joined and that unit's gradient bucket is all-reduced (comm: a GradComm, or None)."""
+        main = torch.cuda.current_stream(self.device)
+        two_streams = self._side is not None and self._overlap
+        if two_streams:      # (also forks the side stream into a hipGraph capture before its first event is recorded)
+            self._side.wait_stream(main)
+        buckets = self.grad_buckets() if comm is not None else None
+        side_mark = None
+        for i, u in enumerate(reversed(units)):
+            if two_streams:
+                if side_mark is not None:
+                    main.wait_event(side_mark)
+                side_mark = torch.cuda.Event()
+                side_mark.record(self._side)
+            yield i, u
+            if comm is not None and u["key"] in self.bucket_units:
+                self.join_side_stream()
+                comm.reduce_range(self.store.grad, *buckets[self.bucket_units.index(u["key"])])
+                self._reserve_for(comm)
+
+    def _end_backward(self, comm):
+        self.join_side_stream()      # every gradient is complete on the caller's stream when backward returns
+        if comm is not None:
+            comm.reduce_range(self.store.grad, *self.grad_buckets()[2])
+            comm.finish(self.store.grad)
+            self._reserve_for(None)
 
     def bn(self, name, c):
         b = BatchNorm(self.store, name, c, self)
@@ -761,7 +829,7 @@ class _Engine:
         if self._wt_n:     # forward tiles are needed by the very next forward: caller's stream
             ops.weight_tile_batched(self.store.bf16, self._wt_ftable, self._wt_n, self._wt_ftotal, self._wt_fwd)
         self._retile_seg(False)
-        if self._side is None or not getattr(self, "_overlap", True):
+        if self._side is None or not self._overlap:
             ops.weight_prep_batched(self.store.flat, self._wd_table, len(self.convs), self._wd_total, self._wd_flat)
             if self._wt_n:
                 ops.weight_tile_batched(self._wd_flat, self._wt_dtable, self._wt_n, self._wt_dtotal, self._wt_dgrad)
@@ -787,7 +855,7 @@ class _Engine:
         self.refresh_derived_weights()
 
     def zero_grad(self):
-        if not getattr(self, "_grad_is_zero", False):
+        if not self._grad_is_zero:
             self.store.zero_grad()
         self._grad_is_zero = False       # whatever runs next may accumulate into it
 
@@ -879,6 +947,7 @@ class WRNEngine(_Engine):
                     "idconv": (self.conv(pre + "identity_conv.weight", cin, cout, 1, stride)
                                if (cin != cout or stride != 1) else None),
                     "cin": cin, "cout": cout, "stride": stride, "key": f"s{i + 1}u{j + 1}",
+                    "seg": False,    # forward(): this unit ran on the slice-list kernel (training mode, shortcut conv)
                 }
                 self.units.append(u)
                 cin = cout
@@ -917,20 +986,19 @@ class WRNEngine(_Engine):
     def _seg_conv2_sc(self, u, B, ho, wo):
         """conv2 + shortcut in one launch (the residual add disappears into the K loop); None where the plan would fall
         back to 256-pixel half tiles (8x8 grids cannot hold three halo buffers of a 512-pixel tile: the dense kernel + a
-        separate 1x1 launch are faster there; engine.seg_fuse_half_tiles = True fuses anyway, A/B)."""
+        separate 1x1 launch are faster there)."""
         c2, ci = u["conv2"], u["idconv"]
         key = (u["key"], "conv2sc", B, ho, wo)
         if key in self._seg_ops:
             return self._seg_ops[key]
-        skip = self.__dict__.setdefault("_seg_skip", set())
-        if key in skip:
+        if key in self._seg_skip:
             return None
         try:
             plan = ops.seg_conv3x3_plus_1x1(B, ho, wo, c2.cin, c2.cout, ci.cin, (4 if u["stride"] == 2 else 1) * ci.cin)
         except _C.NBDTHipError:
             plan = None
-        if plan is None or (plan.tile != 512 and not getattr(self, "seg_fuse_half_tiles", False)):
-            skip.add(key)
+        if plan is None or plan.tile != 512:
+            self._seg_skip.add(key)
             return None
         return self.seg_op(key, lambda: plan,
                            lambda: [self.store.pb(c2.name).view(c2.cout, 9 * c2.cin), self.store.pb(ci.name).view(ci.cout, ci.cin)],
@@ -960,10 +1028,8 @@ class WRNEngine(_Engine):
         """head=False: stop at the pooled features [B, feat_c] (fp32) -- the caller runs the classifier inside the
         fused head + loss kernel (train_step) and hands dL/dpooled to backward(gpooled=...)."""
         training = self.training if training is None else training
-        if img.dtype != torch.float32 or not img.is_contiguous():
-            img = img.float().contiguous()
+        img = self._input(img)
         B, _, H, W = img.shape
-        self._img, self._B = img, B
         x = self.buf("x0", B, H, W, self.stem_cpad)
         ops.stem_conv(img, self.store.p("features.init_block.weight"), x, self.stem_c)
         h, w = H, W
@@ -981,7 +1047,7 @@ class WRNEngine(_Engine):
             # written as its space-to-depth copy -- its only readers are conv1, the shortcut and their weight gradients,
             # all stride 2 -- conv1 runs as a slice list over it, and conv2 takes the shortcut as one more term of its K
             # loop (no shortcut launch, no residual read in the epilogue).
-            seg = training and self.use_seg and u["idconv"] is not None
+            seg = training and u["idconv"] is not None
             u["seg"] = seg
             if seg and s == 2:
                 a1 = self.s2d_buf(k + ".a1", B, h, w, cin)
@@ -1016,15 +1082,9 @@ class WRNEngine(_Engine):
             u["x_in"], u["x_out"] = x, out
             x, h, w = out, ho, wo
         self._x_last, self._hw = x, (h, w)
-        self.post_bn.stats(x, training, fused=training and self.fuse_stats)
-        self._pooled = self._tensor("pooled", (B, self.feat_c))
-        ops.bn_relu_pool(x, self.post_bn.mean, self.post_bn.rstd, self.post_bn.gamma, self.post_bn.beta,
-                         self._pooled)
-        if not head:
-            return self._pooled
-        z = self._tensor("z", (B, self.num_classes))
-        ops.linear_fwd(self._pooled, self.store.p("output.weight"), self.store.p("output.bias"), z)
-        return z
+        pb = self.post_bn
+        pb.stats(x, training, fused=training and self.fuse_stats)
+        return self._pool_head(x, pb.mean, pb.rstd, pb.gamma, pb.beta, head)
 
     def grad_buckets(self):
         """(lo, hi) ranges of the flat gradient buffer in the order backward completes them:
@@ -1034,187 +1094,147 @@ class WRNEngine(_Engine):
         s3 = ent["features.stage3.unit1.body.conv1.bn.weight"][0]
         return [(s3, self.store.grad.numel()), (s2, s3), (0, s2)]
 
+    bucket_units = ("s3u1", "s2u1")
+
     def backward(self, gz, comm=None, gpooled=None):
         """Accumulates d(loss)/d(params) into the flat gradient buffer given gz = dloss/dz [B, classes] -- or, after
         forward(head=False), given gpooled = dloss/dpooled [B, feat_c] (the fused head kernel already accumulated the
         classifier's gradients).  With a GradComm, each stage's gradient bucket is all-reduced as soon as it is
         complete."""
-        self._grad_is_zero = False   # this call accumulates into the gradient buffer
-        B = self._B
-        self.join_side_stream()      # dgrad weight copies (built on the second stream after the last update)
-        if self._cu_share is not None and not self._share_calibrated:
-            self.calibrate_cu_share(comm)      # once per set_cu_share(): keep the sharing only if it is faster here
-        self.reset_slot_pairs()      # the confined BatchNorm backward's slot buffers start every step from (zero, zero)
-        two_streams = self._side is not None and self._overlap
-        buckets = self.grad_buckets() if comm is not None else None
-        st = self.store
-        if gpooled is not None:
-            gpool = gpooled
-        else:
-            gz = gz.contiguous()
-            gpool = self._tensor("gpool", (B, self.feat_c))
-            ops.linear_bwd(self._pooled, st.p("output.weight"), gz, gpool, st.g("output.weight"), st.g("output.bias"))
+        self._begin_backward(comm)
+        B, st = self._B, self.store
+        gpool = self._head_backward(gz, gpooled)
         h, w = self._hw
         C = _pad32(self.feat_c)
         g = self.buf(f"g_out{C}", B, h, w, C)
         pb = self.post_bn
         ops.pool_bn_bwd(gpool, self._x_last, pb.mean, pb.rstd, pb.gamma, pb.beta, self.scratch(C), pb.dsum,
                         st.g(pb.name + ".weight"), st.g(pb.name + ".bias"), g)
-        toggle, n_unit, side_mark = 0, 0, None
-        if two_streams:      # (also forks the side stream into a hipGraph capture before its first event is recorded)
-            self._side.wait_stream(torch.cuda.current_stream(self.device))
-        for u in reversed(self.units):
-            # Gradient buffers are shared between units, and a weight gradient still running on the side stream may be
-            # reading what a later unit is about to overwrite: conv1's reads `gt`, conv2's the unit's output gradient
-            # (the previous unit's g_in).  Joining the side stream here would order that, but it makes the main
-            # stream wait for the weight gradient issued LAST (the previous unit's conv1, ~70 us of a 1 ms unit with
-            # 96 CUs idle: 0.95 ms of launch gaps per backward in profiles/r03_split_*two_streams*).  Instead the
-            # main stream waits for everything the side stream had been given ONE UNIT AGO (an event recorded at the
-            # top of the previous unit), and the buffers a weight gradient of the previous unit can still be reading
-            # are not the ones this unit writes: `gt` alternates between two buffers, g_in rotates through three.
-            # (tests/test_engine_gpu.py::test_deterministic_mode_makes_the_schedules_bit_comparable: this schedule
-            # gives the same bits as one stream with private buffers.)
-            if two_streams and self.debug_join_each_unit:
-                self.join_side_stream()
-            elif two_streams:
-                main = torch.cuda.current_stream(self.device)
-                if side_mark is not None:
-                    main.wait_event(side_mark)
-                side_mark = torch.cuda.Event()
-                side_mark.record(self._side)
+        form, share = self._backward_form()
+        for i, u in self._units_backward(self.units, comm):
+            # The buffers a weight gradient of unit i - 1 can still be reading (see _units_backward) are not the ones unit
+            # i writes: conv1's reads `gt`, which alternates between two buffers, conv2's the unit's output gradient (the
+            # previous unit's g_in), which rotates through three.  (tests/test_engine_gpu.py::
+            # test_deterministic_mode_makes_the_schedules_bit_comparable: this gives the same bits as one stream with
+            # private buffers.)
             k, s = u["key"], u["stride"]
             cin, cout = _pad32(u["cin"]), _pad32(u["cout"])
-            ho, wo = h, w
-            hi, wi = ho * s, wo * s
-            seg = bool(u.get("seg"))
-            a1 = self.s2d_buf(k + ".a1", B, hi, wi, cin) if (seg and s == 2) else self.buf(k + ".a1", B, hi, wi, cin)
-            t = self.buf(k + ".t", B, ho, wo, cout)
-            a2 = self.buf(k + ".a2", B, ho, wo, cout)
+            hi, wi = h * s, w * s
+            a1 = self.s2d_buf(k + ".a1", B, hi, wi, cin) if (u["seg"] and s == 2) else self.buf(k + ".a1", B, hi, wi, cin)
+            t = self.buf(k + ".t", B, h, w, cout)
+            a2 = self.buf(k + ".a2", B, h, w, cout)
             tag = ("@" + k) if self.debug_keep else ""
-            ga2 = self.buf(f"ga2_{cout}{tag}", B, ho, wo, cout)
-            gt = self.buf(f"gt_{cout}_{n_unit & 1}{tag}", B, ho, wo, cout)
+            ga2 = self.buf(f"ga2_{cout}{tag}", B, h, w, cout)
+            gt = self.buf(f"gt_{cout}_{i & 1}{tag}", B, h, w, cout)
             ga1 = self.buf(f"ga1_{cin}_{hi}{tag}", B, hi, wi, cin)
             # the unit's input gradient must not alias its output gradient `g` (nor, see above, the one before that)
-            toggle = (toggle + 1) % 3
-            n_unit += 1
-            g_in = self.buf(f"g_in{cin}_{hi}_{toggle}{tag}", B, hi, wi, cin)
+            g_in = self.buf(f"g_in{cin}_{hi}_{(i + 1) % 3}{tag}", B, hi, wi, cin)
             u["dbg"] = {"g_out": g, "ga2": ga2, "gt": gt, "ga1": ga1, "g_in": g_in}
-            fuse = self.fuse_stats
-            # CU sharing (set_cu_share): each weight gradient is issued AFTER the data gradient of its conv and sized
-            # for 256 - n CUs, and the BatchNorm-backward pass that follows on this stream is confined to n CUs, so
-            # the HBM-bound pass and the MFMA-bound kernel run at the same time on disjoint CUs.  In its split form
-            # the BatchNorm-backward sums move out of the data gradient's epilogue (which reads the BatchNorm input in
-            # an HBM burst while the matrix pipes wait) into the CU-confined pass beside the weight gradient.
-            share = self._cu_share is not None and fuse and (two_streams or self.debug_share_serial)
-            split = share and self._share_split[0]
-            fused_here = bool(split and self.share_fused_hw and ho * wo >= self.share_fused_hw and not seg)
-            if fused_here:
-                split = False
-            split_us = self._split_us(ho * wo, B)
-            if self._cu_share is not None and self._share_split[0] and fuse and not share:
-                # one-stream mode (profiling passes, bench.py's roofline pass) of the split schedule: the same MFMA
-                # kernels as the timed step -- data gradients with their plain epilogue -- and the BatchNorm sums in a
-                # pass of their own, back to back on all CUs
-                fuse = False
-            if split:
-                u["conv2"].backward_data(g, ga2)
-                n2 = self._share_pair(u["conv2"], a2, g, B * ho * wo * cout, self.share_bn2_tensors, split_us)
-                u["bn2"].backward_cus(ga2, t, gt, n2)
-                if self._share_join:
-                    self.join_side_stream()
-            elif fuse:   # the dgrad epilogue also produces bn2's backward sums (ga2 is not re-read for them)
-                if not share:
-                    u["conv2"].backward_weight(a2, g)
-                u["conv2"].backward_data(g, ga2, bn=u["bn2"], bn_x=t, partials=self.partials(t))
-                n2 = self._share_pair(u["conv2"], a2, g, B * ho * wo * cout, 3,
-                                      self.share_fused_target_us if fused_here else None) if share else 0
-                u["bn2"].backward_fused(ga2, t, gt, self.partials(t), cus=n2)
-                if share and self._share_join:
-                    # The next data gradient is one persistent block per CU with a fixed share of the tiles: blocks
-                    # that found their CU still held by the weight gradient would start late and finish late, and
-                    # the delay would push the next weight gradient under the next data gradient, and so on (measured:
-                    # 19.1 -> 26 ms per step with the passes slightly too fast for the weight gradients).  Waiting
-                    # here makes an unbalanced pair cost max(pass, weight gradient), never more.
-                    self.join_side_stream()
+            self._conv2_backward(u, form, share, g, a2, t, ga2, gt)
+            if u["seg"]:
+                self._seg_conv1_backward(u, form, g, a1, gt, ga1, g_in)
             else:
-                u["conv2"].backward_weight(a2, g)
-                u["conv2"].backward_data(g, ga2)
-                u["bn2"].backward(ga2, None, t, gt, relu=True)   # mask recomputed from t: a2 not re-read
-            if split and u["idconv"] is None:
-                x_in = u["x_in"]
-                u["conv1"].backward_data(gt, ga1)
-                n1 = self._share_pair(u["conv1"], a1, gt, B * hi * wi * cin, self.share_bn1_tensors, split_us)
-                u["bn1"].backward_cus(ga1, x_in, g_in, n1, gx_add=g)
-                g, h, w = g_in, hi, wi
-                continue
-            if fuse and u["idconv"] is None:
-                x_in = u["x_in"]
-                if not share:
-                    u["conv1"].backward_weight(a1, gt)
-                u["conv1"].backward_data(gt, ga1, bn=u["bn1"], bn_x=x_in, partials=self.partials(x_in))
-                n1 = self._share_pair(u["conv1"], a1, gt, B * hi * wi * cin, 4,
-                                      self.share_fused_target_us if fused_here else None) if share else 0
-                u["bn1"].backward_fused(ga1, x_in, g_in, self.partials(x_in), gx_add=g, cus=n1)
-                g, h, w = g_in, hi, wi
-                continue
-            if seg:
-                # conv1's and the shortcut's data gradients in one launch (strided: the four parity classes, the
-                # shortcut's gradient one more term of the even/even class); weight gradients read the same a1
-                x_in = u["x_in"]
-                if split and self.seg_share and (s == 2 or self.seg_share == "all"):
-                    # the CU-sharing order of the dense units: data gradient on the whole chip, then conv1's weight
-                    # gradient sized for 256 - n CUs beside bn1's backward on n (the unit's input gradient is bn1's alone:
-                    # conv1 and the shortcut both read relu(bn1(x)))
-                    if self.seg_join == "all" or (self.seg_join == "small" and ho * wo <= 64):
-                        # conv2's weight gradient outlasts the short BatchNorm pass it was paired with: the one-block-per-CU
-                        # data gradient that follows would find most CUs held and take as long as both
-                        self.join_side_stream()
-                    self._seg_dgrad(u, B, hi, wi)([gt, g], ga1)
-                    desc = u["conv1"].s2d_plan(B, hi, wi)[1] if s == 2 else u["conv1"].plan(B, hi, wi)[3]
-                    gbps, _, lo, hi_cus = self._cu_share
-                    budget, n1 = ops.plan_cu_share(desc, B * hi * wi * cin, self.share_bn2_tensors, gbps, split_us, lo, hi_cus)
-                    if s == 2:
-                        u["conv1"].backward_weight_s2d(a1, gt, hi, wi, cu_budget=budget)
-                        u["idconv"].backward_weight_s2d(a1, g, hi, wi)
-                    else:
-                        u["conv1"].backward_weight(a1, gt, cu_budget=budget)
-                        u["idconv"].backward_weight(a1, g)
-                    u["bn1"].backward_cus(ga1, x_in, g_in, n1)
-                else:
-                    if s == 2:
-                        u["conv1"].backward_weight_s2d(a1, gt, hi, wi)
-                        u["idconv"].backward_weight_s2d(a1, g, hi, wi)
-                    else:
-                        u["conv1"].backward_weight(a1, gt)
-                        u["idconv"].backward_weight(a1, g)
-                    self._seg_dgrad(u, B, hi, wi)([gt, g], ga1)
-                    u["bn1"].backward(ga1, None, x_in, g_in, relu=True)
-                g, h, w = g_in, hi, wi
-                if comm is not None and u["key"] in ("s3u1", "s2u1"):
-                    self.join_side_stream()
-                    comm.reduce_range(st.grad, *buckets[0 if u["key"] == "s3u1" else 1])
-                    self._reserve_for(comm)
-                continue
-            u["conv1"].backward_weight(a1, gt)
-            u["conv1"].backward_data(gt, ga1)
+                self._conv1_backward(u, form, share, g, a1, gt, ga1, g_in)
+            g, h, w = g_in, hi, wi
+        ops.stem_wgrad(self._img, g, st.g("features.init_block.weight"), self.stem_c)
+        self._end_backward(comm)
+
+    def _backward_form(self):
+        """(form, share) of this backward's units.  share: each weight gradient is issued AFTER the data gradient of its
+        conv and sized for 256 - n CUs, and the BatchNorm-backward pass that follows on the main stream is confined to n
+        CUs, so the HBM-bound pass and the MFMA-bound kernel run at the same time on disjoint CUs (set_cu_share).  form:
+          "split"  shared, and the BatchNorm-backward sums move out of the data gradient's epilogue (which reads the
+                   BatchNorm input in an HBM burst while the matrix pipes wait) into the confined pass;
+          "fused"  the sums come out of the data gradient's epilogue; the elementwise pass is confined when shared;
+          "plain"  data gradients with their plain epilogue, the sums in a pass of their own on all CUs: fuse_stats off,
+                   and the one-stream mode of the split schedule (profiling passes, bench.py's roofline pass: the same
+                   MFMA kernels as the timed step, back to back)."""
+        two_streams = self._side is not None and self._overlap
+        share = self._cu_share is not None and self.fuse_stats and (two_streams or self.debug_share_serial)
+        if share and self._share_split[0]:
+            return "split", True
+        if self.fuse_stats and not (self._cu_share is not None and self._share_split[0]):
+            return "fused", share
+        return "plain", False
+
+    def _conv2_backward(self, u, form, share, g, a2, t, ga2, gt):
+        """conv2 and bn2 of one unit: dL/d(out) `g` -> dL/dt `gt`."""
+        conv, bn = u["conv2"], u["bn2"]
+        B, Hp, Wp, C = gt.shape
+        elements = B * (Hp - 2) * (Wp - 2) * C
+        if form == "split":
+            conv.backward_data(g, ga2)
+            n2 = self._share_pair(conv, a2, g, elements, self.share_bn2_tensors, self._split_us(gt))
+            bn.backward_cus(ga2, t, gt, n2)
+        elif form == "fused":   # the dgrad epilogue also produces bn2's backward sums (ga2 is not re-read for them)
+            if not share:
+                conv.backward_weight(a2, g)
+            conv.backward_data(g, ga2, bn=bn, bn_x=t, partials=self.partials(t))
+            n2 = self._share_pair(conv, a2, g, elements, 3) if share else 0
+            bn.backward_fused(ga2, t, gt, self.partials(t), cus=n2)
+        else:
+            conv.backward_weight(a2, g)
+            conv.backward_data(g, ga2)
+            bn.backward(ga2, None, t, gt, relu=True)   # mask recomputed from t: a2 not re-read
+        if share and self._share_join:
+            # The next data gradient is one persistent block per CU with a fixed share of the tiles: blocks that found
+            # their CU still held by the weight gradient would start late and finish late, and the delay would push the
+            # next weight gradient under the next data gradient, and so on (measured: 19.1 -> 26 ms per step with the
+            # passes slightly too fast for the weight gradients).  Waiting here makes an unbalanced pair cost
+            # max(pass, weight gradient), never more.
+            self.join_side_stream()
+
+    def _conv1_backward(self, u, form, share, g, a1, gt, ga1, g_in):
+        """conv1, the shortcut conv (if any) and bn1 of a unit on the dense kernels: dL/dt `gt` and dL/d(out) `g` ->
+        dL/d(x_in) `g_in`.  The shared and fused forms are for units without a shortcut conv."""
+        conv, bn, x_in = u["conv1"], u["bn1"], u["x_in"]
+        B, Hp, Wp, C = ga1.shape
+        if u["idconv"] is None and form == "split":
+            conv.backward_data(gt, ga1)
+            n1 = self._share_pair(conv, a1, gt, B * (Hp - 2) * (Wp - 2) * C, self.share_bn1_tensors, self._split_us(gt))
+            bn.backward_cus(ga1, x_in, g_in, n1, gx_add=g)
+        elif u["idconv"] is None and form == "fused":
+            if not share:
+                conv.backward_weight(a1, gt)
+            conv.backward_data(gt, ga1, bn=bn, bn_x=x_in, partials=self.partials(x_in))
+            n1 = self._share_pair(conv, a1, gt, B * (Hp - 2) * (Wp - 2) * C, 4) if share else 0
+            bn.backward_fused(ga1, x_in, g_in, self.partials(x_in), gx_add=g, cus=n1)
+        else:
+            conv.backward_weight(a1, gt)
+            conv.backward_data(gt, ga1)
             if u["idconv"] is not None:
                 u["idconv"].backward_weight(a1, g)
                 u["idconv"].backward_data(g, ga1, accumulate=True)
-                u["bn1"].backward(ga1, None, u["x_in"], g_in, relu=True)
+                bn.backward(ga1, None, x_in, g_in, relu=True)
             else:
-                u["bn1"].backward(ga1, None, u["x_in"], g_in, relu=True, gx_add=g)
-            g, h, w = g_in, hi, wi
-            if comm is not None and u["key"] in ("s3u1", "s2u1"):
-                self.join_side_stream()
-                comm.reduce_range(st.grad, *buckets[0 if u["key"] == "s3u1" else 1])
-                self._reserve_for(comm)
-        ops.stem_wgrad(self._img, g, st.g("features.init_block.weight"), self.stem_c)
-        self.join_side_stream()      # every gradient is complete on the caller's stream when backward returns
-        if comm is not None:
-            comm.reduce_range(st.grad, *buckets[2])
-            comm.finish(st.grad)
-            self._reserve_for(None)
+                bn.backward(ga1, None, x_in, g_in, relu=True, gx_add=g)
 
+    def _seg_conv1_backward(self, u, form, g, a1, gt, ga1, g_in):
+        """conv1, shortcut and bn1 of a slice-list unit: the two data gradients in one launch (strided: the four parity
+        classes, the shortcut's gradient one more term of the even/even class); both weight gradients read the same a1."""
+        c1, ci, bn, x_in, s = u["conv1"], u["idconv"], u["bn1"], u["x_in"], u["stride"]
+        B, Hp, Wp, C = ga1.shape
+        hi, wi = Hp - 2, Wp - 2
+        if form == "split" and s == 2:
+            # the CU-sharing order of the dense units: data gradient on the whole chip, then conv1's weight gradient
+            # sized for 256 - n CUs beside bn1's backward on n (the unit's input gradient is bn1's alone: conv1 and the
+            # shortcut both read relu(bn1(x)))
+            self._seg_dgrad(u, B, hi, wi)([gt, g], ga1)
+            gbps, _, lo, hi_cus = self._cu_share
+            budget, n1 = ops.plan_cu_share(c1.s2d_plan(B, hi, wi)[1], B * hi * wi * C, self.share_bn2_tensors, gbps,
+                                           self._split_us(gt), lo, hi_cus)
+            c1.backward_weight_s2d(a1, gt, hi, wi, cu_budget=budget)
+            ci.backward_weight_s2d(a1, g, hi, wi)
+            bn.backward_cus(ga1, x_in, g_in, n1)
+            return
+        if s == 2:
+            c1.backward_weight_s2d(a1, gt, hi, wi)
+            ci.backward_weight_s2d(a1, g, hi, wi)
+        else:
+            c1.backward_weight(a1, gt)
+            ci.backward_weight(a1, g)
+        self._seg_dgrad(u, B, hi, wi)([gt, g], ga1)
+        bn.backward(ga1, None, x_in, g_in, relu=True)
     # ------------------------------------------------------------------ reference-named views
     def extra_param_views(self, buf):
         return {
@@ -1286,14 +1306,14 @@ class ResNetEngine(_Engine):
         l2 = ent["layer2.0.conv1.weight"][0]
         return [(l3, self.store.grad.numel()), (l2, l3), (0, l2)]
 
+    bucket_units = ("l3b0", "l2b0")
+
     classifier_names = ("linear.weight", "linear.bias")
 
     def forward(self, img, training=None, head=True):
         training = self.training if training is None else training
-        if img.dtype != torch.float32 or not img.is_contiguous():
-            img = img.float().contiguous()
+        img = self._input(img)
         B, _, H, W = img.shape
-        self._img, self._B = img, B
         t0 = self.buf("t0", B, H, W, 64)
         x = self.buf("a0", B, H, W, 64)
         ops.stem_conv(img, self.store.p("conv1.weight"), t0, 64)
@@ -1340,52 +1360,27 @@ class ResNetEngine(_Engine):
             blk["x_in"] = x
             x, h, w = out, ho, wo
         self._x_last, self._hw = x, (h, w)
-        self._pooled = self._tensor("pooled", (B, self.feat_c))
-        ops.bn_relu_pool(x, self._id_mean, self._id_rstd, self._id_gamma, self._id_beta, self._pooled)
-        if not head:
-            return self._pooled
-        z = self._tensor("z", (B, self.num_classes))
-        ops.linear_fwd(self._pooled, self.store.p("linear.weight"), self.store.p("linear.bias"), z)
-        return z
+        return self._pool_head(x, self._id_mean, self._id_rstd, self._id_gamma, self._id_beta, head)
 
     def backward(self, gz, comm=None, gpooled=None):
-        self._grad_is_zero = False   # this call accumulates into the gradient buffer
-        B = self._B
-        self.join_side_stream()      # dgrad weight copies (built on the second stream after the last update)
-        st = self.store
-        buckets = self.grad_buckets() if comm is not None else None
-        if gpooled is not None:      # after forward(head=False): the fused head kernel did the classifier's backward
-            gpool = gpooled
-        else:
-            gz = gz.contiguous()
-            gpool = self._tensor("gpool", (B, self.feat_c))
-            ops.linear_bwd(self._pooled, st.p("linear.weight"), gz, gpool, st.g("linear.weight"), st.g("linear.bias"))
+        self._begin_backward(comm)
+        B, st = self._B, self.store
+        gpool = self._head_backward(gz, gpooled)
         h, w = self._hw
         g = self.buf(f"g_out{self.feat_c}", B, h, w, self.feat_c)
         # plain avg-pool backward: identity BN with zero batch sums (the x>0 mask it applies is the
         # same mask the following ReLU backward applies anyway)
         ops.pool_bn_bwd_apply(gpool, self._x_last, self._id_mean, self._id_rstd, self._id_gamma, self._id_beta,
                               self._id_dsum, g)
-        toggle, n_blk, side_mark = 0, 0, None
         two_streams = self._side is not None and self._overlap
-        if two_streams:
-            self._side.wait_stream(torch.cuda.current_stream(self.device))
-        for blk in reversed(self.blocks):
-            # Shared gradient buffers vs weight gradients still running on the second stream: as in WRNEngine.backward,
-            # wait for what the side stream had been given one block ago, and alternate the buffers a weight gradient
-            # reads (gt2 / gt1 / gts) between consecutive blocks, so that the block in flight never overwrites them.
-            if two_streams:
-                main = torch.cuda.current_stream(self.device)
-                if side_mark is not None:
-                    main.wait_event(side_mark)
-                side_mark = torch.cuda.Event()
-                side_mark.record(self._side)
+        for i, blk in self._units_backward(self.blocks, comm):
+            # the buffers a weight gradient reads (gt2 / gt1 / gts) alternate between consecutive blocks, and so does
+            # the block's input gradient: the block in flight never overwrites what the previous one's may be reading
             k, s, cin, cout = blk["key"], blk["stride"], blk["cin"], blk["cout"]
             ho, wo = h, w
             hi, wi = ho * s, wo * s
             tag = ("@" + k) if self.debug_keep else ""
-            par = n_blk & 1
-            n_blk += 1
+            par = i & 1
             t1 = self.buf(k + ".t1", B, ho, wo, cout)
             a1 = self.buf(k + ".a1", B, ho, wo, cout)
             t2 = self.buf(k + ".t2", B, ho, wo, cout)
@@ -1393,8 +1388,7 @@ class ResNetEngine(_Engine):
             gt2 = self.buf(f"gt2_{cout}_{par}{tag}", B, ho, wo, cout)
             ga1 = self.buf(f"ga1_{cout}{tag}", B, ho, wo, cout)
             gt1 = self.buf(f"gt1_{cout}_{par}{tag}", B, ho, wo, cout)
-            toggle ^= 1
-            g_in = self.buf(f"g_in{cin}_{hi}_{toggle}{tag}", B, hi, wi, cin)
+            g_in = self.buf(f"g_in{cin}_{hi}_{par ^ 1}{tag}", B, hi, wi, cin)
             x_in = blk["x_in"]
             if blk["sconv"] is not None:
                 gsc = self.buf(f"gsc_{cout}{tag}", B, ho, wo, cout)
@@ -1437,18 +1431,10 @@ class ResNetEngine(_Engine):
                 blk["conv1"].backward_data(gt1, g_in, accumulate=True)
             blk["dbg"] = {"g_out": g, "g_in": g_in}
             g, h, w = g_in, hi, wi
-            if comm is not None and k in ("l3b0", "l2b0"):
-                self.join_side_stream()
-                comm.reduce_range(st.grad, *buckets[0 if k == "l3b0" else 1])
-                self._reserve_for(comm)
         gt0 = self.buf("gt0", B, h, w, 64)
         self.bn0.backward(g, None, self.buf("t0", B, h, w, 64), gt0, relu=True)
         ops.stem_wgrad(self._img, gt0, st.g("conv1.weight"), 64)
-        self.join_side_stream()
-        if comm is not None:
-            comm.reduce_range(st.grad, *buckets[2])
-            comm.finish(st.grad)
-            self._reserve_for(None)
+        self._end_backward(comm)
 
 
 def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5e-4, comm=None, fused_head=True,
@@ -1534,7 +1520,7 @@ class GraphedStep:
         self.targets.copy_(targets, non_blocking=True)
         # the captured step holds no gradient fill when it was captured after a step whose SGD pass left the buffer
         # zeroed (zero_grad() was free then): anything eager that accumulated since must be cleared here, not summed in
-        if not getattr(self.engine, "_grad_is_zero", False):
+        if not self.engine._grad_is_zero:
             self.engine.store.zero_grad()
         self.graph.replay()
         self.engine._grad_is_zero = True     # the replayed SGD pass zeroed it again

@@ -43,6 +43,7 @@ class DepthwiseConv:
             v[:, :c_real].uniform_(-bound, bound, generator=gen)
 
         store.add(name, (k * k, self.C), init)
+        self.side_stream = None     # the engine's second stream for weight gradients, or None: the caller's
 
     def logical(self, buf):
         v = self.store._view(buf, self.name).view(self.k, self.k, self.C)
@@ -54,20 +55,18 @@ class DepthwiseConv:
     def backward_data(self, gy, gx):
         ops.dwconv_bwd_data(gy, self.store.p(self.name), gx, self.k, self.stride)
 
-    def backward_weight(self, x, gy, also=None):
+    def backward_weight(self, x, gy, also):
         """also: a further launch that only feeds the optimizer (the SE block's parameter gradients), issued behind the
         weight gradient on the same stream -- one cross-stream dependency for both."""
-        side = getattr(self, "side_stream", None)
+        side = self.side_stream
         if side is None:
             ops.dwconv_bwd_weight(x, gy, self.store.g(self.name), self.k, self.stride)
-            if also is not None:
-                also()
+            also()
             return
         side.wait_stream(torch.cuda.current_stream(x.device))     # second stream: see WRNEngine
         with torch.cuda.stream(side):
             ops.dwconv_bwd_weight(x, gy, self.store.g(self.name), self.k, self.stride)
-            if also is not None:
-                also()
+            also()
 
 
 class SqueezeExcite:
@@ -96,17 +95,15 @@ class SqueezeExcite:
         ops.se_gate_fwd(pooled, p(self.name + ".conv1.weight"), p(self.name + ".conv1.bias"),
                         p(self.name + ".conv2.weight"), p(self.name + ".conv2.bias"), pre1, gate, self.c_real)
 
-    def backward(self, dgate, gate, pre1, pooled, dpre2, dpre1, gpool, defer_params=False):
-        """defer_params: the data part only; returns the launch of the parameter gradients for the caller to place (they
-        read dpre2 / dpre1 / pre1 / pooled and feed nothing but the optimizer)."""
+    def backward(self, dgate, gate, pre1, pooled, dpre2, dpre1, gpool):
+        """The data part only; returns the launch of the parameter gradients for the caller to place (they read
+        dpre2 / dpre1 / pre1 / pooled and feed nothing but the optimizer)."""
         p, g = self.store.p, self.store.g
         grads = (g(self.name + ".conv1.weight"), g(self.name + ".conv1.bias"), g(self.name + ".conv2.weight"),
                  g(self.name + ".conv2.bias"))
         ops.se_gate_bwd(dgate, gate, pre1, pooled, p(self.name + ".conv1.weight"), p(self.name + ".conv2.weight"),
-                        dpre2, dpre1, gpool, *((None,) * 4 if defer_params else grads), self.c_real)
-        if defer_params:
-            return lambda: ops.se_param_grad(dpre2, dpre1, pre1, pooled, *grads, self.c_real)
-        return None
+                        dpre2, dpre1, gpool, None, None, None, None, self.c_real)
+        return lambda: ops.se_param_grad(dpre2, dpre1, pre1, pooled, *grads, self.c_real)
 
 
 class EfficientNetEngine(_Engine):
@@ -157,8 +154,7 @@ class EfficientNetEngine(_Engine):
         self.finalize()
         self._step = 0
         self.dropout_seed = seed
-        self.defer_se_params = True   # SE parameter gradients behind the depthwise weight gradient on the second stream
-        self.fuse_se_bwd = True   # SE backward: dL/dgate and bn2's backward sums from ONE pass over (gd, d_raw)
+        self._se_sums_dirty = set()    # ids of the one-pass SE sums a backward has summed into and not yet re-zeroed
         self._side = side_stream(self.device)     # weight gradients on the process's second stream (see WRNEngine)
         for c in self.convs + self.dws:
             c.side_stream = self._side
@@ -185,6 +181,8 @@ class EfficientNetEngine(_Engine):
         s5 = ent["features.stage5.unit1.conv1.conv.weight"][0]
         return [(s5, self.store.grad.numel()), (s3, s5), (0, s3)]
 
+    bucket_units = ("s5u1", "s3u1")
+
     def _vec(self, key, B, n):
         return self._tensor(key, (B, n))
 
@@ -197,8 +195,8 @@ class EfficientNetEngine(_Engine):
         the unit's input, expanded (before the depthwise conv), depthwise-output and output tensors:
           forward   expand conv X + E | BatchNorm + swish 2E | depthwise E + D | squeeze D | scale 2D | project D + O |
                     BatchNorm (+ skip) 2O (+ X)
-          backward  bn3 5O | project weight gradient D + O, data gradient O + D | dL/dgate + bn2's sums 2D (one pass since round
-                    6; fuse_se_bwd off: 2D + 2D) | bn2 + SE elementwise 3D | depthwise
+          backward  bn3 5O | project weight gradient D + O, data gradient O + D | dL/dgate + bn2's sums 2D (one pass) |
+                    bn2 + SE elementwise 3D | depthwise
                     weight gradient E + D, data gradient + bn1 sums D + 2E | bn1 elementwise 3E | expand weight gradient
                     X + E, data gradient E + X (+ X when it accumulates onto the skip gradient)"""
         h = w = size // 2
@@ -206,7 +204,6 @@ class EfficientNetEngine(_Engine):
         stem = e(h, w, self.stem_c)
         total = 12 * B * size * size + 2 * stem + 2 * stem      # image in, stem conv out, BatchNorm + swish (read + write)
         total += 5 * stem + 12 * B * size * size + stem         # backward of that BatchNorm, stem weight gradient
-        se = 2 if self.fuse_se_bwd else 4                      # tensor reads of the reduction pass(es) over (gd, d_raw)
         for u in self.units:
             s = u["stride"]
             ho, wo = h // s, w // s
@@ -215,10 +212,10 @@ class EfficientNetEngine(_Engine):
             res = X if u["residual"] else 0
             if u["conv1"] is not None:
                 fwd = (X + E) + 2 * E + (E + D) + D + 2 * D + (D + O) + 2 * O + res
-                bwd = 5 * O + (D + O) + (O + D) + se * D + 3 * D + (E + D) + (D + 2 * E) + 3 * E + (X + E) + (E + X) + res
+                bwd = 5 * O + (D + O) + (O + D) + 2 * D + 3 * D + (E + D) + (D + 2 * E) + 3 * E + (X + E) + (E + X) + res
             else:       # stage 1: depthwise on the unit's input, no expand conv
                 fwd = (X + D) + D + 2 * D + (D + O) + 2 * O + res
-                bwd = 5 * O + (D + O) + (O + D) + se * D + 3 * D + (X + D) + (D + X)
+                bwd = 5 * O + (D + O) + (O + D) + 2 * D + 3 * D + (X + D) + (D + X)
             total += fwd + bwd
             h, w = ho, wo
         F, L = e(h, w, self.feat_c), e(h, w, self.units[-1]["cout"])
@@ -229,12 +226,10 @@ class EfficientNetEngine(_Engine):
     # ------------------------------------------------------------------ forward
     def forward(self, img, training=None):
         training = self.training if training is None else training
-        if img.dtype != torch.float32 or not img.is_contiguous():
-            img = img.float().contiguous()
-        B, _, H, W = img.shape
-        if H % 32 or W % 32:
+        if img.shape[2] % 32 or img.shape[3] % 32:
             raise ValueError("EfficientNet input size must be a multiple of 32")
-        self._img, self._B = img, B
+        img = self._input(img)
+        B, _, H, W = img.shape
         fuse = training and self.fuse_stats
         h, w = H // 2, W // 2
         c0 = _pad32(self.stem_c)
@@ -312,11 +307,8 @@ class EfficientNetEngine(_Engine):
 
     # ------------------------------------------------------------------ backward
     def backward(self, gz, comm=None):
-        self._grad_is_zero = False   # this call accumulates into the gradient buffer
-        B = self._B
-        self.join_side_stream()      # dgrad weight copies (built on the second stream after the last update)
-        st = self.store
-        buckets = self.grad_buckets() if comm is not None else None
+        self._begin_backward(comm)
+        B, st = self._B, self.store
         gz = gz.contiguous()
         gfeat = self._vec("gfeat", B, self.feat_c)
         ops.linear_bwd(self._feat, st.p("output.fc.weight"), gz, gfeat, st.g("output.fc.weight"),
@@ -335,24 +327,11 @@ class EfficientNetEngine(_Engine):
         self.final_conv.backward_weight(self._x_last, gf)
         g = self.buf(f"g_{self._x_last.shape[3]}_{h}", B, h, w, self._x_last.shape[3])
         self.final_conv.backward_data(gf, g)
-        two_streams = self._side is not None and self._overlap
-        n_unit, side_mark = 0, None
-        if two_streams:
-            self._side.wait_stream(torch.cuda.current_stream(self.device))
-        for u in reversed(self.units):
-            # Gradient buffers are shared between units and the weight gradients run on the second stream: as in
-            # WRNEngine.backward the main stream waits for what the side stream had been given ONE UNIT AGO, and the
-            # three buffers a weight gradient reads (gp, gd, ge) alternate between consecutive units, so that a unit
+        for i, u in self._units_backward(self.units, comm):
+            # the three buffers a weight gradient reads (gp, gd, ge) alternate between consecutive units, so that a unit
             # never overwrites what the previous unit's weight gradients may still be reading (checked bit for bit
-            # against one stream with private buffers: tests/test_effnet_gpu.py).
-            if two_streams:
-                main = torch.cuda.current_stream(self.device)
-                if side_mark is not None:
-                    main.wait_event(side_mark)
-                side_mark = torch.cuda.Event()
-                side_mark.record(self._side)
-            par = n_unit & 1
-            n_unit += 1
+            # against one stream with private buffers: tests/test_effnet_gpu.py)
+            par = i & 1
             k, s = u["key"], u["stride"]
             cin, mid, cout = _pad32(u["cin"]), _pad32(u["mid"]), _pad32(u["cout"])
             ho, wo = h, w
@@ -372,15 +351,14 @@ class EfficientNetEngine(_Engine):
             bn = u["bn2"]
             gpool = self._vec(f"gpool{tag}", B, mid)
             gate = self._vec(k + ".gate", B, mid)
-            one_pass = self.fuse_se_bwd and gd.dtype == torch.bfloat16 and not ops.is_deterministic()
+            one_pass = gd.dtype == torch.bfloat16 and not ops.is_deterministic()
             if one_pass:
                 # dL/dgate AND what bn2's backward sums are linear in, in one pass over (gd, d_raw): the reduction pass
                 # of bn_act_bwd (a second read of both tensors) becomes a [B, C]-sized fold once gpool exists
                 sums = self._zeroed(f"se_sums{tag}", (5, B, mid))     # zero on entry, re-zeroed by its last reader
-                dirty = self.__dict__.setdefault("_se_sums_dirty", set())
-                if id(sums) in dirty:        # a backward that stopped between the two calls (an exception, an interrupt) left
-                    sums.zero_()             # its sums behind: never accumulate on top of them
-                dirty.add(id(sums))
+                if id(sums) in self._se_sums_dirty:   # a backward that stopped between the two calls (an exception, an
+                    sums.zero_()                      # interrupt) left its sums behind: never accumulate on top of them
+                self._se_sums_dirty.add(id(sums))
                 ops.bn_act_se_sums(gd, d_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, sums, act=ACT)
                 dgate = sums[0]
             else:
@@ -390,12 +368,11 @@ class EfficientNetEngine(_Engine):
             # workspaces alternate between consecutive units like the gradient buffers)
             se_params = u["se"].backward(dgate, gate, self._vec(k + ".pre1", B, u["se"].mid),
                                          self._vec(k + ".pooled", B, mid), self._vec(f"dpre2_{par}{tag}", B, mid),
-                                         self._vec(f"dpre1_{par}{tag}", B, u["se"].mid), gpool,
-                                         defer_params=self.defer_se_params)
+                                         self._vec(f"dpre1_{par}{tag}", B, u["se"].mid), gpool)
             if one_pass:
                 ops.bn_act_se_bwd_apply(gd, gate, gpool, sums, d_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, bn.dsum,
                                         st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), gd, act=ACT)
-                dirty.discard(id(sums))
+                self._se_sums_dirty.discard(id(sums))
             else:
                 ops.bn_act_bwd(gd, d_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
                                st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), gd, act=ACT, gate=gate, gpool=gpool)
@@ -406,7 +383,7 @@ class EfficientNetEngine(_Engine):
                 ge = self.buf(f"ge_{mid}_{hi}_{par}{tag}", B, hi, wi, mid)
                 u["dw"].backward_weight(e_act, gd, also=se_params)
                 bn = u["bn1"]
-                if u["dw"].stride == 1 and self.fuse_dw_bn_bwd:
+                if u["dw"].stride == 1:
                     # the depthwise data gradient's epilogue leaves bn1's backward sums in the slots: no reduction
                     # pass over ge and e_raw (5.5 % of a step), e_raw is read once there
                     ops.dwconv_bwd_data_bn(gd, st.p(u["dw"].name), ge, u["dw"].k, e_raw, bn.mean, bn.rstd, bn.gamma,
@@ -432,17 +409,9 @@ class EfficientNetEngine(_Engine):
                 u["dw"].backward_data(gd, g_in)
             u["dbg"] = {"g_out": g, "g_in": g_in, "gp": gp, "gd": gd}
             g, h, w = g_in, hi, wi
-            if comm is not None and k in ("s5u1", "s3u1"):
-                self.join_side_stream()
-                comm.reduce_range(st.grad, *buckets[0 if k == "s5u1" else 1])
-                self._reserve_for(comm)
         bn = self.bn0
         t0 = self.buf("t0", B, h, w, _pad32(self.stem_c))
         ops.bn_act_bwd(g, t0, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
                        st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), g, act=ACT)
         ops.stem_wgrad(self._img, g, st.g("features.init_block.conv.conv.weight"), self.stem_c, stride=2)
-        self.join_side_stream()
-        if comm is not None:
-            comm.reduce_range(st.grad, *buckets[2])
-            comm.finish(st.grad)
-            self._reserve_for(None)
+        self._end_backward(comm)

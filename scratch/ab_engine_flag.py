@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Same-box A/B of one engine attribute on the bench workload (WRN-28-10, 512 images): alternating rounds of ms/step.
-usage: ab_engine_flag.py <attribute> [--steps 30] [--rounds 3]     e.g. ab_engine_flag.py debug_join_each_unit"""
+usage: ab_engine_flag.py <attribute> [--steps 30] [--rounds 3]     e.g. ab_engine_flag.py fuse_stats"""
 import argparse, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -545,7 +545,7 @@ def test_hipgraph_captures_the_wrn_step_with_cu_sharing_and_lagged_events():
                 cg.capture_end()
 
 
-def test_hipgraph_replays_start_the_confined_bn_backward_from_zeroed_slots():
+def test_hipgraph_replays_start_the_confined_bn_backward_from_zeroed_slot_pairs():
     """nbdt_bn_bwd_cus sums into `slots`, which must be zero on entry, and leaves it dirty; the engine
     alternates two buffers per channel count, and a WRN step makes an ODD number of calls per channel count (2n-1), so a
     captured graph -- pointers baked in -- used to start replay k+1 on the buffer replay k left dirty: dsum / dgamma /
@@ -559,7 +559,6 @@ def test_hipgraph_replays_start_the_confined_bn_backward_from_zeroed_slots():
     graphed = E.WRNEngine(num_classes=10, blocks=16, width_factor=4, device=DEV, seed=5)
     for e in (eager, graphed):
         e.set_cu_share(47.0, calibrate=False)
-    assert graphed.fuse_bn_fold                         # the two-launch form with the slot pairs is the default
     step = E.GraphedStep(graphed, crit, xs[0], ys[0], lr=0.0, momentum=0.0, weight_decay=0.0, warmup=1)
     assert getattr(graphed, "_slot_pairs", None), "the captured step did not use the slot pairs"
     worst = 0.0
