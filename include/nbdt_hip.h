@@ -89,6 +89,15 @@ int nbdt_get_wgrad_store_epilogue(void);
  * (same tiles, other block -> tile assignment).  Replaces nothing in the reference (DataParallel, main.py:160-162). */
 int nbdt_set_reserved_cus(int32_t n);
 int nbdt_get_reserved_cus(void);
+/* Nontemporal-load threshold of the streaming BatchNorm passes (process-wide, default 96 MiB = 100663296 bytes;
+ * nbdt_version() >= 109).  nbdt_bn_apply, nbdt_bn_bwd_apply_cus, nbdt_bn_bwd_reduce_cus and nbdt_bn_bwd_cus read their
+ * operands with nontemporal loads when the padded tensor, B * (H+2) * (W+2) * C * 2 bytes, is at least this many bytes,
+ * and with plain loads otherwise.  The two forms compute the same bits; only what the caches keep differs.  Must be
+ * >= 0; 0 makes every launch nontemporal.  nbdt_debug_last_stream_nt: what the calling thread's last launch of those
+ * four chose (1 nontemporal, 0 plain, -1 none yet) -- for tests that must know which instantiation they ran. */
+int nbdt_set_stream_nt_min_bytes(int64_t bytes);
+int64_t nbdt_get_stream_nt_min_bytes(void);
+int nbdt_debug_last_stream_nt(void);
 /* number of visible HIP devices (0 => the product path must refuse to run) */
 int nbdt_device_count(void);
 
@@ -244,7 +253,7 @@ int nbdt_conv_igemm_multi(const nbdt_conv_desc* descs, int32_t n, const void* in
  * owns the device-side step tables (which LDS-DMA piece goes out in which K step); weights are re-tiled into DMA
  * order by nbdt_conv_seg_tile_weights whenever they change. */
 typedef struct nbdt_conv_seg_slice {
-  int32_t tensor;               /* input tensor index 0..3 */
+  int32_t tensor;               /* input tensor index 0..ntensors-1 */
   int32_t ch0;                  /* first of the slice's 32 channels inside a pixel of that tensor (multiple of 8) */
   int32_t ntaps;                /* 1..9 */
   int32_t tap[9];               /* 3*R + S: input pixel (y + R - 1, x + S - 1) of the launch's pixel grid */
@@ -261,8 +270,8 @@ typedef struct nbdt_conv_seg_desc {
   int32_t B, gh, gw;            /* pixel grid shared by every input tensor ([B][gh+2][gw+2][pix_stride], zero border)
                                    and by the classes' output maps */
   int32_t cout;                 /* multiple of 32; rows of every weight matrix */
-  int32_t ntensors;             /* 1..4 */
-  int32_t pix_stride[4];        /* elements per pixel of each input tensor */
+  int32_t ntensors;             /* 1..2: the kernel reads two input tensors; nbdt_conv_seg_create refuses more */
+  int32_t pix_stride[4];        /* elements per pixel of each input tensor (entries past ntensors unused) */
   int32_t nmatrices;            /* 1..4 */
   int32_t w_row_stride[4];      /* elements per row of each weight matrix ([cout][row_stride] bf16) */
   int32_t nclasses;             /* 1..4 */

@@ -267,7 +267,9 @@ __device__ __forceinline__ u32x4_t ld16_stream(const void* p) {
 #ifndef NBDT_NT_MIN_MB
 #define NBDT_NT_MIN_MB 96
 #endif
-inline bool stream_nt(long long tensor_bytes) { return tensor_bytes >= ((long long)NBDT_NT_MIN_MB << 20); }
+// tensor_bytes >= the process-wide threshold (nbdt_set_stream_nt_min_bytes; default NBDT_NT_MIN_MB MiB); records the
+// choice for nbdt_debug_last_stream_nt (misc.hip)
+bool stream_nt(long long tensor_bytes);
 
 // 16-byte WRITE-THROUGH store (sc1: the line leaves the XCD's L2 as it is written).  Plain stores leave up to 32 MB dirty in
 // the L2s, and the kernel boundary that follows writes them back before the next kernel starts (MI355X_MICROARCH.md,

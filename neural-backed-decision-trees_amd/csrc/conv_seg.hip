@@ -819,7 +819,9 @@ extern "C" int nbdt_conv_seg_create(const nbdt_conv_seg_desc* d, void** plan) {
   NBDT_REQUIRE(d && plan, "null argument");
   NBDT_REQUIRE(d->B > 0 && d->gh > 0 && d->gw > 0, "empty pixel grid");
   NBDT_REQUIRE(d->cout > 0 && d->cout % 32 == 0, "cout must be a multiple of 32");
-  NBDT_REQUIRE(d->ntensors >= 1 && d->ntensors <= 4 && d->nmatrices >= 1 && d->nmatrices <= 4, "1..4 tensors / matrices");
+  // (the kernel reads in[0] / in[1] only: a third tensor would silently be read as the second)
+  NBDT_REQUIRE(d->ntensors >= 1 && d->ntensors <= 2, "ntensors must be 1 or 2 (conv_seg_kernel reads two input tensors)");
+  NBDT_REQUIRE(d->nmatrices >= 1 && d->nmatrices <= 4, "1..4 weight matrices");
   NBDT_REQUIRE(d->nclasses >= 1 && d->nclasses <= 4, "1..4 classes");
   NBDT_REQUIRE(d->tile == 0 || d->tile == 256 || d->tile == 512, "tile: 0, 256 or 512");
   NBDT_REQUIRE(d->nbuf == 0 || d->nbuf == 2 || d->nbuf == 3, "nbuf: 0, 2 or 3");

@@ -1100,7 +1100,10 @@ extern "C" int nbdt_bn_act_se_bwd_apply(const void* gu, const float* gate, const
                                         const float* gamma, const float* beta, int32_t act, int32_t B, int32_t H,
                                         int32_t W, int32_t C, float* dsum, float* dgamma, float* dbeta, void* gx,
                                         void* stream) {
-  NBDT_REQUIRE(gu && gate && gpool && sums && dsum, "null argument");
+  // every check of bn_act_bwd_impl before the first launch: the finalize kernel consumes and zeroes sums and adds into
+  // dgamma / dbeta, so a call refused after it would leave them changed (and a retry would count them twice)
+  NBDT_REQUIRE(gu && gate && gpool && sums && dsum && x && save_mean && save_rstd && gamma && beta && gx, "null argument");
+  NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
   int rc = check_mb(B, H, W, C);
   if (rc) return rc;
   hipLaunchKernelGGL(mb_se_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, sums, gate, gpool,

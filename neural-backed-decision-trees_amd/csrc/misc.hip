@@ -135,6 +135,23 @@ extern "C" int nbdt_set_wgrad_store_epilogue(int32_t on) {
 extern "C" int nbdt_get_wgrad_store_epilogue(void) { return nbdt::wgrad_store_epilogue() ? 1 : 0; }
 
 namespace nbdt {
+static std::atomic<long long> g_stream_nt_min{(long long)NBDT_NT_MIN_MB << 20};
+static thread_local int g_last_stream_nt = -1;
+bool stream_nt(long long tensor_bytes) {
+  const bool nt = tensor_bytes >= g_stream_nt_min.load(std::memory_order_relaxed);
+  g_last_stream_nt = nt ? 1 : 0;
+  return nt;
+}
+}  // namespace nbdt
+extern "C" int nbdt_set_stream_nt_min_bytes(int64_t bytes) {
+  NBDT_REQUIRE(bytes >= 0, "the nontemporal threshold must be >= 0 bytes");
+  nbdt::g_stream_nt_min.store((long long)bytes, std::memory_order_relaxed);
+  return NBDT_OK;
+}
+extern "C" int64_t nbdt_get_stream_nt_min_bytes(void) { return nbdt::g_stream_nt_min.load(std::memory_order_relaxed); }
+extern "C" int nbdt_debug_last_stream_nt(void) { return nbdt::g_last_stream_nt; }
+
+namespace nbdt {
 static std::atomic<int> g_reserved_cus{0};
 int reserved_cus() { return g_reserved_cus.load(std::memory_order_relaxed); }
 }  // namespace nbdt

@@ -85,6 +85,9 @@ SIGNATURES = {
     "nbdt_probe_mfma_stream": (c_int, [c_int32, c_int32, _P, _P]),
     "nbdt_probe_lds_mfma": (c_int, [c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_get_reserved_cus": (c_int, []),
+    "nbdt_set_stream_nt_min_bytes": (c_int, [c_int64]),
+    "nbdt_get_stream_nt_min_bytes": (c_int64, []),
+    "nbdt_debug_last_stream_nt": (c_int, []),
     "nbdt_tree_create": (c_int, [c_int, c_int, c_int, c_int, _I32P, _I32P, _I32P, _I32P, _I32P, _I32P,
                                  POINTER(c_void_p)]),
     "nbdt_tree_destroy": (c_int, [c_void_p]),

@@ -51,6 +51,21 @@ def reserved_cus():
     return int(lib().nbdt_get_reserved_cus())
 
 
+def set_stream_nt_min_bytes(n):
+    """Tensors of at least n bytes take the nontemporal-load BatchNorm passes (nbdt_set_stream_nt_min_bytes)."""
+    check(lib().nbdt_set_stream_nt_min_bytes(int(n)))
+
+
+def stream_nt_min_bytes():
+    return int(lib().nbdt_get_stream_nt_min_bytes())
+
+
+def last_stream_nt():
+    """Whether the calling thread's last NT-selecting BatchNorm launch took the nontemporal form (None: none yet)."""
+    v = int(lib().nbdt_debug_last_stream_nt())
+    return None if v < 0 else bool(v)
+
+
 def padded(B, H, W, C, device, dtype=torch.bfloat16):
     """Zero-initialised padded NHWC activation buffer: bf16 (the product path), or fp32 for the engines'
     verification-only reference mode (see _ref below)."""

@@ -153,3 +153,21 @@ def test_process_wide_switches_are_host_only():
     assert ops.conv_fwd_desc(8, 8, 8, 64, 64, 3, 1).ksplit == 0
     (d,) = ops.conv_dgrad_descs(8, 8, 8, 64, 64, 3, 1)
     assert d.ksplit == 0 and d.wide_tile == 0 and ops.conv_fwd_desc(8, 8, 8, 64, 64, 3, 1).wide_tile == 1
+
+
+def test_stream_nt_threshold_is_a_host_only_switch():
+    """nbdt_set/get_stream_nt_min_bytes: default 96 MiB as the header states, settable to 0 and to huge values,
+    negative sizes refused and the old value kept; no launch yet on this thread -> the readback says none."""
+    from nbdt import ops
+    assert _C.lib().nbdt_version() >= 109
+    assert ops.stream_nt_min_bytes() == 96 << 20
+    try:
+        for v in (0, 1, 2 ** 62):
+            ops.set_stream_nt_min_bytes(v)
+            assert ops.stream_nt_min_bytes() == v
+        with pytest.raises(_C.NBDTHipError, match="threshold"):
+            ops.set_stream_nt_min_bytes(-1)
+        assert ops.stream_nt_min_bytes() == 2 ** 62
+    finally:
+        ops.set_stream_nt_min_bytes(96 << 20)
+    assert ops.stream_nt_min_bytes() == 96 << 20

@@ -121,3 +121,27 @@ def test_bad_descriptions_are_refused():
                                                 "out": ops._plain_out(8, 8, 32)}], nbuf=2)
     plan = ops.ConvSeg(8, 8, 8, 32, [32], [32], [{"slices": ok, "out": ops._plain_out(8, 8, 32)}])
     assert plan.nsteps == [1] and plan.tile in (256, 512)
+
+
+@pytest.mark.parametrize("ntensors", [3, 4])
+def test_more_than_two_input_tensors_are_refused(ntensors):
+    """conv_seg_kernel reads in[0] and in[1] only: a slice of tensor 2 or 3 would read tensor 1 with tensor 1's stride.
+    nbdt_conv_seg_create refuses such a description with an error that names the limit -- also when every slice
+    uses tensor 0 -- and still takes the same description with two tensors."""
+    strides = [32, 64, 96, 128][:ntensors]
+    for t in (0, ntensors - 1):
+        sl = [(t, 0, [4], 0, [0])]
+        with pytest.raises(ops._C.NBDTHipError, match="ntensors must be 1 or 2"):
+            ops.ConvSeg(8, 8, 8, 32, strides, [32], [{"slices": sl, "out": ops._plain_out(8, 8, 32)}])
+    plan = ops.ConvSeg(8, 8, 8, 32, strides[:2], [32], [{"slices": [(1, 32, [4], 0, [0])], "out": ops._plain_out(8, 8, 32)}])
+    assert plan.nsteps == [1]
+
+
+@pytest.mark.parametrize("B,Hi,Wi,cin,cout,nbuf", [(8, 16, 16, 64, 64, 2), (16, 16, 16, 32, 128, 3), (3, 16, 16, 64, 64, 0)])
+def test_forced_512_pixel_tiles_are_refused_on_8x8_grids(B, Hi, Wi, cin, cout, nbuf):
+    """The halo buffers of a 512-pixel tile do not fit on an 8x8 output grid: a forced tile is an error, never a silent
+    fall-back to half tiles; the automatic choice takes half tiles, and a 16x16 grid takes the forced full tiles."""
+    with pytest.raises(ops._C.NBDTHipError, match="no tile / buffer choice fits"):
+        ops.seg_fwd_s2(B, Hi, Wi, cin, cout, tile=512, nbuf=nbuf)
+    assert ops.seg_fwd_s2(B, Hi, Wi, cin, cout).tile == 256
+    assert ops.seg_fwd_s2(B, 2 * Hi, 2 * Wi, cin, cout, tile=512).tile == 512

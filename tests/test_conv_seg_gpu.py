@@ -12,6 +12,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from nbdt import ops  # noqa: E402
+from nbdt._C import NBDTHipError  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -71,9 +72,10 @@ def test_bn_apply_s2d_is_bn_apply_rearranged():
 
 FWD_CASES = [   # B, Hi, Wi, cin, cout, tile, nbuf
     (4, 16, 16, 64, 64, 0, 0),       # 8x8 out, NT=2
-    (8, 16, 16, 64, 64, 512, 2),     # forced 512-pixel tiles need 3 buffers here: refused below
+    (8, 16, 16, 64, 64, 512, 2),     # 8x8 out, forced 512-pixel tiles: refused below
     (3, 32, 32, 32, 160, 0, 0),      # 16x16 out, NT=5, ragged (768 pixels: one and a half 512 tiles)
-    (16, 16, 16, 32, 128, 512, 3),   # 8x8 out, full tiles, NT=4
+    (16, 16, 16, 32, 128, 512, 3),   # 8x8 out: three halo buffers of a 512-pixel tile do not fit: refused below
+    (4, 32, 32, 32, 128, 512, 3),    # 16x16 out, forced full tiles, NT=4
     (2, 64, 64, 64, 32, 0, 0),       # 32x32 out, NT=1, row tiles
     (5, 8, 8, 96, 160, 256, 3),      # 4x4 out: 16 images per half tile, ragged
 ]
@@ -84,15 +86,12 @@ def test_strided_forward_over_space_to_depth(B, Hi, Wi, cin, cout, tile, nbuf):
     xf, xp = _rand_act(B, Hi, Wi, cin, seed=1)
     w_oihw, wb = _rand_weight(cout, cin, 3, seed=2)
     Ho, Wo = Hi // 2, Wi // 2
-    if (tile, nbuf) == (512, 2):
-        with pytest.raises(Exception):
+    if tile == 512 and Ho * Wo < 256:     # 8x8 output grids: the halo buffers of a 512-pixel tile do not fit
+        with pytest.raises(NBDTHipError, match="no tile / buffer choice fits"):
             ops.seg_fwd_s2(B, Hi, Wi, cin, cout, tile=tile, nbuf=nbuf)
         return
-    try:
-        plan = ops.seg_fwd_s2(B, Hi, Wi, cin, cout, tile=tile, nbuf=nbuf)
-    except Exception:
-        assert tile == 512 and Ho * Wo * 4 > 160     # (three halo buffers of a 512-pixel tile do not fit)
-        pytest.skip("shape does not fit the forced tile")
+    plan = ops.seg_fwd_s2(B, Hi, Wi, cin, cout, tile=tile, nbuf=nbuf)
+    assert tile == 0 or plan.tile == tile
     xs = _s2d(xp, B, Hi, Wi, cin)
     wt = plan.tile_weights([wb])
     out = ops.padded(B, Ho, Wo, cout, DEV)
@@ -297,15 +296,15 @@ def _followed_by_nan(t):
     return buf[:n].view(t.shape)
 
 
-@pytest.mark.parametrize("B,Hi,Wi,cin,cout,tile", [(5, 8, 8, 96, 160, 256), (3, 16, 16, 64, 64, 512), (9, 16, 16, 32, 160, 256)])
+@pytest.mark.parametrize("B,Hi,Wi,cin,cout,tile", [(5, 8, 8, 96, 160, 256), (3, 32, 32, 64, 64, 512), (9, 16, 16, 32, 160, 256)])
 def test_ragged_tiles_never_read_past_the_tensors(B, Hi, Wi, cin, cout, tile):
+    """(3 x 16 x 16 output pixels: one and a half forced 512-pixel tiles.  8x8 output grids cannot take forced 512-pixel
+    tiles at all: tests/test_conv_seg.py asserts that refusal.)"""
     xf, xp = _rand_act(B, Hi, Wi, cin, seed=1)
     w_oihw, wb = _rand_weight(cout, cin, 3, seed=2)
     Ho, Wo = Hi // 2, Wi // 2
-    try:
-        plan = ops.seg_fwd_s2(B, Hi, Wi, cin, cout, tile=tile)
-    except Exception:
-        pytest.skip("shape does not fit the forced tile")
+    plan = ops.seg_fwd_s2(B, Hi, Wi, cin, cout, tile=tile)
+    assert plan.tile == tile
     xs = _followed_by_nan(_s2d(xp, B, Hi, Wi, cin))
     wt = plan.tile_weights([wb])
     out = ops.padded(B, Ho, Wo, cout, DEV)
@@ -319,6 +318,7 @@ def test_ragged_tiles_never_read_past_the_tensors(B, Hi, Wi, cin, cout, tile):
     gf, gp = _rand_act(B, Ho, Wo, cout, seed=4)
     wd = wb.flip(1).permute(2, 1, 0).contiguous()
     dplan = ops.seg_dgrad_s2(B, Hi, Wi, cin, cout, tile=tile)
+    assert dplan.tile == tile
     dwt = dplan.tile_weights([wd])
     gx = ops.padded(B, Hi, Wi, cin, DEV)
     dplan([_followed_by_nan(gp)], dwt, gx)
