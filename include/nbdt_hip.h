@@ -617,6 +617,57 @@ int nbdt_linear_bwd(const float* x, const float* w, const float* gz, int32_t B, 
 int nbdt_sgd_step(float* p, float* g, float* buf, int64_t n, float lr, float momentum,
                   float weight_decay, float grad_scale, void* p_bf16, int32_t zero_grad, void* stream);
 
+/* ------------------------------------------------------------------ device-resident datasets (nbdt_version() >= 110) */
+/* One launch builds a training batch from a dataset that lives in device memory: gather by index, then the reference's
+ * RandomCrop(size, padding) -> RandomHorizontalFlip -> ToTensor -> Normalize (nbdt/data/cifar.py:11-21 pads CIFAR by 4,
+ * nbdt/data/imagenet.py:37-48 pads TinyImagenet200 by 8), written as the fp32 NCHW tensor nbdt_stem_conv reads, with the
+ * gathered targets.  csrc/augment.hip.
+ *
+ * Inputs
+ *   src         the dataset [N,3,H,W] (NCHW), uint8 (src_dtype = NBDT_U8) or fp32 (NBDT_F32)
+ *   labels_src  int64 [N]
+ *   index       int64 [B], device memory: the samples of the batch, repeats allowed
+ *   B, N, H, W  B > 0, N > 0, 1 <= H, W <= 4096; the crop size is always H x W, as in the reference
+ *   pad         0 .. NBDT_AUGMENT_MAX_PAD pixels of padding on every side before the crop
+ *   flip        0 | 1: enables the random horizontal flip of the generator
+ *   mean, std   HOST float[3], copied into the kernel's arguments; uint8 sources only (may be NULL for fp32); std != 0
+ *   fill        HOST float[3], the value of a padded pixel; fp32 sources only (may be NULL for uint8)
+ *   seed, epoch the generator's key
+ *   params_in   optional int8 [B,3] (dy, dx, flip), device memory: when non-NULL it REPLACES the generator (and `flip`).
+ *               The entry validates every host-known argument; these values are device data, so the kernel clamps dy and
+ *               dx to [0, 2*pad] and takes flip as (value != 0): a bad value can never index out of bounds.
+ * Outputs
+ *   out         fp32 [B,3,H,W]
+ *   labels_out  int64 [B]
+ *   params_out  optional int8 [B,3]: the (dy, dx, flip) actually used
+ *
+ * Semantics (crop, then flip: torchvision's order).  Output pixel (c, y, x) reads source (c, y + dy - pad, xs + dx - pad)
+ * with xs = W-1-x when the sample is flipped, else x; dy, dx in [0, 2*pad].
+ *   uint8:  value = ((float)u / 255.0f - mean[c]) / std[c] with u = 0 outside the image: the image is padded with byte 0
+ *           BEFORE conversion, so a padded pixel is (0 - mean)/std, not 0.  Three IEEE fp32 operations in this order,
+ *           no contraction, correctly rounded divisions: the bits of torch's CPU x.float().div(255).sub(mean).div(std).
+ *   fp32:   the value is copied; outside the image it is fill[c].
+ * pad = 0, flip = 0 is the evaluation transform: a plain gather + normalise.
+ *
+ * Out-of-range indices.  index is device data and cannot be checked on the host.  A sample whose index is outside [0, N)
+ * is written as an all-zero image with label -1 and params (0, 0, 0); no address is formed from it.  (The loss kernels
+ * answer a label outside [0, C) with a NaN loss, so the wrong batch is loud.)
+ *
+ * The draw is a pure function of (seed, epoch, dataset index, pad) -- not of the position in the batch, the batch size or
+ * the rank -- so a batch is the concatenation of its halves and a sample gets the same crop in a 1-GPU and an 8-GPU run:
+ *   mix64(x): x = (x ^ x>>30) * 0xBF58476D1CE4E5B9;  x = (x ^ x>>27) * 0x94D049BB133111EB;  return x ^ x>>31   (mod 2^64)
+ *   key = mix64(seed * 0x9E3779B97F4A7C15 + epoch)
+ *   r   = mix64(key ^ (index * 0xD1342543DE82EF95))
+ *   dy  = ((r & 0xFFFFFF) * (2*pad+1)) >> 24;  dx = (((r >> 24) & 0xFFFFFF) * (2*pad+1)) >> 24;  flip = r >> 63
+ * (nbdt/data.py draw_params restates it on the host.)  Replaces the DataLoader + torchvision transforms of reference
+ * main.py:100-141. */
+#define NBDT_U8 3                  /* src_dtype: uint8 (NBDT_F32 for fp32) */
+#define NBDT_AUGMENT_MAX_PAD 32
+int nbdt_augment_batch(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index, int32_t B,
+                       int64_t N, int32_t H, int32_t W, int32_t pad, int32_t flip, const float* mean, const float* std,
+                       const float* fill, uint64_t seed, uint64_t epoch, const int8_t* params_in, float* out,
+                       int64_t* labels_out, int8_t* params_out, void* stream);
+
 /* ------------------------------------------------------------------ measurement probe (not on the product path) */
 /* A register-only stream of independent v_mfma_f32_32x32x16_bf16 on `blocks` CUs (one 512-thread block each, two waves
  * per SIMD): every wave issues iters x 16 of them (x 32768 flop).  bench.py times the launch for `roofline.mfma_stream`

@@ -15,7 +15,14 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   layer is out of scope, so samples come from ``--data-file`` (a ``torch.save``d
   dict with ``train_x [N,3,H,W]`` uint8|float, ``train_y``, ``test_x``, ``test_y``; already
   normalised if float, scaled to [0,1] and normalised with the reference's CIFAR statistics if uint8)
-  or from ``--synthetic N`` (CIFAR-shaped noise with a learnable class signal, for smoke runs).
+  or from ``--synthetic N`` (CIFAR-shaped noise with a learnable class signal, for smoke runs).  ``--augment none``
+  (the default) feeds them as they are, gathered on the host.  ``--augment reference`` is the reference's training
+  transform -- ``RandomCrop(size, padding) -> RandomHorizontalFlip -> ToTensor -> Normalize`` with the statistics and
+  padding of ``nbdt.data.DATASET_STATS`` (reference nbdt/data/cifar.py:11-21, nbdt/data/imagenet.py:37-48): both splits
+  become ``nbdt.data.DeviceDataset``s held on the GPU, and one launch per step gathers, crops, flips and normalises the
+  batch there (a uint8 file is normalised in the kernel, a float file or ``--synthetic`` is taken as normalised and
+  padded with ``(0 - mean)/std``); evaluation is the plain gather + normalise.  ``Imagenet1000`` is refused: its
+  ``RandomResizedCrop`` is a different transform.
 * ``--analysis Noop | SoftEmbeddedDecisionRules | HardEmbeddedDecisionRules`` drives an analyzer of ``nbdt.analysis``
   through the reference's hook protocol (reference main.py:212-288, nbdt/analysis.py:81-130): ``epoch_context`` around
   every epoch, ``start_train`` / ``end_train`` around the training pass, ``start_test`` / ``update_batch(logits,
@@ -40,6 +47,7 @@ from nbdt import analysis  # noqa: E402
 from nbdt import dist as ndist  # noqa: E402
 from nbdt import loss as losses  # noqa: E402
 from nbdt import models  # noqa: E402
+from nbdt.data import DATASET_STATS, DeviceDataset  # noqa: E402
 from nbdt.engine import train_step  # noqa: E402
 from nbdt.model import coerce_state_dict  # noqa: E402
 from nbdt.tree import Tree  # noqa: E402
@@ -95,6 +103,9 @@ def build_parser():
     p.add_argument("--synthetic", type=int, default=0, help="number of synthetic training samples")
     p.add_argument("--image-size", type=int, default=0, help="synthetic image size (default: dataset's)")
     p.add_argument("--seed", type=int, default=0)
+    p.add_argument("--augment", choices=("none", "reference"), default="none",
+                   help="reference: the reference's RandomCrop(padding) + RandomHorizontalFlip + Normalize on a "
+                        "device-resident dataset, one launch per step (nbdt.data); none: samples as they are")
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible training steps, like the reference's CPU path: every cross-block reduction in "
                         "a fixed order instead of fp32 atomics (nbdt_set_deterministic; ResNet / WideResNet backbones)")
@@ -172,12 +183,17 @@ class _PlainCE:
         return self.inner.loss_and_grad(z, y, grad_scale)
 
 
-def load_data(args, num_classes, device):
+def load_data(args, num_classes, device, raw=False):
+    """train_x, train_y, test_x, test_y on the host.  raw: a uint8 --data-file stays uint8 (the augmentation kernel
+    normalises it)."""
     if args.data_file:
         blob = torch.load(args.data_file, map_location="cpu")
         out = []
         for split in ("train", "test"):
             x, y = blob[f"{split}_x"], blob[f"{split}_y"].long()
+            if raw and x.dtype == torch.uint8:
+                out += [x.contiguous(), y]
+                continue
             if x.dtype == torch.uint8:
                 x = x.float().div_(255.0)
                 mean = torch.tensor(CIFAR_MEAN).view(1, 3, 1, 1)
@@ -204,8 +220,12 @@ def evaluate(net, criterion_module, analyzer, k, x, y, batch, device):
     loss_sum = torch.zeros((), device=device)
     batches = 0
     with torch.no_grad():
+        order = torch.arange(x.shape[0], device=device) if isinstance(x, DeviceDataset) else None
         for i in range(0, x.shape[0], batch):
-            xb, yb = x[i:i + batch].to(device), y[i:i + batch].to(device)
+            if order is not None:           # device-resident split: the evaluation transform, one launch per batch
+                xb, yb = x.batch(order[i:i + batch], train=False)
+            else:
+                xb, yb = x[i:i + batch].to(device), y[i:i + batch].to(device)
             z = net(xb)
             loss_sum += criterion_module(z, yb)
             batches += 1
@@ -216,6 +236,9 @@ def evaluate(net, criterion_module, analyzer, k, x, y, batch, device):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.augment == "reference" and args.dataset not in DATASET_STATS:
+        raise SystemExit(f"--augment reference: {args.dataset} trains with RandomResizedCrop in the reference, a different "
+                         f"transform; supported: {', '.join(sorted(DATASET_STATS))}")
     rank, world, local = ndist.init_from_env()
     if not torch.cuda.is_available():
         raise SystemExit("main.py needs an MI355X: the NBDT hot path has no CPU fallback")
@@ -229,7 +252,11 @@ def main(argv=None):
 
     num_classes = DATASET_TO_NUM_CLASSES[args.dataset]
     log("==> Preparing data..")
-    train_x, train_y, test_x, test_y = load_data(args, num_classes, device)
+    train_x, train_y, test_x, test_y = load_data(args, num_classes, device, raw=args.augment == "reference")
+    if args.augment == "reference":
+        stats = DATASET_STATS[args.dataset]
+        train_x = DeviceDataset(train_x, train_y, stats["mean"], stats["std"], stats["pad"], flip=True, device=device)
+        test_x = DeviceDataset(test_x, test_y, stats["mean"], stats["std"], stats["pad"], flip=True, device=device)
     log(f"Training with dataset {args.dataset} and {num_classes} classes: {train_x.shape[0]} train / "
         f"{test_x.shape[0]} test samples of shape {tuple(train_x.shape[1:])}")
 
@@ -285,10 +312,15 @@ def main(argv=None):
         perm = torch.randperm(train_x.shape[0], generator=g)
         steps = train_x.shape[0] // args.batch_size
         total = torch.zeros((), device=device)
+        if args.augment == "reference":
+            perm = perm.to(device)           # once per epoch; every step slices it there
         for i in range(steps):
             idx = perm[i * args.batch_size:(i + 1) * args.batch_size]
             idx = ndist.shard_batch(idx, rank, world)
-            xb, yb = train_x[idx].to(device, non_blocking=True), train_y[idx].to(device, non_blocking=True)
+            if args.augment == "reference":
+                xb, yb = train_x.batch(idx, epoch=epoch, seed=args.seed)
+            else:
+                xb, yb = train_x[idx].to(device, non_blocking=True), train_y[idx].to(device, non_blocking=True)
             total += train_step(engine, fast, xb, yb, lr, comm=comm)
         log("Loss: %.3f (%d steps of %d x %d images)" % (total.item() / max(steps, 1), steps, world, per_rank))
 

@@ -16,6 +16,8 @@ _LIBPATH = os.environ.get("NBDT_HIP_LIB") or os.path.join(os.path.dirname(os.pat
 _lib = None
 
 NBDT_F32, NBDT_BF16, NBDT_F16 = 0, 1, 2
+NBDT_U8 = 3                     # nbdt_augment_batch's src_dtype for a uint8 dataset
+NBDT_AUGMENT_MAX_PAD = 32
 _ZTYPE = {torch.float32: NBDT_F32, torch.bfloat16: NBDT_BF16, torch.float16: NBDT_F16}
 
 
@@ -182,6 +184,9 @@ SIGNATURES = {
     "nbdt_se_param_grad": (c_int, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
     "nbdt_dropout_fwd": (c_int, [_P, c_int64, c_float, ctypes.c_uint32, _P, _P, _P]),
     "nbdt_dropout_bwd": (c_int, [_P, c_int64, c_float, _P, _P, _P]),
+    "nbdt_augment_batch": (c_int, [_P, c_int32, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                   POINTER(c_float), POINTER(c_float), POINTER(c_float), ctypes.c_uint64, ctypes.c_uint64,
+                                   _P, _P, _P, _P, _P]),
     "nbdt_linear_fwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_linear_bwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "nbdt_sgd_step": (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_int32, _P]),

@@ -22,6 +22,7 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno
 # per-source flags: the rules layer keeps plain IEEE ordering (bit-exact decisions vs the oracle)
 FLAGS = {
     "rules.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    "augment.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],   # bit-exact vs torch's CPU normalise
     "conv.hip": ["-munsafe-fp-atomics"],
     "conv_dma.hip": ["-munsafe-fp-atomics"],
     "conv_halo.hip": ["-munsafe-fp-atomics"],

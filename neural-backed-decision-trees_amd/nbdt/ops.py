@@ -600,6 +600,19 @@ def stem_wgrad(img, gy, dw, cout_real, stride=1):
                                 stream_ptr(img.device)))
 
 
+def augment_batch(src, labels_src, index, out, labels_out, pad, flip, mean=None, std=None, fill=None, seed=0, epoch=0,
+                  params_in=None, params_out=None):
+    """nbdt_augment_batch: out[B,3,H,W] fp32, labels_out[B] <- gather + zero-padded random crop + flip (+ /255 and normalise
+    for a uint8 `src`) of src[N,3,H,W] at `index` (int64 [B], device).  mean / std / fill: three host floats each."""
+    N, _, H, W = src.shape
+    f3 = lambda v: None if v is None else (ctypes.c_float * 3)(*[float(a) for a in v])
+    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
+    mask = (1 << 64) - 1
+    check(lib().nbdt_augment_batch(ptr(src), dtype, ptr(labels_src), ptr(index), index.shape[0], N, H, W, int(pad),
+                                   1 if flip else 0, f3(mean), f3(std), f3(fill), int(seed) & mask, int(epoch) & mask,
+                                   ptr(params_in), ptr(out), ptr(labels_out), ptr(params_out), stream_ptr(src.device)))
+
+
 def linear_fwd(x, w, b, z):
     B, K = x.shape
     N = w.shape[0]
