@@ -668,6 +668,81 @@ int nbdt_augment_batch(const void* src, int32_t src_dtype, const int64_t* labels
                        const float* fill, uint64_t seed, uint64_t epoch, const int8_t* params_in, float* out,
                        int64_t* labels_out, int8_t* params_out, void* stream);
 
+/* ------------------------------------------------------------------ resized-crop datasets (nbdt_version() >= 111) */
+/* The ImageNet transform family, one launch per batch from a uint8 dataset in device memory: gather by index, then
+ * RandomResizedCrop(size) -> RandomHorizontalFlip -> ToTensor -> Normalize (training) or Resize(size + 32) ->
+ * CenterCrop(size) -> ToTensor -> Normalize (evaluation), written as the fp32 NCHW tensor nbdt_stem_conv reads, with the
+ * gathered targets.  Replaces the transforms of reference nbdt/data/imagenet.py:152-172.  csrc/resample.hip.
+ *
+ * Inputs
+ *   src         the dataset [N,3,H,W] (NCHW), uint8: src_dtype must be NBDT_U8 (fp32 sources are refused, NBDT_EINVAL)
+ *   labels_src  int64 [N]
+ *   index       int64 [B], device memory, repeats allowed;  1 <= B <= 65535
+ *   N, H, W     N > 0, 1 <= H, W <= 4096
+ *   rs_h, rs_w  every sample's crop box is resampled to rs_h x rs_w (1..4096) ...
+ *   win_top, win_left, out_h, out_w
+ *               ... and only this window of the resampled image is computed and written.  Training: rs = out = size,
+ *               window at (0, 0).  Evaluation: box = the whole image, rs = the image with its short side at size + 32
+ *               (the long side int(short' * long / short), torchvision's Resize), window = the central size x size:
+ *               Resize + CenterCrop without the discarded border.
+ *   flip        0 | 1: enables the random horizontal flip of the generator
+ *   mean, std   HOST float[3], std != 0
+ *   scale, ratio  HOST double[2] each: the area-fraction range (0 < lo <= hi <= 1) and the aspect-ratio range
+ *               (1/64 <= lo <= hi <= 64) of the draw; may be NULL with params_in
+ *   ratio_table double [NBDT_RESIZED_CROP_RATIOS], DEVICE memory: the aspect ratios the draw chooses from, increasing from
+ *               ratio[0] to ratio[1] (the caller fills it, in fp64, with exp(linspace(log lo, log hi, 4096))); may be NULL
+ *               with params_in
+ *   seed, epoch the generator's key
+ *   params_in   optional int32 [B,5] (top, left, h, w, flip), device memory: when non-NULL it REPLACES the generator.
+ *               Device data, so the kernel clamps: top to [0, H-1], left to [0, W-1], h to [1, H-top], w to [1, W-left],
+ *               flip is (value != 0); a bad value can never index out of bounds.
+ * Outputs
+ *   out         fp32 [B,3,out_h,out_w]
+ *   labels_out  int64 [B]
+ *   params_out  optional int32 [B,5]: the (top, left, h, w, flip) actually used
+ *
+ * Resampling: PIL's BILINEAR as Image.resize applies it to an 8-bit image that was cropped to the box first.  Per axis,
+ * for a box side `in` resampled to `out`: scale = in / out, support = max(1, scale), and output pixel i takes the taps
+ * [xmin, xmax) with center = (i + 0.5) * scale, xmin = max(0, trunc(center - support + 0.5)),
+ * xmax = min(in, trunc(center + support + 0.5)), weight(x) = max(0, 1 - |x - center + 0.5| / support), all in fp64; the
+ * weights are divided by their sum and rounded to fixed point, k = trunc(0.5 + weight * 2^22).  The horizontal pass is
+ * u8 = clip((2^21 + sum k * src) >> 22) to [0, 255]; the vertical pass does the same over those bytes.  Pure integer
+ * arithmetic on fp64 coefficients: the result is PIL's, byte for byte (nbdt/data.py resample_reference restates it).
+ * Then crop, then flip (output x reads resampled column out_w-1-x), then value = ((float)u8 / 255.0f - mean[c]) / std[c]:
+ * the three IEEE fp32 operations of nbdt_augment_batch.
+ *
+ * The draw is torchvision's RandomResizedCrop.get_params, a pure function of (seed, epoch, dataset index) -- not of the
+ * position in the batch, the batch size or the rank.  With mix64 and key as for nbdt_augment_batch and
+ * G = 0x9E3779B97F4A7C15:
+ *   base = mix64(key ^ (index * 0xD1342543DE82EF95));  flip = base >> 63
+ *   attempt t = 0 .. NBDT_RESIZED_CROP_ATTEMPTS-1:  ra = mix64(base + (2t+1) * G);  rb = mix64(base + (2t+2) * G)
+ *     target = (double)(H*W) * (scale[0] + (ra >> 11) * 2^-53 * (scale[1] - scale[0]))
+ *     r      = ratio_table[rb & (NBDT_RESIZED_CROP_RATIOS-1)]
+ *     w = round(sqrt(target * r));  h = round(sqrt(target / r))         (round half to even of the exact square root)
+ *     accepted when 0 < w <= W and 0 < h <= H:  top = (((rb >> 12) & 0xFFFFFF) * (H-h+1)) >> 24,
+ *                                               left = (((rb >> 36) & 0xFFFFFF) * (W-w+1)) >> 24
+ *   no attempt accepted: the whole image, or with W/H < ratio[0]: h = round(W / ratio[0]); with W/H > ratio[1]:
+ *   w = round(H * ratio[1]); centred.
+ * Only fp64 multiply, divide, square root and rounding, one IEEE operation each, so nbdt/data.py
+ * draw_resized_crop_params returns exactly these boxes.  The table quantises torchvision's log-uniform ratio to 4096
+ * values: exp() is not correctly rounded on either side.
+ *
+ * Out-of-range indices: as for nbdt_augment_batch, a zero image with label -1 and params (0, 0, 0, 0, 0). */
+#define NBDT_RESIZED_CROP_RATIOS 4096
+#define NBDT_RESIZED_CROP_ATTEMPTS 10
+int nbdt_resized_crop_batch(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index, int32_t B,
+                            int64_t N, int32_t H, int32_t W, int32_t rs_h, int32_t rs_w, int32_t win_top, int32_t win_left,
+                            int32_t out_h, int32_t out_w, int32_t flip, const float* mean, const float* std,
+                            const double* scale, const double* ratio, const double* ratio_table, uint64_t seed,
+                            uint64_t epoch, const int32_t* params_in, float* out, int64_t* labels_out, int32_t* params_out,
+                            void* stream);
+/* Host only: the number of output rows one block of nbdt_resized_crop_batch computes for this geometry, with the source
+ * rows of the band staged in LDS (16, 8, 4, 2 or 1: the largest whose worst-case tile fits 64 KB); 0 when no band fits and
+ * the launch reads every source byte from global memory instead (same result, slower); -1 for a geometry the entry
+ * refuses. */
+int nbdt_resized_crop_band_rows(int32_t H, int32_t W, int32_t rs_h, int32_t rs_w, int32_t win_top, int32_t win_left,
+                                int32_t out_h, int32_t out_w);
+
 /* ------------------------------------------------------------------ measurement probe (not on the product path) */
 /* A register-only stream of independent v_mfma_f32_32x32x16_bf16 on `blocks` CUs (one 512-thread block each, two waves
  * per SIMD): every wave issues iters x 16 of them (x 32768 flop).  bench.py times the launch for `roofline.mfma_stream`

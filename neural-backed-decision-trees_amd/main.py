@@ -21,8 +21,13 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   padding of ``nbdt.data.DATASET_STATS`` (reference nbdt/data/cifar.py:11-21, nbdt/data/imagenet.py:37-48): both splits
   become ``nbdt.data.DeviceDataset``s held on the GPU, and one launch per step gathers, crops, flips and normalises the
   batch there (a uint8 file is normalised in the kernel, a float file or ``--synthetic`` is taken as normalised and
-  padded with ``(0 - mean)/std``); evaluation is the plain gather + normalise.  ``Imagenet1000`` is refused: its
-  ``RandomResizedCrop`` is a different transform.
+  padded with ``(0 - mean)/std``); evaluation is the plain gather + normalise.  ``Imagenet1000`` is refused there: its
+  ``RandomResizedCrop`` is a different transform, ``--augment resized-crop``.  That one is the reference's ImageNet recipe
+  (nbdt/data/imagenet.py:152-172) on ``nbdt.data.ResizedCropDataset``s: a uint8 ``--data-file`` of any fixed ``H x W`` (or
+  uint8 ``--synthetic`` images of side ``--image-size``) stays on the GPU as bytes; training batches are
+  ``RandomResizedCrop(S) -> RandomHorizontalFlip -> Normalize``, evaluation batches ``Resize(S + 32) -> CenterCrop(S) ->
+  Normalize``, one launch each, resampled with PIL's bilinear filter.  ``S`` is 224 (``nbdt.data.RESIZED_CROP_STATS``)
+  unless ``--crop-size`` says otherwise.
 * ``--analysis Noop | SoftEmbeddedDecisionRules | HardEmbeddedDecisionRules`` drives an analyzer of ``nbdt.analysis``
   through the reference's hook protocol (reference main.py:212-288, nbdt/analysis.py:81-130): ``epoch_context`` around
   every epoch, ``start_train`` / ``end_train`` around the training pass, ``start_test`` / ``update_batch(logits,
@@ -47,7 +52,7 @@ from nbdt import analysis  # noqa: E402
 from nbdt import dist as ndist  # noqa: E402
 from nbdt import loss as losses  # noqa: E402
 from nbdt import models  # noqa: E402
-from nbdt.data import DATASET_STATS, DeviceDataset  # noqa: E402
+from nbdt.data import DATASET_STATS, RESIZED_CROP_STATS, DeviceDataset, ResizedCropDataset  # noqa: E402
 from nbdt.engine import train_step  # noqa: E402
 from nbdt.model import coerce_state_dict  # noqa: E402
 from nbdt.tree import Tree  # noqa: E402
@@ -103,9 +108,13 @@ def build_parser():
     p.add_argument("--synthetic", type=int, default=0, help="number of synthetic training samples")
     p.add_argument("--image-size", type=int, default=0, help="synthetic image size (default: dataset's)")
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--augment", choices=("none", "reference"), default="none",
+    p.add_argument("--augment", choices=("none", "reference", "resized-crop"), default="none",
                    help="reference: the reference's RandomCrop(padding) + RandomHorizontalFlip + Normalize on a "
-                        "device-resident dataset, one launch per step (nbdt.data); none: samples as they are")
+                        "device-resident dataset, one launch per step (nbdt.data); resized-crop: its ImageNet recipe, "
+                        "RandomResizedCrop + RandomHorizontalFlip + Normalize for training and Resize + CenterCrop for "
+                        "evaluation, on a device-resident uint8 dataset; none: samples as they are")
+    p.add_argument("--crop-size", type=int, default=0,
+                   help="--augment resized-crop: output side S (default: the dataset's, 224); evaluation resizes to S + 32")
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible training steps, like the reference's CPU path: every cross-block reduction in "
                         "a fixed order instead of fp32 atomics (nbdt_set_deterministic; ResNet / WideResNet backbones)")
@@ -194,6 +203,9 @@ def load_data(args, num_classes, device, raw=False):
             if raw and x.dtype == torch.uint8:
                 out += [x.contiguous(), y]
                 continue
+            if args.augment == "resized-crop":
+                raise SystemExit(f"--augment resized-crop resamples bytes: {split}_x of {args.data_file} must be uint8, "
+                                 f"not {x.dtype}")
             if x.dtype == torch.uint8:
                 x = x.float().div_(255.0)
                 mean = torch.tensor(CIFAR_MEAN).view(1, 3, 1, 1)
@@ -208,7 +220,10 @@ def load_data(args, num_classes, device, raw=False):
 
     def make(m):
         y = torch.randint(0, num_classes, (m,), generator=g)
-        return (proto[y] + torch.randn(m, 3, size, size, generator=g)).contiguous(), y
+        x = proto[y] + torch.randn(m, 3, size, size, generator=g)
+        if args.augment == "resized-crop":       # the resized crop reads bytes: the same signal around mid-grey
+            x = (128.0 + 40.0 * x).round_().clamp_(0, 255).to(torch.uint8)
+        return x.contiguous(), y
     return [*make(n), *make(max(n // 4, args.batch_size))]
 
 
@@ -220,7 +235,7 @@ def evaluate(net, criterion_module, analyzer, k, x, y, batch, device):
     loss_sum = torch.zeros((), device=device)
     batches = 0
     with torch.no_grad():
-        order = torch.arange(x.shape[0], device=device) if isinstance(x, DeviceDataset) else None
+        order = torch.arange(x.shape[0], device=device) if isinstance(x, (DeviceDataset, ResizedCropDataset)) else None
         for i in range(0, x.shape[0], batch):
             if order is not None:           # device-resident split: the evaluation transform, one launch per batch
                 xb, yb = x.batch(order[i:i + batch], train=False)
@@ -238,7 +253,13 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.augment == "reference" and args.dataset not in DATASET_STATS:
         raise SystemExit(f"--augment reference: {args.dataset} trains with RandomResizedCrop in the reference, a different "
-                         f"transform; supported: {', '.join(sorted(DATASET_STATS))}")
+                         f"transform (--augment resized-crop); supported: {', '.join(sorted(DATASET_STATS))}")
+    if args.augment == "resized-crop" and args.dataset not in RESIZED_CROP_STATS:
+        raise SystemExit(f"--augment resized-crop: {args.dataset} trains with RandomCrop(padding) in the reference "
+                         f"(--augment reference); supported: {', '.join(sorted(RESIZED_CROP_STATS))}")
+    if args.crop_size and args.augment != "resized-crop":
+        raise SystemExit("--crop-size belongs to --augment resized-crop")
+    on_device = args.augment in ("reference", "resized-crop")      # both splits are datasets held on the GPU
     rank, world, local = ndist.init_from_env()
     if not torch.cuda.is_available():
         raise SystemExit("main.py needs an MI355X: the NBDT hot path has no CPU fallback")
@@ -252,11 +273,18 @@ def main(argv=None):
 
     num_classes = DATASET_TO_NUM_CLASSES[args.dataset]
     log("==> Preparing data..")
-    train_x, train_y, test_x, test_y = load_data(args, num_classes, device, raw=args.augment == "reference")
+    train_x, train_y, test_x, test_y = load_data(args, num_classes, device, raw=on_device)
     if args.augment == "reference":
         stats = DATASET_STATS[args.dataset]
         train_x = DeviceDataset(train_x, train_y, stats["mean"], stats["std"], stats["pad"], flip=True, device=device)
         test_x = DeviceDataset(test_x, test_y, stats["mean"], stats["std"], stats["pad"], flip=True, device=device)
+    elif args.augment == "resized-crop":
+        stats = RESIZED_CROP_STATS[args.dataset]
+        size = args.crop_size or stats["size"]
+        resize = size + 32 if args.crop_size else stats["resize"]       # reference: Resize(input_size + 32)
+        kwargs = dict(size=size, resize=resize, scale=stats["scale"], ratio=stats["ratio"], flip=True, device=device)
+        train_x = ResizedCropDataset(train_x, train_y, stats["mean"], stats["std"], **kwargs)
+        test_x = ResizedCropDataset(test_x, test_y, stats["mean"], stats["std"], **kwargs)
     log(f"Training with dataset {args.dataset} and {num_classes} classes: {train_x.shape[0]} train / "
         f"{test_x.shape[0]} test samples of shape {tuple(train_x.shape[1:])}")
 
@@ -312,12 +340,12 @@ def main(argv=None):
         perm = torch.randperm(train_x.shape[0], generator=g)
         steps = train_x.shape[0] // args.batch_size
         total = torch.zeros((), device=device)
-        if args.augment == "reference":
+        if on_device:
             perm = perm.to(device)           # once per epoch; every step slices it there
         for i in range(steps):
             idx = perm[i * args.batch_size:(i + 1) * args.batch_size]
             idx = ndist.shard_batch(idx, rank, world)
-            if args.augment == "reference":
+            if on_device:
                 xb, yb = train_x.batch(idx, epoch=epoch, seed=args.seed)
             else:
                 xb, yb = train_x[idx].to(device, non_blocking=True), train_y[idx].to(device, non_blocking=True)

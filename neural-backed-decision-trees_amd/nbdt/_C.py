@@ -18,6 +18,8 @@ _lib = None
 NBDT_F32, NBDT_BF16, NBDT_F16 = 0, 1, 2
 NBDT_U8 = 3                     # nbdt_augment_batch's src_dtype for a uint8 dataset
 NBDT_AUGMENT_MAX_PAD = 32
+NBDT_RESIZED_CROP_RATIOS = 4096     # entries of nbdt_resized_crop_batch's aspect-ratio table
+NBDT_RESIZED_CROP_ATTEMPTS = 10
 _ZTYPE = {torch.float32: NBDT_F32, torch.bfloat16: NBDT_BF16, torch.float16: NBDT_F16}
 
 
@@ -187,6 +189,10 @@ SIGNATURES = {
     "nbdt_augment_batch": (c_int, [_P, c_int32, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
                                    POINTER(c_float), POINTER(c_float), POINTER(c_float), ctypes.c_uint64, ctypes.c_uint64,
                                    _P, _P, _P, _P, _P]),
+    "nbdt_resized_crop_batch": (c_int, [_P, c_int32, _P, _P, c_int32, c_int64] + [c_int32] * 9 +
+                                [POINTER(c_float), POINTER(c_float), POINTER(ctypes.c_double), POINTER(ctypes.c_double), _P,
+                                 ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P, _P]),
+    "nbdt_resized_crop_band_rows": (c_int, [c_int32] * 8),
     "nbdt_linear_fwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_linear_bwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "nbdt_sgd_step": (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_int32, _P]),

@@ -1,11 +1,20 @@
-"""Device-resident datasets: the reference's training transform as one HIP launch per step.
+"""Device-resident datasets: the reference's training transforms as one HIP launch per step.
 
 The reference builds every training batch through ``RandomCrop(size, padding) -> RandomHorizontalFlip -> ToTensor ->
 Normalize`` in DataLoader workers (nbdt/data/cifar.py:11-21, nbdt/data/imagenet.py:37-48).  Here the whole dataset sits in
 device memory (CIFAR as uint8 is 150 MB, TinyImagenet200 1.2 GB) and ``nbdt_augment_batch`` (csrc/augment.hip) gathers a
 batch by index, crops, flips, scales and normalises it into the fp32 NCHW tensor the engines take.  No CPU fallback:
 ``draw_params`` is the only part that runs without a GPU, and it computes no pixel.
+
+ImageNet trains with a different family (nbdt/data/imagenet.py:152-172): ``RandomResizedCrop(224) -> RandomHorizontalFlip
+-> ToTensor -> Normalize``, evaluated with ``Resize(256) -> CenterCrop(224)``.  ``ResizedCropDataset`` is its device-side
+form, ``nbdt_resized_crop_batch`` (csrc/resample.hip): the crop box is drawn in the kernel (``draw_resized_crop_params``
+restates the draw) and resampled with PIL's bilinear filter, byte for byte (``resample_reference`` restates the pixels; it
+is documentation and test infrastructure, never called on the training path).
 """
+import functools
+import math
+
 import numpy as np
 import torch
 
@@ -18,7 +27,15 @@ DATASET_STATS = {
     "TinyImagenet200": {"mean": (0.4802, 0.4481, 0.3975), "std": (0.2302, 0.2265, 0.2262), "pad": 8},
 }
 
+# the resized-crop family: statistics, output side, evaluation resize and the draw's ranges of the reference's
+# transform_train / transform_val (nbdt/data/imagenet.py:152-172; scale and ratio are torchvision's defaults)
+RESIZED_CROP_STATS = {
+    "Imagenet1000": {"mean": (0.485, 0.456, 0.406), "std": (0.229, 0.224, 0.225), "size": 224, "resize": 256,
+                     "scale": (0.08, 1.0), "ratio": (3.0 / 4.0, 4.0 / 3.0)},
+}
+
 MAX_PAD = _C.NBDT_AUGMENT_MAX_PAD
+MAX_SIDE = 4096                      # nbdt_resized_crop_batch: image and resized sides
 _M64 = (1 << 64) - 1
 
 
@@ -128,4 +145,263 @@ class DeviceDataset:
         used = torch.empty((B, 3), dtype=torch.int8, device=self.device) if return_params else None
         ops.augment_batch(self.x, self.y, index, img, targets, pad, flip, mean=self.mean, std=self.std, fill=self.fill,
                           seed=seed, epoch=epoch, params_in=params, params_out=used)
+        return (img, targets, used) if return_params else (img, targets)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# the resized-crop family (nbdt_resized_crop_batch)
+
+@functools.lru_cache(maxsize=8)
+def _ratio_table(lo, hi):
+    t = np.exp(np.linspace(math.log(lo), math.log(hi), _C.NBDT_RESIZED_CROP_RATIOS))
+    t[0], t[-1] = lo, hi
+    t.setflags(write=False)
+    return t
+
+
+def ratio_table(ratio=(3.0 / 4.0, 4.0 / 3.0)):
+    """The fp64 aspect ratios the draw chooses from: NBDT_RESIZED_CROP_RATIOS log-spaced values from ratio[0] to ratio[1].
+    torchvision draws ``exp(uniform(log lo, log hi))``; exp is not correctly rounded on the host or the device, so the law is
+    quantised to this table, which both sides index with random bits."""
+    return _ratio_table(float(ratio[0]), float(ratio[1]))
+
+
+def _check_ranges(scale, ratio):
+    if len(scale) != 2 or not 0.0 < scale[0] <= scale[1] <= 1.0:
+        raise ValueError(f"scale must satisfy 0 < lo <= hi <= 1, got {tuple(scale)}")
+    if len(ratio) != 2 or not 1.0 / 64.0 <= ratio[0] <= ratio[1] <= 64.0:
+        raise ValueError(f"ratio must satisfy 1/64 <= lo <= hi <= 64, got {tuple(ratio)}")
+
+
+def _round_sqrt(v):
+    """round-half-to-even of sqrt(v), decided by exact comparisons (c*c and (c + 1/2)**2 are exact in fp64 here), so it
+    does not depend on how sqrt itself is rounded."""
+    c = np.sqrt(v).astype(np.int64)
+    c = c - ((c * c).astype(np.float64) > v)
+    c = c + (((c + 1) * (c + 1)).astype(np.float64) <= v)
+    half = (c.astype(np.float64) + 0.5) * (c.astype(np.float64) + 0.5)
+    return c + (v > half) + ((v == half) & ((c & 1) == 1))
+
+
+def draw_resized_crop_params(seed, epoch, index, H, W, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0),
+                             return_attempt=False):
+    """The generator of nbdt_resized_crop_batch (include/nbdt_hip.h), restated with numpy: (top, left, h, w, flip) int64
+    arrays shaped like `index`.  torchvision's RandomResizedCrop.get_params: up to 10 attempts of (area fraction uniform
+    in `scale`, aspect ratio from ``ratio_table(ratio)``, w = round(sqrt(area * r)), h = round(sqrt(area / r)), accepted if
+    it fits, position uniform), else the centre crop with the ratio clamped.  A pure function of (seed, epoch, dataset
+    index, H, W, scale, ratio).  return_attempt: also the attempt that was accepted, NBDT_RESIZED_CROP_ATTEMPTS for the
+    fallback."""
+    H, W = int(H), int(W)
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"image sides must be 1..{MAX_SIDE}, got {H} x {W}")
+    _check_ranges(scale, ratio)
+    s0, s1, r0, r1 = float(scale[0]), float(scale[1]), float(ratio[0]), float(ratio[1])
+    table = ratio_table(ratio)
+    if isinstance(index, torch.Tensor):
+        index = index.cpu().numpy()
+    idx = np.asarray(index).astype(np.int64).astype(np.uint64)
+    u64 = np.uint64
+    m24, golden = u64(0xFFFFFF), 0x9E3779B97F4A7C15
+    attempts = _C.NBDT_RESIZED_CROP_ATTEMPTS
+    with np.errstate(over="ignore"):
+        key = _mix64(np.asarray([(int(seed) * golden + int(epoch)) & _M64], dtype=np.uint64))[0]
+        base = _mix64(key ^ (idx * u64(0xD1342543DE82EF95)))
+        flip = (base >> u64(63)).astype(np.int64)
+        # the fallback first; accepted attempts overwrite it, the earliest one last
+        h = np.full(idx.shape, H, dtype=np.int64)
+        w = np.full(idx.shape, W, dtype=np.int64)
+        if W / H < r0:
+            h[...] = min(max(int(np.rint(W / r0)), 1), H)
+        elif W / H > r1:
+            w[...] = min(max(int(np.rint(H * r1)), 1), W)
+        top, left = (H - h) // 2, (W - w) // 2
+        which = np.full(idx.shape, attempts, dtype=np.int64)
+        for t in reversed(range(attempts)):
+            ra = _mix64(base + u64(((2 * t + 1) * golden) & _M64))
+            rb = _mix64(base + u64(((2 * t + 2) * golden) & _M64))
+            u = (ra >> u64(11)).astype(np.float64) * 2.0 ** -53
+            target = float(H * W) * (s0 + u * (s1 - s0))
+            r = table[(rb & u64(_C.NBDT_RESIZED_CROP_RATIOS - 1)).astype(np.int64)]
+            cw, ch = _round_sqrt(target * r), _round_sqrt(target / r)
+            ok = (cw > 0) & (cw <= W) & (ch > 0) & (ch <= H)
+            ct = (((rb >> u64(12)) & m24) * np.clip(H - ch + 1, 0, None).astype(np.uint64)) >> u64(24)
+            cl = (((rb >> u64(36)) & m24) * np.clip(W - cw + 1, 0, None).astype(np.uint64)) >> u64(24)
+            top, left = np.where(ok, ct.astype(np.int64), top), np.where(ok, cl.astype(np.int64), left)
+            h, w, which = np.where(ok, ch, h), np.where(ok, cw, w), np.where(ok, t, which)
+    out = (top, left, h, w, flip)
+    return out + (which,) if return_attempt else out
+
+
+def _axis_coefficients(in_size, out_size, first, count):
+    """PIL's precompute_coeffs + normalize_coeffs_8bpc for the bilinear (triangle) filter: for output pixels
+    [first, first + count) of an axis of `in_size` pixels resampled to `out_size`, a list of (xmin, int64 coefficients)."""
+    scale = in_size / out_size
+    filterscale = max(scale, 1.0)
+    support, ss = 1.0 * filterscale, 1.0 / filterscale
+    taps = []
+    for xx in range(first, first + count):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size)
+        x = np.arange(xmin, xmax, dtype=np.float64)
+        v = np.abs((x - center + 0.5) * ss)
+        k = np.where(v < 1.0, 1.0 - v, 0.0)
+        ww = 0.0
+        for kk in k:              # summed in tap order, as PIL does
+            ww += kk
+        if ww != 0.0:
+            k = k / ww
+        taps.append((xmin, (0.5 + k * float(1 << 22)).astype(np.int64)))
+    return taps
+
+
+def resample_reference(img_u8, box, out_size, window=None):
+    """``PIL.Image.fromarray(img).crop(box).resize(out_size, BILINEAR)`` restated with numpy for one uint8 ``[3,H,W]`` image
+    (an array or a CPU tensor); returns a uint8 array.  box: (top, left, h, w) inside the image; out_size: (rs_h, rs_w);
+    window: (top, left, h, w) inside the resized image, the part that is returned (default: all of it).
+
+    PIL's arithmetic for an 8-bit image: triangle filter with support max(1, in/out) per axis, clipped at the box,
+    coefficients in fp64, normalised, rounded to 22-bit fixed point; horizontal pass, rounded and clipped to uint8; vertical
+    pass over those uint8 values, rounded and clipped to uint8.  What nbdt_resized_crop_batch computes before it flips and
+    normalises.  Test infrastructure and documentation: it must not be called on the training path."""
+    if isinstance(img_u8, torch.Tensor):
+        img_u8 = img_u8.cpu().numpy()
+    img = np.asarray(img_u8)
+    if img.ndim != 3 or img.shape[0] != 3 or img.dtype != np.uint8:
+        raise ValueError(f"img must be uint8 [3,H,W], got {img.dtype} {img.shape}")
+    top, left, h, w = (int(v) for v in box)
+    if not (0 <= top and 0 <= left and h >= 1 and w >= 1 and top + h <= img.shape[1] and left + w <= img.shape[2]):
+        raise ValueError(f"box {tuple(box)} is not inside the {img.shape[1]} x {img.shape[2]} image")
+    rs_h, rs_w = (int(v) for v in out_size)
+    wt, wl, wh, ww_ = (0, 0, rs_h, rs_w) if window is None else (int(v) for v in window)
+    if not (0 <= wt and 0 <= wl and wh >= 1 and ww_ >= 1 and wt + wh <= rs_h and wl + ww_ <= rs_w):
+        raise ValueError(f"window {tuple(window)} is not inside the {rs_h} x {rs_w} resized image")
+    src = img[:, top:top + h, left:left + w].astype(np.int64)
+    half = 1 << 21
+    horiz = np.empty((3, h, ww_), dtype=np.int64)
+    for j, (xmin, k) in enumerate(_axis_coefficients(w, rs_w, wl, ww_)):
+        horiz[:, :, j] = np.clip((half + (src[:, :, xmin:xmin + len(k)] * k).sum(axis=2)) >> 22, 0, 255)
+    out = np.empty((3, wh, ww_), dtype=np.int64)
+    for i, (ymin, k) in enumerate(_axis_coefficients(h, rs_h, wt, wh)):
+        out[:, i, :] = np.clip((half + (horiz[:, ymin:ymin + len(k), :] * k[None, :, None]).sum(axis=1)) >> 22, 0, 255)
+    return out.astype(np.uint8)
+
+
+def resize_center_crop_geometry(H, W, size, resize):
+    """torchvision's ``Resize(resize) -> CenterCrop(size)`` on an H x W image as (resized (rs_h, rs_w), window (top, left)):
+    the short side becomes `resize`, the long side ``int(resize * long / short)``, and the crop starts at
+    ``int(round((side - size) / 2))``."""
+    H, W, size, resize = int(H), int(W), int(size), int(resize)
+    if W <= H:
+        rs_h, rs_w = int(resize * H / W), resize
+    else:
+        rs_h, rs_w = resize, int(resize * W / H)
+    if size > min(rs_h, rs_w):
+        raise ValueError(f"the {size} x {size} crop does not fit the resized {rs_h} x {rs_w} image")
+    return (rs_h, rs_w), (int(round((rs_h - size) / 2.0)), int(round((rs_w - size) / 2.0)))
+
+
+class ResizedCropDataset:
+    """A uint8 dataset held on the device, batched by `nbdt_resized_crop_batch`: the reference's ImageNet transforms.
+
+    x: uint8 ``[N,3,H,W]`` (any fixed H x W up to 4096: ImageNet stored at 256 x 256, a downsampled ImageNet); y: integer
+    ``[N]``; both are moved to `device` once.  Training batches are ``RandomResizedCrop(size, scale, ratio) ->
+    RandomHorizontalFlip -> ToTensor -> Normalize(mean, std)``; evaluation batches are ``Resize(resize) -> CenterCrop(size)
+    -> ToTensor -> Normalize`` (resize defaults to size + 32, as in the reference).  The resampling is PIL's bilinear filter.
+    """
+
+    def __init__(self, x, y, mean, std, size=224, resize=None, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip=True,
+                 device="cuda"):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise _C.NBDTHipError(f"ResizedCropDataset lives on an MI355X, not on {device} (no CPU fallback)")
+        if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.uint8:
+            raise ValueError(f"x must be uint8 [N,3,H,W], got {x.dtype} {tuple(x.shape)}")
+        if y.dim() != 1 or y.shape[0] != x.shape[0] or y.is_floating_point():
+            raise ValueError(f"y must be integer [N] with N = {x.shape[0]}, got {y.dtype} {tuple(y.shape)}")
+        if not (1 <= x.shape[2] <= MAX_SIDE and 1 <= x.shape[3] <= MAX_SIDE):
+            raise ValueError(f"image sides must be 1..{MAX_SIDE}, got {tuple(x.shape[2:])}")
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("mean and std have one entry per channel (3)")
+        _check_ranges(scale, ratio)
+        self.mean = tuple(float(m) for m in mean)
+        self.std = tuple(float(s) for s in std)
+        self.size = int(size)
+        self.resize = self.size + 32 if resize is None else int(resize)
+        if not 1 <= self.size <= self.resize <= MAX_SIDE:
+            raise ValueError(f"need 1 <= size <= resize <= {MAX_SIDE}, got size {size}, resize {self.resize}")
+        self.scale = tuple(float(v) for v in scale)
+        self.ratio = tuple(float(v) for v in ratio)
+        self.flip = bool(flip)
+        self.eval_resize, self.eval_window = resize_center_crop_geometry(x.shape[2], x.shape[3], self.size, self.resize)
+        if max(self.eval_resize) > MAX_SIDE:
+            raise ValueError(f"the evaluation resize {self.eval_resize} exceeds {MAX_SIDE}")
+        self.x = x.to(device).contiguous()
+        self.y = y.to(device=device, dtype=torch.int64).contiguous()
+        self.device = self.x.device
+        self._table = torch.from_numpy(ratio_table(self.ratio).copy()).to(self.device)
+        self._whole = torch.empty((0, 5), dtype=torch.int32, device=self.device)     # evaluation boxes, grown on demand
+
+    def __len__(self):
+        return self.x.shape[0]
+
+    @property
+    def shape(self):
+        return self.x.shape
+
+    def _whole_image(self, B):
+        if self._whole.shape[0] < B:
+            row = torch.tensor([0, 0, self.x.shape[2], self.x.shape[3], 0], dtype=torch.int32)
+            self._whole = row.repeat(B, 1).to(self.device)
+        return self._whole[:B]
+
+    def batch(self, index, epoch=0, seed=0, train=True, params=None, return_params=False):
+        """(img fp32 [B,3,size,size], targets int64 [B][, params int32 [B,5]]) for the samples `index`, in ONE launch on
+        torch's current stream.
+
+        index: a host sequence / array / CPU tensor is range-checked (IndexError) and copied; a device tensor goes straight
+        to the kernel, which writes a zero image with target -1 for an index outside [0, N).  train=False is the evaluation
+        transform (the whole image resized so that its short side is `resize`, the central size x size of it, no flip).
+        params: int32 [B,5] of (top, left, h, w, flip) replaces the generator; a CPU tensor is range-checked and copied, a
+        device tensor is clamped into the image by the kernel.  Without it the draw is
+        ``draw_resized_crop_params(seed, epoch, index, H, W, scale, ratio)``.
+
+        Every call returns freshly allocated tensors, as DeviceDataset.batch does."""
+        n, H, W = len(self), self.x.shape[2], self.x.shape[3]
+        if not isinstance(index, torch.Tensor):
+            index = torch.as_tensor(np.asarray(index))
+        if index.dim() != 1 or index.is_floating_point() or index.shape[0] == 0:
+            raise ValueError(f"index must be a non-empty integer vector, got {index.dtype} {tuple(index.shape)}")
+        if not index.is_cuda:
+            if int(index.min()) < 0 or int(index.max()) >= n:
+                raise IndexError(f"index outside [0, {n}): min {int(index.min())}, max {int(index.max())}")
+            index = index.to(self.device, non_blocking=True)
+        _C.require_gpu(index, "ResizedCropDataset.batch")
+        index = index.to(dtype=torch.int64).contiguous()
+        B = index.shape[0]
+        if params is not None:
+            if not train:
+                raise ValueError("params replace the training draw; train=False has none")
+            if tuple(params.shape) != (B, 5) or params.dtype != torch.int32:
+                raise ValueError(f"params must be int32 [{B},5], got {params.dtype} {tuple(params.shape)}")
+            if not params.is_cuda:
+                p = params.long()
+                ok = (p[:, 0] >= 0) & (p[:, 1] >= 0) & (p[:, 2] >= 1) & (p[:, 3] >= 1) & (p[:, 0] + p[:, 2] <= H) \
+                    & (p[:, 1] + p[:, 3] <= W) & (p[:, 4] >= 0) & (p[:, 4] <= 1)
+                if not bool(ok.all()):
+                    raise ValueError(f"params outside the {H} x {W} image (top, left >= 0, h, w >= 1, top + h <= H, "
+                                     "left + w <= W) or flip outside {0, 1}")
+                params = params.to(self.device, non_blocking=True)
+            _C.require_gpu(params, "ResizedCropDataset.batch")
+            params = params.contiguous()
+        if train:
+            resize, window = (self.size, self.size), (0, 0)
+        else:
+            resize, window, params = self.eval_resize, self.eval_window, self._whole_image(B)
+        img = torch.empty((B, 3, self.size, self.size), dtype=torch.float32, device=self.device)
+        targets = torch.empty((B,), dtype=torch.int64, device=self.device)
+        used = torch.empty((B, 5), dtype=torch.int32, device=self.device) if return_params else None
+        ops.resized_crop_batch(self.x, self.y, index, img, targets, resize, window, self.flip and train, self.mean, self.std,
+                               scale=self.scale, ratio=self.ratio, ratio_table=self._table, seed=seed, epoch=epoch,
+                               params_in=params, params_out=used)
         return (img, targets, used) if return_params else (img, targets)

@@ -613,6 +613,34 @@ def augment_batch(src, labels_src, index, out, labels_out, pad, flip, mean=None,
                                    ptr(params_in), ptr(out), ptr(labels_out), ptr(params_out), stream_ptr(src.device)))
 
 
+def resized_crop_batch(src, labels_src, index, out, labels_out, resize, window, flip, mean, std, scale=None, ratio=None,
+                       ratio_table=None, seed=0, epoch=0, params_in=None, params_out=None):
+    """nbdt_resized_crop_batch: out[B,3,out_h,out_w] fp32, labels_out[B] <- gather + crop box + PIL-bilinear resample to
+    `resize` = (rs_h, rs_w), of which `window` = (top, left) + out's size is written, + flip + /255 + normalise of the uint8
+    src[N,3,H,W] at `index` (int64 [B], device).  The boxes are params_in (int32 [B,5]: top, left, h, w, flip) or drawn
+    from (seed, epoch, index) with `scale`, `ratio` (two host floats each) and `ratio_table` (fp64 [4096], device)."""
+    N, _, H, W = src.shape
+    f3 = lambda v: (ctypes.c_float * 3)(*[float(a) for a in v])
+    d2 = lambda v: None if v is None else (ctypes.c_double * 2)(*[float(a) for a in v])
+    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
+    mask = (1 << 64) - 1
+    check(lib().nbdt_resized_crop_batch(ptr(src), dtype, ptr(labels_src), ptr(index), index.shape[0], N, H, W,
+                                        int(resize[0]), int(resize[1]), int(window[0]), int(window[1]), out.shape[2],
+                                        out.shape[3], 1 if flip else 0, f3(mean), f3(std), d2(scale), d2(ratio),
+                                        ptr(ratio_table), int(seed) & mask, int(epoch) & mask, ptr(params_in), ptr(out),
+                                        ptr(labels_out), ptr(params_out), stream_ptr(src.device)))
+
+
+def resized_crop_band_rows(H, W, resize, window, out_size):
+    """nbdt_resized_crop_band_rows (host only): output rows per block of the LDS-staged kernel, 0 = the global-memory
+    kernel runs for this geometry."""
+    rows = lib().nbdt_resized_crop_band_rows(int(H), int(W), int(resize[0]), int(resize[1]), int(window[0]), int(window[1]),
+                                             int(out_size[0]), int(out_size[1]))
+    if rows < 0:
+        check(rows)
+    return rows
+
+
 def linear_fwd(x, w, b, z):
     B, K = x.shape
     N = w.shape[0]
