@@ -343,10 +343,9 @@ __global__ __launch_bounds__(kMaxThreads) void bn_bwd_apply_kernel(
 // takes k0 / k1 from there; block 0 also writes dsum, accumulates dbeta / dgamma and zeroes `zero_other` -- the
 // OTHER slot buffer of the caller's pair, which nobody touches during this launch (the slots being read here cannot
 // be zeroed before every block has read them; the caller alternates the two buffers).
-#ifndef NBDT_CUS_IN_FLIGHT
-#define NBDT_CUS_IN_FLIGHT 2   // 4 measured equal, 8 slower (profiles/r06_session2_small_abs.txt)
-#endif
-constexpr int kCusInFlight = NBDT_CUS_IN_FLIGHT;   // pixels (16-byte loads per tensor) in flight per thread of the confined passes
+// pixels (16-byte loads per tensor) in flight per thread of the confined passes: 4 measured equal, 8 slower
+// (profiles/r06_session2_small_abs.txt)
+constexpr int kCusInFlight = 2;
 template <bool HAS_ADD, bool FOLD, bool NT>
 __global__ __launch_bounds__(1024) void bn_bwd_apply_cus_kernel(
     const bf16_t* __restrict__ gy, const bf16_t* __restrict__ x, const float* __restrict__ mean,

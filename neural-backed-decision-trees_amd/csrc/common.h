@@ -11,20 +11,17 @@
 
 #include "../../include/nbdt_hip.h"
 
-// ---- timing-experiment switches.  A handful of -D switches in the kernel sources skip, fake or re-time part of a kernel
-// (ablations, "what would X buy" experiments, s_memtime stamps): several of them produce WRONG results by design.  They
-// compile only together with -DNBDT_TIMING_BUILD (scratch/build_variants.sh passes it), and such an object exports
-// nbdt_timing_build, which makes nbdt/_C.py refuse the library unless NBDT_ALLOW_TIMING_BUILD=1 -- a stray -D in a
-// product build is a compile error, not a silently wrong gradient.
+// ---- timing switches.  Five -D switches add s_memtime stamps to a kernel (NBDT_PP_TIMING, NBDT_EPI_TIMING,
+// NBDT_WPP_TIMING, NBDT_SEG_TIMING, NBDT_RULES_TIMING; readers: scratch/*_timing.py, pp_trace.py).  They leave what the
+// kernels compute alone, but they add device globals, nbdt_debug_* exports and stamp instructions, so the object is not
+// the product.  They compile only together with -DNBDT_TIMING_BUILD (scratch/build_variants.sh passes it), and such an
+// object exports nbdt_timing_build, which makes nbdt/_C.py refuse the library unless NBDT_ALLOW_TIMING_BUILD=1 -- a stray
+// -D in a product build is a compile error, not a slower library with a different ABI.
 #if !defined(NBDT_TIMING_BUILD) &&                                                                                    \
-    (defined(NBDT_WPP_NO_EPI) || defined(NBDT_WKS_NO_EXCHANGE) || defined(NBDT_WKS_DMA_IN_M) || defined(NBDT_WPP_MIN_STAGES) || defined(NBDT_WPP_FRAC8) || defined(NBDT_PP_KFRAC5) ||    \
-     defined(NBDT_DMA_WTILED_FAKE) || defined(NBDT_PP_DUMMY_VALU) || defined(NBDT_PP_NO_PERSIST) || defined(NBDT_PP_NO_PAD) ||                    \
-     defined(NBDT_HALO_NO_ACCUMULATE) || defined(NBDT_DW_TARGET) || defined(NBDT_DW_U) || defined(NBDT_HEAD_SPB) ||    \
-     defined(NBDT_EPI_TIMING) || defined(NBDT_EPI_STATS_ATOMICS) || defined(NBDT_WGT_NSTAGE) || defined(NBDT_NO_XCD_CONTIGUOUS) || defined(NBDT_CUS_IN_FLIGHT) || defined(NBDT_NT_MIN_MB) || defined(NBDT_PLAIN_STORES) ||                      \
-     (defined(NBDT_HEAD_SKIP) && (NBDT_HEAD_SKIP + 0) != 0) || (defined(NBDT_PP_ABLATE) && (NBDT_PP_ABLATE + 0) != 0) || \
-     (defined(NBDT_PP_SCHED) && (NBDT_PP_SCHED + 0) != 0) || (defined(NBDT_PP_TIMING) && (NBDT_PP_TIMING + 0) != 0) ||  \
-     (defined(NBDT_WPP_TIMING) && (NBDT_WPP_TIMING + 0) != 0) || (defined(NBDT_SEG_TIMING) && (NBDT_SEG_TIMING + 0) != 0) || (defined(NBDT_RULES_TIMING) && (NBDT_RULES_TIMING + 0) != 0))
-#error "timing-experiment switch without -DNBDT_TIMING_BUILD: these switches change what the kernels compute (csrc/common.h)"
+    (defined(NBDT_EPI_TIMING) || (defined(NBDT_PP_TIMING) && (NBDT_PP_TIMING + 0) != 0) ||                            \
+     (defined(NBDT_WPP_TIMING) && (NBDT_WPP_TIMING + 0) != 0) || (defined(NBDT_SEG_TIMING) && (NBDT_SEG_TIMING + 0) != 0) || \
+     (defined(NBDT_RULES_TIMING) && (NBDT_RULES_TIMING + 0) != 0))
+#error "timing switch without -DNBDT_TIMING_BUILD: a stamped build is not a product library (csrc/common.h)"
 #endif
 #ifdef NBDT_TIMING_BUILD
 extern "C" __attribute__((weak, used, visibility("default"))) int nbdt_timing_build() { return 1; }
@@ -264,10 +261,8 @@ __device__ __forceinline__ u32x4_t ld16_stream(const void* p) {
   if (NT) return __builtin_nontemporal_load((const u32x4_t*)p);
   return *(const u32x4_t*)p;
 }
-#ifndef NBDT_NT_MIN_MB
-#define NBDT_NT_MIN_MB 96
-#endif
-// tensor_bytes >= the process-wide threshold (nbdt_set_stream_nt_min_bytes; default NBDT_NT_MIN_MB MiB); records the
+constexpr int kStreamNtMinMiB = 96;
+// tensor_bytes >= the process-wide threshold (nbdt_set_stream_nt_min_bytes; default kStreamNtMinMiB); records the
 // choice for nbdt_debug_last_stream_nt (misc.hip)
 bool stream_nt(long long tensor_bytes);
 
@@ -277,14 +272,10 @@ bool stream_nt(long long tensor_bytes);
 // would have hit these lines anyway (another XCD's L2 is not coherent with it).  st16<false> is the plain store (timing A/B).
 template <bool WT = true>
 __device__ __forceinline__ void st16(void* p, const u32x4_t v) {
-#ifdef NBDT_PLAIN_STORES          // timing-only builds: rounds 1-5
-  *(u32x4_t*)p = v;
-#else
   // (s_nop: a VALU write of the data registers within two wait states of a > 8-byte store corrupts it, and hipcc's hazard
   //  recogniser does not look inside an asm string -- without it the BatchNorm passes lost 2 % of their stores)
   if (WT) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 2" ::"v"(p), "v"(v) : "memory");
   else *(u32x4_t*)p = v;
-#endif
 }
 
 __device__ __forceinline__ void unpack8(const u32x4_t v, float* f) {

@@ -133,11 +133,7 @@ __device__ __forceinline__ void conv_epilogue(f32x16 (&acc)[NT][MW], const nbdt:
   // (free after its last row walk), one barrier, and 2*BN threads add the NWV * RL partials of their channel in a fixed
   // order: no atomics, ~1 k cycles, and run-to-run identical bits without a deterministic-mode special case.
   // (NT == 1: a wave's 64 x 64 B of partials do not fit its 2.5 KB region -- those small launches keep the atomics.)
-#ifdef NBDT_EPI_STATS_ATOMICS      // A/B build (scratch/variants): the LDS-atomic form everywhere
-  constexpr bool STATS_VIA_REGIONS = false;
-#else
   constexpr bool STATS_VIA_REGIONS = RL * NCH * 64 <= REGION_BYTES;
-#endif
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();          // every wave is done with the K ring
   asm volatile("" ::: "memory");

@@ -71,10 +71,6 @@ __device__ __forceinline__ TileOrigin tile_origin(const nbdt_conv_desc& d, const
   return o;
 }
 
-#ifndef NBDT_PP_SCHED
-#define NBDT_PP_SCHED 0    // schedule experiments: 1 no s_setprio around the MFMA segment, 2 no MFMA/VALU interleave
-                           // directives, 4 per-block rotation of the weight pieces
-#endif
 #ifndef NBDT_PP_TIMING
 #define NBDT_PP_TIMING 0   // 1: s_memtime stamps around the segments of every step, per-wave sums in g_pp_timing
                            // 2: four stamps per block + HW_ID / XCC_ID (scratch/pp_trace.py: a CU's timeline)
@@ -93,10 +89,6 @@ __device__ __forceinline__ unsigned stamp() {
   asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
   return (unsigned)t;
 }
-#endif
-#ifndef NBDT_PP_ABLATE
-#define NBDT_PP_ABLATE 0   // compile-time timing experiments (scratch/ablate_pp.sh): 1 no DMA, 2 no halo DMA after the
-                           // prologue, 4 no MFMA, 8 no LDS fragment reads, 32 no epilogue stores
 #endif
 
 // ------------------------------------------------------------------------------------------------------------
@@ -137,7 +129,6 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pp_kernel(nbdt::ConvDmaPa
   constexpr int BMH = 32 * MW * NWV;
   constexpr int W_BYTES = BN * BK * 2;
   constexpr int W_INSTR = W_BYTES / 1024;
-  constexpr int abl = NBDT_PP_ABLATE;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];   // [A buf 0][A buf 1][W ring x3]
 #if NBDT_PP_TIMING == 2
   unsigned tr_entry = stamp();   // entry of the block, then the end of the previous tile
@@ -162,11 +153,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pp_kernel(nbdt::ConvDmaPa
 #define NBDT_PIN(x) __builtin_amdgcn_readfirstlane(x)
   const int cin = NBDT_PIN(d.cin);
   const int kchunks_w = cin >> 5;            // K chunks the weight tiles were laid out for
-#ifdef NBDT_PP_KFRAC5       // timing experiment (scratch/variants): only KFRAC5/5 of the K loop -- a main loop that much faster
-  const int kchunks_all = kchunks_w * NBDT_PP_KFRAC5 / 5;
-#else
   const int kchunks_all = kchunks_w;
-#endif
   int kchunks = kchunks_all;                 // K slices of the CURRENT tile (split K: this block's range of them)
   int nk = 9 * kchunks;
   const int a_bytes = NBDT_PIN(hg.a_bytes);
@@ -238,17 +225,12 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pp_kernel(nbdt::ConvDmaPa
   // so piece id of step t is  w_tiles + (t * W_INSTR + id) KiB  and every lane reads 16 B at 16 * lane.
   unsigned w_voff;
   const unsigned w_ring = lds_base + 2 * a_bytes;
-  // Blocks run in lockstep (same start, same step time): without the rotation every CU of an XCD would ask its L2
-  // for the SAME KiB at the same moment.  Block b starts W_ROT pieces further into the tile.
-  const int w_rot = (NBDT_PP_SCHED & 4) ? item % W_INSTR : 0;
   constexpr int IPW = (W_INSTR + NWV - 1) / NWV;
   auto issue_w = [&](const bf16_t* w_tiles, int slot, int t) {
 #pragma unroll
     for (int k = 0; k < IPW; ++k) {
-      const int slot_id = wave + NWV * k;
-      if (slot_id < W_INSTR) {   // wave-uniform
-        int id = slot_id + w_rot;
-        id = id >= W_INSTR ? id - W_INSTR : id;
+      const int id = wave + NWV * k;
+      if (id < W_INSTR) {   // wave-uniform
         glds16_s(w_tiles + (t * W_INSTR + id) * 512, w_voff, w_ring + slot * W_BYTES + id * 1024);
       }
     }
@@ -343,7 +325,6 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pp_kernel(nbdt::ConvDmaPa
 
   // ---- a tile's first LDS-DMA: A(0) (every piece) into halo buffer 0, W(0), W(1) into ring slots 0, 1
   auto issue_first = [&](const Tile& t) {
-    if (abl & 1) return;
 #pragma unroll
     for (int k = 0; k < (PAD ? 8 : 7) * APW; ++k)
       if (wave + NWV * k < a_instr) issue_a_piece(t.in_k, t.base_pix, 0, wave + NWV * k);
@@ -405,25 +386,15 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pp_kernel(nbdt::ConvDmaPa
     for (int tap = 0; tap < 9; ++tap) {
       // ================= L(t): fragments -> registers, this wave's DMA pieces =================
       bf16x8 pf[2][MW], wf[2][NT];
-      if (!(abl & 8)) {
 #pragma unroll
-        for (int tm = 0; tm < MW; ++tm) {
-          pf[0][tm] = *(const __attribute__((address_space(3))) bf16x8*)plan.ra[0][tm];
-          pf[1][tm] = *(const __attribute__((address_space(3))) bf16x8*)plan.ra[1][tm];
-        }
+      for (int tm = 0; tm < MW; ++tm) {
+        pf[0][tm] = *(const __attribute__((address_space(3))) bf16x8*)plan.ra[0][tm];
+        pf[1][tm] = *(const __attribute__((address_space(3))) bf16x8*)plan.ra[1][tm];
+      }
 #pragma unroll
-        for (int tn = 0; tn < NT; ++tn) {
-          wf[0][tn] = *(const bf16x8*)(smem + w_rd0 + ((tap % 3) * W_BYTES + tn * 2048));
-          wf[1][tn] = *(const bf16x8*)(smem + w_rd1 + ((tap % 3) * W_BYTES + tn * 2048));
-        }
-      } else {
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-          for (int tm = 0; tm < MW; ++tm) { pf[ks][tm] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; asm volatile("" : "+v"(pf[ks][tm])); }
-#pragma unroll
-          for (int tn = 0; tn < NT; ++tn) { wf[ks][tn] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0}; asm volatile("" : "+v"(wf[ks][tn])); }
-        }
+      for (int tn = 0; tn < NT; ++tn) {
+        wf[0][tn] = *(const bf16x8*)(smem + w_rd0 + ((tap % 3) * W_BYTES + tn * 2048));
+        wf[1][tn] = *(const bf16x8*)(smem + w_rd1 + ((tap % 3) * W_BYTES + tn * 2048));
       }
       // Wait for the weight pieces this wave issued one step ago.  A halo piece issued in that step came LAST in
       // issue order and is not needed before the next slice: it may stay in flight (vmcnt counts in order), so
@@ -431,21 +402,17 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pp_kernel(nbdt::ConvDmaPa
       if (prev_a == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       else if (prev_a == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      if (!(abl & 1)) {
-        const int t2 = kc * 9 + tap + 2;                    // W(t+2) -> ring slot (t+2) % 3 = (tap+2) % 3
-        if (t2 < nk) issue_w(w_tiles, (tap + 2) % 3, t2);
-        if (!(abl & 2)) {                                   // pieces (tap*APW + j)*NWV + wave of slice kc+1
+      const int t2 = kc * 9 + tap + 2;                      // W(t+2) -> ring slot (t+2) % 3 = (tap+2) % 3
+      if (t2 < nk) issue_w(w_tiles, (tap + 2) % 3, t2);
 #pragma unroll
-          for (int j = 0; j < APW; ++j)
-            if (j < plan.a_n)
-              glds16_s(in_k + (kc + 1) * BK, plan.a_voff[j],
-                       lds_base + ((kc + 1) & 1) * a_bytes + ((tap * APW + j) * NWV + wave) * 1024);
-          if (PAD && tap == 0 && plan.a_x)
-            glds16_sf(in_k + (kc + 1) * BK, plan.a_xoff,
-                      lds_base + ((kc + 1) & 1) * a_bytes + (7 * APW * NWV + wave) * 1024);
-        }
-      }
-      prev_a = (abl & 3) ? 0 : plan.a_n + ((PAD && tap == 0) ? plan.a_x : 0);
+      for (int j = 0; j < APW; ++j)                         // pieces (tap*APW + j)*NWV + wave of slice kc+1
+        if (j < plan.a_n)
+          glds16_s(in_k + (kc + 1) * BK, plan.a_voff[j],
+                   lds_base + ((kc + 1) & 1) * a_bytes + ((tap * APW + j) * NWV + wave) * 1024);
+      if (PAD && tap == 0 && plan.a_x)
+        glds16_sf(in_k + (kc + 1) * BK, plan.a_xoff,
+                  lds_base + ((kc + 1) & 1) * a_bytes + (7 * APW * NWV + wave) * 1024);
+      prev_a = plan.a_n + ((PAD && tap == 0) ? plan.a_x : 0);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       NBDT_STAMP(tm_l)
       __builtin_amdgcn_sched_barrier(0);
@@ -453,48 +420,27 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pp_kernel(nbdt::ConvDmaPa
       __builtin_amdgcn_sched_barrier(0);
       NBDT_STAMP(tm_b1)
       // ================= M(t): 4*NT MFMAs; the idle issue slots between them prepare L(t+1) =================
-      if (!(NBDT_PP_SCHED & 1)) __builtin_amdgcn_s_setprio(1);
+      __builtin_amdgcn_s_setprio(1);
       plan = tap < 8 ? prepare(tap + 1, kc) : prepare(0, kc + 1);     // (after the last step: computed, never used)
-      if (!(abl & 4)) {
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks)
+      for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
-          for (int tn = 0; tn < NT; ++tn)
+        for (int tn = 0; tn < NT; ++tn)
 #pragma unroll
-            for (int tm = 0; tm < MW; ++tm)
-              acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks][tn], pf[ks][tm], acc[tn][tm], 0, 0, 0);
-      }
-#ifdef NBDT_PP_DUMMY_VALU   // experiment: how much does extra VALU work in the MFMA shadow cost (an in-LDS BatchNorm pass)?
-      {
-        float d0 = __int_as_float(lane), d1 = d0 + 1.f, d2 = d0 + 2.f, d3 = d0 + 3.f;
-#pragma unroll
-        for (int i = 0; i < NBDT_PP_DUMMY_VALU / 4; ++i) {
-          asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(d0) : "v"(d1), "v"(d2));
-          asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(d1) : "v"(d2), "v"(d3));
-          asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(d2) : "v"(d3), "v"(d0));
-          asm volatile("v_fma_f32 %0, %0, %1, %2" : "+v"(d3) : "v"(d0), "v"(d1));
-        }
-        asm volatile("" ::"v"(d0), "v"(d1), "v"(d2), "v"(d3));
-      }
-#endif
+          for (int tm = 0; tm < MW; ++tm)
+            acc[tn][tm] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[ks][tn], pf[ks][tm], acc[tn][tm], 0, 0, 0);
       // one MFMA, then at most two of the preparation's VALU / SALU instructions in its shadow, 20 times
-      if (!(NBDT_PP_SCHED & 2)) {
 #pragma unroll
-        for (int i = 0; i < 2 * MW * NT; ++i) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-#ifdef NBDT_PP_DUMMY_VALU
-          __builtin_amdgcn_sched_group_barrier(0x002, 2 + NBDT_PP_DUMMY_VALU / 20 + 1, 0);   // VALU
-#else
-          __builtin_amdgcn_sched_group_barrier(0x002, MW == 2 ? 2 : 3, 0);   // VALU (half tile: the same preparation, half the MFMAs)
-#endif
-          __builtin_amdgcn_sched_group_barrier(0x004, 1, 0);   // SALU
-        }
+      for (int i = 0; i < 2 * MW * NT; ++i) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
+        __builtin_amdgcn_sched_group_barrier(0x002, MW == 2 ? 2 : 3, 0);   // VALU (half tile: the same preparation, half the MFMAs)
+        __builtin_amdgcn_sched_group_barrier(0x004, 1, 0);   // SALU
       }
       asm volatile("" : "+v"(plan.ra[0][0]), "+v"(plan.ra[1][0]), "+v"(plan.a_voff[0]));
       if (MW == 2) asm volatile("" : "+v"(plan.ra[0][MW - 1]), "+v"(plan.ra[1][MW - 1]));
       if (APW == 2) asm volatile("" : "+v"(plan.a_voff[APW - 1]));
       if (PAD && tap == 8) asm volatile("" : "+v"(plan.a_xoff));
-      if (!(NBDT_PP_SCHED & 1)) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
       NBDT_STAMP(tm_m)
       __builtin_amdgcn_sched_barrier(0);
       if (PP) __builtin_amdgcn_s_barrier();      // (one group: L(t+1) only needs what the barrier after L(t) ordered)
@@ -518,7 +464,7 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pp_kernel(nbdt::ConvDmaPa
   const int next_item = item + item_step;
   const bool more = next_item < item_end;
   const Tile nxt = more ? tile_of(next_item) : cur;
-  const bool early = more && p.overlap && !(abl & 32);
+  const bool early = more && p.overlap;
   auto hook = [&]() {
     if (early) issue_first(nxt);
   };
@@ -607,19 +553,9 @@ __global__ __launch_bounds__(64 * NWV, 2) void conv3x3_pp_kernel(nbdt::ConvDmaPa
   if (lane == 0 && item < 1024)
     for (int i = 0; i < 6; ++i) g_pp_epi[(item * 8 + wave) * 8 + i] = epi_t[i + 1] - epi_t[i];
 #else
-  if (!(abl & 32) && run_epilogue)
+  if (run_epilogue)
     conv_epilogue<NT, HAS_RES, STATS, NWV, MW>(acc, p, epi_lds, m0, n0, m_blk, wave, lane, tid, nullptr, hook);
 #endif
-  if (abl & 32) {   // timing experiment: no epilogue, but every accumulator stays live
-    float sum = 0.f;
-#pragma unroll
-    for (int tn = 0; tn < NT; ++tn)
-#pragma unroll
-      for (int tm = 0; tm < MW; ++tm)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) sum += acc[tn][tm][r];
-    if (sum == 12345.f) p.out[0] = 0;
-  }
   if (!more) break;
   if (!early) {   // the packed epilogue LDS overlaps halo buffer 0 and the ring: every wave must be out of it
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -903,10 +839,6 @@ static int launch_halo(ConvDmaParams& p, const HaloGeom& hg, hipStream_t st) {
     // 32 CUs per XCD, minus the ones reserved for a collective's kernels (nbdt_set_reserved_cus, spread over the XCDs):
     // a persistent block that found its CU held by an RCCL block would start when that block ends, a millisecond late
     per_round = std::min(p.per_xcd, std::max(1, 32 - (reserved_cus() + 7) / 8));
-#ifdef NBDT_PP_NO_PERSIST                    // timing experiment: one block per item, packed epilogue LDS
-    per_round = p.per_xcd;
-    p.overlap = 0;
-#endif
   }
   static DeviceAttr site;     // one per (NT, KIND, PAD) instantiation; re-raised when a launch needs more LDS
   const dim3 grid(per_round * 8), blk(64 * NWV);
@@ -995,9 +927,6 @@ static bool halo_geom_for(const nbdt_conv_desc* d, int tile, int nwv, bool pad, 
 // desc.wide_tile: 0/1 automatic, 2 force 512-pixel tiles, 3 force the 4-wave 256-pixel kernel, 4 force 512-pixel tiles
 // with the padded LDS pitch, 5 force half tiles (tests, A/B).
 bool conv_halo_applicable(const nbdt_conv_desc* d, int M, HaloGeom* hg) {
-#ifdef NBDT_HALO_NO_ACCUMULATE          // A/B builds: accumulating data gradients on the first-generation kernel (rounds 1-3)
-  if (d->accumulate) return false;
-#endif
   // (an accumulating launch passes its own output as the residual: every element is read and written by the one thread
   // that owns it, so in place is safe)
   if (d->ntaps != 9 || d->in_base != 0) return false;

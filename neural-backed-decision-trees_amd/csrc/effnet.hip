@@ -64,9 +64,6 @@ __device__ __forceinline__ int pix_off(const MbGeom& g, int b, int p, int cx) {
 // blocks (linear index i, i + 8, ...) to ONE contiguous logical range, so neighbours in the logical order run on the
 // same XCD at about the same time.  A bijection on [0, total) for any total; only speed depends on the dispatch order.
 __device__ __forceinline__ unsigned xcd_contiguous(unsigned lin, unsigned total) {
-#ifdef NBDT_NO_XCD_CONTIGUOUS      // timing-only builds (scratch/build_variants.sh): the dispatch order of rounds 2-5
-  return lin;
-#endif
   const unsigned q = total >> 3, r = total & 7u, x = lin & 7u, k = lin >> 3;
   return x * q + (x < r ? x : r) + k;
 }
@@ -1201,13 +1198,9 @@ extern "C" int nbdt_dwconv_bwd_weight(const void* x, const void* gy, int32_t B, 
   if (PY > Ho) PY = Ho;
   const int threads = CB * PY;
   // every block ends in CB*k*8 global atomics on addresses every other block of its channels adds to as well: let a
-  // thread walk about NBDT_DW_TARGET output pixels (several images when rows are short) before the block folds
+  // thread walk about target_px output pixels (several images when rows are short) before the block folds
   // (profiles/r04_dw_wgrad.txt: rows of 28+ outputs are fastest at ~128 pixels per thread, shorter ones at ~64)
-#ifdef NBDT_DW_TARGET            // timing-only builds: one target everywhere
-  const int target_px = NBDT_DW_TARGET;
-#else
   const int target_px = W / stride >= 28 ? 128 : 64;
-#endif
   int bchunk = target_px / (W / stride);
   if (bchunk < 1) bchunk = 1;
   if (bchunk > B) bchunk = B;
@@ -1225,16 +1218,11 @@ extern "C" int nbdt_dwconv_bwd_weight(const void* x, const void* gy, int32_t B, 
     row_stride = (long long)n_dw;
   }
 #define NBDT_GO(K, S, U) hipLaunchKernelGGL((dw_bwd_weight_kernel<K, S, U>), grid, blk, shmem, st, (const bf16_t*)x, (const bf16_t*)gy, d, PY, CB, cblocks, bchunk, target, row_stride)
-#ifdef NBDT_DW_U          // timing-only builds: one U everywhere
-#define NBDT_GO_S1(K) { NBDT_GO(K, 1, NBDT_DW_U); }
-#define NBDT_GO_S2(K) { NBDT_GO(K, 2, NBDT_DW_U); }
-#else
   // pixels in flight per thread: the short-row layers (<= 28 wide: few waves per CU, a row is a chain of round trips)
   // want 8; the long-row stride-1 layers are bandwidth-bound and lose occupancy to the registers of more than 1
   const bool long_rows = W / stride >= 56;
 #define NBDT_GO_S1(K) { if (long_rows) NBDT_GO(K, 1, 1); else NBDT_GO(K, 1, 8); }
 #define NBDT_GO_S2(K) { NBDT_GO(K, 2, 4); }
-#endif
   if (k == 3) { if (stride == 1) NBDT_GO_S1(3) else NBDT_GO_S2(3) }
   else { if (stride == 1) NBDT_GO_S1(5) else NBDT_GO_S2(5) }
 #undef NBDT_GO_S1

@@ -135,7 +135,7 @@ extern "C" int nbdt_set_wgrad_store_epilogue(int32_t on) {
 extern "C" int nbdt_get_wgrad_store_epilogue(void) { return nbdt::wgrad_store_epilogue() ? 1 : 0; }
 
 namespace nbdt {
-static std::atomic<long long> g_stream_nt_min{(long long)NBDT_NT_MIN_MB << 20};
+static std::atomic<long long> g_stream_nt_min{(long long)kStreamNtMinMiB << 20};
 static thread_local int g_last_stream_nt = -1;
 bool stream_nt(long long tensor_bytes) {
   const bool nt = tensor_bytes >= g_stream_nt_min.load(std::memory_order_relaxed);

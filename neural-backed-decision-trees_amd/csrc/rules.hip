@@ -717,9 +717,6 @@ __global__ __launch_bounds__(block_of(TPS)) void soft_loss_kernel(TreeView t, co
 //     dpooled[b][k] = sum_c gz[c] W[c][k]              (ascending c, fused multiply-adds: linear_bwd_x_kernel's order)
 //     dW[c][k] += sum over the block's SPB samples of gz[c] x[k],  db[c] += sum of gz[c]   (one add per block and
 //     address; deterministic mode: a zeroed row per block, summed in block order by det_fold).
-#ifndef NBDT_HEAD_SKIP
-#define NBDT_HEAD_SKIP 0     // timing-only builds: bit 0 drops the forward, 1 the dpooled, 2 the dW / db phase
-#endif
 template <int TPS, int SPB>
 __global__ __launch_bounds__(TPS * SPB) void head_soft_loss_kernel(TreeView t, const float* __restrict__ pooled,
                                                                    const float* __restrict__ W,
@@ -750,7 +747,6 @@ __global__ __launch_bounds__(TPS * SPB) void head_soft_loss_kernel(TreeView t, c
     for (int k = g_tid; k < K; k += TPS) xs[k] = pooled[sample * K + k];
   __syncthreads();
   const int n_live = (int)((B - (int64_t)blockIdx.x * SPB) < SPB ? (B - (int64_t)blockIdx.x * SPB) : SPB);
-#if !(NBDT_HEAD_SKIP & 1)
   {  // classifier forward, the whole block together: wave wv takes classes wv, wv + NWB, ... FOUR at a time, and forms
      // their inner products for ALL the block's samples from one read of the W rows (4 rows x 8 x 64 features in
      // registers, so 32 loads per lane are in flight together; a row used to be re-read per sample, one dependent load
@@ -811,12 +807,10 @@ __global__ __launch_bounds__(TPS * SPB) void head_soft_loss_kernel(TreeView t, c
       }
     }
   }
-#endif
   __syncthreads();
   soft_loss_from_lds_logits<TPS>(t, o, active, g_tid, sample, y, w_x, w_t, scale, row_loss, zs, ss, ps, pq, gx, red,
                                  stage, ga, gbk, nullptr);
   __syncthreads();      // every sample's gx is complete: the block-wide weight-gradient sums read all of them
-#if !(NBDT_HEAD_SKIP & 2)
   if (gpooled) {      // thread = feature k for ALL the block's samples: one read of W's column per block, 32 rows in flight;
     const int gx_off = (int)(gx - xs);      // each (sample, k) sum stays one ascending chain of fused multiply-adds
     for (int k = threadIdx.x; k < K; k += TPS * SPB) {
@@ -839,8 +833,6 @@ __global__ __launch_bounds__(TPS * SPB) void head_soft_loss_kernel(TreeView t, c
         if (j < n_live) gpooled[((int64_t)blockIdx.x * SPB + j) * K + k] = s[j];
     }
   }
-#endif
-#if !(NBDT_HEAD_SKIP & 4)
   if (gW) {
     const int gx_off = (int)(gx - xs);
     float* dw = gW + (size_t)blockIdx.x * row_stride_w;
@@ -866,7 +858,6 @@ __global__ __launch_bounds__(TPS * SPB) void head_soft_loss_kernel(TreeView t, c
       }
     }
   }
-#endif
 }
 
 // HardTreeSupLoss forward+backward for criterion = nn.CrossEntropyLoss() (nbdt/loss.py:212-257):
@@ -1400,13 +1391,7 @@ extern "C" int nbdt_head_soft_tree_loss(const nbdt_tree* t, const float* pooled,
   // samples per block: 8 for one-wave groups (16 / 8 / 4 measure the same inside the training step, 8 is the fastest
   // alone: profiles/r03_head.txt), fewer if the hierarchy's LDS rows do not fit
   if (tps == 64) { NBDT_HEAD(64, 8); NBDT_HEAD(64, 4); NBDT_HEAD(64, 1); }
-#if defined(NBDT_HEAD_SPB) && NBDT_HEAD_SPB == 2
-  else { NBDT_HEAD(256, 2); NBDT_HEAD(256, 1); }
-#elif defined(NBDT_HEAD_SPB) && NBDT_HEAD_SPB == 1
-  else { NBDT_HEAD(256, 1); }
-#else
   else { NBDT_HEAD(256, 4); NBDT_HEAD(256, 2); NBDT_HEAD(256, 1); }
-#endif
 #undef NBDT_HEAD
   NBDT_REQUIRE(rc != 1, "hierarchy + feature row too large for LDS");
   if (rc) return rc;

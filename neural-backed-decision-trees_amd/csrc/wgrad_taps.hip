@@ -49,10 +49,7 @@ struct WgradTapsParams {
 }  // namespace nbdt
 
 constexpr int KS = 32;
-#ifndef NBDT_WGT_NSTAGE
-#define NBDT_WGT_NSTAGE 3
-#endif
-constexpr int NSTAGE = NBDT_WGT_NSTAGE;   // LDS ring depth; stages are prefetched NSTAGE-1 ahead
+constexpr int NSTAGE = 3;                      // LDS ring depth; stages are prefetched NSTAGE-1 ahead
 constexpr int XSLOTS = 128;                    // halo slots per ci chunk (hp <= 102 used)
 // x tile: (CX/8) chunks x 128 slots x 16 B = 8 KiB for 32 cins (4 waves), 16 KiB for 64 cins (8 waves)
 constexpr int x_bytes(int nwv) { return (nwv * 8 / 8) * XSLOTS * 16; }
@@ -336,11 +333,7 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_pp_kernel(nbdt::WgradTapsPa
   int s_end = s_begin + p.stages_per_split;
   s_end = s_end < p.stages ? s_end : p.stages;
   if (s_begin >= s_end) return;
-#ifdef NBDT_WPP_FRAC8        // timing experiment (scratch/variants): only FRAC8/8 of the stages -- a kernel that much faster
-  const int n_st = (s_end - s_begin) * NBDT_WPP_FRAC8 / 8;
-#else
   const int n_st = s_end - s_begin;
-#endif
 
 #define NBDT_PIN(x) __builtin_amdgcn_readfirstlane(x)
   const int g_bs = NBDT_PIN(d.g_bs), g_hs = NBDT_PIN(d.g_hs), g_ws = NBDT_PIN(d.g_ws);
@@ -627,16 +620,6 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_pp_kernel(nbdt::WgradTapsPa
     // ---- epilogue: acc[t][a][r]: co = co0 + (wm*WM + a)*16 + 4*g4 + r ; ci = ci0 + wn*16 + t16
     if (grp == 0) __builtin_amdgcn_s_barrier();
     const int ci = ci0 + wn * 16 + t16;
-#ifdef NBDT_WPP_NO_EPI       // timing experiment: what the fp32 atomics of the epilogue cost (accumulators stay live)
-    float keep = 0.f;
-#pragma unroll
-    for (int t = 0; t < NTP; ++t)
-#pragma unroll
-      for (int a = 0; a < WM; ++a)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) keep += acc[t][a][r];
-    if (keep == 12345.678f) p.dw[ci] = keep;
-#else
 #pragma unroll
     for (int t = 0; t < NTP; ++t) {
       const int w_tap = d.w_tap[T0 + t];
@@ -648,7 +631,6 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_pp_kernel(nbdt::WgradTapsPa
           atomicAdd(p.dw + (int64_t)split * p.dw_split_stride + ((int64_t)co * d.w_ntaps + w_tap) * d.cin + ci, acc[t][a][r]);
         }
     }
-#endif
   };
   if (grp == 0) run(std::integral_constant<int, 0>{}, std::integral_constant<int, NT0>{});
   else run(std::integral_constant<int, NT0>{}, std::integral_constant<int, 9 - NT0>{});
@@ -856,18 +838,12 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_ks_kernel(nbdt::WgradTapsPa
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-#ifndef NBDT_WKS_DMA_IN_M
     if (u + PD < n_st) issue(slot_d, g_next, x_next);
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     // ================= M(u): 9 x WM MFMAs; their shadow prepares L(u+1) =================
-#ifdef NBDT_WKS_DMA_IN_M      // experiment: this wave's pieces at the head of its MFMA segment instead of in the load segment
-    if (u + PD < n_st) issue(slot_d, g_next, x_next);
-    __builtin_amdgcn_sched_barrier(0);
-#endif
     __builtin_amdgcn_s_setprio(1);
     prepare(slot_n);
     stage_off(s_begin + u + 1 + PD, g_next, x_next);       // (past the end: computed, never used)
@@ -906,7 +882,6 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_ks_kernel(nbdt::WgradTapsPa
   // Lane to lane through LDS ([f32x4 index][lane] x 16 B: lane-linear, conflict-free), two rounds; the ring is dead (every
   // wave is past its last read and no LDS-DMA is in flight: the last load segments drained vmcnt).
   __builtin_amdgcn_sched_barrier(0);
-#ifndef NBDT_WKS_NO_EXCHANGE
   {
     typedef __attribute__((address_space(3))) f32x4* lds_f4;
     const lds_f4 ex = (lds_f4)(__attribute__((address_space(3))) unsigned char*)smem + (w4 * (5 * WM) * 64 + lane);
@@ -938,14 +913,11 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad_ks_kernel(nbdt::WgradTapsPa
         for (int a = 0; a < WM; ++a) acc[t][a] += ex[((t - 5) * WM + a) * 64];
     }
   }
-#endif
   // ---- epilogue: group 0 owns taps 0-4, group 1 taps 5-8; co = co0 + (wm*WM + a)*16 + 4*g4 + r ; ci = ci0 + wn*16 + t16
   const int ci = ci0 + wn * 16 + t16;
 #pragma unroll
   for (int t = 0; t < 9; ++t) {
-#ifndef NBDT_WKS_NO_EXCHANGE                   // (debug build: no exchange, both groups add all their partial sums)
     if ((t < 5) != (grp == 0)) continue;       // wave-uniform
-#endif
     const int w_tap = d.w_tap[t];
 #pragma unroll
     for (int a = 0; a < WM; ++a)
@@ -1359,10 +1331,8 @@ static bool pp_fits_shape(const nbdt_wgrad_desc* d) {
 constexpr bool kKsDefault = true;        // the K-split kernel won its A/B (profiles/r05_wgrad_ksplit_ab.txt: 2-7 % by shape)
 static bool takes_pp(const nbdt_wgrad_desc* d, bool pp_fits) {
   const long long M = (long long)d->B * d->gh * d->gw;
-#ifndef NBDT_WPP_MIN_STAGES
-#define NBDT_WPP_MIN_STAGES 64             // (round 5: 256 -> 64, profiles/r05_other_configs_wgrad_ab.txt; A/B builds: other thresholds)
-#endif
-  return pp_fits && (d->variant == 2 || d->variant == 4 || d->variant == 5 || (d->variant != 3 && M / 64 >= NBDT_WPP_MIN_STAGES));
+  constexpr int kMinStages = 64;           // (round 5: 256 -> 64, profiles/r05_other_configs_wgrad_ab.txt)
+  return pp_fits && (d->variant == 2 || d->variant == 4 || d->variant == 5 || (d->variant != 3 && M / 64 >= kMinStages));
 }
 
 int wgrad_taps_blocks(const nbdt_wgrad_desc* d) {
