@@ -66,7 +66,8 @@ int nbdt_version(void);
  * (device, stream), allocated with hipMalloc on first use -- not capturable in a hipGraph); the arithmetic differs
  * from the default mode only in summation order.  Scope: every kernel of the three backbones -- the EfficientNet-
  * specific reductions too (nbdt_dwconv_fwd's statistics, nbdt_dwconv_bwd_weight, nbdt_bn_act_pool, nbdt_bn_act_bwd,
- * nbdt_se_gate_bwd's parameter gradients) -- and the rules layer, which has no atomics. */
+ * nbdt_se_gate_bwd's parameter gradients) -- and the rules layer, whose only atomics add integers
+ * (nbdt_tree_stats_accumulate) and give the same sums in any order. */
 int nbdt_set_deterministic(int32_t on);
 int nbdt_get_deterministic(void);
 /* Epilogue of the K-split weight-gradient kernel (nbdt_conv_wgrad on the 3x3 stride-1 shapes; process-wide, default 1).
@@ -116,7 +117,7 @@ int nbdt_weight_tile_batched(const void* src_bf16, const int64_t* table, int32_t
  *   N inner nodes in `tree.inodes` order (sorted wnid), node n owns child slots
  *   [node_off[n], node_off[n+1]);  slot s averages the logits of classes
  *   slot_cls[slot_off[s] .. slot_off[s+1]) (ascending);  class c lies under slots
- *   cls_slot[cls_off[c] .. cls_off[c+1]) (inode order);  slot_next[s] = inode index of the
+ *   cls_slot[cls_off[c] .. cls_off[c+1]) (inode order: strictly ascending slot index, checked);  slot_next[s] = inode index of the
  *   child if it is an inner node, else -(class_index)-1.   All arrays are HOST pointers and are
  *   copied to `device`, together with the order in which a sample's lanes take the slots (longest first, dealt to
  *   the waves by load: csrc/rules.hip build_slot_schedule).
@@ -185,6 +186,45 @@ int nbdt_hard_forward(const nbdt_tree* t, const void* z, int ztype, int64_t B, i
  * per-node preds [B,N] int64 and entropy [B,N]; any output may be NULL. */
 int nbdt_node_outputs(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz,
                       float* logits, float* probs, int64_t* preds, float* entropy, void* stream);
+
+/* Tree diagnostics of one evaluation batch in ONE launch (nbdt_version() >= 112): what the reference's ConfusionMatrix,
+ * Entropy, TopDifference and NBDTEntropyMaxMin analyzers compute on the host (nbdt/analysis.py:133-180, 324-427), plus
+ * per-node statistics it does not have.  The logits are read once and the node logits formed once; the per-node
+ * softmax, the hard walk and the soft path product all work on them in LDS.
+ *   y [B] int64 labels (required when any counter is requested).  A label outside [0, C) makes the sample count
+ *   NOWHERE (the device-resident datasets hand out -1 for an out-of-range index row).
+ *   stats (host pointer, nullable) holds device pointers; each may be NULL = not wanted.  Every counter is int64 and
+ *   is ADDED TO, never overwritten: the caller zeroes once per pass and may split the pass into batches any way it
+ *   likes -- all sums are integer sums, so the result is bit-identical whatever the split or the order of the atomics.
+ *     totals[4]            samples with a valid label, backbone top-1 hits, hard-rules hits, soft-rules hits
+ *     confusion_net / _hard / _soft [C*C]   entry [label * C + prediction]; predictions = argmax of z, the hard
+ *                          walk's leaf, argmax of the soft path product; the first maximum wins everywhere
+ *     node_counts[N*5]     per inner node (tree.inodes order), five counters side by side:
+ *                          on_path (the label lies under the node), on_path_right (on_path and the node's argmax child
+ *                          contains the label), visited (the hard walk passes the node), visited_on_path,
+ *                          visited_on_path_right.  "Contains the label" is membership in the child's leaf set: in a
+ *                          single-parent hierarchy the reference's class_index_to_child_index[y][0]; in the multi-parent
+ *                          WordNet graphs ANY child that holds the class counts.
+ *     node_entropy[N*2]    per inner node, over the valid samples: sum of the node's entropy (the Categorical entropy
+ *                          nbdt_node_outputs reports) and sum of its square, each fp32 value rounded to the nearest
+ *                          multiple of 2^-32 and added as an integer (divide by 2^32 to read it)
+ *     first_error_depth[max_depth + 1]   index d: samples whose hard walk first picks a child that does not contain
+ *                          the label at depth d (root = 0); index max_depth: samples that never leave the path
+ *   scores (nullable) fp32 [B,3], WRITTEN: entropy of softmax(z) (Entropy.score), top-1 minus top-2 softmax
+ *   probability (TopDifference.score), max minus min of the entropies along the hard walk with the reference's
+ *   leading 0 of the root entry included (NBDTEntropyMaxMin.score).
+ * Limits: as the other rules kernels, plus 28 bytes of LDS per inner node for the block's counters. */
+typedef struct nbdt_tree_stats {
+  int64_t* totals;
+  int64_t* confusion_net;
+  int64_t* confusion_hard;
+  int64_t* confusion_soft;
+  int64_t* node_counts;
+  int64_t* node_entropy;
+  int64_t* first_error_depth;
+} nbdt_tree_stats;
+int nbdt_tree_stats_accumulate(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz,
+                               const int64_t* y, const nbdt_tree_stats* stats, float* scores, void* stream);
 
 /* ------------------------------------------------------------------ backbone: implicit-GEMM conv
  * One launch = one "tap table": out[pix(m)][n] (+)= sum_t sum_c in[pix_in(m) + tap_off[t]][c] *

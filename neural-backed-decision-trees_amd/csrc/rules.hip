@@ -38,6 +38,7 @@ using namespace nbdt;
 
 struct nbdt_tree {
   int device;
+  int cus;  // compute units of `device` (sizes the persistent grid of tree_stats_kernel)
   int C, N, R, L, root, max_depth;
   int sched_len;   // rows * lanes-per-sample of the slot schedule (see build_slot_schedule)
   int32_t* d_all;  // one allocation
@@ -1098,10 +1099,250 @@ __global__ __launch_bounds__(block_of(TPS)) void node_outputs_kernel(TreeView t,
 }
 
 // ------------------------------------------------------------------------------------------
+// tree diagnostics (nbdt_tree_stats_accumulate): everything an evaluation pass wants to know about a batch -- the three
+// predictions (backbone argmax, hard walk, soft path product) against the label, per-node arrival / correctness counts,
+// per-node entropy sums, the depth at which the walk leaves the label's path and three per-sample scores -- from ONE read
+// of the logits and ONE set of node logits in LDS.  The grid is persistent (at most two blocks per CU -- what the kernel's 190-233
+// VGPRs keep resident -- fewer where LDS admits fewer; a block strides over the batch); the per-node counters, the totals and the depth histogram live in the block's LDS as integers and are
+// added to the caller's int64 counters once, when the block is done, so the global atomics scale with blocks x N and not
+// with samples x N.  Only the three confusion entries of a sample go to global memory directly.  Every sum is an
+// integer sum (the entropies as multiples of 2^-32), so the result does not depend on the order of the atomics.
+struct StatsArgs {
+  const int64_t* y;
+  int64_t *totals, *conf_net, *conf_hard, *conf_soft, *node_counts, *node_entropy, *first_error;
+  float* scores;
+};
+
+// LDS ints of a block's accumulators: [5N node counters][4 totals][max_depth + 1 first-error depths], padded to an
+// even count, then 2N 64-bit entropy sums; the whole padded to 16 bytes
+__host__ __device__ constexpr int stats_small_ints(int N, int max_depth) { return (5 * N + 4 + max_depth + 1 + 1) & ~1; }
+__host__ __device__ constexpr int stats_block_ints(int N, int max_depth) {
+  return (stats_small_ints(N, max_depth) + 4 * N + 3) & ~3;
+}
+
+// the largest value of the group and, among equal values, the smallest index (first maximum wins)
+template <int TPS>
+__device__ __forceinline__ void group_argmax(float& v, int& i, float* red, int g_tid) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(v, o, 64);
+    const int oi = __shfl_xor(i, o, 64);
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+  }
+  if (TPS > 64) {
+    int* redi = (int*)red + 16;
+    if ((g_tid & 63) == 0) { red[g_tid >> 6] = v; redi[g_tid >> 6] = i; }
+    __syncthreads();
+    v = red[0]; i = redi[0];
+#pragma unroll
+    for (int w = 1; w < TPS / 64; ++w) {
+      const float ov = red[w];
+      const int oi = redi[w];
+      if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+    }
+    __syncthreads();
+  }
+}
+
+__device__ __forceinline__ void lds_count(int* p) { atomicAdd(p, 1); }
+__device__ __forceinline__ unsigned long long entropy_fixed(float h) {  // nearest multiple of 2^-32 (the product is exact)
+  return (unsigned long long)__float2ll_rn(h * 4294967296.0f);
+}
+__device__ __forceinline__ void add_i64(int64_t* p, long long v) { atomicAdd((unsigned long long*)p, (unsigned long long)v); }
+
+template <int TPS, typename LD>
+__global__ __launch_bounds__(block_of(TPS)) void tree_stats_kernel(TreeView t, const void* z, int64_t B, int64_t ldz,
+                                                            StatsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int SPB = block_of(TPS) / TPS;
+  constexpr int kOnPath = 1 << 30, kRight = 1 << 29;  // info[n]: winning slot + the label's flags
+  const int g = threadIdx.x / TPS, g_tid = threadIdx.x % TPS;
+  const int stride = t.C + 2 * t.R + 2 * t.N + 32 + (t.staged ? t.L : 0);
+  const int nsmall = stats_small_ints(t.N, t.max_depth);
+  const bool want_soft = a.totals != nullptr || a.conf_soft != nullptr;
+  const bool want_scores = a.scores != nullptr;
+  Gather<TPS> ga, gb;  // ga: slot -> classes, gb: class -> slots (soft rules only)
+  const TreeLds o = stage_tree<false>(t, lds);
+  int* cnt = (int*)lds + (t.tl_ints - stats_block_ints(t.N, t.max_depth));  // behind the offset arrays
+  int* tot = cnt + 5 * t.N;
+  int* fed = tot + 4;
+  unsigned long long* ent = (unsigned long long*)(cnt + nsmall);
+  for (int i = threadIdx.x; i < nsmall; i += (int)blockDim.x) cnt[i] = 0;
+  for (int i = threadIdx.x; i < 2 * t.N; i += (int)blockDim.x) ent[i] = 0ull;
+  float* zs = lds + t.tl_ints + (size_t)g * stride;
+  float* ss = zs + t.C;
+  float* ps = ss + t.R;
+  int* info = (int*)(ps + t.R);  // [N] winning slot of every inner node | kOnPath | kRight
+  int* next_of = info + t.N;     // [N] where that slot leads (inner node, or -(class+1))
+  float* red = (float*)(next_of + t.N);
+  float* stage = red + 32;
+
+  for (int64_t base = (int64_t)blockIdx.x * SPB; base < B; base += (int64_t)gridDim.x * SPB) {
+    const int64_t sample = base + g;
+    const bool active = sample < B;
+    if (t.staged) ga.issue(t.slot_cls, t.L, active, g_tid);
+    // the first barrier in here also publishes the offset arrays and the zeroed accumulators
+    load_and_node_logits<TPS, LD>(t, o, z, sample * ldz, active, g_tid, zs, ss, stage, ga, gb,
+                                  want_soft ? t.cls_slot : nullptr);
+    node_softmax<TPS>(t, o, active, g_tid, ss, ps);
+    int64_t yy = -1;
+    if (active && a.y != nullptr) yy = a.y[sample];
+    const bool valid = yy >= 0 && yy < t.C;
+
+    // every node decides in parallel (hard_fwd_kernel's rule); its entropy joins the block's sums
+    if (active)
+      for (int n = g_tid; n < t.N; n += TPS) {
+        const int b = o.node_off[n], e = o.node_off[n + 1];
+        int best = b;
+        for (int s = b + 1; s < e; ++s)
+          if (ss[s] > ss[best]) best = s;  // first maximum wins
+        info[n] = best;
+        next_of[n] = t.slot_next[best];
+        if (valid && a.node_entropy != nullptr) {
+          const float h = node_entropy(ps, b, e);
+          atomicAdd(ent + 2 * n, entropy_fixed(h));
+          atomicAdd(ent + 2 * n + 1, entropy_fixed(h * h));
+        }
+      }
+
+    // the backbone's own prediction and, for the scores, its softmax entropy and top-1 minus top-2 probability
+    float vz = -INFINITY;
+    int iz = 0x7fffffff;
+    if (active)
+      for (int c = g_tid; c < t.C; c += TPS)
+        if (zs[c] > vz) { vz = zs[c]; iz = c; }
+    group_argmax<TPS>(vz, iz, red, g_tid);
+    float h_net = 0.f, top_diff = 0.f;
+    if (want_scores) {
+      float sum = 0.f, v2 = -INFINITY;
+      if (active)
+        for (int c = g_tid; c < t.C; c += TPS) {
+          sum += expf(zs[c] - vz);
+          if (c != iz) v2 = fmaxf(v2, zs[c]);
+        }
+      sum = group_sum<TPS>(sum, red, g_tid);
+      v2 = group_max<TPS>(v2, red, g_tid);
+      const float eps = 1.1920928955078125e-07f;
+      float h = 0.f;
+      if (active)
+        for (int c = g_tid; c < t.C; c += TPS) {
+          const float p = expf(zs[c] - vz) / sum;
+          h += p * logf(fminf(fmaxf(p, eps), 1.0f - eps));
+        }
+      h_net = -group_sum<TPS>(h, red, g_tid);
+      top_diff = 1.0f / sum - expf(v2 - vz) / sum;
+    }
+    __syncthreads();
+
+    // the label's path: class -> slots lists every child that holds the label, in inode order, so the children of one
+    // node are neighbours and the lane that has the first of them speaks for the node
+    if (valid) {
+      const int pb = o.cls_off[yy], pe = o.cls_off[yy + 1];
+      for (int j = pb + g_tid; j < pe; j += TPS) {
+        const int s = t.cls_slot[j];
+        int lo = 0, hi = t.N - 1;  // node owning slot s: last n with node_off[n] <= s
+        while (lo < hi) {
+          const int mid = (lo + hi + 1) >> 1;
+          if (o.node_off[mid] <= s) lo = mid; else hi = mid - 1;
+        }
+        const int b = o.node_off[lo], e = o.node_off[lo + 1];
+        if (j > pb && t.cls_slot[j - 1] >= b) continue;
+        const int best = info[lo];
+        bool right = s == best;
+        for (int jj = j + 1; jj < pe && !right; ++jj) {
+          const int s2 = t.cls_slot[jj];
+          if (s2 >= e) break;
+          right = s2 == best;
+        }
+        info[lo] = best | kOnPath | (right ? kRight : 0);
+        if (a.node_counts != nullptr) {
+          lds_count(cnt + 5 * lo);
+          if (right) lds_count(cnt + 5 * lo + 1);
+        }
+      }
+    }
+    __syncthreads();
+    if (want_soft) stage_paths<TPS>(t, ps, stage, g_tid, gb);
+
+    // the hard walk, by the lane of the group that has the fewest classes to fold afterwards
+    int hard_cls = -1, first_err = t.max_depth;
+    float spread = 0.f;
+    if (active && g_tid == TPS - 1) {
+      int n = t.root;
+      float emax = 0.f, emin = 0.f;  // the reference's decision list opens with the root at entropy 0
+      for (int d = 0; d < t.max_depth; ++d) {
+        const int inf = info[n];
+        if (valid && a.node_counts != nullptr) {
+          lds_count(cnt + 5 * n + 2);
+          if (inf & kOnPath) lds_count(cnt + 5 * n + 3);
+          if (inf & kRight) lds_count(cnt + 5 * n + 4);
+        }
+        if (first_err == t.max_depth && !(inf & kRight)) first_err = d;
+        if (want_scores) {
+          const float h = node_entropy(ps, o.node_off[n], o.node_off[n + 1]);
+          emax = fmaxf(emax, h);
+          emin = fminf(emin, h);
+        }
+        const int nx = next_of[n];
+        if (nx < 0) { hard_cls = -nx - 1; break; }
+        n = nx;
+      }
+      spread = emax - emin;
+    }
+
+    float vp = -INFINITY;
+    int ip = 0x7fffffff;
+    if (want_soft) {
+      if (active)
+        for (int c0 = g_tid; c0 < t.C; c0 += joint_of<TPS>() * TPS) {
+          float p[joint_of<TPS>()];
+          class_chains<TPS, ChainMul>(t, o, c0, ps, stage, 1.0f, p);
+#pragma unroll
+          for (int m = 0; m < joint_of<TPS>(); ++m)
+            if (c0 + m * TPS < t.C && p[m] > vp) { vp = p[m]; ip = c0 + m * TPS; }
+        }
+      group_argmax<TPS>(vp, ip, red, g_tid);
+    }
+
+    if (active && g_tid == TPS - 1) {
+      if (valid) {
+        lds_count(tot);
+        if (iz == yy) lds_count(tot + 1);
+        if (hard_cls == yy) lds_count(tot + 2);
+        if (want_soft && ip == yy) lds_count(tot + 3);
+        lds_count(fed + first_err);
+        const int64_t row = yy * t.C;
+        if (a.conf_net != nullptr && iz >= 0 && iz < t.C) add_i64(a.conf_net + row + iz, 1);
+        if (a.conf_hard != nullptr && hard_cls >= 0 && hard_cls < t.C) add_i64(a.conf_hard + row + hard_cls, 1);
+        if (a.conf_soft != nullptr && ip >= 0 && ip < t.C) add_i64(a.conf_soft + row + ip, 1);
+      }
+      if (want_scores) {
+        a.scores[sample * 3] = h_net;
+        a.scores[sample * 3 + 1] = top_diff;
+        a.scores[sample * 3 + 2] = spread;
+      }
+    }
+    __syncthreads();  // the rows are rewritten by the next sample
+  }
+
+  // one flush per block; untouched counters cost nothing
+  if (a.node_counts != nullptr)
+    for (int i = threadIdx.x; i < 5 * t.N; i += (int)blockDim.x)
+      if (cnt[i] != 0) add_i64(a.node_counts + i, cnt[i]);
+  if (a.totals != nullptr && threadIdx.x < 4 && tot[threadIdx.x] != 0) add_i64(a.totals + threadIdx.x, tot[threadIdx.x]);
+  if (a.first_error != nullptr)
+    for (int i = threadIdx.x; i <= t.max_depth; i += (int)blockDim.x)
+      if (fed[i] != 0) add_i64(a.first_error + i, fed[i]);
+  if (a.node_entropy != nullptr)
+    for (int i = threadIdx.x; i < 2 * t.N; i += (int)blockDim.x)
+      if (ent[i] != 0ull) add_i64(a.node_entropy + i, (long long)ent[i]);
+}
+
+// ------------------------------------------------------------------------------------------
 // host side
 
 extern "C" const char* nbdt_last_error(void) { return nbdt::g_err; }
-extern "C" int nbdt_version(void) { return 111; }     // 111: nbdt_resized_crop_batch, nbdt_resized_crop_band_rows (RandomResizedCrop / Resize + CenterCrop datasets); 110: nbdt_augment_batch (device-resident datasets: gather + crop + flip + normalise), NBDT_U8; 109: nbdt_set/get_stream_nt_min_bytes, nbdt_debug_last_stream_nt, nbdt_conv_seg_create refuses ntensors > 2; 108: nbdt_se_param_grad, nbdt_se_gate_bwd without parameter gradients; 107: nbdt_bn_act_se_sums / _se_bwd_apply; 106: nbdt_conv_desc.ksplit is live (was reserved), nbdt_conv_seg_*
+extern "C" int nbdt_version(void) { return 112; }     // 112: nbdt_tree_stats_accumulate (tree diagnostics: per-node counters, confusion matrices, entropy sums, scores in one launch); 111: nbdt_resized_crop_batch, nbdt_resized_crop_band_rows (RandomResizedCrop / Resize + CenterCrop datasets); 110: nbdt_augment_batch (device-resident datasets: gather + crop + flip + normalise), NBDT_U8; 109: nbdt_set/get_stream_nt_min_bytes, nbdt_debug_last_stream_nt, nbdt_conv_seg_create refuses ntensors > 2; 108: nbdt_se_param_grad, nbdt_se_gate_bwd without parameter gradients; 107: nbdt_bn_act_se_sums / _se_bwd_apply; 106: nbdt_conv_desc.ksplit is live (was reserved), nbdt_conv_seg_*
 extern "C" int nbdt_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1168,6 +1409,10 @@ extern "C" int nbdt_tree_create(int device, int C, int N, int root, const int32_
     NBDT_REQUIRE(slot_cls[j] >= 0 && slot_cls[j] < C, "class index out of range");
     NBDT_REQUIRE(cls_slot[j] >= 0 && cls_slot[j] < R, "slot index out of range");
   }
+  // tree_stats_kernel finds the children of one node that hold a class side by side in the class's list
+  for (int c = 0; c < C; ++c)
+    for (int j = cls_off[c] + 1; j < cls_off[c + 1]; ++j)
+      NBDT_REQUIRE(cls_slot[j] > cls_slot[j - 1], "cls_slot must list a class's slots in ascending order");
   // longest decision path (number of inner nodes visited); also rejects cycles
   int max_depth = 0;
   {
@@ -1194,11 +1439,13 @@ extern "C" int nbdt_tree_create(int device, int C, int N, int root, const int32_
   int prev = 0;
   NBDT_HIP_CHECK(hipGetDevice(&prev));
   NBDT_HIP_CHECK(hipSetDevice(device));
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) cus = 1;
   std::vector<int32_t> sched;
   int sched_len = 0;
   build_slot_schedule(R, slot_off, pick_tps(C, R), &sched, &sched_len);
   nbdt_tree* t = new nbdt_tree();
-  t->device = device; t->C = C; t->N = N; t->R = R; t->L = L; t->root = root; t->max_depth = max_depth;
+  t->device = device; t->cus = cus; t->C = C; t->N = N; t->R = R; t->L = L; t->root = root; t->max_depth = max_depth;
   t->sched_len = sched_len;
   const size_t n_ints = (size_t)(N + 1) + (R + 1) + L + (C + 1) + L + R + sched.size();
   hipError_t e = hipMalloc((void**)&t->d_all, n_ints * sizeof(int32_t));
@@ -1261,17 +1508,24 @@ static int launch_rules(void (*kernel)(KA...), unsigned grid, int block, size_t 
   return NBDT_OK;
 }
 
-#define NBDT_DISPATCH_RULES(KERNEL, NEXT, BASE_FLOATS, ...)                                                \
+// BLOCK_INTS: LDS ints of per-block state behind the offset arrays (counted in tl_ints); BLOCKS_PER_CU > 0 makes the grid
+// persistent: at most that many blocks per CU (fewer when LDS admits fewer), the kernel strides over the batch.
+#define NBDT_DISPATCH_RULES_EX(KERNEL, NEXT, BASE_FLOATS, BLOCK_INTS, BLOCKS_PER_CU, ...)                  \
   do {                                                                                               \
     const int tps = pick_tps(t);                                                                     \
     const int spb = block_of(tps) / tps;                                                             \
     size_t floats = (size_t)(BASE_FLOATS);                                                           \
-    v.tl_ints = tree_lds_ints(t, NEXT);                                                              \
+    v.tl_ints = tree_lds_ints(t, NEXT) + (BLOCK_INTS);                                               \
     v.staged = ((size_t)v.tl_ints + (size_t)spb * (floats + t->L) + kStagePad) * sizeof(float) <= kLdsBytes; \
     if (v.staged) floats += t->L;                                                                    \
     const size_t shmem = ((size_t)v.tl_ints + (size_t)spb * floats + kStagePad) * sizeof(float);     \
     NBDT_REQUIRE(shmem <= kLdsBytes, "hierarchy too large for LDS");                                 \
-    const unsigned grid = (unsigned)((B + spb - 1) / spb);                                           \
+    unsigned grid = (unsigned)((B + spb - 1) / spb);                                                 \
+    if ((BLOCKS_PER_CU) > 0) {                                                                       \
+      const int cus = t->cus;                                                                        \
+      const size_t fit = std::max<size_t>(1, std::min<size_t>((BLOCKS_PER_CU), kLdsBytes / shmem));  \
+      grid = (unsigned)std::min<size_t>(grid, fit * (size_t)std::max(cus, 1));                       \
+    }                                                                                                \
     hipStream_t st = (hipStream_t)stream;                                                            \
     int lrc;                                                                                         \
     const int blk = block_of(tps);                                                                   \
@@ -1290,6 +1544,7 @@ static int launch_rules(void (*kernel)(KA...), unsigned grid, int block, size_t 
     }                                                                                                \
     if (lrc) return lrc;                                                                             \
   } while (0)
+#define NBDT_DISPATCH_RULES(KERNEL, NEXT, BASE_FLOATS, ...) NBDT_DISPATCH_RULES_EX(KERNEL, NEXT, BASE_FLOATS, 0, 0, __VA_ARGS__)
 
 static int check_common(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz) {
   NBDT_REQUIRE(t != nullptr, "null tree handle");
@@ -1454,5 +1709,29 @@ extern "C" int nbdt_node_outputs(const nbdt_tree* t, const void* z, int ztype, i
   if (B == 0) return NBDT_OK;
   TreeView v = view_of(t);
   NBDT_DISPATCH_RULES(node_outputs_kernel, false, t->C + 2 * t->R, v, z, B, ldz, logits, probs, preds, entropy);
+  return NBDT_OK;
+}
+
+extern "C" int nbdt_tree_stats_accumulate(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz,
+                                          const int64_t* y, const nbdt_tree_stats* stats, float* scores,
+                                          void* stream) {
+  int rc = check_common(t, z, ztype, B, ldz);
+  if (rc) return rc;
+  StatsArgs a = {};
+  if (stats) {
+    a.totals = stats->totals; a.conf_net = stats->confusion_net; a.conf_hard = stats->confusion_hard;
+    a.conf_soft = stats->confusion_soft; a.node_counts = stats->node_counts; a.node_entropy = stats->node_entropy;
+    a.first_error = stats->first_error_depth;
+  }
+  const bool counted = a.totals || a.conf_net || a.conf_hard || a.conf_soft || a.node_counts || a.node_entropy ||
+                       a.first_error;
+  NBDT_REQUIRE(!counted || y != nullptr || B == 0, "statistics against the labels need the labels");
+  NBDT_REQUIRE(counted || scores != nullptr || B == 0, "nothing requested: every statistic and the scores are NULL");
+  if (B == 0) return NBDT_OK;
+  a.y = y;
+  a.scores = scores;
+  TreeView v = view_of(t);
+  NBDT_DISPATCH_RULES_EX(tree_stats_kernel, false, t->C + 2 * t->R + 2 * t->N + 32,
+                         stats_block_ints(t->N, t->max_depth), 2, v, z, B, ldz, a);
   return NBDT_OK;
 }

@@ -34,10 +34,15 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   targets, images)`` per evaluation batch / ``end_test``.  The two rules analyzers report the accuracy of the decision
   rules applied to the backbone's logits (reference nbdt/analysis.py:204-252) next to the backbone's ``--metric``; their
   counters stay on the device, one host transfer per evaluation.  The training pass does not call ``update_batch``: the
-  fused step (classifier + rules + loss + their backward in one launch) never materialises the logits.  The
-  reference's presentation analyzers are out of scope.
+  fused step (classifier + rules + loss + their backward in one launch) never materialises the logits.
+* ``--diagnostics TreeStatistics ConfusionMatrix Entropy TopDifference NBDTEntropyMaxMin`` (any of them) runs the
+  analyzers of ``nbdt.diagnostics`` beside the ``--analysis`` analyzer, in a ``diagnostics.Chain``: per-node accuracy and
+  entropy, the depth of the first wrong turn, confusion matrices and entropy rankings from one fused launch per
+  evaluation batch; ``--diagnostics-out FILE`` writes the last evaluation's report as JSON.  Every rank evaluates the
+  whole test split, so rank 0 reports and nothing is reduced across ranks.
 """
 import argparse
+import json
 import math
 import os
 import sys
@@ -49,6 +54,7 @@ import torch.nn as nn
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from nbdt import analysis  # noqa: E402
+from nbdt import diagnostics  # noqa: E402
 from nbdt import dist as ndist  # noqa: E402
 from nbdt import loss as losses  # noqa: E402
 from nbdt import models  # noqa: E402
@@ -98,6 +104,9 @@ def build_parser():
     p.add_argument("--loss", choices=losses.names, default=["CrossEntropyLoss"], nargs="+")
     p.add_argument("--metric", choices=sorted(METRICS), default="top1")
     p.add_argument("--analysis", choices=analysis.names, help="analyzer run during every evaluation (nbdt.analysis)")
+    p.add_argument("--diagnostics", choices=diagnostics.names, nargs="+", default=[],
+                   help="tree diagnostics run beside --analysis during every evaluation (nbdt.diagnostics)")
+    p.add_argument("--diagnostics-out", metavar="FILE", help="write the diagnostics of the last evaluation as JSON")
     # nbdt/tree.py:26-35
     p.add_argument("--hierarchy")
     p.add_argument("--path-graph")
@@ -227,6 +236,14 @@ def load_data(args, num_classes, device, raw=False):
     return [*make(n), *make(max(n // 4, args.batch_size))]
 
 
+def build_diagnostic(name, tree):
+    """One analyzer of nbdt.diagnostics on the run's hierarchy (ConfusionMatrix: the backbone's own predictions)."""
+    cls = getattr(diagnostics, name)
+    if name in ("TreeStatistics", "NBDTEntropyMaxMin"):
+        return cls(tree=tree)
+    return cls(tree.classes)
+
+
 def evaluate(net, criterion_module, analyzer, k, x, y, batch, device):
     """reference main.py:262-277: top-k accuracy of the backbone's logits and the mean loss over (x, y); every batch's
     logits also go to the analyzer (update_batch), which keeps its own statistic."""
@@ -249,8 +266,20 @@ def evaluate(net, criterion_module, analyzer, k, x, y, batch, device):
     return plain.percent(), float(loss_sum) / max(batches, 1)
 
 
+def parse_args(argv=None):
+    """The command line, with the combinations no run can honour refused before anything is built."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if "ConfusionMatrix" in args.diagnostics and not args.eval:
+        parser.error("--diagnostics ConfusionMatrix needs --eval: like the reference's, the analyzer refuses a training "
+                     "pass (its start_train raises NotImplementedError)")
+    if args.diagnostics_out and not args.diagnostics:
+        parser.error("--diagnostics-out needs --diagnostics")
+    return args
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.augment == "reference" and args.dataset not in DATASET_STATS:
         raise SystemExit(f"--augment reference: {args.dataset} trains with RandomResizedCrop in the reference, a different "
                          f"transform (--augment resized-crop); supported: {', '.join(sorted(DATASET_STATS))}")
@@ -295,7 +324,7 @@ def main(argv=None):
     net = getattr(models, args.arch)(num_classes=num_classes, device=device, seed=args.seed)
     engine = net.engine
 
-    if not args.hierarchy and not args.path_graph and any("Tree" in l for l in args.loss) or args.analysis:
+    if not args.hierarchy and not args.path_graph and any("Tree" in l for l in args.loss) or args.analysis or args.diagnostics:
         args.hierarchy = args.hierarchy or f"induced-{args.arch}"       # reference nbdt/model.py:296-298 default
     tree = Tree.create_from_args(args)
     ck_args = dict(vars(args))
@@ -325,6 +354,9 @@ def main(argv=None):
     fast = criterion if hasattr(criterion, "loss_and_grad") else _PlainCE(tree)
     analyzer_cls = getattr(analysis, args.analysis or "Noop")
     analyzer = analyzer_cls(tree=tree, metric=args.metric) if args.analysis not in (None, "Noop") else analyzer_cls(tree.classes)
+    extras = [build_diagnostic(name, tree) for name in args.diagnostics]
+    if extras:                                    # every rank evaluates the whole test split: rank 0 reports
+        analyzer = diagnostics.Chain(analyzer, *extras)
     analyzer.verbose = rank == 0                  # one rank prints
     comm = ndist.GradComm() if world > 1 else None
     per_rank = args.batch_size // world
@@ -367,6 +399,9 @@ def main(argv=None):
             torch.save({"net": {k: v.cpu() for k, v in net.state_dict().items()}, "acc": acc, "epoch": epoch},
                        checkpoint_path)
         best_acc = max(best_acc, acc)
+        if extras and args.diagnostics_out and rank == 0:
+            with open(args.diagnostics_out, "w") as f:
+                json.dump({a.name: a.report() for a in extras}, f, indent=1)
         return acc, nbdt_acc
 
     if args.eval:

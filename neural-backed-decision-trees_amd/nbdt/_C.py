@@ -55,6 +55,13 @@ class WgradDesc(ctypes.Structure):
     ]
 
 
+class TreeStats(ctypes.Structure):
+    """nbdt_tree_stats: device pointers of the int64 counters nbdt_tree_stats_accumulate adds to (NULL = not wanted)."""
+    FIELDS = ("totals", "confusion_net", "confusion_hard", "confusion_soft", "node_counts", "node_entropy",
+              "first_error_depth")
+    _fields_ = [(name, c_void_p) for name in FIELDS]
+
+
 class ConvSegSlice(ctypes.Structure):
     _fields_ = [("tensor", c_int32), ("ch0", c_int32), ("ntaps", c_int32), ("tap", c_int32 * 9),
                 ("w_matrix", c_int32), ("w_off", c_int32 * 9)]
@@ -112,6 +119,7 @@ SIGNATURES = {
     "nbdt_node_logits_backward": (c_int, [c_void_p, _P, c_int64, _P, _P]),
     "nbdt_hard_forward": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "nbdt_node_outputs": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, _P, _P, _P]),
+    "nbdt_tree_stats_accumulate": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, _P, _P]),
     "nbdt_conv_igemm": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "nbdt_conv_igemm_multi": (c_int, [_P, c_int32, _P, _P, _P, _P]),
     "nbdt_conv_igemm_stats": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),

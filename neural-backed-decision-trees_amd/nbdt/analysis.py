@@ -4,8 +4,8 @@ API surface of the reference's ``nbdt/analysis.py`` for the hot path -- the hook
 (reference nbdt/analysis.py:81-130: ``start_epoch / start_train / update_batch / end_train / start_test / end_test /
 end_epoch``, the ``epoch_context`` / ``*_function`` wrappers, main.py:212-288) and the two analyzers that run the
 embedded decision rules on the backbone's logits (``HardEmbeddedDecisionRules`` / ``SoftEmbeddedDecisionRules``,
-reference :204-252), so that ``--analysis <name>`` and a user's own subclass keep working.  The presentation analyzers
-(confusion matrices, entropy rankings, image dumps) are out of scope.
+reference :204-252), so that ``--analysis <name>`` and a user's own subclass keep working.  Confusion matrices, entropy
+rankings and per-node statistics live in ``nbdt.diagnostics``; image dumps are out of scope.
 
 What is behind the surface is this repository's: the rules are the fused HIP kernels of ``nbdt.model`` (one launch per
 batch), and the hit counters live ON THE DEVICE -- ``update_batch`` enqueues work and returns without a host

@@ -654,6 +654,45 @@ def linear_bwd(x, w, gz, gx, gw, gb):
                                 stream_ptr(x.device)))
 
 
+STATS_FIELDS = _C.TreeStats.FIELDS
+ENTROPY_ONE = 1 << 32      # node_entropy sums are integers in units of 2^-32
+
+
+def tree_stats_sizes(handle):
+    """Element counts of the int64 counters of nbdt_tree_stats, by field name, for one hierarchy handle."""
+    C, N = handle.flat.num_classes, handle.flat.num_inodes
+    return {"totals": 4, "confusion_net": C * C, "confusion_hard": C * C, "confusion_soft": C * C,
+            "node_counts": N * 5, "node_entropy": N * 2, "first_error_depth": handle.max_depth + 1}
+
+
+def tree_stats_accumulate(handle, z, y, stats=None, scores=None):
+    """One launch of nbdt_tree_stats_accumulate: ADDS the statistics of the batch (logits z [B, C], labels y [B]) to the
+    int64 device tensors in ``stats`` (a dict by nbdt_tree_stats field name; a missing or None entry is not computed)
+    and WRITES the per-sample scores into ``scores`` (fp32 [B, 3], optional).  Enqueues only: no host synchronisation."""
+    _C.require_gpu(z, "tree_stats_accumulate")
+    z, B, ld = _C._rows(z, handle)
+    block = _C.TreeStats()
+    sizes = tree_stats_sizes(handle)
+    for name, t in (stats or {}).items():
+        if name not in sizes:
+            raise _C.NBDTHipError(f"unknown statistic {name!r}; nbdt_tree_stats has {', '.join(STATS_FIELDS)}")
+        if t is None:
+            continue
+        if t.dtype != torch.int64 or t.device != z.device or not t.is_contiguous() or t.numel() != sizes[name]:
+            raise _C.NBDTHipError(f"{name}: expected a contiguous int64 tensor of {sizes[name]} elements on {z.device}, "
+                                  f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        setattr(block, name, t.data_ptr())
+    if y is not None:
+        if y.is_floating_point() or y.dim() != 1 or y.shape[0] != B:
+            raise _C.NBDTHipError(f"tree_stats_accumulate takes class-index labels [B], got {y.dtype} {tuple(y.shape)}")
+        y = y.to(device=z.device, dtype=torch.int64).contiguous()
+    if scores is not None and (scores.dtype != torch.float32 or scores.device != z.device or not scores.is_contiguous()
+                               or tuple(scores.shape) != (B, 3)):
+        raise _C.NBDTHipError(f"scores: expected a contiguous fp32 [{B}, 3] tensor on {z.device}")
+    check(lib().nbdt_tree_stats_accumulate(handle.h, ptr(z), _C.ztype_of(z), B, ld, ptr(y), ctypes.byref(block),
+                                           ptr(scores), _C.stream_of(z)))
+
+
 def sgd_step(p, g, buf, lr, momentum, weight_decay, grad_scale=1.0, p_bf16=None, zero_grad=False):
     """zero_grad: the same pass leaves g zeroed (the next step's zero_grad())."""
     check(lib().nbdt_sgd_step(ptr(p), ptr(g), ptr(buf), p.numel(), lr, momentum, weight_decay, grad_scale,
