@@ -363,6 +363,22 @@ int nbdt_conv_igemm_affine(const nbdt_conv_desc* d, const void* in, const void* 
                            const void* residual, const float* scale, const float* shift, int32_t act,
                            void* stream);
 
+/* stride-1 1x1 convolution as a GEMM (nbdt_version() >= 113): out[pix(m)][n] (+)= sum_c in[pix(m)][c] * w[n][c] over the
+ * B*gh*gw interior pixels of padded NHWC tensors -- conv1 / conv3 of the reference's Bottleneck block, forward (w =
+ * [cout][1][cin]) and data gradient (w = the transposed copy [cin][1][cout] nbdt_weight_prep builds).  Replaces
+ * nn.Conv2d(kernel_size=1) of nbdt/models/resnet.py:82, 88-90 and its autograd.  Takes the descriptors of a stride-1
+ * 1x1 launch of nbdt_conv_igemm and requires ntaps == w_ntaps == 1, in_ws == cin, out_ws == cout, cin % 32 == 0,
+ * cout % 32 == 0 and 16-byte aligned pixel offsets; anything else (a strided 1x1, a 3x3, a null pointer) is NBDT_EINVAL,
+ * decided before the first launch.  bf16 operands, fp32 accumulation over all of cin in ascending order, one rounding
+ * at the store; accumulate = 1 reads out, adds in fp32 and rounds once.  Only interior pixels are written (the halo
+ * ring of out keeps its bytes) and the halo of in is never read.  bn_partials (nullable; NBDT_EINVAL together with
+ * accumulate): per-channel sum and sum of squares of the bf16 outputs of every 256-pixel tile, to
+ * bn_partials[ceil(M/256)][2][cout] exactly as nbdt_conv_igemm_stats writes them (plain stores, every row fully
+ * overwritten, run-to-run identical bits; nbdt_bn_finalize folds them).  wide_tile, ksplit and w_tiled are ignored.
+ * No residual operand, no eval-affine and no BatchNorm-backward epilogue: those stay with nbdt_conv_igemm_*. */
+int nbdt_conv_pw(const nbdt_conv_desc* d, const void* in, const void* w, void* out,
+                 float* bn_partials /* nullable */, void* stream);
+
 /* weight gradient (replaces cuDNN wgrad): dw[cout][w_ntaps][cin] fp32 += sum over the pixel grid
  * of gy[pix_g(m)][co] * x[pix_x(m) + tap_off[t]][ci]; split over pixels with fp32 atomics, so dw
  * must be zeroed (or hold the running .grad) before the call. */

@@ -121,6 +121,7 @@ SIGNATURES = {
     "nbdt_node_outputs": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "nbdt_tree_stats_accumulate": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, _P, _P]),
     "nbdt_conv_igemm": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
+    "nbdt_conv_pw": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "nbdt_conv_igemm_multi": (c_int, [_P, c_int32, _P, _P, _P, _P]),
     "nbdt_conv_igemm_stats": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
     "nbdt_conv_seg_create": (c_int, [POINTER(ConvSegDesc), POINTER(c_void_p)]),

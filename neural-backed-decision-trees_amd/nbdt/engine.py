@@ -127,6 +127,7 @@ class Conv:
         self.wd = None
         self.wt_fwd = self.wt_dgrad = None   # DMA-ordered weight tiles (dense 3x3 / stride 1: _Engine.finalize)
         self.side_stream = None              # the engine's second stream for weight gradients, or None: the caller's
+        self.pointwise = False               # stride-1 1x1 launches go to ops.conv_pw (BottleneckEngine.pointwise)
 
     def logical(self, buf):
         """[cout_real, cin_real, k, k] view (OIHW semantics, channels_last memory) of a flat buffer."""
@@ -176,8 +177,23 @@ class Conv:
         one (reference mode; plumbing on parameters, rebuilt by refresh_derived_weights)."""
         return self.wd32 if g.dtype == torch.float32 else self.wd
 
+    # Shapes that stay on nbdt_conv_igemm (form 0) although the conv is pointwise: STATISTICS launches (the training
+    # forward) with fewer than this many input channels.  The pointwise kernel's statistics pass (the first-generation
+    # kernel's summation order, so that both leave the same bits) costs 3-5 us per launch; measured at 128 images
+    # (profiles/bottleneck_pw_ab.txt) it is 5-51 % slower there for cin <= 512 and 10-24 % faster for cin >= 1024.
+    # Plain and accumulating launches (every data gradient) are faster on every shape and have no exception.
+    PW_STATS_MIN_CIN = 1024
+
+    def _pw(self):
+        """This conv's forward and data gradient run on the pointwise GEMM kernel (ops.conv_pw): stride-1 1x1 convs of an
+        engine that asked for it.  The only routing point ("Pointwise convolutions")."""
+        return self.pointwise and self.k == 1 and self.stride == 1
+
     def forward(self, x, out, residual=None, bn_scratch=None):
         B, Hp, Wp, _ = x.shape
+        if self._pw() and residual is None and (bn_scratch is None or self.cin >= self.PW_STATS_MIN_CIN):
+            ops.conv_pw(self.plan(B, Hp - 2, Wp - 2)[0], x, self._w_for(x), out, bn_scratch)
+            return
         ops.conv_igemm(self.plan(B, Hp - 2, Wp - 2)[0], x, self._w_for(x), out, residual, bn_scratch)
 
     def forward_affine(self, x, out, bn, act=1, residual=None):
@@ -202,7 +218,10 @@ class Conv:
             ops.conv_igemm_multi(descs, gout, self._wd_for(gout), gin)
             return
         for d in descs:
-            ops.conv_igemm(d, gout, self._wd_for(gout), gin)
+            if self._pw():
+                ops.conv_pw(d, gout, self._wd_for(gout), gin)
+            else:
+                ops.conv_igemm(d, gout, self._wd_for(gout), gin)
 
     def s2d_plan(self, B, Hi, Wi):
         """(forward desc [1x1 only], wgrad desc) of this stride-2 conv over the space-to-depth copy of its input."""
@@ -1427,6 +1446,196 @@ class ResNetEngine(_Engine):
                 blk["sbn"].backward(gsc, None, ts, gts, relu=False)
                 blk["sconv"].backward_weight(x_in, gts)
                 blk["sconv"].backward_data(gts, g_in, accumulate=True)
+            else:
+                blk["conv1"].backward_data(gt1, g_in, accumulate=True)
+            blk["dbg"] = {"g_out": g, "g_in": g_in}
+            g, h, w = g_in, hi, wi
+        gt0 = self.buf("gt0", B, h, w, 64)
+        self.bn0.backward(g, None, self.buf("t0", B, h, w, 64), gt0, relu=True)
+        ops.stem_wgrad(self._img, gt0, st.g("conv1.weight"), 64)
+        self._end_backward(comm)
+
+
+class BottleneckEngine(ResNetEngine):
+    """CIFAR-style Bottleneck ResNet of the reference (nbdt/models/resnet.py:77-112 Bottleneck, expansion 4; :193-223
+    ResNet50 / 101 / 152): ResNetEngine's stem, stage widths, head, gradient buckets and backward protocol around blocks of
+    1x1 -> 3x3 (stride s) -> 1x1 (x 4).  State-dict names are the reference's (layerN.M.conv1/bn1/conv2/bn2/conv3/bn3,
+    shortcut.0/1, linear); parameters are created in the reference's module order.
+
+    While ``pointwise`` is true the stride-1 1x1 convolutions -- conv1, conv3 and layer1.0's shortcut -- run on the
+    pointwise GEMM kernel (csrc/conv_pw.hip): every data gradient, the eval-mode unfused forward, and the training
+    forward (a statistics launch) from Conv.PW_STATS_MIN_CIN = 1024 input channels on.  Training forwards with fewer
+    input channels -- 25 of ResNet50's 33 -- stay on nbdt_conv_igemm, where they are faster (Conv.PW_STATS_MIN_CIN says
+    why).  Both kernels leave the same bits, statistics included, so the routing is not a numerical event.
+    ``engine.pointwise = False`` sends every launch through nbdt_conv_igemm (the A/B, and a test handle).  3x3 convs,
+    strided shortcuts and every weight gradient take the kernels they take in ResNetEngine."""
+
+    expansion = 4
+
+    def __init__(self, num_classes=10, num_blocks=(3, 4, 6, 3), device="cuda", seed=0):
+        _Engine.__init__(self, device, seed)
+        self.num_classes = num_classes
+        gen = self.gen
+        self.stem_c = 64
+        b0 = 1.0 / math.sqrt(27)
+        self.store.add("conv1.weight", (64, 3, 3, 3), lambda v: v.uniform_(-b0, b0, generator=gen))
+        self.bn0 = self.bn("bn1", 64)
+        self.blocks = []
+        cin = 64
+        for i, (planes, stride0, n) in enumerate(zip((64, 128, 256, 512), (1, 2, 2, 2), num_blocks)):
+            cout = self.expansion * planes
+            for j in range(n):
+                stride = stride0 if j == 0 else 1
+                pre = f"layer{i + 1}.{j}."
+                short = stride != 1 or cin != cout
+                blk = {
+                    "conv1": self.conv(pre + "conv1.weight", cin, planes, 1, 1, init="torch_default"),
+                    "bn1": self.bn(pre + "bn1", planes),
+                    "conv2": self.conv(pre + "conv2.weight", planes, planes, 3, stride, init="torch_default"),
+                    "bn2": self.bn(pre + "bn2", planes),
+                    "conv3": self.conv(pre + "conv3.weight", planes, cout, 1, 1, init="torch_default"),
+                    "bn3": self.bn(pre + "bn3", cout),
+                    "sconv": self.conv(pre + "shortcut.0.weight", cin, cout, 1, stride, init="torch_default") if short else None,
+                    "sbn": self.bn(pre + "shortcut.1", cout) if short else None,
+                    "cin": cin, "planes": planes, "cout": cout, "stride": stride, "key": f"l{i + 1}b{j}",
+                }
+                self.blocks.append(blk)
+                cin = cout
+        self.feat_c = cin
+        kb = 1.0 / math.sqrt(cin)
+        self.store.add("linear.weight", (num_classes, cin), lambda v: v.uniform_(-kb, kb, generator=gen))
+        self.store.add("linear.bias", (num_classes,), lambda v: v.uniform_(-kb, kb, generator=gen))
+        self.finalize()
+        self._side = side_stream(self.device)     # weight gradients on a second stream (see WRNEngine)
+        for c in self.convs:
+            c.side_stream = self._side
+        # No CU sharing: ResNetEngine confines bn1's backward pass beside conv2's weight gradient with a plan measured for
+        # BasicBlocks; nothing has been measured for these blocks, so every launch gets the whole chip.
+        self.res_share = None
+        self.pointwise = True
+        dev = self.device
+        self._id_mean = torch.zeros(cin, device=dev)
+        self._id_rstd = torch.ones(cin, device=dev)
+        self._id_gamma = torch.ones(cin, device=dev)
+        self._id_beta = torch.zeros(cin, device=dev)
+        self._id_dsum = torch.zeros(2 * cin, device=dev)
+
+    @property
+    def pointwise(self):
+        return self._pointwise
+
+    @pointwise.setter
+    def pointwise(self, on):
+        self._pointwise = bool(on)
+        for c in self.convs:
+            c.pointwise = self._pointwise
+
+    def forward(self, img, training=None, head=True):
+        training = self.training if training is None else training
+        img = self._input(img)
+        B, _, H, W = img.shape
+        t0 = self.buf("t0", B, H, W, 64)
+        x = self.buf("a0", B, H, W, 64)
+        ops.stem_conv(img, self.store.p("conv1.weight"), t0, 64)
+        self.bn0.stats(t0, training)
+        self.bn0.apply(t0, x, relu=True)
+        h, w = H, W
+        for blk in self.blocks:
+            k, s, p, cout = blk["key"], blk["stride"], blk["planes"], blk["cout"]
+            ho, wo = h // s, w // s
+            a1 = self.buf(k + ".a1", B, h, w, p)
+            a2 = self.buf(k + ".a2", B, ho, wo, p)
+            out = self.buf(k + ".out", B, ho, wo, cout)
+            fuse = training and self.fuse_stats
+            if not training and self.fuse_eval:
+                # inference: every Conv-BN(-ReLU)(+shortcut) group of the block is ONE launch (three or four per block)
+                blk["conv1"].forward_affine(x, a1, blk["bn1"], act=1)
+                blk["conv2"].forward_affine(a1, a2, blk["bn2"], act=1)
+                if blk["sconv"] is not None:
+                    sc = self.buf(f"sc{cout}", B, ho, wo, cout)
+                    blk["sconv"].forward_affine(x, sc, blk["sbn"], act=0)
+                    res = sc
+                else:
+                    res = x
+                blk["conv3"].forward_affine(a2, out, blk["bn3"], act=1, residual=res)
+                blk["x_in"] = x
+                x, h, w = out, ho, wo
+                continue
+            t1 = self.buf(k + ".t1", B, h, w, p)          # raw conv outputs: only the training path keeps them
+            t2 = self.buf(k + ".t2", B, ho, wo, p)
+            t3 = self.buf(k + ".t3", B, ho, wo, cout)
+            blk["conv1"].forward(x, t1, bn_scratch=self.partials(t1) if fuse else None)
+            blk["bn1"].stats(t1, training, fused=fuse)
+            blk["bn1"].apply(t1, a1, relu=True)
+            blk["conv2"].forward(a1, t2, bn_scratch=self.partials(t2) if fuse else None)
+            blk["bn2"].stats(t2, training, fused=fuse)
+            blk["bn2"].apply(t2, a2, relu=True)
+            blk["conv3"].forward(a2, t3, bn_scratch=self.partials(t3) if fuse else None)
+            blk["bn3"].stats(t3, training, fused=fuse)
+            if blk["sconv"] is not None:
+                ts = self.buf(k + ".ts", B, ho, wo, cout)
+                sc = self.buf(f"sc{cout}", B, ho, wo, cout)
+                blk["sconv"].forward(x, ts, bn_scratch=self.partials(ts) if fuse else None)
+                blk["sbn"].stats(ts, training, fused=fuse)
+                blk["sbn"].apply(ts, sc, relu=False)
+                res = sc
+            else:
+                res = x
+            blk["bn3"].apply(t3, out, relu=True, residual=res)
+            blk["x_in"] = x
+            x, h, w = out, ho, wo
+        self._x_last, self._hw = x, (h, w)
+        return self._pool_head(x, self._id_mean, self._id_rstd, self._id_gamma, self._id_beta, head)
+
+    def backward(self, gz, comm=None, gpooled=None):
+        self._begin_backward(comm)
+        B, st = self._B, self.store
+        gpool = self._head_backward(gz, gpooled)
+        h, w = self._hw
+        g = self.buf(f"g_out{self.feat_c}", B, h, w, self.feat_c)
+        ops.pool_bn_bwd_apply(gpool, self._x_last, self._id_mean, self._id_rstd, self._id_gamma, self._id_beta,
+                              self._id_dsum, g)
+        for i, blk in self._units_backward(self.blocks, comm):
+            # as in ResNetEngine.backward: the buffers a weight gradient reads on the second stream (gt3 / gt2 / gt1 / gts)
+            # alternate between consecutive blocks, and so does the block's input gradient
+            k, s, cin, p, cout = blk["key"], blk["stride"], blk["cin"], blk["planes"], blk["cout"]
+            ho, wo = h, w
+            hi, wi = ho * s, wo * s
+            tag = ("@" + k) if self.debug_keep else ""
+            par = i & 1
+            t1 = self.buf(k + ".t1", B, hi, wi, p)
+            a1 = self.buf(k + ".a1", B, hi, wi, p)
+            t2 = self.buf(k + ".t2", B, ho, wo, p)
+            a2 = self.buf(k + ".a2", B, ho, wo, p)
+            t3 = self.buf(k + ".t3", B, ho, wo, cout)
+            out = self.buf(k + ".out", B, ho, wo, cout)
+            gt3 = self.buf(f"gt3_{cout}_{par}{tag}", B, ho, wo, cout)
+            ga2 = self.buf(f"ga2_{p}{tag}", B, ho, wo, p)
+            gt2 = self.buf(f"gt2_{p}_{par}{tag}", B, ho, wo, p)
+            ga1 = self.buf(f"ga1_{p}{tag}", B, hi, wi, p)
+            gt1 = self.buf(f"gt1_{p}_{par}{tag}", B, hi, wi, p)
+            g_in = self.buf(f"g_in{cin}_{hi}_{par ^ 1}{tag}", B, hi, wi, cin)
+            x_in = blk["x_in"]
+            if blk["sconv"] is not None:
+                gsc = self.buf(f"gsc_{cout}{tag}", B, ho, wo, cout)
+                gts = self.buf(f"gts_{cout}_{par}{tag}", B, ho, wo, cout)
+                blk["bn3"].backward(g, out, t3, gt3, relu=True, g_resid=gsc)
+            else:
+                # identity shortcut: the masked gradient IS part of the block-input gradient
+                blk["bn3"].backward(g, out, t3, gt3, relu=True, g_resid=g_in)
+            blk["conv3"].backward_weight(a2, gt3)
+            blk["conv3"].backward_data(gt3, ga2)
+            blk["bn2"].backward(ga2, None, t2, gt2, relu=True)
+            blk["conv2"].backward_weight(a1, gt2)
+            blk["conv2"].backward_data(gt2, ga1)
+            blk["bn1"].backward(ga1, None, t1, gt1, relu=True)
+            blk["conv1"].backward_weight(x_in, gt1)
+            if blk["sconv"] is not None:
+                blk["conv1"].backward_data(gt1, g_in)
+                ts = self.buf(k + ".ts", B, ho, wo, cout)
+                blk["sbn"].backward(gsc, None, ts, gts, relu=False)
+                blk["sconv"].backward_weight(x_in, gts)
+                blk["sconv"].backward_data(gts, g_in, accumulate=True)     # after conv1's plain one
             else:
                 blk["conv1"].backward_data(gt1, g_in, accumulate=True)
             blk["dbg"] = {"g_out": g, "g_in": g_in}

@@ -1,13 +1,14 @@
-"""CIFAR ResNets (BasicBlock variants) -- reference nbdt/models/resnet.py:42-74, 115-149, 161-199.
-Bottleneck variants (ResNet50+) are not on the hot path configs and are not built."""
-from nbdt.engine import ResNetEngine
+"""CIFAR ResNets -- reference nbdt/models/resnet.py: BasicBlock variants (:42-74, 115-149, 161-199) on ResNetEngine,
+Bottleneck variants (:77-112, 193-223) on BottleneckEngine."""
+from nbdt.engine import BottleneckEngine, ResNetEngine
 from nbdt.models._hip_module import HipBackbone
 
 
-def _resnet(num_blocks, num_classes=10, pretrained=False, progress=True, dataset="CIFAR10", device="cuda", seed=0):
+def _resnet(num_blocks, num_classes=10, pretrained=False, progress=True, dataset="CIFAR10", device="cuda", seed=0,
+            engine=ResNetEngine):
     if pretrained:
         raise NotImplementedError("pretrained checkpoints need network access; use load_state_dict")
-    return HipBackbone(ResNetEngine(num_classes=num_classes, num_blocks=num_blocks, device=device, seed=seed))
+    return HipBackbone(engine(num_classes=num_classes, num_blocks=num_blocks, device=device, seed=seed))
 
 
 def ResNet10(**kwargs):
@@ -20,3 +21,15 @@ def ResNet18(**kwargs):
 
 def ResNet34(**kwargs):
     return _resnet((3, 4, 6, 3), **kwargs)
+
+
+def ResNet50(**kwargs):
+    return _resnet((3, 4, 6, 3), engine=BottleneckEngine, **kwargs)
+
+
+def ResNet101(**kwargs):
+    return _resnet((3, 4, 23, 3), engine=BottleneckEngine, **kwargs)
+
+
+def ResNet152(**kwargs):
+    return _resnet((3, 8, 36, 3), engine=BottleneckEngine, **kwargs)

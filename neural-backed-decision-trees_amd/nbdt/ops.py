@@ -304,6 +304,24 @@ def conv_igemm(desc, inp, w_bf16, out, residual=None, bn_scratch=None):
         _timer.count(last_igemm_kernel_full())
 
 
+def conv_pw(desc, inp, w_bf16, out, bn_scratch=None):
+    """Stride-1 1x1 convolution (forward or data gradient) on the pointwise GEMM kernel (nbdt_conv_pw, csrc/conv_pw.hip);
+    bn_scratch as in conv_igemm.  fp32 tensors (the engines' reference mode) go to the fp32 reference kernel."""
+    if _ref(inp):
+        conv_igemm(desc, inp, w_bf16, out, None, bn_scratch)
+        return
+    ev = None
+    if _timer is not None and _timer.wants("conv_igemm"):
+        flops = desc_flops(desc)
+        ev = _timer.bracket("conv_igemm", flops, inp.device)
+        ev[0].record()
+    check(lib().nbdt_conv_pw(ctypes.byref(desc), ptr(inp), ptr(w_bf16), ptr(out), ptr(bn_scratch),
+                             stream_ptr(inp.device)))
+    if ev is not None:
+        ev[1].record()
+        _timer.count(last_igemm_kernel_full())
+
+
 def desc_flops(desc):
     """Algorithmic flops of one conv / data-gradient / weight-gradient launch: 2 x pixels x taps x cin x cout with the
     layer's REAL channel counts when the engine attached them (desc.flop_channels; the kernels multiply channels padded
