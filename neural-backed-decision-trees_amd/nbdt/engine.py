@@ -239,30 +239,24 @@ class Conv:
         ops.conv_igemm(self.s2d_plan(xs.shape[0], Hi, Wi)[0], xs, self._w_for(xs), out)
 
     def backward_weight_s2d(self, xs, gout, Hi, Wi, cu_budget=0):
-        desc = self.s2d_plan(xs.shape[0], Hi, Wi)[1]
-        side = self.side_stream
-        if side is None:
-            ops.conv_wgrad(desc, xs, gout, self.store.g(self.name), cu_budget)
-            return
-        main = torch.cuda.current_stream(xs.device)
-        side.wait_stream(main)
-        with torch.cuda.stream(side):
-            ops.conv_wgrad(desc, xs, gout, self.store.g(self.name), cu_budget)
+        self._wgrad(self.s2d_plan(xs.shape[0], Hi, Wi)[1], xs, gout, cu_budget)
 
     def backward_weight(self, x, gout, cu_budget=0):
         """cu_budget: CUs this launch is sized for when it runs on the second stream (0 = all of them): the caller
         is about to launch an HBM-bound pass on the main stream that should get the remaining CUs."""
         B, Hp, Wp, _ = x.shape
+        self._wgrad(self.plan(B, Hp - 2, Wp - 2)[3], x, gout, cu_budget)
+
+    def _wgrad(self, desc, x, gout, cu_budget):
         side = self.side_stream
         if side is None:
-            ops.conv_wgrad(self.plan(B, Hp - 2, Wp - 2)[3], x, gout, self.store.g(self.name), cu_budget)
+            ops.conv_wgrad(desc, x, gout, self.store.g(self.name), cu_budget)
             return
         # the weight gradient only feeds the optimizer, so it runs on a second stream next to the
         # data-gradient chain (see WRNEngine.backward for the buffer-reuse ordering)
-        main = torch.cuda.current_stream(x.device)
-        side.wait_stream(main)
+        side.wait_stream(torch.cuda.current_stream(x.device))
         with torch.cuda.stream(side):
-            ops.conv_wgrad(self.plan(B, Hp - 2, Wp - 2)[3], x, gout, self.store.g(self.name), cu_budget)
+            ops.conv_wgrad(desc, x, gout, self.store.g(self.name), cu_budget)
 
 
 class SegOp:
@@ -1266,7 +1260,15 @@ class WRNEngine(_Engine):
 class ResNetEngine(_Engine):
     """CIFAR-style ResNet of the reference (nbdt/models/resnet.py:42-74 BasicBlock, :115-149 ResNet,
     :171-179 ResNet18): 3x3 stem, 4 stages of post-activation BasicBlocks, global average pool,
-    ``linear``.  State-dict names are the reference's (conv1, bn1, layerN.M.*, shortcut.0/1, linear)."""
+    ``linear``.  State-dict names are the reference's (conv1, bn1, layerN.M.*, shortcut.0/1, linear).
+
+    A residual block is data: a chain of main stages (conv, bn) -- two for a BasicBlock, three for a Bottleneck
+    (BottleneckEngine) -- plus an optional shortcut (sconv, sbn).  ``_block_stages`` is the recipe; forward() and
+    backward() walk whatever chain it made, so the cross-stream buffer protocol below exists once.  A new block type
+    overrides ``_block_stages``; a new stem overrides ``_stem_forward`` / ``_stem_backward``."""
+
+    # (GB/s per CU, time budget of bn1's confined pass at 128 images in us, min CUs, max CUs) or None: see backward()
+    res_share = (47.0, 15.0, 16, 128)
 
     def __init__(self, num_classes=10, num_blocks=(2, 2, 2, 2), device="cuda", seed=0):
         super().__init__(device, seed)
@@ -1278,20 +1280,35 @@ class ResNetEngine(_Engine):
         self.bn0 = self.bn("bn1", 64)
         self.blocks = []
         cin = 64
-        for i, (cout, stride0, n) in enumerate(zip((64, 128, 256, 512), (1, 2, 2, 2), num_blocks)):
+        # Parameters are created in the reference's module order -- per block conv1, bn1, conv2, bn2, [conv3, bn3], then
+        # shortcut.0, shortcut.1: the seeded generator is drawn from in creation order and every offset in the flat
+        # buffers follows from it, so reordering these calls changes the initial weights and every checkpoint's layout.
+        for i, (planes, stride0, n) in enumerate(zip((64, 128, 256, 512), (1, 2, 2, 2), num_blocks)):
             for j in range(n):
                 stride = stride0 if j == 0 else 1
-                pre = f"layer{i + 1}.{j}."
+                pre, k = f"layer{i + 1}.{j}.", f"l{i + 1}b{j}"
+                stages = self._block_stages(pre, cin, planes, stride)
+                cout = stages[-1][0].cout_real
                 short = stride != 1 or cin != cout
                 blk = {
-                    "conv1": self.conv(pre + "conv1.weight", cin, cout, 3, stride, init="torch_default"),
-                    "bn1": self.bn(pre + "bn1", cout),
-                    "conv2": self.conv(pre + "conv2.weight", cout, cout, 3, 1, init="torch_default"),
-                    "bn2": self.bn(pre + "bn2", cout),
                     "sconv": self.conv(pre + "shortcut.0.weight", cin, cout, 1, stride, init="torch_default") if short else None,
                     "sbn": self.bn(pre + "shortcut.1", cout) if short else None,
-                    "cin": cin, "cout": cout, "stride": stride, "key": f"l{i + 1}b{j}",
+                    "cin": cin, "cout": cout, "stride": stride, "key": k,
                 }
+                # what forward() / backward() iterate, resolved once (the small configurations run at the host's launch
+                # rate): per stage m its conv, bn, channels and the keys of its raw output t, its activation a and their
+                # gradients gt (alternating: the key lacks its parity) and ga
+                head, pairs = [], []
+                for m, (conv, bn, fusable) in enumerate(stages, 1):
+                    blk[f"conv{m}"], blk[f"bn{m}"] = conv, bn
+                    c = conv.cout_real
+                    if m > 1:               # backward's pair: conv m with stage m - 1
+                        pairs.append((conv, fusable) + prev)
+                    if m < len(stages):
+                        head.append((conv, bn, c, f"{k}.t{m}", f"{k}.a{m}"))
+                        prev = (bn, c, f"{k}.t{m}", f"{k}.a{m}", f"gt{m}_{c}_", f"ga{m}_{c}")
+                blk["head"], blk["last"] = tuple(head), (conv, bn, f"{k}.t{m}", f"gt{m}_{c}_")
+                blk["pairs"] = tuple(reversed(pairs))
                 self.blocks.append(blk)
                 cin = cout
         self.feat_c = cin
@@ -1302,8 +1319,6 @@ class ResNetEngine(_Engine):
         self._side = side_stream(self.device)     # weight gradients on a second stream (see WRNEngine)
         for c in self.convs:
             c.side_stream = self._side
-        # (GB/s per CU, time budget of bn1's confined pass at 128 images in us, min CUs, max CUs) or None: see backward()
-        self.res_share = (47.0, 15.0, 16, 128)
         dev = self.device
         # identity "BN" for the plain average-pool head (features are already post-ReLU)
         self._id_mean = torch.zeros(cin, device=dev)
@@ -1311,6 +1326,16 @@ class ResNetEngine(_Engine):
         self._id_gamma = torch.ones(cin, device=dev)
         self._id_beta = torch.zeros(cin, device=dev)
         self._id_dsum = torch.zeros(2 * cin, device=dev)
+
+    def _block_stages(self, pre, cin, planes, stride):
+        """The main chain of one block as [(conv, bn, fusable)], created in order.  BasicBlock: 3x3 (stride s) -> 3x3.
+        fusable: backward() may take the (this conv, previous stage's bn) pair in its fused / CU-sharing forms --
+        measured for this block's (conv2, bn1) only."""
+        return [self._stage(pre, 1, cin, planes, 3, stride), self._stage(pre, 2, planes, planes, 3, 1, fusable=True)]
+
+    def _stage(self, pre, m, cin, cout, k, stride, fusable=False):
+        return (self.conv(f"{pre}conv{m}.weight", cin, cout, k, stride, init="torch_default"), self.bn(f"{pre}bn{m}", cout),
+                fusable)
 
     def extra_param_views(self, buf):
         return {
@@ -1329,61 +1354,81 @@ class ResNetEngine(_Engine):
 
     classifier_names = ("linear.weight", "linear.bias")
 
-    def forward(self, img, training=None, head=True):
-        training = self.training if training is None else training
-        img = self._input(img)
+    def _stem_forward(self, img, training):
+        """conv1 -> bn1 -> ReLU; returns the first block's input."""
         B, _, H, W = img.shape
         t0 = self.buf("t0", B, H, W, 64)
         x = self.buf("a0", B, H, W, 64)
         ops.stem_conv(img, self.store.p("conv1.weight"), t0, 64)
         self.bn0.stats(t0, training)
         self.bn0.apply(t0, x, relu=True)
-        h, w = H, W
+        return x
+
+    def _stem_backward(self, g):
+        """From g = dL/d(first block's input): bn1's backward and conv1's weight gradient."""
+        B, Hp, Wp, _ = g.shape
+        gt0 = self.buf("gt0", B, Hp - 2, Wp - 2, 64)
+        self.bn0.backward(g, None, self.buf("t0", B, Hp - 2, Wp - 2, 64), gt0, relu=True)
+        ops.stem_wgrad(self._img, gt0, self.store.g("conv1.weight"), 64)
+
+    def forward(self, img, training=None, head=True):
+        training = self.training if training is None else training
+        img = self._input(img)
+        B = self._B
+        x = self._stem_forward(img, training)
+        h, w = x.shape[1] - 2, x.shape[2] - 2
+        fuse = training and self.fuse_stats
+        affine = not training and self.fuse_eval
         for blk in self.blocks:
-            k, s, cin, cout = blk["key"], blk["stride"], blk["cin"], blk["cout"]
-            ho, wo = h // s, w // s
-            a1 = self.buf(k + ".a1", B, ho, wo, cout)
-            out = self.buf(k + ".out", B, ho, wo, cout)
-            fuse = training and self.fuse_stats
-            if not training and self.fuse_eval:
-                # inference: every Conv-BN(-ReLU)(+shortcut) group of the BasicBlock is ONE launch
-                blk["conv1"].forward_affine(x, a1, blk["bn1"], act=1)
-                if blk["sconv"] is not None:
-                    sc = self.buf(f"sc{cout}", B, ho, wo, cout)
-                    blk["sconv"].forward_affine(x, sc, blk["sbn"], act=0)
-                    res = sc
-                else:
-                    res = x
-                blk["conv2"].forward_affine(a1, out, blk["bn2"], act=1, residual=res)
-                blk["x_in"] = x
-                x, h, w = out, ho, wo
-                continue
-            t1 = self.buf(k + ".t1", B, ho, wo, cout)     # raw conv outputs: only the training path keeps them
-            t2 = self.buf(k + ".t2", B, ho, wo, cout)
-            scr = self.partials(t1) if fuse else None
-            blk["conv1"].forward(x, t1, bn_scratch=scr)
-            blk["bn1"].stats(t1, training, fused=fuse)
-            blk["bn1"].apply(t1, a1, relu=True)
-            blk["conv2"].forward(a1, t2, bn_scratch=scr)
-            blk["bn2"].stats(t2, training, fused=fuse)
-            if blk["sconv"] is not None:
-                ts = self.buf(k + ".ts", B, ho, wo, cout)
-                sc = self.buf(f"sc{cout}", B, ho, wo, cout)
-                blk["sconv"].forward(x, ts, bn_scratch=scr)
-                blk["sbn"].stats(ts, training, fused=fuse)
-                blk["sbn"].apply(ts, sc, relu=False)
-                res = sc
-            else:
+            k, cout, sconv = blk["key"], blk["cout"], blk["sconv"]
+            y = x
+            if affine:
+                # inference: every Conv-BN(-ReLU)(+shortcut) group of the block is ONE launch
+                for conv, bn, c, _, ak in blk["head"]:
+                    h, w = h // conv.stride, w // conv.stride
+                    a = self.buf(ak, B, h, w, c)
+                    conv.forward_affine(y, a, bn, act=1)
+                    y = a
+                conv, bn, _, _ = blk["last"]
+                h, w = h // conv.stride, w // conv.stride
                 res = x
-            blk["bn2"].apply(t2, out, relu=True, residual=res)
+                if sconv is not None:
+                    res = self.buf(f"sc{cout}", B, h, w, cout)
+                    sconv.forward_affine(x, res, blk["sbn"], act=0)
+                out = self.buf(k + ".out", B, h, w, cout)
+                conv.forward_affine(y, out, bn, act=1, residual=res)
+                blk["x_in"] = x
+                x = out
+                continue
+            for conv, bn, c, tk, ak in blk["head"]:
+                h, w = h // conv.stride, w // conv.stride
+                t = self.buf(tk, B, h, w, c)              # raw conv outputs: only the training path keeps them
+                conv.forward(y, t, bn_scratch=self.partials(t) if fuse else None)
+                bn.stats(t, training, fused=fuse)
+                y = self.buf(ak, B, h, w, c)
+                bn.apply(t, y, relu=True)
+            conv, bn, tk, _ = blk["last"]
+            h, w = h // conv.stride, w // conv.stride
+            t = self.buf(tk, B, h, w, cout)
+            conv.forward(y, t, bn_scratch=self.partials(t) if fuse else None)
+            bn.stats(t, training, fused=fuse)
+            res = x
+            if sconv is not None:
+                ts = self.buf(k + ".ts", B, h, w, cout)
+                res = self.buf(f"sc{cout}", B, h, w, cout)
+                sconv.forward(x, ts, bn_scratch=self.partials(ts) if fuse else None)
+                blk["sbn"].stats(ts, training, fused=fuse)
+                blk["sbn"].apply(ts, res, relu=False)
+            out = self.buf(k + ".out", B, h, w, cout)
+            bn.apply(t, out, relu=True, residual=res)
             blk["x_in"] = x
-            x, h, w = out, ho, wo
+            x = out
         self._x_last, self._hw = x, (h, w)
         return self._pool_head(x, self._id_mean, self._id_rstd, self._id_gamma, self._id_beta, head)
 
     def backward(self, gz, comm=None, gpooled=None):
         self._begin_backward(comm)
-        B, st = self._B, self.store
+        B = self._B
         gpool = self._head_backward(gz, gpooled)
         h, w = self._hw
         g = self.buf(f"g_out{self.feat_c}", B, h, w, self.feat_c)
@@ -1392,75 +1437,76 @@ class ResNetEngine(_Engine):
         ops.pool_bn_bwd_apply(gpool, self._x_last, self._id_mean, self._id_rstd, self._id_gamma, self._id_beta,
                               self._id_dsum, g)
         two_streams = self._side is not None and self._overlap
+        # how a fusable (conv, previous bn) pair runs -- the same for every block of a step:
+        # fused: the conv's data gradient is dL/d(relu(bn(t))): its epilogue also emits that bn's backward sums (as in
+        #   WRNEngine's fused order), so the gradient is not re-read for them -- one HBM-bound pass fewer per block
+        # share: CU sharing as in WRNEngine (fused-sums form): the conv's weight gradient is issued AFTER its data gradient,
+        #   sized for 256 - n CUs, and the bn's elementwise pass that follows on this stream is confined to n CUs -- in the
+        #   plain order the pass's blocks waited for the weight gradient's to leave their CUs (bn_bwd_fold_partials: 42 us
+        #   in the trace for 5 us of work, profiles/r06_c4_step_dump_before.txt)
+        fused = self.fuse_bn1_bwd and self.act_dtype == torch.bfloat16
+        share = (fused and self.res_share is not None and (two_streams or self.debug_share_serial)
+                 and ops.cu_topology_is_mi355x(self.device))
+        if share:
+            gbps, us, lo, hi_cus = self.res_share
         for i, blk in self._units_backward(self.blocks, comm):
-            # the buffers a weight gradient reads (gt2 / gt1 / gts) alternate between consecutive blocks, and so does
+            # the buffers a weight gradient reads (every gt / gts) alternate between consecutive blocks, and so does
             # the block's input gradient: the block in flight never overwrites what the previous one's may be reading
-            k, s, cin, cout = blk["key"], blk["stride"], blk["cin"], blk["cout"]
-            ho, wo = h, w
-            hi, wi = ho * s, wo * s
+            k, s, cin, cout, sconv = blk["key"], blk["stride"], blk["cin"], blk["cout"], blk["sconv"]
+            hi, wi = h * s, w * s
             tag = ("@" + k) if self.debug_keep else ""
             par = i & 1
-            t1 = self.buf(k + ".t1", B, ho, wo, cout)
-            a1 = self.buf(k + ".a1", B, ho, wo, cout)
-            t2 = self.buf(k + ".t2", B, ho, wo, cout)
-            out = self.buf(k + ".out", B, ho, wo, cout)
-            gt2 = self.buf(f"gt2_{cout}_{par}{tag}", B, ho, wo, cout)
-            ga1 = self.buf(f"ga1_{cout}{tag}", B, ho, wo, cout)
-            gt1 = self.buf(f"gt1_{cout}_{par}{tag}", B, ho, wo, cout)
             g_in = self.buf(f"g_in{cin}_{hi}_{par ^ 1}{tag}", B, hi, wi, cin)
             x_in = blk["x_in"]
-            if blk["sconv"] is not None:
-                gsc = self.buf(f"gsc_{cout}{tag}", B, ho, wo, cout)
-                gts = self.buf(f"gts_{cout}_{par}{tag}", B, ho, wo, cout)
-                blk["bn2"].backward(g, out, t2, gt2, relu=True, g_resid=gsc)
+            _, bn, tk, gtk = blk["last"]
+            gt = self.buf(f"{gtk}{par}{tag}", B, h, w, cout)
+            if sconv is not None:
+                gsc = g_resid = self.buf(f"gsc_{cout}{tag}", B, h, w, cout)
+                gts = self.buf(f"gts_{cout}_{par}{tag}", B, h, w, cout)
             else:
-                # identity shortcut: the masked gradient IS part of the block-input gradient
-                blk["bn2"].backward(g, out, t2, gt2, relu=True, g_resid=g_in)
-            share = (self.res_share is not None and (two_streams or self.debug_share_serial) and self.fuse_bn1_bwd
-                     and self.act_dtype == torch.bfloat16 and ops.cu_topology_is_mi355x(self.device))
-            if share:
-                # CU sharing as in WRNEngine (fused-sums form): conv2's weight gradient is issued AFTER its data gradient,
-                # sized for 256 - n CUs, and bn1's elementwise pass that follows on this stream is confined to n CUs --
-                # in the plain order the pass's blocks waited for the weight gradient's to leave their CUs
-                # (bn_bwd_fold_partials: 42 us in the trace for 5 us of work, profiles/r06_c4_step_dump_before.txt)
-                gbps, us, lo, hi_cus = self.res_share
-                blk["conv2"].backward_data(gt2, ga1, bn=blk["bn1"], bn_x=t1, partials=self.partials(t1))
-                budget, n1 = ops.plan_cu_share(blk["conv2"].plan(B, ho, wo)[3], B * ho * wo * cout, 3, gbps,
-                                               us * B / 128.0, lo, hi_cus)
-                blk["conv2"].backward_weight(a1, gt2, cu_budget=budget)
-                blk["bn1"].backward_fused(ga1, t1, gt1, self.partials(t1), cus=n1)
-            elif self.fuse_bn1_bwd and self.act_dtype == torch.bfloat16:
-                # conv2's data gradient is dL/d(relu(bn1(t1))): its epilogue also emits bn1's backward sums (as in
-                # WRNEngine's fused order), so ga1 is not re-read for them -- one HBM-bound pass fewer per block
-                blk["conv2"].backward_weight(a1, gt2)
-                blk["conv2"].backward_data(gt2, ga1, bn=blk["bn1"], bn_x=t1, partials=self.partials(t1))
-                blk["bn1"].backward_fused(ga1, t1, gt1, self.partials(t1))
+                g_resid = g_in      # identity shortcut: the masked gradient IS part of the block-input gradient
+            bn.backward(g, self.buf(k + ".out", B, h, w, cout), self.buf(tk, B, h, w, cout), gt, relu=True, g_resid=g_resid)
+            hh, ww = h, w
+            for conv, fusable, bn, c, tk, ak, gtk, gak in blk["pairs"]:     # conv m with stage m - 1, m = n ... 2
+                hh, ww = hh * conv.stride, ww * conv.stride
+                t, a = self.buf(tk, B, hh, ww, c), self.buf(ak, B, hh, ww, c)
+                ga = self.buf(gak + tag, B, hh, ww, c)
+                gt_prev = self.buf(f"{gtk}{par}{tag}", B, hh, ww, c)
+                if share and fusable:
+                    conv.backward_data(gt, ga, bn=bn, bn_x=t, partials=self.partials(t))
+                    budget, n1 = ops.plan_cu_share(conv.plan(B, hh, ww)[3], B * hh * ww * c, 3, gbps, us * B / 128.0, lo,
+                                                   hi_cus)
+                    conv.backward_weight(a, gt, cu_budget=budget)
+                    bn.backward_fused(ga, t, gt_prev, self.partials(t), cus=n1)
+                elif fused and fusable:
+                    conv.backward_weight(a, gt)
+                    conv.backward_data(gt, ga, bn=bn, bn_x=t, partials=self.partials(t))
+                    bn.backward_fused(ga, t, gt_prev, self.partials(t))
+                else:
+                    conv.backward_weight(a, gt)
+                    conv.backward_data(gt, ga)
+                    bn.backward(ga, None, t, gt_prev, relu=True)
+                gt = gt_prev
+            conv1 = blk["conv1"]
+            conv1.backward_weight(x_in, gt)
+            if sconv is not None:
+                conv1.backward_data(gt, g_in)
+                blk["sbn"].backward(gsc, None, self.buf(k + ".ts", B, h, w, cout), gts, relu=False)
+                sconv.backward_weight(x_in, gts)
+                sconv.backward_data(gts, g_in, accumulate=True)      # after conv1's plain one
             else:
-                blk["conv2"].backward_weight(a1, gt2)
-                blk["conv2"].backward_data(gt2, ga1)
-                blk["bn1"].backward(ga1, None, t1, gt1, relu=True)
-            blk["conv1"].backward_weight(x_in, gt1)
-            if blk["sconv"] is not None:
-                blk["conv1"].backward_data(gt1, g_in)
-                ts = self.buf(k + ".ts", B, ho, wo, cout)
-                blk["sbn"].backward(gsc, None, ts, gts, relu=False)
-                blk["sconv"].backward_weight(x_in, gts)
-                blk["sconv"].backward_data(gts, g_in, accumulate=True)
-            else:
-                blk["conv1"].backward_data(gt1, g_in, accumulate=True)
+                conv1.backward_data(gt, g_in, accumulate=True)
             blk["dbg"] = {"g_out": g, "g_in": g_in}
             g, h, w = g_in, hi, wi
-        gt0 = self.buf("gt0", B, h, w, 64)
-        self.bn0.backward(g, None, self.buf("t0", B, h, w, 64), gt0, relu=True)
-        ops.stem_wgrad(self._img, gt0, st.g("conv1.weight"), 64)
+        self._stem_backward(g)
         self._end_backward(comm)
 
 
 class BottleneckEngine(ResNetEngine):
     """CIFAR-style Bottleneck ResNet of the reference (nbdt/models/resnet.py:77-112 Bottleneck, expansion 4; :193-223
-    ResNet50 / 101 / 152): ResNetEngine's stem, stage widths, head, gradient buckets and backward protocol around blocks of
-    1x1 -> 3x3 (stride s) -> 1x1 (x 4).  State-dict names are the reference's (layerN.M.conv1/bn1/conv2/bn2/conv3/bn3,
-    shortcut.0/1, linear); parameters are created in the reference's module order.
+    ResNet50 / 101 / 152): ResNetEngine -- its stem, stage widths, head, gradient buckets, forward() and backward() -- with
+    blocks of 1x1 -> 3x3 (stride s) -> 1x1 (x 4).  State-dict names are the reference's (layerN.M.conv1/bn1/conv2/bn2/
+    conv3/bn3, shortcut.0/1, linear); parameters are created in the reference's module order.
 
     While ``pointwise`` is true the stride-1 1x1 convolutions -- conv1, conv3 and layer1.0's shortcut -- run on the
     pointwise GEMM kernel (csrc/conv_pw.hip): every data gradient, the eval-mode unfused forward, and the training
@@ -1472,53 +1518,19 @@ class BottleneckEngine(ResNetEngine):
 
     expansion = 4
 
+    # No CU sharing: ResNetEngine confines bn1's backward pass beside conv2's weight gradient with a plan measured for
+    # BasicBlocks; nothing has been measured for these blocks, so every launch gets the whole chip.
+    res_share = None
+
     def __init__(self, num_classes=10, num_blocks=(3, 4, 6, 3), device="cuda", seed=0):
-        _Engine.__init__(self, device, seed)
-        self.num_classes = num_classes
-        gen = self.gen
-        self.stem_c = 64
-        b0 = 1.0 / math.sqrt(27)
-        self.store.add("conv1.weight", (64, 3, 3, 3), lambda v: v.uniform_(-b0, b0, generator=gen))
-        self.bn0 = self.bn("bn1", 64)
-        self.blocks = []
-        cin = 64
-        for i, (planes, stride0, n) in enumerate(zip((64, 128, 256, 512), (1, 2, 2, 2), num_blocks)):
-            cout = self.expansion * planes
-            for j in range(n):
-                stride = stride0 if j == 0 else 1
-                pre = f"layer{i + 1}.{j}."
-                short = stride != 1 or cin != cout
-                blk = {
-                    "conv1": self.conv(pre + "conv1.weight", cin, planes, 1, 1, init="torch_default"),
-                    "bn1": self.bn(pre + "bn1", planes),
-                    "conv2": self.conv(pre + "conv2.weight", planes, planes, 3, stride, init="torch_default"),
-                    "bn2": self.bn(pre + "bn2", planes),
-                    "conv3": self.conv(pre + "conv3.weight", planes, cout, 1, 1, init="torch_default"),
-                    "bn3": self.bn(pre + "bn3", cout),
-                    "sconv": self.conv(pre + "shortcut.0.weight", cin, cout, 1, stride, init="torch_default") if short else None,
-                    "sbn": self.bn(pre + "shortcut.1", cout) if short else None,
-                    "cin": cin, "planes": planes, "cout": cout, "stride": stride, "key": f"l{i + 1}b{j}",
-                }
-                self.blocks.append(blk)
-                cin = cout
-        self.feat_c = cin
-        kb = 1.0 / math.sqrt(cin)
-        self.store.add("linear.weight", (num_classes, cin), lambda v: v.uniform_(-kb, kb, generator=gen))
-        self.store.add("linear.bias", (num_classes,), lambda v: v.uniform_(-kb, kb, generator=gen))
-        self.finalize()
-        self._side = side_stream(self.device)     # weight gradients on a second stream (see WRNEngine)
-        for c in self.convs:
-            c.side_stream = self._side
-        # No CU sharing: ResNetEngine confines bn1's backward pass beside conv2's weight gradient with a plan measured for
-        # BasicBlocks; nothing has been measured for these blocks, so every launch gets the whole chip.
-        self.res_share = None
+        super().__init__(num_classes, num_blocks, device, seed)
         self.pointwise = True
-        dev = self.device
-        self._id_mean = torch.zeros(cin, device=dev)
-        self._id_rstd = torch.ones(cin, device=dev)
-        self._id_gamma = torch.ones(cin, device=dev)
-        self._id_beta = torch.zeros(cin, device=dev)
-        self._id_dsum = torch.zeros(2 * cin, device=dev)
+
+    def _block_stages(self, pre, cin, planes, stride):
+        """1x1 (cin -> planes) -> 3x3 (stride s) -> 1x1 (-> 4 planes); every pair's backward in the plain form (nothing
+        else has been measured for these blocks)."""
+        return [self._stage(pre, 1, cin, planes, 1, 1), self._stage(pre, 2, planes, planes, 3, stride),
+                self._stage(pre, 3, planes, self.expansion * planes, 1, 1)]
 
     @property
     def pointwise(self):
@@ -1529,121 +1541,6 @@ class BottleneckEngine(ResNetEngine):
         self._pointwise = bool(on)
         for c in self.convs:
             c.pointwise = self._pointwise
-
-    def forward(self, img, training=None, head=True):
-        training = self.training if training is None else training
-        img = self._input(img)
-        B, _, H, W = img.shape
-        t0 = self.buf("t0", B, H, W, 64)
-        x = self.buf("a0", B, H, W, 64)
-        ops.stem_conv(img, self.store.p("conv1.weight"), t0, 64)
-        self.bn0.stats(t0, training)
-        self.bn0.apply(t0, x, relu=True)
-        h, w = H, W
-        for blk in self.blocks:
-            k, s, p, cout = blk["key"], blk["stride"], blk["planes"], blk["cout"]
-            ho, wo = h // s, w // s
-            a1 = self.buf(k + ".a1", B, h, w, p)
-            a2 = self.buf(k + ".a2", B, ho, wo, p)
-            out = self.buf(k + ".out", B, ho, wo, cout)
-            fuse = training and self.fuse_stats
-            if not training and self.fuse_eval:
-                # inference: every Conv-BN(-ReLU)(+shortcut) group of the block is ONE launch (three or four per block)
-                blk["conv1"].forward_affine(x, a1, blk["bn1"], act=1)
-                blk["conv2"].forward_affine(a1, a2, blk["bn2"], act=1)
-                if blk["sconv"] is not None:
-                    sc = self.buf(f"sc{cout}", B, ho, wo, cout)
-                    blk["sconv"].forward_affine(x, sc, blk["sbn"], act=0)
-                    res = sc
-                else:
-                    res = x
-                blk["conv3"].forward_affine(a2, out, blk["bn3"], act=1, residual=res)
-                blk["x_in"] = x
-                x, h, w = out, ho, wo
-                continue
-            t1 = self.buf(k + ".t1", B, h, w, p)          # raw conv outputs: only the training path keeps them
-            t2 = self.buf(k + ".t2", B, ho, wo, p)
-            t3 = self.buf(k + ".t3", B, ho, wo, cout)
-            blk["conv1"].forward(x, t1, bn_scratch=self.partials(t1) if fuse else None)
-            blk["bn1"].stats(t1, training, fused=fuse)
-            blk["bn1"].apply(t1, a1, relu=True)
-            blk["conv2"].forward(a1, t2, bn_scratch=self.partials(t2) if fuse else None)
-            blk["bn2"].stats(t2, training, fused=fuse)
-            blk["bn2"].apply(t2, a2, relu=True)
-            blk["conv3"].forward(a2, t3, bn_scratch=self.partials(t3) if fuse else None)
-            blk["bn3"].stats(t3, training, fused=fuse)
-            if blk["sconv"] is not None:
-                ts = self.buf(k + ".ts", B, ho, wo, cout)
-                sc = self.buf(f"sc{cout}", B, ho, wo, cout)
-                blk["sconv"].forward(x, ts, bn_scratch=self.partials(ts) if fuse else None)
-                blk["sbn"].stats(ts, training, fused=fuse)
-                blk["sbn"].apply(ts, sc, relu=False)
-                res = sc
-            else:
-                res = x
-            blk["bn3"].apply(t3, out, relu=True, residual=res)
-            blk["x_in"] = x
-            x, h, w = out, ho, wo
-        self._x_last, self._hw = x, (h, w)
-        return self._pool_head(x, self._id_mean, self._id_rstd, self._id_gamma, self._id_beta, head)
-
-    def backward(self, gz, comm=None, gpooled=None):
-        self._begin_backward(comm)
-        B, st = self._B, self.store
-        gpool = self._head_backward(gz, gpooled)
-        h, w = self._hw
-        g = self.buf(f"g_out{self.feat_c}", B, h, w, self.feat_c)
-        ops.pool_bn_bwd_apply(gpool, self._x_last, self._id_mean, self._id_rstd, self._id_gamma, self._id_beta,
-                              self._id_dsum, g)
-        for i, blk in self._units_backward(self.blocks, comm):
-            # as in ResNetEngine.backward: the buffers a weight gradient reads on the second stream (gt3 / gt2 / gt1 / gts)
-            # alternate between consecutive blocks, and so does the block's input gradient
-            k, s, cin, p, cout = blk["key"], blk["stride"], blk["cin"], blk["planes"], blk["cout"]
-            ho, wo = h, w
-            hi, wi = ho * s, wo * s
-            tag = ("@" + k) if self.debug_keep else ""
-            par = i & 1
-            t1 = self.buf(k + ".t1", B, hi, wi, p)
-            a1 = self.buf(k + ".a1", B, hi, wi, p)
-            t2 = self.buf(k + ".t2", B, ho, wo, p)
-            a2 = self.buf(k + ".a2", B, ho, wo, p)
-            t3 = self.buf(k + ".t3", B, ho, wo, cout)
-            out = self.buf(k + ".out", B, ho, wo, cout)
-            gt3 = self.buf(f"gt3_{cout}_{par}{tag}", B, ho, wo, cout)
-            ga2 = self.buf(f"ga2_{p}{tag}", B, ho, wo, p)
-            gt2 = self.buf(f"gt2_{p}_{par}{tag}", B, ho, wo, p)
-            ga1 = self.buf(f"ga1_{p}{tag}", B, hi, wi, p)
-            gt1 = self.buf(f"gt1_{p}_{par}{tag}", B, hi, wi, p)
-            g_in = self.buf(f"g_in{cin}_{hi}_{par ^ 1}{tag}", B, hi, wi, cin)
-            x_in = blk["x_in"]
-            if blk["sconv"] is not None:
-                gsc = self.buf(f"gsc_{cout}{tag}", B, ho, wo, cout)
-                gts = self.buf(f"gts_{cout}_{par}{tag}", B, ho, wo, cout)
-                blk["bn3"].backward(g, out, t3, gt3, relu=True, g_resid=gsc)
-            else:
-                # identity shortcut: the masked gradient IS part of the block-input gradient
-                blk["bn3"].backward(g, out, t3, gt3, relu=True, g_resid=g_in)
-            blk["conv3"].backward_weight(a2, gt3)
-            blk["conv3"].backward_data(gt3, ga2)
-            blk["bn2"].backward(ga2, None, t2, gt2, relu=True)
-            blk["conv2"].backward_weight(a1, gt2)
-            blk["conv2"].backward_data(gt2, ga1)
-            blk["bn1"].backward(ga1, None, t1, gt1, relu=True)
-            blk["conv1"].backward_weight(x_in, gt1)
-            if blk["sconv"] is not None:
-                blk["conv1"].backward_data(gt1, g_in)
-                ts = self.buf(k + ".ts", B, ho, wo, cout)
-                blk["sbn"].backward(gsc, None, ts, gts, relu=False)
-                blk["sconv"].backward_weight(x_in, gts)
-                blk["sconv"].backward_data(gts, g_in, accumulate=True)     # after conv1's plain one
-            else:
-                blk["conv1"].backward_data(gt1, g_in, accumulate=True)
-            blk["dbg"] = {"g_out": g, "g_in": g_in}
-            g, h, w = g_in, hi, wi
-        gt0 = self.buf("gt0", B, h, w, 64)
-        self.bn0.backward(g, None, self.buf("t0", B, h, w, 64), gt0, relu=True)
-        ops.stem_wgrad(self._img, gt0, st.g("conv1.weight"), 64)
-        self._end_backward(comm)
 
 
 def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5e-4, comm=None, fused_head=True,
