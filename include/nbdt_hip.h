@@ -799,6 +799,34 @@ int nbdt_resized_crop_batch(const void* src, int32_t src_dtype, const int64_t* l
 int nbdt_resized_crop_band_rows(int32_t H, int32_t W, int32_t rs_h, int32_t rs_w, int32_t win_top, int32_t win_left,
                                 int32_t out_h, int32_t out_w);
 
+/* ------------------------------------------------------------------ rank-sharded datasets (nbdt_version() >= 114) */
+/* nbdt_augment_batch / nbdt_resized_crop_batch for a rank that keeps only its contiguous part of the dataset: src and
+ * labels_src hold the N samples [index_base, index_base + N) of a larger dataset, and index[] still holds indices into
+ * that larger dataset.  Every other argument, every output and the arithmetic are those of the unsharded entry.
+ *
+ *   draw    from index[i] itself: the crop / flip / box of a sample stays a pure function of (seed, epoch, dataset index),
+ *           whichever rank holds the sample and however many ranks there are
+ *   gather  image row and label at index[i] - index_base
+ *
+ * index_base >= 0 and index_base + N must fit int64 (NBDT_EINVAL otherwise).  The unsharded entries ARE these with
+ * index_base = 0: one kernel per family, the same bits.
+ *
+ * Out-of-range indices.  index is device data.  The kernel forms index[i] - index_base mod 2^64 and compares it unsigned
+ * with N, so an index outside [index_base, index_base + N) -- another rank's sample, a negative value, anything -- never
+ * becomes an address: the sample is written as an all-zero image with label -1 and zero params, as in the unsharded
+ * entries.  nbdt/data.py refuses such an index on the host (ValueError) whenever the index tensor is host data. */
+int nbdt_augment_batch_sharded(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index,
+                               int64_t index_base, int32_t B, int64_t N, int32_t H, int32_t W, int32_t pad, int32_t flip,
+                               const float* mean, const float* std, const float* fill, uint64_t seed, uint64_t epoch,
+                               const int8_t* params_in, float* out, int64_t* labels_out, int8_t* params_out, void* stream);
+int nbdt_resized_crop_batch_sharded(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index,
+                                    int64_t index_base, int32_t B, int64_t N, int32_t H, int32_t W, int32_t rs_h,
+                                    int32_t rs_w, int32_t win_top, int32_t win_left, int32_t out_h, int32_t out_w,
+                                    int32_t flip, const float* mean, const float* std, const double* scale,
+                                    const double* ratio, const double* ratio_table, uint64_t seed, uint64_t epoch,
+                                    const int32_t* params_in, float* out, int64_t* labels_out, int32_t* params_out,
+                                    void* stream);
+
 /* ------------------------------------------------------------------ measurement probe (not on the product path) */
 /* A register-only stream of independent v_mfma_f32_32x32x16_bf16 on `blocks` CUs (one 512-thread block each, two waves
  * per SIMD): every wave issues iters x 16 of them (x 32768 flop).  bench.py times the launch for `roofline.mfma_stream`

@@ -35,9 +35,15 @@ __device__ __forceinline__ float pick3(const float* v, int c) { return c == 0 ? 
 // most NBDT_AUGMENT_LDS_BYTES); else every element is a guarded global read (fp32 sources, ImageNet-sized uint8 images).
 // Every address is formed only after its index has been checked: idx against [0, N), (sy, sx) against the image, and
 // (dy, dx) are clamped to [0, 2 * pad] whatever params_in holds.
+//
+// A shard (nbdt_augment_batch_sharded): src / labels_src hold the N samples [index_base, index_base + N) of a larger
+// dataset and index[] holds that dataset's indices.  The draw hashes index[b] itself, the gather reads row
+// index[b] - index_base: a sample gets the crop it gets from the whole dataset.  The difference is taken mod 2^64 and
+// compared unsigned, so no index, however far outside the shard, passes as a row of it (the entry bounds index_base).
 template <bool U8, bool LDS>
 __global__ __launch_bounds__(256) void augment_kernel(const void* __restrict__ src, const long long* __restrict__ labels_src,
-                                                      const long long* __restrict__ index, long long N, int H, int W,
+                                                      const long long* __restrict__ index, long long index_base,
+                                                      long long N, int H, int W,
                                                       int pad, int flip_on, AugStats st, unsigned long long key,
                                                       const signed char* __restrict__ params_in, int vec_in, int vec_out,
                                                       float* __restrict__ out, long long* __restrict__ labels_out,
@@ -45,8 +51,9 @@ __global__ __launch_bounds__(256) void augment_kernel(const void* __restrict__ s
   extern __shared__ __attribute__((aligned(16))) unsigned char tile[];  // [3][H][W] (LDS only)
   const int b = blockIdx.x, tid = threadIdx.x;
   const int n = 3 * H * W;
-  const long long idx = index[b];
-  const bool valid = idx >= 0 && idx < N;
+  const long long gidx = index[b];                 // the dataset's index: what the draw hashes
+  const unsigned long long idx = (unsigned long long)gidx - (unsigned long long)index_base;      // the row held here
+  const bool valid = idx < (unsigned long long)N;
   float* o = out + (size_t)b * n;
   int dy = 0, dx = 0, fl = 0;
   if (valid) {
@@ -57,7 +64,7 @@ __global__ __launch_bounds__(256) void augment_kernel(const void* __restrict__ s
       dy = dy < 0 ? 0 : (dy > 2 * pad ? 2 * pad : dy);
       dx = dx < 0 ? 0 : (dx > 2 * pad ? 2 * pad : dx);
     } else {
-      const unsigned long long r = mix64(key ^ ((unsigned long long)idx * 0xD1342543DE82EF95ull));
+      const unsigned long long r = mix64(key ^ ((unsigned long long)gidx * 0xD1342543DE82EF95ull));
       const unsigned span = 2u * (unsigned)pad + 1u;
       dy = (int)((((unsigned)r & 0xFFFFFFu) * span) >> 24);
       dx = (int)((((unsigned)(r >> 24) & 0xFFFFFFu) * span) >> 24);
@@ -122,12 +129,14 @@ __global__ __launch_bounds__(256) void augment_kernel(const void* __restrict__ s
 
 }  // namespace
 
-extern "C" int nbdt_augment_batch(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index,
-                                  int32_t B, int64_t N, int32_t H, int32_t W, int32_t pad, int32_t flip,
-                                  const float* mean, const float* std, const float* fill, uint64_t seed, uint64_t epoch,
-                                  const int8_t* params_in, float* out, int64_t* labels_out, int8_t* params_out,
-                                  void* stream) {
+extern "C" int nbdt_augment_batch_sharded(const void* src, int32_t src_dtype, const int64_t* labels_src,
+                                          const int64_t* index, int64_t index_base, int32_t B, int64_t N, int32_t H,
+                                          int32_t W, int32_t pad, int32_t flip, const float* mean, const float* std,
+                                          const float* fill, uint64_t seed, uint64_t epoch, const int8_t* params_in,
+                                          float* out, int64_t* labels_out, int8_t* params_out, void* stream) {
   NBDT_REQUIRE(src && labels_src && index && out && labels_out, "null argument");
+  NBDT_REQUIRE(N <= 0 || (index_base >= 0 && index_base <= INT64_MAX - N),
+               "index_base must be >= 0 and index_base + N must fit int64");
   NBDT_REQUIRE(src_dtype == NBDT_U8 || src_dtype == NBDT_F32, "the dataset is uint8 (NBDT_U8) or fp32 (NBDT_F32)");
   NBDT_REQUIRE(B > 0, "empty batch");
   NBDT_REQUIRE(N > 0, "empty dataset");
@@ -153,16 +162,26 @@ extern "C" int nbdt_augment_batch(const void* src, int32_t src_dtype, const int6
   signed char* pout = (signed char*)params_out;
   hipStream_t s = (hipStream_t)stream;
   if (src_dtype == NBDT_F32) {
-    hipLaunchKernelGGL((augment_kernel<false, false>), dim3(B), dim3(256), 0, s, src, ls, ix, (long long)N, H, W, pad, flip,
-                       st, key, pin, 0, vec_out, out, lo, pout);
+    hipLaunchKernelGGL((augment_kernel<false, false>), dim3(B), dim3(256), 0, s, src, ls, ix, (long long)index_base,
+                       (long long)N, H, W, pad, flip, st, key, pin, 0, vec_out, out, lo, pout);
   } else if (n <= NBDT_AUGMENT_LDS_BYTES) {
     const int vec_in = (n % 16 == 0 && (uintptr_t)src % 16 == 0) ? 1 : 0;
     hipLaunchKernelGGL((augment_kernel<true, true>), dim3(B), dim3(256), (size_t)((n + 15) & ~15), s, src, ls, ix,
-                       (long long)N, H, W, pad, flip, st, key, pin, vec_in, vec_out, out, lo, pout);
+                       (long long)index_base, (long long)N, H, W, pad, flip, st, key, pin, vec_in, vec_out, out, lo, pout);
   } else {
-    hipLaunchKernelGGL((augment_kernel<true, false>), dim3(B), dim3(256), 0, s, src, ls, ix, (long long)N, H, W, pad, flip,
-                       st, key, pin, 0, vec_out, out, lo, pout);
+    hipLaunchKernelGGL((augment_kernel<true, false>), dim3(B), dim3(256), 0, s, src, ls, ix, (long long)index_base,
+                       (long long)N, H, W, pad, flip, st, key, pin, 0, vec_out, out, lo, pout);
   }
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;
+}
+
+// the whole dataset is the shard at base 0: the same kernels, the same bits
+extern "C" int nbdt_augment_batch(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index,
+                                  int32_t B, int64_t N, int32_t H, int32_t W, int32_t pad, int32_t flip,
+                                  const float* mean, const float* std, const float* fill, uint64_t seed, uint64_t epoch,
+                                  const int8_t* params_in, float* out, int64_t* labels_out, int8_t* params_out,
+                                  void* stream) {
+  return nbdt_augment_batch_sharded(src, src_dtype, labels_src, index, 0, B, N, H, W, pad, flip, mean, std, fill, seed,
+                                    epoch, params_in, out, labels_out, params_out, stream);
 }

@@ -36,6 +36,7 @@ struct RcArgs {
   const unsigned char* src;
   const long long* labels_src;
   const long long* index;
+  long long index_base;        // src / labels_src hold the samples [index_base, index_base + N) of the dataset index[] names
   long long N;
   int H, W;
   int rs_h, rs_w;              // the box is resampled to rs_h x rs_w ...
@@ -106,7 +107,7 @@ __device__ inline void draw_box(const RcArgs& a, unsigned long long base, int& t
 }
 
 // (top, left, h, w, flip) of the block's sample: drawn, or params_in clamped into the image
-__device__ inline void sample_params(const RcArgs& a, int b, long long idx, int* p) {
+__device__ inline void sample_params(const RcArgs& a, int b, long long gidx, int* p) {
   int top, left, h, w, fl;
   if (a.params_in) {
     const int* q = a.params_in + (size_t)b * 5;
@@ -116,7 +117,7 @@ __device__ inline void sample_params(const RcArgs& a, int b, long long idx, int*
     h = h < 1 ? 1 : (h > a.H - top ? a.H - top : h);
     w = w < 1 ? 1 : (w > a.W - left ? a.W - left : w);
   } else {
-    const unsigned long long base = mix64(a.key ^ ((unsigned long long)idx * 0xD1342543DE82EF95ull));
+    const unsigned long long base = mix64(a.key ^ ((unsigned long long)gidx * 0xD1342543DE82EF95ull));
     draw_box(a, base, top, left, h, w);
     fl = a.flip_on ? (int)(base >> 63) : 0;
   }
@@ -160,21 +161,24 @@ __device__ __forceinline__ int clip8(int acc) {
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
 
-__device__ __forceinline__ void write_header(const RcArgs& a, int b, bool valid, long long idx, const int* p) {
+__device__ __forceinline__ void write_header(const RcArgs& a, int b, bool valid, unsigned long long idx, const int* p) {
   a.labels_out[b] = valid ? a.labels_src[idx] : -1ll;
   if (a.params_out)
     for (int k = 0; k < 5; ++k) a.params_out[(size_t)b * 5 + k] = valid ? p[k] : 0;
 }
 
 // grid (bands, B).  Every address is formed only after its index has been checked: idx against [0, N), the box against the
-// image (sample_params), taps against the box (Axis::bounds), LDS rows against a.srows.
+// image (sample_params), taps against the box (Axis::bounds), LDS rows against a.srows.  idx is index[b] - index_base mod
+// 2^64, compared unsigned (nbdt_resized_crop_batch_sharded; base 0 is the whole dataset): the draw hashes index[b], rows
+// and labels are read at idx.
 __global__ __launch_bounds__(256) void resized_crop_lds(const RcArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   __shared__ int hdr[8];
   const int tid = threadIdx.x, b = blockIdx.y, y0 = blockIdx.x * a.band;
   const int rows = min(a.band, a.out_h - y0);
-  const long long idx = a.index[b];
-  const bool valid = idx >= 0 && idx < a.N;
+  const long long gidx = a.index[b];               // the dataset's index: what the draw hashes
+  const unsigned long long idx = (unsigned long long)gidx - (unsigned long long)a.index_base;    // the row held here
+  const bool valid = idx < (unsigned long long)a.N;
   const size_t n_out = (size_t)a.out_h * a.out_w;
   float* o = a.out + (size_t)b * 3 * n_out;
   if (!valid) {      // (block-uniform) a zero image, label -1, no source address formed
@@ -187,7 +191,7 @@ __global__ __launch_bounds__(256) void resized_crop_lds(const RcArgs a) {
     return;
   }
   if (tid == 0) {
-    sample_params(a, b, idx, hdr);
+    sample_params(a, b, gidx, hdr);
     if (blockIdx.x == 0) write_header(a, b, true, idx, hdr);
   }
   __syncthreads();
@@ -302,8 +306,9 @@ __global__ __launch_bounds__(256) void resized_crop_lds(const RcArgs a) {
 __global__ __launch_bounds__(256) void resized_crop_global(const RcArgs a) {
   __shared__ int hdr[8];
   const int tid = threadIdx.x, b = blockIdx.y;
-  const long long idx = a.index[b];
-  const bool valid = idx >= 0 && idx < a.N;
+  const long long gidx = a.index[b];               // the dataset's index: what the draw hashes
+  const unsigned long long idx = (unsigned long long)gidx - (unsigned long long)a.index_base;    // the row held here
+  const bool valid = idx < (unsigned long long)a.N;
   const int n_out = a.out_h * a.out_w;
   const int e = blockIdx.x * 256 + tid;
   float* o = a.out + (size_t)b * 3 * n_out;
@@ -313,7 +318,7 @@ __global__ __launch_bounds__(256) void resized_crop_global(const RcArgs a) {
     return;
   }
   if (tid == 0) {
-    sample_params(a, b, idx, hdr);
+    sample_params(a, b, gidx, hdr);
     if (blockIdx.x == 0) write_header(a, b, true, idx, hdr);
   }
   __syncthreads();
@@ -386,13 +391,17 @@ extern "C" int nbdt_resized_crop_band_rows(int32_t H, int32_t W, int32_t rs_h, i
   return plan_band(H, W, rs_h, rs_w, out_h, out_w, nullptr);
 }
 
-extern "C" int nbdt_resized_crop_batch(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index,
-                                       int32_t B, int64_t N, int32_t H, int32_t W, int32_t rs_h, int32_t rs_w,
-                                       int32_t win_top, int32_t win_left, int32_t out_h, int32_t out_w, int32_t flip,
-                                       const float* mean, const float* std, const double* scale, const double* ratio,
-                                       const double* ratio_table, uint64_t seed, uint64_t epoch, const int32_t* params_in,
-                                       float* out, int64_t* labels_out, int32_t* params_out, void* stream) {
+extern "C" int nbdt_resized_crop_batch_sharded(const void* src, int32_t src_dtype, const int64_t* labels_src,
+                                               const int64_t* index, int64_t index_base, int32_t B, int64_t N, int32_t H,
+                                               int32_t W, int32_t rs_h, int32_t rs_w, int32_t win_top, int32_t win_left,
+                                               int32_t out_h, int32_t out_w, int32_t flip, const float* mean,
+                                               const float* std, const double* scale, const double* ratio,
+                                               const double* ratio_table, uint64_t seed, uint64_t epoch,
+                                               const int32_t* params_in, float* out, int64_t* labels_out,
+                                               int32_t* params_out, void* stream) {
   NBDT_REQUIRE(src && labels_src && index && out && labels_out, "null argument");
+  NBDT_REQUIRE(N <= 0 || (index_base >= 0 && index_base <= INT64_MAX - N),
+               "index_base must be >= 0 and index_base + N must fit int64");
   NBDT_REQUIRE(src_dtype == NBDT_U8, "the resized crop takes a uint8 dataset (NBDT_U8)");
   NBDT_REQUIRE(B > 0 && B <= 65535, "batch must be 1..65535");
   NBDT_REQUIRE(N > 0, "empty dataset");
@@ -412,6 +421,7 @@ extern "C" int nbdt_resized_crop_batch(const void* src, int32_t src_dtype, const
   a.src = (const unsigned char*)src;
   a.labels_src = (const long long*)labels_src;
   a.index = (const long long*)index;
+  a.index_base = index_base;
   a.N = N; a.H = H; a.W = W;
   a.rs_h = rs_h; a.rs_w = rs_w; a.win_top = win_top; a.win_left = win_left; a.out_h = out_h; a.out_w = out_w;
   a.flip_on = flip;
@@ -432,4 +442,16 @@ extern "C" int nbdt_resized_crop_batch(const void* src, int32_t src_dtype, const
   }
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;
+}
+
+// the whole dataset is the shard at base 0: the same kernels, the same bits
+extern "C" int nbdt_resized_crop_batch(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index,
+                                       int32_t B, int64_t N, int32_t H, int32_t W, int32_t rs_h, int32_t rs_w,
+                                       int32_t win_top, int32_t win_left, int32_t out_h, int32_t out_w, int32_t flip,
+                                       const float* mean, const float* std, const double* scale, const double* ratio,
+                                       const double* ratio_table, uint64_t seed, uint64_t epoch, const int32_t* params_in,
+                                       float* out, int64_t* labels_out, int32_t* params_out, void* stream) {
+  return nbdt_resized_crop_batch_sharded(src, src_dtype, labels_src, index, 0, B, N, H, W, rs_h, rs_w, win_top, win_left,
+                                         out_h, out_w, flip, mean, std, scale, ratio, ratio_table, seed, epoch, params_in,
+                                         out, labels_out, params_out, stream);
 }

@@ -38,8 +38,17 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
 * ``--diagnostics TreeStatistics ConfusionMatrix Entropy TopDifference NBDTEntropyMaxMin`` (any of them) runs the
   analyzers of ``nbdt.diagnostics`` beside the ``--analysis`` analyzer, in a ``diagnostics.Chain``: per-node accuracy and
   entropy, the depth of the first wrong turn, confusion matrices and entropy rankings from one fused launch per
-  evaluation batch; ``--diagnostics-out FILE`` writes the last evaluation's report as JSON.  Every rank evaluates the
-  whole test split, so rank 0 reports and nothing is reduced across ranks.
+  evaluation batch; ``--diagnostics-out FILE`` writes the last evaluation's report as JSON.
+* Evaluation is distributed whenever there is more than one rank: rank r of w evaluates the samples
+  ``nbdt.data.shard_range(N, r, w)`` of the test split, the hit counts and the loss are summed over ranks with one
+  all-reduce, and every analyzer's ``reduce()`` merges the ranks' statistics, so what rank 0 prints, writes and
+  checkpoints on is the whole split's, as in a one-rank run.
+* ``--shard-data`` (with ``--augment reference | resized-crop``) keeps on each GPU only that rank's contiguous part of
+  both splits (``shard=(rank, world)``: ImageNet at 256 x 256 is 252 GB whole, 31.5 GB per rank at 8 ranks); a
+  ``--data-file`` is then memory-mapped, so a rank reads only its part of it.  Training shuffles WITHIN each rank's shard
+  (``nbdt.dist.epoch_indices(..., sharded=True)``), not across the whole set as the reference's sampler does: a global
+  batch is ``batch / world`` samples from every rank's part.  That is the price of never moving an image between GPUs;
+  the augmentation a sample gets is the same either way (it depends on seed, epoch and the sample's index alone).
 """
 import argparse
 import json
@@ -58,7 +67,7 @@ from nbdt import diagnostics  # noqa: E402
 from nbdt import dist as ndist  # noqa: E402
 from nbdt import loss as losses  # noqa: E402
 from nbdt import models  # noqa: E402
-from nbdt.data import DATASET_STATS, RESIZED_CROP_STATS, DeviceDataset, ResizedCropDataset  # noqa: E402
+from nbdt.data import DATASET_STATS, RESIZED_CROP_STATS, DeviceDataset, ResizedCropDataset, shard_range  # noqa: E402
 from nbdt.engine import train_step  # noqa: E402
 from nbdt.model import coerce_state_dict  # noqa: E402
 from nbdt.tree import Tree  # noqa: E402
@@ -124,6 +133,10 @@ def build_parser():
                         "evaluation, on a device-resident uint8 dataset; none: samples as they are")
     p.add_argument("--crop-size", type=int, default=0,
                    help="--augment resized-crop: output side S (default: the dataset's, 224); evaluation resizes to S + 32")
+    p.add_argument("--shard-data", action="store_true",
+                   help="--augment reference | resized-crop: every rank keeps only its contiguous part of both splits on "
+                        "its GPU (nbdt.data shard=(rank, world)), a --data-file is memory-mapped, and training shuffles "
+                        "within each rank's part")
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible training steps, like the reference's CPU path: every cross-block reduction in "
                         "a fixed order instead of fp32 atomics (nbdt_set_deterministic; ResNet / WideResNet backbones)")
@@ -203,9 +216,11 @@ class _PlainCE:
 
 def load_data(args, num_classes, device, raw=False):
     """train_x, train_y, test_x, test_y on the host.  raw: a uint8 --data-file stays uint8 (the augmentation kernel
-    normalises it)."""
+    normalises it).  --shard-data memory-maps the file: the datasets slice their rank's part out of it, and only that part
+    is ever read."""
     if args.data_file:
-        blob = torch.load(args.data_file, map_location="cpu")
+        blob = torch.load(args.data_file, map_location="cpu", mmap=True) if getattr(args, "shard_data", False) \
+            else torch.load(args.data_file, map_location="cpu")
         out = []
         for split in ("train", "test"):
             x, y = blob[f"{split}_x"], blob[f"{split}_y"].long()
@@ -244,25 +259,51 @@ def build_diagnostic(name, tree):
     return cls(tree.classes)
 
 
-def evaluate(net, criterion_module, analyzer, k, x, y, batch, device):
-    """reference main.py:262-277: top-k accuracy of the backbone's logits and the mean loss over (x, y); every batch's
-    logits also go to the analyzer (update_batch), which keeps its own statistic."""
+def evaluate_part(net, criterion_module, analyzer, k, x, y, batch, device, rank=0, world=1):
+    """One rank's part of an evaluation, nothing exchanged: the samples ``shard_range(N, rank, world)`` of (x, y) in
+    batches of `batch`; every batch's logits also go to the analyzer (update_batch).  Returns (HitCounter, loss sum as a
+    device scalar, number of batches).  x is a device-resident dataset -- sharded (it must be this rank's shard) or whole
+    -- or a host tensor."""
     net.eval()
     plain = HitCounter(k, device)
     loss_sum = torch.zeros((), device=device)
     batches = 0
+    on_device = isinstance(x, (DeviceDataset, ResizedCropDataset))
+    lo, hi = shard_range(x.global_size if on_device else x.shape[0], rank, world)
+    if on_device and x.sharded and tuple(x.shard_range) != (lo, hi):
+        raise ValueError(f"rank {rank} of {world} evaluates [{lo}, {hi}), the dataset holds {tuple(x.shard_range)}")
+    if hasattr(analyzer, "set_sample_offset"):
+        analyzer.set_sample_offset(lo)
     with torch.no_grad():
-        order = torch.arange(x.shape[0], device=device) if isinstance(x, (DeviceDataset, ResizedCropDataset)) else None
-        for i in range(0, x.shape[0], batch):
+        order = torch.arange(lo, hi, device=device) if on_device else None
+        for i in range(0, hi - lo, batch):
             if order is not None:           # device-resident split: the evaluation transform, one launch per batch
                 xb, yb = x.batch(order[i:i + batch], train=False)
             else:
-                xb, yb = x[i:i + batch].to(device), y[i:i + batch].to(device)
+                j = min(lo + i + batch, hi)
+                xb, yb = x[lo + i:j].to(device), y[lo + i:j].to(device)
             z = net(xb)
             loss_sum += criterion_module(z, yb)
             batches += 1
             plain.add(z, yb)
             analyzer.update_batch(z, yb, xb)
+    return plain, loss_sum, batches
+
+
+def evaluate(net, criterion_module, analyzer, k, x, y, batch, device, rank=0, world=1, group=None):
+    """reference main.py:262-277: top-k accuracy of the backbone's logits and the mean loss over (x, y); every batch's
+    logits also go to the analyzer (update_batch), which keeps its own statistic.  With world > 1 every rank evaluates its
+    part (evaluate_part), hits / seen / loss sum / batch count are summed over ranks with ONE all-reduce and the analyzer
+    is reduced (analyzer.reduce): every rank returns, and its analyzer holds, the numbers of the whole split."""
+    plain, loss_sum, batches = evaluate_part(net, criterion_module, analyzer, k, x, y, batch, device, rank, world)
+    if world > 1:
+        # one fp64 vector: the counts are integers far below 2^53, so their sums are exact
+        part = torch.tensor([0.0, 0.0, plain.seen, batches], dtype=torch.float64, device=device)
+        part[0], part[1] = plain.hits, loss_sum
+        hits, loss_sum, seen, batches = ndist.sum_over_ranks(part, group).tolist()
+        plain.hits.fill_(int(hits))
+        plain.seen, batches = int(seen), int(batches)
+        analyzer.reduce(group)
     return plain.percent(), float(loss_sum) / max(batches, 1)
 
 
@@ -275,6 +316,9 @@ def parse_args(argv=None):
                      "pass (its start_train raises NotImplementedError)")
     if args.diagnostics_out and not args.diagnostics:
         parser.error("--diagnostics-out needs --diagnostics")
+    if args.shard_data and args.augment not in ("reference", "resized-crop"):
+        parser.error("--shard-data shards the device-resident datasets: it needs --augment reference or --augment "
+                     "resized-crop")
     return args
 
 
@@ -303,19 +347,27 @@ def main(argv=None):
     num_classes = DATASET_TO_NUM_CLASSES[args.dataset]
     log("==> Preparing data..")
     train_x, train_y, test_x, test_y = load_data(args, num_classes, device, raw=on_device)
+    shard = (rank, world) if args.shard_data else None         # each rank keeps its contiguous part of both splits
     if args.augment == "reference":
         stats = DATASET_STATS[args.dataset]
-        train_x = DeviceDataset(train_x, train_y, stats["mean"], stats["std"], stats["pad"], flip=True, device=device)
-        test_x = DeviceDataset(test_x, test_y, stats["mean"], stats["std"], stats["pad"], flip=True, device=device)
+        kwargs = dict(flip=True, device=device, shard=shard)
+        train_x = DeviceDataset(train_x, train_y, stats["mean"], stats["std"], stats["pad"], **kwargs)
+        test_x = DeviceDataset(test_x, test_y, stats["mean"], stats["std"], stats["pad"], **kwargs)
     elif args.augment == "resized-crop":
         stats = RESIZED_CROP_STATS[args.dataset]
         size = args.crop_size or stats["size"]
         resize = size + 32 if args.crop_size else stats["resize"]       # reference: Resize(input_size + 32)
-        kwargs = dict(size=size, resize=resize, scale=stats["scale"], ratio=stats["ratio"], flip=True, device=device)
+        kwargs = dict(size=size, resize=resize, scale=stats["scale"], ratio=stats["ratio"], flip=True, device=device,
+                      shard=shard)
         train_x = ResizedCropDataset(train_x, train_y, stats["mean"], stats["std"], **kwargs)
         test_x = ResizedCropDataset(test_x, test_y, stats["mean"], stats["std"], **kwargs)
-    log(f"Training with dataset {args.dataset} and {num_classes} classes: {train_x.shape[0]} train / "
-        f"{test_x.shape[0]} test samples of shape {tuple(train_x.shape[1:])}")
+    n_train = train_x.global_size if on_device else train_x.shape[0]
+    n_test = test_x.global_size if on_device else test_x.shape[0]
+    log(f"Training with dataset {args.dataset} and {num_classes} classes: {n_train} train / "
+        f"{n_test} test samples of shape {tuple(train_x.shape[1:])}")
+    if shard is not None:
+        log(f"--shard-data: rank {rank} of {world} holds train samples {tuple(train_x.shard_range)} and test samples "
+            f"{tuple(test_x.shard_range)}")
 
     log("==> Building model..")
     if args.deterministic:
@@ -355,7 +407,7 @@ def main(argv=None):
     analyzer_cls = getattr(analysis, args.analysis or "Noop")
     analyzer = analyzer_cls(tree=tree, metric=args.metric) if args.analysis not in (None, "Noop") else analyzer_cls(tree.classes)
     extras = [build_diagnostic(name, tree) for name in args.diagnostics]
-    if extras:                                    # every rank evaluates the whole test split: rank 0 reports
+    if extras:                                    # every rank ends up with the reduced statistic: rank 0 reports
         analyzer = diagnostics.Chain(analyzer, *extras)
     analyzer.verbose = rank == 0                  # one rank prints
     comm = ndist.GradComm() if world > 1 else None
@@ -368,15 +420,16 @@ def main(argv=None):
         lr = multistep_lr(args.lr, epoch, args.epochs)
         log("\nEpoch: %d / LR: %.04f" % (epoch, lr))
         net.train()
-        g = torch.Generator().manual_seed(args.seed * 1000 + epoch)       # same shuffle on every rank
-        perm = torch.randperm(train_x.shape[0], generator=g)
-        steps = train_x.shape[0] // args.batch_size
+        # unsharded: the same shuffle of the whole set on every rank, each takes its slice of every global batch;
+        # --shard-data: every rank shuffles the part it holds
+        plan = ndist.epoch_indices(n_train, args.batch_size, rank, world, args.seed, epoch,
+                                   sharded=shard is not None)
+        steps = plan.shape[0]
         total = torch.zeros((), device=device)
         if on_device:
-            perm = perm.to(device)           # once per epoch; every step slices it there
+            plan = plan.to(device)           # once per epoch; every step takes a row of it there
         for i in range(steps):
-            idx = perm[i * args.batch_size:(i + 1) * args.batch_size]
-            idx = ndist.shard_batch(idx, rank, world)
+            idx = plan[i]
             if on_device:
                 xb, yb = train_x.batch(idx, epoch=epoch, seed=args.seed)
             else:
@@ -387,7 +440,8 @@ def main(argv=None):
     def test(epoch, checkpoint=True):
         nonlocal best_acc
         analyzer.start_test(epoch)
-        acc, loss = evaluate(net, criterion, analyzer, METRICS[args.metric], test_x, test_y, 100, device)
+        acc, loss = evaluate(net, criterion, analyzer, METRICS[args.metric], test_x, test_y, 100, device, rank=rank,
+                             world=world)
         nbdt_acc = analyzer.accuracy() if hasattr(analyzer, "accuracy") else None
         extra = f" | {analyzer.name}: {nbdt_acc:.3f}%" if nbdt_acc is not None else ""
         log("Loss: %.3f | Acc: %.3f%%%s" % (loss, acc, extra))

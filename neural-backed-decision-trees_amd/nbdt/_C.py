@@ -202,6 +202,12 @@ SIGNATURES = {
                                 [POINTER(c_float), POINTER(c_float), POINTER(ctypes.c_double), POINTER(ctypes.c_double), _P,
                                  ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P, _P]),
     "nbdt_resized_crop_band_rows": (c_int, [c_int32] * 8),
+    "nbdt_augment_batch_sharded": (c_int, [_P, c_int32, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                           POINTER(c_float), POINTER(c_float), POINTER(c_float), ctypes.c_uint64,
+                                           ctypes.c_uint64, _P, _P, _P, _P, _P]),
+    "nbdt_resized_crop_batch_sharded": (c_int, [_P, c_int32, _P, _P, c_int64, c_int32, c_int64] + [c_int32] * 9 +
+                                        [POINTER(c_float), POINTER(c_float), POINTER(ctypes.c_double),
+                                         POINTER(ctypes.c_double), _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P, _P]),
     "nbdt_linear_fwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_linear_bwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "nbdt_sgd_step": (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_int32, _P]),

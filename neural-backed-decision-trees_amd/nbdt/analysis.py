@@ -11,10 +11,16 @@ What is behind the surface is this repository's: the rules are the fused HIP ker
 batch), and the hit counters live ON THE DEVICE -- ``update_batch`` enqueues work and returns without a host
 synchronisation; the only transfer is the one ``end_test`` / ``accuracy()`` needs to print.  (The reference computes a
 running accuracy on the host after every batch; pass ``sync_every_batch=True`` to get that return value.)
+
+Distributed evaluation: every rank feeds its part of the test split to its own analyzer, then calls ``reduce()`` once,
+between the last ``update_batch`` and ``end_test``; afterwards every rank holds the statistic of the whole split.
+``reduce`` is ``load_state(merge(all ranks' state()))``: ``state`` is the pass's statistic as host data, ``merge`` a pure
+function of a list of such states (it can be called, and tested, without any process group).
 """
 import contextlib
 import functools
 
+import numpy as np
 import torch
 
 from nbdt.model import HardEmbeddedDecisionRules as _HardRules
@@ -26,6 +32,26 @@ _TOPK = {"top1": 1, "top2": 2, "top5": 5, "top10": 10}      # the reference's --
 
 def add_arguments(parser):
     """The reference registers flags of its presentation analyzers here; the analyzers of this module have none."""
+
+
+def merge_sum(states):
+    """The element-wise sum of states that share one layout: numbers, numpy arrays and tensors are added, dicts and lists
+    / tuples are merged entry by entry, None stays None.  A dict key some states lack counts as zero there (a rank that
+    saw no batch has no counters)."""
+    states = [s for s in states if s is not None]
+    if not states:
+        return None
+    first = states[0]
+    if isinstance(first, dict):
+        keys = list(dict.fromkeys(k for s in states for k in s))
+        return {k: merge_sum([s[k] for s in states if k in s]) for k in keys}
+    if isinstance(first, (list, tuple)):
+        return type(first)(merge_sum([s[i] for s in states]) for i in range(len(first)))
+    total = first.clone() if isinstance(first, torch.Tensor) else np.array(first).copy() if isinstance(first, np.ndarray) \
+        else first
+    for s in states[1:]:
+        total = total + s
+    return total
 
 
 class _Phase:
@@ -114,6 +140,33 @@ class Noop:
     def _update_batch(self, outputs, targets):
         return None
 
+    # ---- distributed evaluation: state / merge / load_state / reduce
+    def set_sample_offset(self, offset):
+        """The next sample this analyzer is fed is sample `offset` of the whole split (a rank's part of a distributed
+        evaluation starts at its shard_range's lo).  Only the analyzers that name samples care."""
+
+    def state(self):
+        """The statistic of the pass so far as host data (a dict of numbers / arrays): what ranks exchange."""
+        return {}
+
+    def merge(self, states):
+        """The state of the pass over everything the given states saw.  Pure: reads the states (and the analyzer's
+        configuration), touches nothing."""
+        return merge_sum(states) or {}
+
+    def load_state(self, state):
+        """Adopt a state as this analyzer's statistic."""
+
+    def reduce(self, group=None):
+        """Called once between the last update_batch and end_test of a distributed evaluation: leaves every rank holding
+        the statistic of the whole split.  A no-op with one rank or without an initialised process group."""
+        import torch.distributed as dist
+        if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+            return self
+        from nbdt.dist import gather_states
+        self.load_state(self.merge(gather_states(self.state(), group)))
+        return self
+
     def _same_epoch(self, epoch):
         if epoch != self.epoch:
             raise AssertionError(f"hook called for epoch {epoch} inside epoch {self.epoch}")
@@ -175,6 +228,14 @@ class DecisionRules(Noop):
         with torch.no_grad():
             self._count(self.rules.forward(outputs), targets)
         return round(self.accuracy(), 2) if self.sync_every_batch else None
+
+    def state(self):
+        return {"hits": self.correct, "seen": self._seen}      # (host transfer)
+
+    def load_state(self, state):
+        device = self._hits.device if self._hits is not None else "cpu"
+        self._hits = torch.tensor(int(state["hits"]), dtype=torch.long, device=device)
+        self._seen = int(state["seen"])
 
     def end_test(self, epoch):
         super().end_test(epoch)

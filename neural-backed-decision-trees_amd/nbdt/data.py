@@ -11,6 +11,12 @@ ImageNet trains with a different family (nbdt/data/imagenet.py:152-172): ``Rando
 form, ``nbdt_resized_crop_batch`` (csrc/resample.hip): the crop box is drawn in the kernel (``draw_resized_crop_params``
 restates the draw) and resampled with PIL's bilinear filter, byte for byte (``resample_reference`` restates the pixels; it
 is documentation and test infrastructure, never called on the training path).
+
+Both classes take ``shard=(rank, world)``: the rank then keeps only its contiguous part ``shard_range(N, rank, world)`` of
+the dataset on its GPU (ImageNet at 256 x 256 is 252 GB whole, 31.5 GB per rank at 8 ranks) and ``batch`` still takes
+indices into the whole dataset.  The kernels draw from that index and gather from ``index - lo``
+(``nbdt_augment_batch_sharded`` / ``nbdt_resized_crop_batch_sharded``), so a sample's augmentation does not depend on
+which rank holds it.
 """
 import functools
 import math
@@ -37,6 +43,44 @@ RESIZED_CROP_STATS = {
 MAX_PAD = _C.NBDT_AUGMENT_MAX_PAD
 MAX_SIDE = 4096                      # nbdt_resized_crop_batch: image and resized sides
 _M64 = (1 << 64) - 1
+
+
+def shard_range(n, rank, world):
+    """[lo, hi) of the n samples that rank `rank` of `world` owns: ``lo = rank * n // world``, ``hi = (rank + 1) * n //
+    world``.  The ranges are contiguous, tile [0, n) in rank order and their sizes differ by at most one; with n < world
+    some are empty.  THE rule: the datasets, the sampler (nbdt.dist.epoch_indices) and main.py's evaluation all use it."""
+    n, rank, world = int(n), int(rank), int(world)
+    if n < 0 or world < 1 or not 0 <= rank < world:
+        raise ValueError(f"need n >= 0 and 0 <= rank < world, got n {n}, rank {rank}, world {world}")
+    return rank * n // world, (rank + 1) * n // world
+
+
+def _place(name, x, y, shard, device):
+    """(x, y on the device, (lo, hi), N): the whole of the N samples, or with shard = (rank, world) only the rank's
+    range of them -- sliced on the host, so the rest of `x` (a memory-mapped file, say) is never read or copied."""
+    n = x.shape[0]
+    lo, hi = 0, n
+    if shard is not None:
+        if len(shard) != 2:
+            raise ValueError(f"shard must be (rank, world), got {shard!r}")
+        lo, hi = shard_range(n, shard[0], shard[1])
+        if hi <= lo:
+            raise ValueError(f"{name}: rank {int(shard[0])} of {int(shard[1])} owns none of the {n} samples (an empty "
+                             f"shard [{lo}, {hi})); use at most {n} ranks")
+        x, y = x[lo:hi], y[lo:hi]
+    return x.to(device).contiguous(), y.to(device=device, dtype=torch.int64).contiguous(), (lo, hi), n
+
+
+def _check_host_index(index, span, sharded):
+    """A host index tensor against the range the dataset holds: IndexError for a whole dataset (as ever), ValueError naming
+    the owned range for a shard."""
+    lo, hi = span
+    imin, imax = int(index.min()), int(index.max())
+    if imin < lo or imax >= hi:
+        if sharded:
+            raise ValueError(f"index outside the range this shard owns, [{lo}, {hi}): min {imin}, max {imax} (batch takes "
+                             "global dataset indices; another rank holds the rest)")
+        raise IndexError(f"index outside [0, {hi}): min {imin}, max {imax}")
 
 
 def _mix64(x):
@@ -73,9 +117,13 @@ class DeviceDataset:
     ``(0 - mean)/std``).  An fp32 `x` is taken as already normalised and copied; its padded pixels get `fill`, by default
     ``(0 - mean)/std`` -- a file normalised with the dataset's statistics then yields the same batches as its uint8
     original.  pad: pixels of zero padding before the random ``H x W`` crop; flip: random horizontal flip.
+
+    shard=(rank, world): only the samples ``shard_range(N, rank, world)`` are moved to the device.  ``shape[0]`` and
+    ``len()`` are then the number held, ``global_size`` is N, ``shard_range`` the owned [lo, hi); ``batch`` keeps taking
+    indices into the whole dataset and returns, for an index it owns, the very batch the unsharded dataset returns.
     """
 
-    def __init__(self, x, y, mean, std, pad, flip=True, fill=None, device="cuda"):
+    def __init__(self, x, y, mean, std, pad, flip=True, fill=None, device="cuda", shard=None):
         device = torch.device(device)
         if device.type != "cuda":
             raise _C.NBDTHipError(f"DeviceDataset lives on an MI355X, not on {device} (no CPU fallback)")
@@ -93,8 +141,8 @@ class DeviceDataset:
             fill = ((torch.zeros(3) - torch.tensor(self.mean)) / torch.tensor(self.std)).tolist()
         self.fill = tuple(float(f) for f in fill)
         self.pad, self.flip = int(pad), bool(flip)
-        self.x = x.to(device).contiguous()
-        self.y = y.to(device=device, dtype=torch.int64).contiguous()
+        self.sharded = shard is not None
+        self.x, self.y, self.shard_range, self.global_size = _place("DeviceDataset", x, y, shard, device)
         self.device = self.x.device
 
     def __len__(self):
@@ -108,21 +156,20 @@ class DeviceDataset:
         """(img fp32 [B,3,H,W], targets int64 [B][, params int8 [B,3]]) for the samples `index`, in ONE launch on torch's
         current stream.
 
-        index: a host sequence / array / CPU tensor is range-checked (IndexError) and copied; a device tensor goes straight
-        to the kernel, which writes a zero image with target -1 for an index outside [0, N).  train=False is the evaluation
-        transform (no crop, no flip).  params: int8 [B,3] of (dy, dx, flip) replaces the generator; a CPU tensor is
+        index: a host sequence / array / CPU tensor is range-checked (IndexError; ValueError naming the owned range for a
+        shard) and copied; a device tensor goes straight to the kernel, which writes a zero image with target -1 for an
+        index outside [0, N), or outside the owned range of a shard.  train=False is the evaluation transform (no crop, no
+        flip).  params: int8 [B,3] of (dy, dx, flip) replaces the generator; a CPU tensor is
         range-checked and copied.  Without it the draw is ``draw_params(seed, epoch, index, pad)``.
 
         Every call returns freshly allocated tensors (torch's caching allocator): train_step is asynchronous and the engine
         keeps `img` until the stem's weight gradient, so nothing handed out is ever overwritten by a later call."""
-        n = len(self)
         if not isinstance(index, torch.Tensor):
             index = torch.as_tensor(np.asarray(index))
         if index.dim() != 1 or index.is_floating_point() or index.shape[0] == 0:
             raise ValueError(f"index must be a non-empty integer vector, got {index.dtype} {tuple(index.shape)}")
         if not index.is_cuda:
-            if int(index.min()) < 0 or int(index.max()) >= n:
-                raise IndexError(f"index outside [0, {n}): min {int(index.min())}, max {int(index.max())}")
+            _check_host_index(index, self.shard_range, self.sharded)
             index = index.to(self.device, non_blocking=True)
         _C.require_gpu(index, "DeviceDataset.batch")
         index = index.to(dtype=torch.int64).contiguous()
@@ -144,7 +191,8 @@ class DeviceDataset:
         targets = torch.empty((B,), dtype=torch.int64, device=self.device)
         used = torch.empty((B, 3), dtype=torch.int8, device=self.device) if return_params else None
         ops.augment_batch(self.x, self.y, index, img, targets, pad, flip, mean=self.mean, std=self.std, fill=self.fill,
-                          seed=seed, epoch=epoch, params_in=params, params_out=used)
+                          seed=seed, epoch=epoch, params_in=params, params_out=used,
+                          index_base=self.shard_range[0] if self.sharded else None)
         return (img, targets, used) if return_params else (img, targets)
 
 
@@ -308,10 +356,13 @@ class ResizedCropDataset:
     ``[N]``; both are moved to `device` once.  Training batches are ``RandomResizedCrop(size, scale, ratio) ->
     RandomHorizontalFlip -> ToTensor -> Normalize(mean, std)``; evaluation batches are ``Resize(resize) -> CenterCrop(size)
     -> ToTensor -> Normalize`` (resize defaults to size + 32, as in the reference).  The resampling is PIL's bilinear filter.
+
+    shard=(rank, world): as for DeviceDataset -- only ``shard_range(N, rank, world)`` is held, ``batch`` takes indices into
+    the whole dataset; ``global_size`` and ``shard_range`` say what is where.
     """
 
     def __init__(self, x, y, mean, std, size=224, resize=None, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip=True,
-                 device="cuda"):
+                 device="cuda", shard=None):
         device = torch.device(device)
         if device.type != "cuda":
             raise _C.NBDTHipError(f"ResizedCropDataset lives on an MI355X, not on {device} (no CPU fallback)")
@@ -336,8 +387,8 @@ class ResizedCropDataset:
         self.eval_resize, self.eval_window = resize_center_crop_geometry(x.shape[2], x.shape[3], self.size, self.resize)
         if max(self.eval_resize) > MAX_SIDE:
             raise ValueError(f"the evaluation resize {self.eval_resize} exceeds {MAX_SIDE}")
-        self.x = x.to(device).contiguous()
-        self.y = y.to(device=device, dtype=torch.int64).contiguous()
+        self.sharded = shard is not None
+        self.x, self.y, self.shard_range, self.global_size = _place("ResizedCropDataset", x, y, shard, device)
         self.device = self.x.device
         self._table = torch.from_numpy(ratio_table(self.ratio).copy()).to(self.device)
         self._whole = torch.empty((0, 5), dtype=torch.int32, device=self.device)     # evaluation boxes, grown on demand
@@ -359,22 +410,22 @@ class ResizedCropDataset:
         """(img fp32 [B,3,size,size], targets int64 [B][, params int32 [B,5]]) for the samples `index`, in ONE launch on
         torch's current stream.
 
-        index: a host sequence / array / CPU tensor is range-checked (IndexError) and copied; a device tensor goes straight
-        to the kernel, which writes a zero image with target -1 for an index outside [0, N).  train=False is the evaluation
-        transform (the whole image resized so that its short side is `resize`, the central size x size of it, no flip).
+        index: a host sequence / array / CPU tensor is range-checked (IndexError; ValueError naming the owned range for a
+        shard) and copied; a device tensor goes straight to the kernel, which writes a zero image with target -1 for an
+        index outside [0, N), or outside the owned range of a shard.  train=False is the evaluation transform (the whole
+        image resized so that its short side is `resize`, the central size x size of it, no flip).
         params: int32 [B,5] of (top, left, h, w, flip) replaces the generator; a CPU tensor is range-checked and copied, a
         device tensor is clamped into the image by the kernel.  Without it the draw is
         ``draw_resized_crop_params(seed, epoch, index, H, W, scale, ratio)``.
 
         Every call returns freshly allocated tensors, as DeviceDataset.batch does."""
-        n, H, W = len(self), self.x.shape[2], self.x.shape[3]
+        H, W = self.x.shape[2], self.x.shape[3]
         if not isinstance(index, torch.Tensor):
             index = torch.as_tensor(np.asarray(index))
         if index.dim() != 1 or index.is_floating_point() or index.shape[0] == 0:
             raise ValueError(f"index must be a non-empty integer vector, got {index.dtype} {tuple(index.shape)}")
         if not index.is_cuda:
-            if int(index.min()) < 0 or int(index.max()) >= n:
-                raise IndexError(f"index outside [0, {n}): min {int(index.min())}, max {int(index.max())}")
+            _check_host_index(index, self.shard_range, self.sharded)
             index = index.to(self.device, non_blocking=True)
         _C.require_gpu(index, "ResizedCropDataset.batch")
         index = index.to(dtype=torch.int64).contiguous()
@@ -403,5 +454,6 @@ class ResizedCropDataset:
         used = torch.empty((B, 5), dtype=torch.int32, device=self.device) if return_params else None
         ops.resized_crop_batch(self.x, self.y, index, img, targets, resize, window, self.flip and train, self.mean, self.std,
                                scale=self.scale, ratio=self.ratio, ratio_table=self._table, seed=seed, epoch=epoch,
-                               params_in=params, params_out=used)
+                               params_in=params, params_out=used,
+                               index_base=self.shard_range[0] if self.sharded else None)
         return (img, targets, used) if return_params else (img, targets)

@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from nbdt import _C, ops
-from nbdt.analysis import Noop
+from nbdt.analysis import Noop, merge_sum
 from nbdt.tree import Tree
 
 __all__ = names = ("TreeStatistics", "ConfusionMatrix", "Entropy", "TopDifference", "NBDTEntropyMaxMin")
@@ -28,6 +28,7 @@ __all__ = names = ("TreeStatistics", "ConfusionMatrix", "Entropy", "TopDifferenc
 COUNTERS = ("on_path", "on_path_right", "visited", "visited_on_path", "visited_on_path_right")
 KINDS = ("net", "hard", "soft")
 _SCORE_COLUMN = {"Entropy": 0, "TopDifference": 1, "NBDTEntropyMaxMin": 2}
+SUMS_DTYPE = torch.float64     # Entropy's running sum and sum of squares (the only floating accumulators here)
 
 
 # ------------------------------------------------------------------------------------------------------------
@@ -212,6 +213,18 @@ class _Fused(Noop):
             self._host = {k: v.cpu().numpy() for k, v in self._block.items()}
         return self._host
 
+    # distributed evaluation (nbdt.analysis.Noop.reduce): the counters are integers, so the merge is an exact sum
+    def state(self, counts=True):
+        """counts=False leaves the counters out (``"counts": None``): a Chain sends a block its members share once."""
+        if not counts:
+            return {"counts": None}
+        have = self.fields and (self._host is not None or self._block is not None)
+        return {"counts": {k: v.copy() for k, v in self.counts().items()} if have else {}}
+
+    def load_state(self, state):
+        if state.get("counts"):
+            self.load_counts(state["counts"])
+
 
 class TreeStatistics(_Fused):
     """Per-node accuracy and entropy, the depth of the first wrong turn and the three confusion matrices of a test
@@ -328,9 +341,35 @@ class ConfusionMatrix(_Fused):
             print(recall.diagonal(), "(diagonal)")
 
 
+def merge_topk(candidates, k, largest):
+    """The k best of several lists of ranked samples: ``candidates`` is a sequence of ``{"score": [n], "index": [n],
+    "images": [n, ...] or None}`` (None entries are skipped); returns one such dict, best first.  The order is total: by
+    score (the largest or the smallest first), then by the smaller sample index.  So as long as every list holds the k
+    best of what its rank saw, under this order, the result does not depend on how the samples were split into lists."""
+    candidates = [c for c in candidates if c is not None and len(c["score"])]
+    if not candidates:
+        return None
+    score = torch.cat([torch.as_tensor(c["score"]).reshape(-1) for c in candidates])
+    index = torch.cat([torch.as_tensor(c["index"]).reshape(-1).long() for c in candidates])
+    with_images = [c.get("images") is not None for c in candidates]
+    if any(with_images) and not all(with_images):
+        raise ValueError("some ranked samples come with images and some without")
+    images = torch.cat([torch.as_tensor(c["images"]) for c in candidates]) if all(with_images) else None
+    pick = _rank_order(score, index, largest)[:int(k)]
+    return {"score": score[pick], "index": index[pick], "images": images[pick] if images is not None else None}
+
+
+def _rank_order(score, index, largest):
+    """The permutation that puts (score, index) into ranking order: two stable sorts, the minor key first."""
+    by_index = torch.sort(index, stable=True).indices
+    by_score = torch.sort(score[by_index], stable=True, descending=largest).indices
+    return by_index[by_score]
+
+
 class _Ranking(_Fused):
     """Keeps the ``save_k`` highest and lowest scorers of a pass on the device: their score, their ordinal within the
-    pass and, when ``update_batch`` is given images, the image."""
+    pass and, when ``update_batch`` is given images, the image.  Equal scores rank by ordinal, the earlier sample first.
+    In a distributed evaluation the ordinal is the sample's index in the whole split (``set_sample_offset``)."""
 
     def __init__(self, classes=(), tree=None, save_k=20):
         super().__init__(classes, tree=tree)
@@ -340,7 +379,11 @@ class _Ranking(_Fused):
 
     def _reset(self):
         self._seen = 0
+        self._next = 0                              # ordinal of the next sample (set_sample_offset moves it)
         self._top = {True: None, False: None}      # largest?: (scores, ordinals, images or None)
+
+    def set_sample_offset(self, offset):
+        self._next = int(offset)
 
     def start_test(self, epoch):
         super().start_test(epoch)
@@ -353,10 +396,11 @@ class _Ranking(_Fused):
         if self._seen and (images is None) != (self._top[True][2] is None):
             raise ValueError(f"{type(self).__name__}: give images with every batch of a pass, or with none")
         self._observe(scores)
-        ordinals = torch.arange(self._seen, self._seen + B, device=scores.device)
+        ordinals = torch.arange(self._next, self._next + B, device=scores.device)
         for largest in (True, False):
             self._top[largest] = self._retain(self._top[largest], scores[:, self.column], ordinals, images, largest)
         self._seen += B
+        self._next += B
 
     def _observe(self, scores):
         pass
@@ -365,8 +409,32 @@ class _Ranking(_Fused):
         if kept is not None:
             score, ordinal = torch.cat((kept[0], score)), torch.cat((kept[1], ordinal))
             images = torch.cat((kept[2], images)) if images is not None else None
-        pick = torch.topk(score, min(self.save_k, score.shape[0]), largest=largest).indices
+        pick = _rank_order(score, ordinal, largest)[:self.save_k]
         return score[pick], ordinal[pick], (images[pick] if images is not None else None)
+
+    def state(self, counts=True):
+        out = {**super().state(counts), "seen": self._seen}
+        for key, kept in (("highest", self._top[True]), ("lowest", self._top[False])):
+            out[key] = None if kept is None else {"score": kept[0].cpu(), "index": kept[1].cpu(),
+                                                  "images": kept[2].cpu() if kept[2] is not None else None}
+        return out
+
+    def merge(self, states):
+        out = {"counts": merge_sum([s.get("counts") for s in states]), "seen": sum(int(s["seen"]) for s in states)}
+        for key, largest in (("highest", True), ("lowest", False)):
+            out[key] = merge_topk([s[key] for s in states], self.save_k, largest)
+        return out
+
+    def load_state(self, state):
+        super().load_state(state)
+        self._seen = int(state["seen"])
+        for key, largest in (("highest", True), ("lowest", False)):
+            kept, had = state[key], self._top[largest]
+            if kept is not None:
+                dev = had[0].device if had is not None else kept["score"].device
+                kept = (kept["score"].to(dev), kept["index"].to(dev),
+                        kept["images"].to(dev) if kept["images"] is not None else None)
+            self._top[largest] = kept
 
     def highest(self):
         """(scores, ordinals within the pass, images or None), the highest score first."""
@@ -410,9 +478,20 @@ class Entropy(_Ranking):
         self._sums = None
 
     def _observe(self, scores):
-        h = scores[:, 0].double()
+        h = scores[:, 0].to(SUMS_DTYPE)
         s = torch.stack((h.sum(), (h * h).sum()))
         self._sums = s if self._sums is None else self._sums + s
+
+    def state(self, counts=True):
+        return {**super().state(counts), "sums": None if self._sums is None else self._sums.cpu()}
+
+    def merge(self, states):
+        return {**super().merge(states), "sums": merge_sum([s["sums"] for s in states])}      # summed in rank order
+
+    def load_state(self, state):
+        dev = self._sums.device if self._sums is not None else "cpu"
+        super().load_state(state)
+        self._sums = None if state["sums"] is None else state["sums"].to(dev)
 
     @property
     def avg(self):
@@ -508,6 +587,37 @@ class Chain(Noop):
 
     def end_test(self, epoch):
         self._fan("end_test", epoch)
+
+    def set_sample_offset(self, offset):
+        self._fan("set_sample_offset", offset)
+
+    # distributed evaluation: the members' states, with a block of counters that fused members share sent (and summed,
+    # and read back from the device) once rather than once per member
+    def _sharing(self):
+        """(field -> tensor of the block the fused members share, the members that are entirely in it)."""
+        block, inside = {}, []
+        for a in self.analyzers:
+            own = a._block if isinstance(a, _Fused) and a._host is None else None
+            if own and all(block.get(f, t) is t for f, t in own.items()):
+                block.update(own)
+                inside.append(a)
+        return block, inside
+
+    def state(self):
+        block, inside = self._sharing()
+        return {"shared": {f: t.cpu().numpy() for f, t in block.items()},
+                "members": [a.state(counts=False) if a in inside else a.state() for a in self.analyzers]}
+
+    def merge(self, states):
+        return {"shared": merge_sum([s["shared"] for s in states]) or {},
+                "members": [a.merge([s["members"][i] for s in states]) for i, a in enumerate(self.analyzers)]}
+
+    def load_state(self, state):
+        for a, member in zip(self.analyzers, state["members"]):
+            a.load_state(member)
+            if isinstance(a, _Fused) and a.fields and not member.get("counts") \
+                    and all(f in state["shared"] for f in a.fields):       # its counters travelled in the shared block
+                a.load_counts({f: state["shared"][f] for f in a.fields})
 
     def update_batch(self, outputs, targets, images=None):
         """Returns the first member's statistic (what the driver's own analyzer would have returned).  The members of

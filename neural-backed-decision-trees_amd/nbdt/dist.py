@@ -15,6 +15,8 @@ import os
 import torch
 import torch.distributed as dist
 
+from nbdt.data import shard_range
+
 # RCCL's footprint on the chip, chosen HERE rather than left to its tuner: an all-reduce kernel is one thread block per
 # channel, and every such block holds a CU that a one-block-per-CU MFMA kernel of the backward pass then cannot use.
 # 8 channels (one per XCD) move the 146 MB of WRN-28-10 gradients in ~1.7 ms at the ~20 GB/s a channel is ASSUMED to
@@ -107,6 +109,52 @@ def shard_batch(t, rank, world):
         raise ValueError(f"global batch {n} is not divisible by world size {world}")
     per = n // world
     return t[rank * per:(rank + 1) * per]
+
+
+def epoch_indices(n, batch_size, rank, world, seed, epoch, sharded=False):
+    """This rank's sample indices for every step of one epoch over n samples: int64 ``[steps, batch_size // world]`` on the
+    host, indices into the whole dataset.  batch_size is the GLOBAL batch and must divide by world.
+
+    sharded=False -- every rank holds the whole dataset: one shuffle of all n samples, the same on every rank
+    (``torch.randperm(n, generator=manual_seed(seed * 1000 + epoch))``), cut into ``n // batch_size`` global batches, of
+    which the rank takes its ``shard_batch``.
+
+    sharded=True -- the rank holds only ``shard_range(n, rank, world)`` (nbdt.data, ``shard=(rank, world)``): it shuffles
+    its own range, with a generator seeded from (seed, epoch, rank), and every rank runs the same number of steps, the one
+    the smallest shard (``n // world`` samples) allows.  Every index lies in the rank's range and none repeats within the
+    epoch.  The shuffle is within shards, not across the whole set: a global batch is always made of ``batch_size //
+    world`` samples from each rank's part.  That is the price of never moving an image between GPUs."""
+    n, batch_size, rank, world = int(n), int(batch_size), int(rank), int(world)
+    if batch_size <= 0 or batch_size % world:
+        raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
+    per = batch_size // world
+    if not sharded:
+        g = torch.Generator().manual_seed(int(seed) * 1000 + int(epoch))
+        perm = torch.randperm(n, generator=g)
+        steps = n // batch_size
+        return perm[:steps * batch_size].view(steps, batch_size)[:, rank * per:(rank + 1) * per].contiguous()
+    lo, hi = shard_range(n, rank, world)
+    steps = (n // world) // per                          # the smallest shard has n // world samples
+    g = torch.Generator().manual_seed((((int(seed) * 1000 + int(epoch)) << 20) + rank) & ((1 << 63) - 1))
+    perm = torch.randperm(hi - lo, generator=g)
+    return (perm[:steps * per] + lo).view(steps, per).contiguous()
+
+
+def gather_states(state, group=None):
+    """Every rank's `state` (any picklable object; tensors should be on the host), in rank order, on every rank: ONE
+    all-gather.  Without an initialised group, or in a group of one, ``[state]`` and no communication."""
+    if not dist.is_available() or not dist.is_initialized() or dist.get_world_size(group) == 1:
+        return [state]
+    out = [None] * dist.get_world_size(group)
+    dist.all_gather_object(out, state, group=group)
+    return out
+
+
+def sum_over_ranks(t, group=None):
+    """`t` (a tensor) summed over the ranks, in place, with one all-reduce; untouched without a group or in a group of one."""
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size(group) > 1:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t
 
 
 class GradComm:

@@ -619,34 +619,43 @@ def stem_wgrad(img, gy, dw, cout_real, stride=1):
 
 
 def augment_batch(src, labels_src, index, out, labels_out, pad, flip, mean=None, std=None, fill=None, seed=0, epoch=0,
-                  params_in=None, params_out=None):
+                  params_in=None, params_out=None, index_base=None):
     """nbdt_augment_batch: out[B,3,H,W] fp32, labels_out[B] <- gather + zero-padded random crop + flip (+ /255 and normalise
-    for a uint8 `src`) of src[N,3,H,W] at `index` (int64 [B], device).  mean / std / fill: three host floats each."""
+    for a uint8 `src`) of src[N,3,H,W] at `index` (int64 [B], device).  mean / std / fill: three host floats each.
+    index_base (nbdt_augment_batch_sharded): `src` holds the samples [index_base, index_base + N) of the dataset `index`
+    names; the draw uses `index`, the gather `index - index_base`."""
     N, _, H, W = src.shape
     f3 = lambda v: None if v is None else (ctypes.c_float * 3)(*[float(a) for a in v])
     dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
     mask = (1 << 64) - 1
-    check(lib().nbdt_augment_batch(ptr(src), dtype, ptr(labels_src), ptr(index), index.shape[0], N, H, W, int(pad),
-                                   1 if flip else 0, f3(mean), f3(std), f3(fill), int(seed) & mask, int(epoch) & mask,
-                                   ptr(params_in), ptr(out), ptr(labels_out), ptr(params_out), stream_ptr(src.device)))
+    tail = (index.shape[0], N, H, W, int(pad), 1 if flip else 0, f3(mean), f3(std), f3(fill), int(seed) & mask,
+            int(epoch) & mask, ptr(params_in), ptr(out), ptr(labels_out), ptr(params_out), stream_ptr(src.device))
+    if index_base is None:
+        check(lib().nbdt_augment_batch(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
+    else:
+        check(lib().nbdt_augment_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
 
 
 def resized_crop_batch(src, labels_src, index, out, labels_out, resize, window, flip, mean, std, scale=None, ratio=None,
-                       ratio_table=None, seed=0, epoch=0, params_in=None, params_out=None):
+                       ratio_table=None, seed=0, epoch=0, params_in=None, params_out=None, index_base=None):
     """nbdt_resized_crop_batch: out[B,3,out_h,out_w] fp32, labels_out[B] <- gather + crop box + PIL-bilinear resample to
     `resize` = (rs_h, rs_w), of which `window` = (top, left) + out's size is written, + flip + /255 + normalise of the uint8
     src[N,3,H,W] at `index` (int64 [B], device).  The boxes are params_in (int32 [B,5]: top, left, h, w, flip) or drawn
-    from (seed, epoch, index) with `scale`, `ratio` (two host floats each) and `ratio_table` (fp64 [4096], device)."""
+    from (seed, epoch, index) with `scale`, `ratio` (two host floats each) and `ratio_table` (fp64 [4096], device).
+    index_base (nbdt_resized_crop_batch_sharded): `src` holds the samples [index_base, index_base + N) of the dataset
+    `index` names; the draw uses `index`, the gather `index - index_base`."""
     N, _, H, W = src.shape
     f3 = lambda v: (ctypes.c_float * 3)(*[float(a) for a in v])
     d2 = lambda v: None if v is None else (ctypes.c_double * 2)(*[float(a) for a in v])
     dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
     mask = (1 << 64) - 1
-    check(lib().nbdt_resized_crop_batch(ptr(src), dtype, ptr(labels_src), ptr(index), index.shape[0], N, H, W,
-                                        int(resize[0]), int(resize[1]), int(window[0]), int(window[1]), out.shape[2],
-                                        out.shape[3], 1 if flip else 0, f3(mean), f3(std), d2(scale), d2(ratio),
-                                        ptr(ratio_table), int(seed) & mask, int(epoch) & mask, ptr(params_in), ptr(out),
-                                        ptr(labels_out), ptr(params_out), stream_ptr(src.device)))
+    tail = (index.shape[0], N, H, W, int(resize[0]), int(resize[1]), int(window[0]), int(window[1]), out.shape[2],
+            out.shape[3], 1 if flip else 0, f3(mean), f3(std), d2(scale), d2(ratio), ptr(ratio_table), int(seed) & mask,
+            int(epoch) & mask, ptr(params_in), ptr(out), ptr(labels_out), ptr(params_out), stream_ptr(src.device))
+    if index_base is None:
+        check(lib().nbdt_resized_crop_batch(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
+    else:
+        check(lib().nbdt_resized_crop_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
 
 
 def resized_crop_band_rows(H, W, resize, window, out_size):
