@@ -827,6 +827,32 @@ int nbdt_resized_crop_batch_sharded(const void* src, int32_t src_dtype, const in
                                     const int32_t* params_in, float* out, int64_t* labels_out, int32_t* params_out,
                                     void* stream);
 
+/* ------------------------------------------------------------------ ImageNet-style stem (nbdt_version() >= 115) */
+/* The front of torchvision's ResNet -- Conv2d(3, 64, 7, stride 2, padding 3) -> BatchNorm -> ReLU -> MaxPool2d(3, 2, 1)
+ * (reference nbdt/models/__init__.py takes these networks from torchvision.models) -- as two data-movement ops around the
+ * launches above.  csrc/stem_pool.hip.  dtype: the storage of the padded NHWC tensors, NBDT_BF16 (product) or NBDT_F32 (the
+ * engines' reference mode).  No atomics anywhere: the same inputs give the same bits.
+ *
+ * nbdt_stem_patches: img fp32 NCHW [B][3][H][W] -> out padded NHWC [B][H/stride+2][W/stride+2][cpad] with
+ *   out[b][oy+1][ox+1][(r*k + s)*3 + ci] = img[b][ci][oy*stride - k/2 + r][ox*stride - k/2 + s]   (0 outside the image)
+ * and zeros in channels [3*k*k, cpad), converted with round-to-nearest-even for bf16.  A k x k / stride / padding k/2
+ * convolution of the image is then the 1x1 convolution of `out` with w[cout][1][cpad] (nbdt_conv_igemm[_stats|_affine]), and
+ * its weight gradient is nbdt_conv_wgrad's.  Only interior pixels are written (the ring is left as it is).  k odd and <= 7,
+ * stride 1 or 2, H and W divisible by stride, cpad a multiple of 32 with cpad >= 3*k*k; anything else is NBDT_EINVAL. */
+int nbdt_stem_patches(const float* img, int32_t B, int32_t H, int32_t W, int32_t k, int32_t stride, int32_t cpad,
+                      int32_t dtype, void* out, void* stream);
+/* MaxPool2d(kernel_size=3, stride=2, padding=1): x padded NHWC [B][H+2][W+2][C] -> y [B][H/2+2][W/2+2][C], interior pixels
+ * only.  torch's semantics: positions outside the image do not take part (decided by their indices; the ring is never
+ * read), the winner is the first maximum in row-major window order, NaN propagates.  idx (NULL in inference): uint8
+ * [B][H/2][W/2][C], the winner's window position 3*dy + dx relative to the window origin (2*oy - 1, 2*ox - 1).
+ * H and W even, C a multiple of 8. */
+int nbdt_maxpool3x3s2_fwd(const void* x, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C, void* y, uint8_t* idx,
+                          void* stream);
+/* Its backward as a gather: gx[b][y][x][c] = the fp32 sum, rounded once, of gy over the (at most 2 x 2) windows that contain
+ * (y, x) and whose idx names it -- zero where none does.  Every interior element of gx is written with a plain store. */
+int nbdt_maxpool3x3s2_bwd(const void* gy, const uint8_t* idx, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C,
+                          void* gx, void* stream);
+
 /* ------------------------------------------------------------------ measurement probe (not on the product path) */
 /* A register-only stream of independent v_mfma_f32_32x32x16_bf16 on `blocks` CUs (one 512-thread block each, two waves
  * per SIMD): every wave issues iters x 16 of them (x 32768 flop).  bench.py times the launch for `roofline.mfma_stream`

@@ -3,7 +3,7 @@
 
 Mirrors reference main.py:28-90 (flags), :164-188 (``--resume`` / ``--path-resume`` with checkpoints
 ``{"net", "acc", "epoch"}`` and ``module.`` prefix coercion), :191-210 (loss construction from
-``--loss``, SGD momentum 0.9 wd 5e-4, MultiStepLR at 3/7 and 5/7 of ``--epochs``), :218-308 (train /
+``--loss``, SGD momentum 0.9 wd 5e-4 (``--weight-decay``; the ImageNet recipe's is 1e-4), MultiStepLR at 3/7 and 5/7 of ``--epochs``), :218-308 (train /
 test loops, best-accuracy checkpointing to ``./checkpoint/<generate_checkpoint_fname>.pth``), so the
 recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs, and why:
 
@@ -105,6 +105,7 @@ def build_parser():
     p.add_argument("--dataset", default="CIFAR10", choices=DATASETS)
     p.add_argument("--arch", default="ResNet18", choices=models.get_model_choices())
     p.add_argument("--lr", default=0.1, type=float)
+    p.add_argument("--weight-decay", default=5e-4, type=float, help="SGD weight decay (the reference's ImageNet recipe: 1e-4)")
     p.add_argument("--resume", "-r", action="store_true")
     p.add_argument("--path-resume", default="")
     p.add_argument("--name", default="")
@@ -412,6 +413,8 @@ def main(argv=None):
     analyzer.verbose = rank == 0                  # one rank prints
     comm = ndist.GradComm() if world > 1 else None
     per_rank = args.batch_size // world
+    # --weight-decay: handed on only when it is not train_step's own default
+    decay = {} if args.weight_decay == 5e-4 else {"weight_decay": args.weight_decay}
 
     @analyzer.train_function
     def train(epoch):
@@ -434,7 +437,7 @@ def main(argv=None):
                 xb, yb = train_x.batch(idx, epoch=epoch, seed=args.seed)
             else:
                 xb, yb = train_x[idx].to(device, non_blocking=True), train_y[idx].to(device, non_blocking=True)
-            total += train_step(engine, fast, xb, yb, lr, comm=comm)
+            total += train_step(engine, fast, xb, yb, lr, comm=comm, **decay)
         log("Loss: %.3f (%d steps of %d x %d images)" % (total.item() / max(steps, 1), steps, world, per_rank))
 
     def test(epoch, checkpoint=True):

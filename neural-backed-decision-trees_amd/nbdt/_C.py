@@ -208,6 +208,9 @@ SIGNATURES = {
     "nbdt_resized_crop_batch_sharded": (c_int, [_P, c_int32, _P, _P, c_int64, c_int32, c_int64] + [c_int32] * 9 +
                                         [POINTER(c_float), POINTER(c_float), POINTER(ctypes.c_double),
                                          POINTER(ctypes.c_double), _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P, _P]),
+    "nbdt_stem_patches": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "nbdt_maxpool3x3s2_fwd": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
+    "nbdt_maxpool3x3s2_bwd": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_linear_fwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_linear_bwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "nbdt_sgd_step": (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_int32, _P]),

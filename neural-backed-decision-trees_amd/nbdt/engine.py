@@ -107,20 +107,26 @@ class ParamStore:
 class Conv:
     """3x3 / 1x1 convolution (bias-free) with forward, data-gradient and weight-gradient launches."""
 
-    def __init__(self, store, name, cin_real, cout_real, k, stride, gen, init="kaiming_a0"):
+    def __init__(self, store, name, cin_real, cout_real, k, stride, gen, init="kaiming_a0", fan_taps=None):
         self.store, self.name = store, name
         self.cin_real, self.cout_real, self.k, self.stride = cin_real, cout_real, k, stride
         self.cin, self.cout = _pad32(cin_real), _pad32(cout_real)
         self.taps = k * k
         fan_in = cin_real * k * k
+        std = None
         if init == "kaiming_a0":       # pytorchcv: init.kaiming_uniform_(w)  (a = 0)
             bound = math.sqrt(2.0) * math.sqrt(3.0 / fan_in)
+        elif init == "kaiming_normal_fan_out":   # torchvision: kaiming_normal_(w, mode="fan_out", nonlinearity="relu");
+            std = math.sqrt(2.0 / (cout_real * (fan_taps or k * k)))      # fan_taps: the taps a patch conv stands for
         else:                          # nn.Conv2d default: kaiming_uniform_(w, a=sqrt(5))
             bound = 1.0 / math.sqrt(fan_in)
 
         def init(v):
             v.zero_()
-            v[:cout_real, :, :cin_real].uniform_(-bound, bound, generator=gen)
+            if std is not None:
+                v[:cout_real, :, :cin_real].normal_(0.0, std, generator=gen)
+            else:
+                v[:cout_real, :, :cin_real].uniform_(-bound, bound, generator=gen)
 
         store.add(name, (self.cout, self.taps, self.cin), init)
         self._plans = {}
@@ -259,6 +265,24 @@ class Conv:
             ops.conv_wgrad(desc, x, gout, self.store.g(self.name), cu_budget)
 
 
+class PatchConv(Conv):
+    """A k x k convolution of the 3-colour image as the 1x1 convolution of its patch tensor (ops.stem_patches): cin_real =
+    3 * k * k channels in (r, s, ci) order.  Always on nbdt_conv_igemm, whatever the engine routes its pointwise convs to."""
+
+    def __init__(self, store, name, cout_real, patch_k, gen, init):
+        super().__init__(store, name, 3 * patch_k * patch_k, cout_real, 1, 1, gen, init, fan_taps=patch_k * patch_k)
+        self.patch_k = patch_k
+
+    def _pw(self):
+        return False
+
+    def logical(self, buf):
+        """[cout_real, 3, k, k] view (OIHW semantics) of a flat buffer: the row's first 3*k*k entries are (r, s, ci)."""
+        k = self.patch_k
+        v = self.store._view(buf, self.name)[:self.cout_real, 0, :self.cin_real]
+        return v.view(self.cout_real, k, k, 3).permute(0, 3, 1, 2)
+
+
 class SegOp:
     """A slice-list launch (ops.ConvSeg, csrc/conv_seg.hip) together with its DMA-ordered weight tiles.  `sources` returns
     the bf16 weight matrices the tiles are built from (views of the engine's flat bf16 mirror / data-gradient copies) and
@@ -280,10 +304,10 @@ class SegOp:
 
 
 class BatchNorm:
-    def __init__(self, store, name, c_real, scratch_owner):
+    def __init__(self, store, name, c_real, scratch_owner, gamma=1.0):
         self.store, self.name, self.c_real = store, name, c_real
         self.C = _pad32(c_real)
-        store.add(name + ".weight", (self.C,), lambda v: v.fill_(1.0))
+        store.add(name + ".weight", (self.C,), lambda v: v.fill_(gamma))
         store.add(name + ".bias", (self.C,), lambda v: v.zero_())
         dev = store.device
         self.running_mean = torch.zeros(self.C, device=dev)
@@ -782,8 +806,8 @@ class _Engine:
             comm.finish(self.store.grad)
             self._reserve_for(None)
 
-    def bn(self, name, c):
-        b = BatchNorm(self.store, name, c, self)
+    def bn(self, name, c, gamma=1.0):
+        b = BatchNorm(self.store, name, c, self, gamma)
         self.bns.append(b)
         return b
 
@@ -1265,7 +1289,8 @@ class ResNetEngine(_Engine):
     A residual block is data: a chain of main stages (conv, bn) -- two for a BasicBlock, three for a Bottleneck
     (BottleneckEngine) -- plus an optional shortcut (sconv, sbn).  ``_block_stages`` is the recipe; forward() and
     backward() walk whatever chain it made, so the cross-stream buffer protocol below exists once.  A new block type
-    overrides ``_block_stages``; a new stem overrides ``_stem_forward`` / ``_stem_backward``."""
+    overrides ``_block_stages``; a new stem overrides ``_make_stem`` and ``_stem_forward`` / ``_stem_backward``
+    (_TorchvisionFront: the ImageNet-style nets)."""
 
     # (GB/s per CU, time budget of bn1's confined pass at 128 images in us, min CUs, max CUs) or None: see backward()
     res_share = (47.0, 15.0, 16, 128)
@@ -1275,9 +1300,7 @@ class ResNetEngine(_Engine):
         self.num_classes = num_classes
         gen = self.gen
         self.stem_c = 64
-        b0 = 1.0 / math.sqrt(27)
-        self.store.add("conv1.weight", (64, 3, 3, 3), lambda v: v.uniform_(-b0, b0, generator=gen))
-        self.bn0 = self.bn("bn1", 64)
+        self._make_stem()
         self.blocks = []
         cin = 64
         # Parameters are created in the reference's module order -- per block conv1, bn1, conv2, bn2, [conv3, bn3], then
@@ -1291,8 +1314,8 @@ class ResNetEngine(_Engine):
                 cout = stages[-1][0].cout_real
                 short = stride != 1 or cin != cout
                 blk = {
-                    "sconv": self.conv(pre + "shortcut.0.weight", cin, cout, 1, stride, init="torch_default") if short else None,
-                    "sbn": self.bn(pre + "shortcut.1", cout) if short else None,
+                    "sconv": self.conv(f"{pre}{self.shortcut_name}.0.weight", cin, cout, 1, stride, init=self.conv_init) if short else None,
+                    "sbn": self.bn(f"{pre}{self.shortcut_name}.1", cout) if short else None,
                     "cin": cin, "cout": cout, "stride": stride, "key": k,
                 }
                 # what forward() / backward() iterate, resolved once (the small configurations run at the host's launch
@@ -1312,9 +1335,10 @@ class ResNetEngine(_Engine):
                 self.blocks.append(blk)
                 cin = cout
         self.feat_c = cin
-        kb = 1.0 / math.sqrt(cin)
-        self.store.add("linear.weight", (num_classes, cin), lambda v: v.uniform_(-kb, kb, generator=gen))
-        self.store.add("linear.bias", (num_classes,), lambda v: v.uniform_(-kb, kb, generator=gen))
+        kb = 1.0 / math.sqrt(cin)          # nn.Linear's default
+        w, b = self.classifier_names
+        self.store.add(w, (num_classes, cin), lambda v: v.uniform_(-kb, kb, generator=gen))
+        self.store.add(b, (num_classes,), lambda v: v.uniform_(-kb, kb, generator=gen))
         self.finalize()
         self._side = side_stream(self.device)     # weight gradients on a second stream (see WRNEngine)
         for c in self.convs:
@@ -1327,6 +1351,18 @@ class ResNetEngine(_Engine):
         self._id_beta = torch.zeros(cin, device=dev)
         self._id_dsum = torch.zeros(2 * cin, device=dev)
 
+    shortcut_name = "shortcut"      # the projection shortcut's module name (torchvision: downsample)
+    conv_init = "torch_default"     # Conv's init of every block conv
+    block_convs = 2                 # main-chain stages of a block
+    zero_init_residual = False      # gamma of each block's last BatchNorm starts at 0 (torchvision's keyword)
+
+    def _make_stem(self):
+        """Create the stem's parameters (first in the store): conv1 [64][3][3][3] (co, r, s, ci), bn1."""
+        gen = self.gen
+        b0 = 1.0 / math.sqrt(27)
+        self.store.add("conv1.weight", (64, 3, 3, 3), lambda v: v.uniform_(-b0, b0, generator=gen))
+        self.bn0 = self.bn("bn1", 64)
+
     def _block_stages(self, pre, cin, planes, stride):
         """The main chain of one block as [(conv, bn, fusable)], created in order.  BasicBlock: 3x3 (stride s) -> 3x3.
         fusable: backward() may take the (this conv, previous stage's bn) pair in its fused / CU-sharing forms --
@@ -1334,14 +1370,16 @@ class ResNetEngine(_Engine):
         return [self._stage(pre, 1, cin, planes, 3, stride), self._stage(pre, 2, planes, planes, 3, 1, fusable=True)]
 
     def _stage(self, pre, m, cin, cout, k, stride, fusable=False):
-        return (self.conv(f"{pre}conv{m}.weight", cin, cout, k, stride, init="torch_default"), self.bn(f"{pre}bn{m}", cout),
-                fusable)
+        gamma = 0.0 if self.zero_init_residual and m == self.block_convs else 1.0
+        return (self.conv(f"{pre}conv{m}.weight", cin, cout, k, stride, init=self.conv_init),
+                self.bn(f"{pre}bn{m}", cout, gamma), fusable)
 
     def extra_param_views(self, buf):
+        w, b = self.classifier_names
         return {
             "conv1.weight": self.store._view(buf, "conv1.weight").permute(0, 3, 1, 2),
-            "linear.weight": self.store._view(buf, "linear.weight"),
-            "linear.bias": self.store._view(buf, "linear.bias"),
+            w: self.store._view(buf, w),
+            b: self.store._view(buf, b),
         }
 
     def grad_buckets(self):
@@ -1517,6 +1555,7 @@ class BottleneckEngine(ResNetEngine):
     strided shortcuts and every weight gradient take the kernels they take in ResNetEngine."""
 
     expansion = 4
+    block_convs = 3
 
     # No CU sharing: ResNetEngine confines bn1's backward pass beside conv2's weight gradient with a plan measured for
     # BasicBlocks; nothing has been measured for these blocks, so every launch gets the whole chip.
@@ -1541,6 +1580,90 @@ class BottleneckEngine(ResNetEngine):
         self._pointwise = bool(on)
         for c in self.convs:
             c.pointwise = self._pointwise
+
+
+class _TorchvisionFront:
+    """What torchvision.models.resnet puts around the four stages, for ResNetEngine and BottleneckEngine alike (mixed in
+    ahead of them): the 7x7 / 2 stem, BatchNorm, ReLU and MaxPool2d(3, 2, 1) in front, ``fc`` behind, torchvision's module
+    names (conv1, bn1, layerN.M.conv{1,2,3} / bnK, downsample.0/1, fc) and its initialisation.
+
+    No new convolution kernel: ops.stem_patches gathers the 7x7 patches (147 -> 160 channels) and ``conv1`` is a 1x1
+    convolution over them -- forward with fused statistics, the eval-mode conv + affine launch and the weight gradient are
+    the launches every other conv takes; the patch tensor is kept for the weight gradient.  BatchNorm and ReLU are bn1's
+    usual passes, the pool is its own op (ops.maxpool_fwd / maxpool_bwd, window positions kept as uint8 in training).
+
+    The stages see H/4 x W/4, H/8, H/16 and H/32 pixels, so H and W must be multiples of 32.  Stage widths that are powers
+    of two (128 x 128 or 256 x 256 images) take the kernels the CIFAR trunks take; 224 x 224 (56 / 28 / 14 / 7) takes the
+    generic implicit-GEMM and weight-gradient kernels for its dense 3x3 convs ("ImageNet-style ResNets")."""
+
+    shortcut_name = "downsample"
+    conv_init = "kaiming_normal_fan_out"
+    classifier_names = ("fc.weight", "fc.bias")
+    res_share = None        # the CU-sharing plan was measured on CIFAR grids: nothing is assumed to carry over
+    PATCH_K = 7
+
+    def __init__(self, num_classes=1000, num_blocks=None, zero_init_residual=False, device="cuda", seed=0):
+        self.zero_init_residual = bool(zero_init_residual)
+        if num_blocks is None:
+            super().__init__(num_classes=num_classes, device=device, seed=seed)
+        else:
+            super().__init__(num_classes=num_classes, num_blocks=num_blocks, device=device, seed=seed)
+
+    def _make_stem(self):
+        self.conv0 = PatchConv(self.store, "conv1.weight", 64, self.PATCH_K, self.gen, self.conv_init)
+        self.convs.append(self.conv0)
+        self.bn0 = self.bn("bn1", 64)
+
+    def extra_param_views(self, buf):
+        w, b = self.classifier_names          # (conv1.weight is a Conv: PatchConv.logical)
+        return {w: self.store._view(buf, w), b: self.store._view(buf, b)}
+
+    def _stem_forward(self, img, training):
+        """patches -> conv1 (+ statistics) -> bn1 + ReLU -> max-pool; returns layer1's input."""
+        B, _, H, W = img.shape
+        if H % 32 or W % 32:
+            raise ValueError(f"ImageNet-style ResNets take images whose sides are multiples of 32, got {H} x {W}")
+        h, w = H // 2, W // 2
+        patches = self.buf("patches", B, h, w, self.conv0.cin)
+        a = self.buf("a0", B, h, w, 64)
+        x = self.buf("p0", B, h // 2, w // 2, 64)
+        ops.stem_patches(img, patches, self.PATCH_K, 2)
+        if not training and self.fuse_eval:
+            self.conv0.forward_affine(patches, a, self.bn0, act=1)
+            ops.maxpool_fwd(a, x, None)
+            return x
+        t0 = self.buf("t0", B, h, w, 64)
+        fuse = training and self.fuse_stats
+        self.conv0.forward(patches, t0, bn_scratch=self.partials(t0) if fuse else None)
+        self.bn0.stats(t0, training, fused=fuse)
+        self.bn0.apply(t0, a, relu=True)
+        ops.maxpool_fwd(a, x, self._pool_idx(B, h // 2, w // 2) if training else None)
+        return x
+
+    def _pool_idx(self, B, h, w):
+        k = ("pool_idx", B, h, w)
+        if k not in self._bufs:
+            self._bufs[k] = torch.empty((B, h, w, 64), dtype=torch.uint8, device=self.device)
+        return self._bufs[k]
+
+    def _stem_backward(self, g):
+        """From g = dL/d(layer1's input): the pool's backward, bn1's backward and conv1's weight gradient."""
+        B, Hp, Wp, _ = g.shape
+        h, w = 2 * (Hp - 2), 2 * (Wp - 2)
+        ga = self.buf("ga0", B, h, w, 64)
+        gt0 = self.buf("gt0", B, h, w, 64)
+        ops.maxpool_bwd(g, self._pool_idx(B, Hp - 2, Wp - 2), ga)
+        self.bn0.backward(ga, None, self.buf("t0", B, h, w, 64), gt0, relu=True)
+        self.conv0.backward_weight(self.buf("patches", B, h, w, self.conv0.cin), gt0)
+
+
+class ImageNetResNetEngine(_TorchvisionFront, ResNetEngine):
+    """torchvision's resnet18 / resnet34 (BasicBlocks; the reference's ImageNet recipe takes them from torchvision.models
+    through nbdt/models/__init__.py): ResNetEngine's stages between _TorchvisionFront's stem and head."""
+
+
+class ImageNetBottleneckEngine(_TorchvisionFront, BottleneckEngine):
+    """torchvision's resnet50 / 101 / 152 (Bottleneck v1.5: the stride is on the 3x3 conv, as in BottleneckEngine)."""
 
 
 def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5e-4, comm=None, fused_head=True,

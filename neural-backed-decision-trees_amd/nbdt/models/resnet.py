@@ -1,6 +1,7 @@
 """CIFAR ResNets -- reference nbdt/models/resnet.py: BasicBlock variants (:42-74, 115-149, 161-199) on ResNetEngine,
-Bottleneck variants (:77-112, 193-223) on BottleneckEngine."""
-from nbdt.engine import BottleneckEngine, ResNetEngine
+Bottleneck variants (:77-112, 193-223) on BottleneckEngine -- and the ImageNet-style ResNets the reference takes from
+torchvision.models (nbdt/models/__init__.py: resnet18 ... resnet152, lower-case) on the ImageNet* engines."""
+from nbdt.engine import BottleneckEngine, ImageNetBottleneckEngine, ImageNetResNetEngine, ResNetEngine
 from nbdt.models._hip_module import HipBackbone
 
 
@@ -33,3 +34,31 @@ def ResNet101(**kwargs):
 
 def ResNet152(**kwargs):
     return _resnet((3, 8, 36, 3), engine=BottleneckEngine, **kwargs)
+
+
+def _tv_resnet(engine, num_blocks, pretrained=False, progress=True, num_classes=1000, zero_init_residual=False,
+               dataset="Imagenet1000", device="cuda", seed=0):
+    if pretrained:
+        raise NotImplementedError("pretrained checkpoints need network access; use load_state_dict")
+    return HipBackbone(engine(num_classes=num_classes, num_blocks=num_blocks, zero_init_residual=zero_init_residual,
+                              device=device, seed=seed))
+
+
+def resnet18(pretrained=False, **kwargs):
+    return _tv_resnet(ImageNetResNetEngine, (2, 2, 2, 2), pretrained, **kwargs)
+
+
+def resnet34(pretrained=False, **kwargs):
+    return _tv_resnet(ImageNetResNetEngine, (3, 4, 6, 3), pretrained, **kwargs)
+
+
+def resnet50(pretrained=False, **kwargs):
+    return _tv_resnet(ImageNetBottleneckEngine, (3, 4, 6, 3), pretrained, **kwargs)
+
+
+def resnet101(pretrained=False, **kwargs):
+    return _tv_resnet(ImageNetBottleneckEngine, (3, 4, 23, 3), pretrained, **kwargs)
+
+
+def resnet152(pretrained=False, **kwargs):
+    return _tv_resnet(ImageNetBottleneckEngine, (3, 8, 36, 3), pretrained, **kwargs)

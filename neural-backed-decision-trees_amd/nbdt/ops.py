@@ -618,6 +618,33 @@ def stem_wgrad(img, gy, dw, cout_real, stride=1):
                                 stream_ptr(img.device)))
 
 
+def _storage(t):
+    return _C.NBDT_F32 if t.dtype == torch.float32 else _C.NBDT_BF16
+
+
+def stem_patches(img, out, k=7, stride=2):
+    """nbdt_stem_patches: fp32 NCHW img [B,3,H,W] -> the interior of the padded NHWC patch tensor out
+    [B, H/stride+2, W/stride+2, cpad], channel (r*k + s)*3 + ci, zeros from 3*k*k on; out is bf16 or (reference mode) fp32.
+    The k x k / stride / pad k/2 convolution is the 1x1 convolution of `out` (conv_igemm, conv_wgrad)."""
+    B, _, H, W = img.shape
+    check(lib().nbdt_stem_patches(ptr(img), B, H, W, int(k), int(stride), out.shape[3], _storage(out), ptr(out),
+                                  stream_ptr(img.device)))
+
+
+def maxpool_fwd(x, y, idx=None):
+    """nbdt_maxpool3x3s2_fwd: MaxPool2d(3, 2, 1) of padded x [B,H+2,W+2,C] into padded y [B,H/2+2,W/2+2,C]; idx (training):
+    uint8 [B,H/2,W/2,C], the winner's window position 3*dy + dx."""
+    B, H, W, C = _dims(x)
+    check(lib().nbdt_maxpool3x3s2_fwd(ptr(x), _storage(x), B, H, W, C, ptr(y), ptr(idx), stream_ptr(x.device)))
+
+
+def maxpool_bwd(gy, idx, gx):
+    """nbdt_maxpool3x3s2_bwd: gx [B,H+2,W+2,C] (every interior element written) from gy [B,H/2+2,W/2+2,C] and the forward's
+    idx; a gather with an fp32 sum in a fixed order, no atomics."""
+    B, H, W, C = _dims(gx)
+    check(lib().nbdt_maxpool3x3s2_bwd(ptr(gy), ptr(idx), _storage(gy), B, H, W, C, ptr(gx), stream_ptr(gx.device)))
+
+
 def augment_batch(src, labels_src, index, out, labels_out, pad, flip, mean=None, std=None, fill=None, seed=0, epoch=0,
                   params_in=None, params_out=None, index_base=None):
     """nbdt_augment_batch: out[B,3,H,W] fp32, labels_out[B] <- gather + zero-padded random crop + flip (+ /255 and normalise
