@@ -173,6 +173,28 @@ int nbdt_head_soft_tree_loss(const nbdt_tree* t, const float* pooled, const floa
 int nbdt_hard_tree_loss(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz,
                         const int64_t* y, float w_xent, float w_node, float grad_scale,
                         float* row_loss, float* loss, float* gz, void* stream);
+/* ---- soft targets and label smoothing (nbdt_version() >= 116): the same two kernels for
+ * criterion = nn.CrossEntropyLoss(label_smoothing = smoothing), 0 <= smoothing < 1, and -- the soft loss only -- for
+ * probability targets [B, C], which is what MixUp / CutMix and soft-label transforms hand to a loss.
+ *
+ * nbdt_soft_tree_loss_ex.  Exactly one of y (int64 [B]) and tprob (fp32, row b at tprob + b*ldt, ldt >= C) is non-NULL.
+ * With t the target row (onehot(y) for class indices) and eps = smoothing:
+ *   t'_c = (1 - eps)*t_c + eps/C,   T = sum_c t'_c      (T is NOT assumed to be 1: torch does not normalise the row)
+ *   row  = w_xent*(T*lse(z) - sum_c t'_c z_c) + w_tree*(T*lse(P) - sum_c t'_c P_c),   loss = mean of row over B
+ *   gz   = grad_scale * dloss/dz: the direct term w_xent*(T*softmax(z) - t')/B plus w_tree*(T*softmax(P) - t')/B carried
+ *          through the path products, as in nbdt_soft_tree_loss.
+ * A class index outside [0, C) still gives a NaN loss; a dense row is used as given.  nbdt_soft_tree_loss is this entry
+ * with tprob = NULL and smoothing = 0 (its kernel instantiation and bits are unchanged).
+ *
+ * nbdt_hard_tree_loss_ex.  Class-index targets only.  Every node term becomes, with K_n children and the label under
+ * child s,  lse(s_n) - (1 - eps)*s_{n,s} - (eps/K_n)*sum_k s_{n,k}  (the criterion applied to the node's K_n logits); the
+ * cross-entropy term is smoothed with eps/C.  nbdt_hard_tree_loss is this entry with smoothing = 0. */
+int nbdt_soft_tree_loss_ex(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz, const int64_t* y,
+                           const float* tprob, int64_t ldt, float smoothing, float w_xent, float w_tree,
+                           float grad_scale, float* row_loss, float* loss, float* gz, void* stream);
+int nbdt_hard_tree_loss_ex(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz, const int64_t* y,
+                           float smoothing, float w_xent, float w_node, float grad_scale, float* row_loss, float* loss,
+                           float* gz, void* stream);
 /* VJP of get_node_logits over every inner node (nbdt/model.py:83-99): gs [B,R] fp32 gradient of
  * the child logits (slot-major, as written by nbdt_node_outputs) -> gz [B,C] fp32. */
 int nbdt_node_logits_backward(const nbdt_tree* t, const float* gs, int64_t B, float* gz, void* stream);
@@ -852,6 +874,24 @@ int nbdt_maxpool3x3s2_fwd(const void* x, int32_t dtype, int32_t B, int32_t H, in
  * (y, x) and whose idx names it -- zero where none does.  Every interior element of gx is written with a plain store. */
 int nbdt_maxpool3x3s2_bwd(const void* gy, const uint8_t* idx, int32_t dtype, int32_t B, int32_t H, int32_t W, int32_t C,
                           void* gx, void* stream);
+
+/* ------------------------------------------------------------------ batch mixing (nbdt_version() >= 116) */
+/* MixUp / CutMix of a training batch with itself rolled by one (torchvision v2's pairing: the partner of sample b is
+ * (b - 1) mod B), and the probability targets that go with it, in ONE streaming launch.  csrc/mix.hip.
+ *   x    fp32 [B][3][H][W];  y int64 [B], device memory;  out fp32 [B][3][H][W], must not overlap x (NBDT_EINVAL)
+ *   out  = x*lam + x_partner*one_minus_lam outside the box (two fp32 multiplies and one add, no contraction: the bits of
+ *          torch's x.mul(lam).add(x.roll(1, 0).mul(one_minus_lam))), and x_partner inside the box [y1, y2) x [x1, x2).
+ *          MixUp: an empty box (y1 == y2 or x1 == x2).  CutMix: lam = 1, one_minus_lam = 0 and a box;
+ *          0 <= y1 <= y2 <= H, 0 <= x1 <= x2 <= W.  With lam = 1 and one_minus_lam = 0 the element outside the box is x
+ *          itself, copied (CutMix's semantics): for MixUp at exactly lam = 1 that is torch's x*1 + x_partner*0 only where
+ *          x_partner is finite (an inf / NaN partner pixel gives NaN there, x here).
+ *   tgt  fp32 [B][C], must not overlap x or out (NBDT_EINVAL), every element written:  tgt[b] = onehot(y_b)*lam_t + onehot(y_partner)*one_minus_lam_t.
+ * A label outside [0, C) (the -1 of a sample a shard does not hold) gives an all-NaN target row, which the loss kernels
+ * turn into a NaN loss; no address is formed from it.  16-byte accesses when W % 4 == 0 and the pointers are 16-byte
+ * aligned, scalar otherwise.  No atomics: the same inputs give the same bits. */
+int nbdt_mix_batch(const float* x, const int64_t* y, int32_t B, int32_t H, int32_t W, float lam, float one_minus_lam,
+                   int32_t y1, int32_t y2, int32_t x1, int32_t x2, float lam_t, float one_minus_lam_t, float* out,
+                   float* tgt, int32_t C, void* stream);
 
 /* ------------------------------------------------------------------ measurement probe (not on the product path) */
 /* A register-only stream of independent v_mfma_f32_32x32x16_bf16 on `blocks` CUs (one 512-thread block each, two waves

@@ -599,6 +599,11 @@ __global__ __launch_bounds__(block_of(TPS)) void soft_bwd_kernel(TreeView t, con
     }
 }
 
+// floats of one sample's LDS row in soft_loss_kernel / soft_target_loss_kernel (zs, ss, ps, pq, gx, red) in front of the
+// optional staging area: the one definition both kernels and their dispatch use.  (A macro, not a function: through a
+// constexpr function the compiler reassociated soft_loss_kernel's address arithmetic.)
+#define NBDT_SOFT_LOSS_ROW_FLOATS(C, R) (3 * (C) + 2 * (R) + 16)
+
 // SoftTreeSupLoss forward+backward for criterion = nn.CrossEntropyLoss() (mean reduction):
 //   row = w_x*(lse(z) - z[y]) + w_t*(lse(P) - P[y])     (P fed to CE as if logits, loss.py:266)
 //   gz  = scale*( w_x*(softmax(z) - 1[y]) + J^T * w_t*(softmax(P) - 1[y]) )
@@ -606,9 +611,20 @@ __global__ __launch_bounds__(block_of(TPS)) void soft_bwd_kernel(TreeView t, con
 // which loads them from HBM, and head_soft_loss_kernel, which computes them from the pooled features.  On return
 // gx[c] holds dL/dz[c] for every class (each written by the lane that owns c; no trailing barrier); gz != nullptr
 // also stores it to gz[sample][c].
-template <int TPS>
+//
+// SOFT: criterion = nn.CrossEntropyLoss(label_smoothing = eps) and / or a probability target row.  The target is
+// t'_c = (1 - eps)*t_c + eps/C with t the dense row `trow` (this sample's, fp32) or, when trow is null, onehot(y); with
+// T = sum_c t'_c (torch does not normalise the row, so T is summed, not assumed)
+//   row = w_x*(T*lse(z) - sum_c t'_c z_c) + w_t*(T*lse(P) - sum_c t'_c P_c),   dL/dz_c direct = w_x*(T*softmax(z)_c - t'_c),
+//   dL/dP_c = w_t*(T*softmax(P)_c - t'_c).
+// t'_c waits in gx[c] between the first class loop and the gradient loop (the same lane owns c in both), so the LDS row
+// is the one of the index form; three more group sums (T, sum t'z, sum t'P), and lane 0 writes the row loss.  A one-hot
+// dense row with eps = 0 gives T = 1 and sums with a single non-zero term: the bits of the index form.
+// !SOFT (y, no smoothing; trow and eps unused) is the arithmetic soft_loss_kernel and head_soft_loss_kernel always had.
+template <int TPS, bool SOFT = false>
 __device__ __forceinline__ void soft_loss_from_lds_logits(const TreeView& t, const TreeLds& o, bool active, int g_tid,
-                                                          int64_t sample, const int64_t* __restrict__ y, float w_x,
+                                                          int64_t sample, const int64_t* __restrict__ y,
+                                                          const float* __restrict__ trow, float eps, float w_x,
                                                           float w_t, float scale, float* __restrict__ row_loss,
                                                           float* zs, float* ss, float* ps, float* pq, float* gx,
                                                           float* red, float* stage, Gather<TPS>& ga, Gather<TPS>& gb,
@@ -619,6 +635,10 @@ __device__ __forceinline__ void soft_loss_from_lds_logits(const TreeView& t, con
   if (t.staged) ga.issue(t.slot_cls, t.L, active, g_tid);  // for the G sums of tree_backward
 
   float mz = -INFINITY, mp = -INFINITY;
+  float st = 0.f, stz = 0.f, stp = 0.f;  // SOFT: this lane's part of T, sum t'z, sum t'P
+  const float uni = SOFT ? eps / (float)t.C : 0.f;  // the smoothing's uniform share (one correctly rounded division)
+  int64_t ys = -1;
+  if (SOFT && active && !trow) ys = y[sample];
   if (active)
     for (int c0 = g_tid; c0 < t.C; c0 += joint_of<TPS>() * TPS) {
       float p[joint_of<TPS>()];
@@ -630,6 +650,14 @@ __device__ __forceinline__ void soft_loss_from_lds_logits(const TreeView& t, con
           pq[c] = p[m];
           mp = fmaxf(mp, p[m]);
           mz = fmaxf(mz, zs[c]);
+          if (SOFT) {
+            const float tc = trow ? trow[c] : ((c == ys) ? 1.f : 0.f);
+            const float ts = (1.f - eps) * tc + uni;
+            gx[c] = ts;
+            st += ts;
+            stz += ts * zs[c];
+            stp += ts * p[m];
+          }
         }
       }
     }
@@ -644,7 +672,25 @@ __device__ __forceinline__ void soft_loss_from_lds_logits(const TreeView& t, con
   sz = group_sum<TPS>(sz, red, g_tid);
   sp = group_sum<TPS>(sp, red, g_tid);
 
-  if (active) {
+  if (SOFT) {
+    st = group_sum<TPS>(st, red, g_tid);
+    stz = group_sum<TPS>(stz, red, g_tid);
+    stp = group_sum<TPS>(stp, red, g_tid);
+    if (active) {
+      for (int c = g_tid; c < t.C; c += TPS) {
+        const float ts = gx[c];
+        const float p = pq[c];
+        gx[c] = (st * (expf(zs[c] - mz) / sz) - ts) * (w_x * scale);
+        const float gp = (st * (expf(p - mp) / sp) - ts) * (w_t * scale);
+        pq[c] = p * gp;
+      }
+      if (g_tid == 0) {
+        const bool valid = trow || (ys >= 0 && ys < t.C);
+        row_loss[sample] = valid ? w_x * (st * (logf(sz) + mz) - stz) + w_t * (st * (logf(sp) + mp) - stp)
+                                 : __uint_as_float(0x7fc00000u);  // loud: NaN loss
+      }
+    }
+  } else if (active) {
     const int64_t yy = y[sample];
     const bool valid = yy >= 0 && yy < t.C;
     for (int c = g_tid; c < t.C; c += TPS) {
@@ -686,7 +732,7 @@ __global__ __launch_bounds__(block_of(TPS)) void soft_loss_kernel(TreeView t, co
   const int g = threadIdx.x / TPS, g_tid = threadIdx.x % TPS;
   const int64_t sample = (int64_t)blockIdx.x * SPB + g;
   const bool active = sample < B;
-  const int stride = 3 * t.C + 2 * t.R + 16 + (t.staged ? t.L : 0);
+  const int stride = NBDT_SOFT_LOSS_ROW_FLOATS(t.C, t.R) + (t.staged ? t.L : 0);
   Gather<TPS> ga, gb;  // ga: slot -> classes (issued here, under the logits load), gb: class -> slots
   if (t.staged) ga.issue(t.slot_cls, t.L, active, g_tid);
   const TreeLds o = stage_tree<false>(t, lds);
@@ -700,8 +746,43 @@ __global__ __launch_bounds__(block_of(TPS)) void soft_loss_kernel(TreeView t, co
   if (active)
     for (int c = g_tid; c < t.C; c += TPS) zs[c] = LD::at(z, sample * ldz + c);
   __syncthreads();
-  soft_loss_from_lds_logits<TPS>(t, o, active, g_tid, sample, y, w_x, w_t, scale, row_loss, zs, ss, ps, pq, gx, red,
-                                 stage, ga, gb, gz);
+  soft_loss_from_lds_logits<TPS>(t, o, active, g_tid, sample, y, nullptr, 0.f, w_x, w_t, scale, row_loss, zs, ss, ps, pq, gx,
+                                 red, stage, ga, gb, gz);
+}
+
+// The same launch for label smoothing and / or probability targets (exactly one of y and tprob is non-null): the SOFT
+// form of the shared loss on the same LDS row.  The row set-up is repeated from soft_loss_kernel on purpose: routed
+// through a shared helper the compiler scheduled soft_loss_kernel differently, and that kernel's instruction stream is
+// kept as it was.
+template <int TPS, typename LD>
+__global__ __launch_bounds__(block_of(TPS)) void soft_target_loss_kernel(TreeView t, const void* z, int64_t B, int64_t ldz,
+                                                                  const int64_t* __restrict__ y,
+                                                                  const float* __restrict__ tprob, int64_t ldt,
+                                                                  float eps, float w_x, float w_t, float scale,
+                                                                  float* __restrict__ row_loss,
+                                                                  float* __restrict__ gz) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int SPB = block_of(TPS) / TPS;
+  const int g = threadIdx.x / TPS, g_tid = threadIdx.x % TPS;
+  const int64_t sample = (int64_t)blockIdx.x * SPB + g;
+  const bool active = sample < B;
+  const int stride = NBDT_SOFT_LOSS_ROW_FLOATS(t.C, t.R) + (t.staged ? t.L : 0);
+  Gather<TPS> ga, gb;  // ga: slot -> classes (issued here, under the logits load), gb: class -> slots
+  if (t.staged) ga.issue(t.slot_cls, t.L, active, g_tid);
+  const TreeLds o = stage_tree<false>(t, lds);
+  float* zs = lds + t.tl_ints + (size_t)g * stride;
+  float* ss = zs + t.C;
+  float* ps = ss + t.R;
+  float* pq = ps + t.R;
+  float* gx = pq + t.C;
+  float* red = gx + t.C;
+  float* stage = red + 16;
+  if (active)
+    for (int c = g_tid; c < t.C; c += TPS) zs[c] = LD::at(z, sample * ldz + c);
+  __syncthreads();
+  const float* trow = (tprob && active) ? tprob + sample * ldt : nullptr;
+  soft_loss_from_lds_logits<TPS, true>(t, o, active, g_tid, sample, y, trow, eps, w_x, w_t, scale, row_loss, zs, ss, ps, pq,
+                                       gx, red, stage, ga, gb, gz);
 }
 
 // ---- N1: the classifier head and the tree loss in ONE launch (north star: "the node-embedding inner product and
@@ -809,8 +890,8 @@ __global__ __launch_bounds__(TPS * SPB) void head_soft_loss_kernel(TreeView t, c
     }
   }
   __syncthreads();
-  soft_loss_from_lds_logits<TPS>(t, o, active, g_tid, sample, y, w_x, w_t, scale, row_loss, zs, ss, ps, pq, gx, red,
-                                 stage, ga, gbk, nullptr);
+  soft_loss_from_lds_logits<TPS>(t, o, active, g_tid, sample, y, nullptr, 0.f, w_x, w_t, scale, row_loss, zs, ss, ps, pq,
+                                 gx, red, stage, ga, gbk, nullptr);
   __syncthreads();      // every sample's gx is complete: the block-wide weight-gradient sums read all of them
   if (gpooled) {      // thread = feature k for ALL the block's samples: one read of W's column per block, 32 rows in flight;
     const int gx_off = (int)(gx - xs);      // each (sample, k) sum stays one ascending chain of fused multiply-adds
@@ -868,9 +949,12 @@ __global__ __launch_bounds__(TPS * SPB) void head_soft_loss_kernel(TreeView t, c
 //    the same weight tsw/(B*N/2), loss.py:228,250-256, times the scheduled tree weight, :195-203)
 // The nodes on the label's path are exactly the class->slot CSR row of y; a class listed under two
 // children of one node counts once, for the first child (model.py:135 `cls[0]`).
+// eps != 0: criterion = nn.CrossEntropyLoss(label_smoothing = eps).  A node with K children and the label under child s
+// contributes lse(s[n,:]) - (1 - eps)*s[n,s] - (eps/K)*sum_k s[n,k], the cross-entropy term is smoothed with eps/C;
+// eps == 0 (a block-uniform branch) keeps the operations above.
 template <int TPS, typename LD>
 __global__ __launch_bounds__(block_of(TPS)) void hard_loss_kernel(TreeView t, const void* z, int64_t B, int64_t ldz,
-                                                           const int64_t* __restrict__ y, float w_x,
+                                                           const int64_t* __restrict__ y, float eps, float w_x,
                                                            float w_h, float scale,
                                                            float* __restrict__ row_loss,
                                                            float* __restrict__ gz) {
@@ -894,6 +978,7 @@ __global__ __launch_bounds__(block_of(TPS)) void hard_loss_kernel(TreeView t, co
     for (int s = g_tid; s < t.R; s += TPS) ds[s] = 0.f;
   __syncthreads();
 
+  const bool smooth = eps != 0.f;
   int64_t yy = 0;
   bool valid = false;
   if (active) {
@@ -917,6 +1002,16 @@ __global__ __launch_bounds__(block_of(TPS)) void hard_loss_kernel(TreeView t, co
       for (int q = b + 1; q < e; ++q) m = fmaxf(m, ss[q]);
       float sum = 0.f;
       for (int q = b; q < e; ++q) sum = sum + expf(ss[q] - m);
+      if (smooth) {
+        const float uni = eps / (float)(e - b);
+        float sl = 0.f;
+        for (int q = b; q < e; ++q) sl = sl + ss[q];
+        tree_rows += ((logf(sum) + m) - (1.f - eps) * ss[s]) - uni * sl;
+        for (int q = b; q < e; ++q)
+          ds[q] = (expf(ss[q] - m) / sum - ((q == s ? 1.f - eps : 0.f) + uni)) * (w_h * scale) /
+                  (float)(o.slot_off[q + 1] - o.slot_off[q]);
+        continue;
+      }
       tree_rows += (logf(sum) + m) - ss[s];
       for (int q = b; q < e; ++q)  // the term each leaf of slot q receives: dL/ds over the slot's leaf count
         ds[q] = (expf(ss[q] - m) / sum - (q == s ? 1.f : 0.f)) * (w_h * scale) /
@@ -933,8 +1028,21 @@ __global__ __launch_bounds__(block_of(TPS)) void hard_loss_kernel(TreeView t, co
   if (active)
     for (int c = g_tid; c < t.C; c += TPS) sz += expf(zs[c] - mz);
   sz = group_sum<TPS>(sz, red, g_tid);
+  float sumz = 0.f;
+  if (smooth) {
+    if (active)
+      for (int c = g_tid; c < t.C; c += TPS) sumz += zs[c];
+    sumz = group_sum<TPS>(sumz, red, g_tid);
+  }
   if (active) {
+    const float uni = eps / (float)t.C;
     for (int c = g_tid; c < t.C; c += TPS) {
+      if (smooth) {
+        if (c == yy)
+          row_loss[sample] = w_x * (((logf(sz) + mz) - (1.f - eps) * zs[c]) - uni * sumz) + w_h * tree_rows;
+        gx[c] = (expf(zs[c] - mz) / sz - ((c == yy ? 1.f - eps : 0.f) + uni)) * (w_x * scale);
+        continue;
+      }
       const float hot = (c == yy) ? 1.f : 0.f;
       if (c == yy) row_loss[sample] = w_x * ((logf(sz) + mz) - zs[c]) + w_h * tree_rows;
       gx[c] = (expf(zs[c] - mz) / sz - hot) * (w_x * scale);
@@ -1342,7 +1450,7 @@ __global__ __launch_bounds__(block_of(TPS)) void tree_stats_kernel(TreeView t, c
 // host side
 
 extern "C" const char* nbdt_last_error(void) { return nbdt::g_err; }
-extern "C" int nbdt_version(void) { return 115; }     // 115: nbdt_stem_patches, nbdt_maxpool3x3s2_fwd / _bwd (the 7x7 / 2 stem as a patch gather in front of the 1x1 convolution, and MaxPool2d(3, 2, 1), for torchvision-shaped ResNets: csrc/stem_pool.hip); 114: nbdt_augment_batch_sharded, nbdt_resized_crop_batch_sharded (a rank keeps its contiguous shard of a device-resident dataset: the draw from the dataset index, the gather from index - index_base); 113: nbdt_conv_pw (stride-1 1x1 convolutions as a GEMM: the Bottleneck ResNets); 112: nbdt_tree_stats_accumulate (tree diagnostics: per-node counters, confusion matrices, entropy sums, scores in one launch); 111: nbdt_resized_crop_batch, nbdt_resized_crop_band_rows (RandomResizedCrop / Resize + CenterCrop datasets); 110: nbdt_augment_batch (device-resident datasets: gather + crop + flip + normalise), NBDT_U8; 109: nbdt_set/get_stream_nt_min_bytes, nbdt_debug_last_stream_nt, nbdt_conv_seg_create refuses ntensors > 2; 108: nbdt_se_param_grad, nbdt_se_gate_bwd without parameter gradients; 107: nbdt_bn_act_se_sums / _se_bwd_apply; 106: nbdt_conv_desc.ksplit is live (was reserved), nbdt_conv_seg_*
+extern "C" int nbdt_version(void) { return 116; }     // 116: nbdt_soft_tree_loss_ex, nbdt_hard_tree_loss_ex (label smoothing in both fused tree losses, probability targets in the soft one), nbdt_mix_batch (MixUp / CutMix and their targets in one launch: csrc/mix.hip); 115: nbdt_stem_patches, nbdt_maxpool3x3s2_fwd / _bwd (the 7x7 / 2 stem as a patch gather in front of the 1x1 convolution, and MaxPool2d(3, 2, 1), for torchvision-shaped ResNets: csrc/stem_pool.hip); 114: nbdt_augment_batch_sharded, nbdt_resized_crop_batch_sharded (a rank keeps its contiguous shard of a device-resident dataset: the draw from the dataset index, the gather from index - index_base); 113: nbdt_conv_pw (stride-1 1x1 convolutions as a GEMM: the Bottleneck ResNets); 112: nbdt_tree_stats_accumulate (tree diagnostics: per-node counters, confusion matrices, entropy sums, scores in one launch); 111: nbdt_resized_crop_batch, nbdt_resized_crop_band_rows (RandomResizedCrop / Resize + CenterCrop datasets); 110: nbdt_augment_batch (device-resident datasets: gather + crop + flip + normalise), NBDT_U8; 109: nbdt_set/get_stream_nt_min_bytes, nbdt_debug_last_stream_nt, nbdt_conv_seg_create refuses ntensors > 2; 108: nbdt_se_param_grad, nbdt_se_gate_bwd without parameter gradients; 107: nbdt_bn_act_se_sums / _se_bwd_apply; 106: nbdt_conv_desc.ksplit is live (was reserved), nbdt_conv_seg_*
 extern "C" int nbdt_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1576,20 +1684,38 @@ extern "C" int nbdt_soft_backward(const nbdt_tree* t, const void* z, int ztype, 
   return NBDT_OK;
 }
 
-extern "C" int nbdt_soft_tree_loss(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz,
-                                   const int64_t* y, float w_xent, float w_tree, float grad_scale,
-                                   float* row_loss, float* loss, float* gz, void* stream) {
+// class-index targets without smoothing launch soft_loss_kernel, as nbdt_soft_tree_loss always did; anything else the
+// SOFT form.  One LDS row layout (BASE_FLOATS) for both, so v.staged and the occupancy do not depend on the targets.
+extern "C" int nbdt_soft_tree_loss_ex(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz,
+                                      const int64_t* y, const float* tprob, int64_t ldt, float smoothing, float w_xent,
+                                      float w_tree, float grad_scale, float* row_loss, float* loss, float* gz,
+                                      void* stream) {
   int rc = check_common(t, z, ztype, B, ldz);
   if (rc) return rc;
-  NBDT_REQUIRE(y && row_loss && loss && gz, "null buffer");
+  NBDT_REQUIRE(row_loss && loss && gz, "null buffer");
+  NBDT_REQUIRE((y != nullptr) != (tprob != nullptr),
+               "exactly one of y (class indices) and tprob (probability targets) must be given");
+  NBDT_REQUIRE(tprob == nullptr || ldt >= t->C, "bad target row stride");
+  NBDT_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "label smoothing must be in [0, 1)");
   NBDT_REQUIRE(B > 0, "empty batch has no mean loss");
   TreeView v = view_of(t);
   const float scale = grad_scale / (float)B;
-  NBDT_DISPATCH_RULES(soft_loss_kernel, false, 3 * t->C + 2 * t->R + 16, v, z, B, ldz, y, w_xent, w_tree, scale,
-                      row_loss, gz);
+  if (y && smoothing == 0.f)
+    NBDT_DISPATCH_RULES(soft_loss_kernel, false, NBDT_SOFT_LOSS_ROW_FLOATS(t->C, t->R), v, z, B, ldz, y, w_xent, w_tree, scale,
+                        row_loss, gz);
+  else
+    NBDT_DISPATCH_RULES(soft_target_loss_kernel, false, NBDT_SOFT_LOSS_ROW_FLOATS(t->C, t->R), v, z, B, ldz, y, tprob, ldt, smoothing,
+                        w_xent, w_tree, scale, row_loss, gz);
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, row_loss, B, loss);
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;
+}
+
+extern "C" int nbdt_soft_tree_loss(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz,
+                                   const int64_t* y, float w_xent, float w_tree, float grad_scale,
+                                   float* row_loss, float* loss, float* gz, void* stream) {
+  return nbdt_soft_tree_loss_ex(t, z, ztype, B, ldz, y, nullptr, 0, 0.f, w_xent, w_tree, grad_scale, row_loss, loss, gz,
+                                stream);
 }
 
 template <int TPS, int SPB>
@@ -1658,14 +1784,21 @@ extern "C" int nbdt_head_soft_tree_loss(const nbdt_tree* t, const float* pooled,
 extern "C" int nbdt_hard_tree_loss(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz,
                                    const int64_t* y, float w_xent, float w_node, float grad_scale,
                                    float* row_loss, float* loss, float* gz, void* stream) {
+  return nbdt_hard_tree_loss_ex(t, z, ztype, B, ldz, y, 0.f, w_xent, w_node, grad_scale, row_loss, loss, gz, stream);
+}
+
+extern "C" int nbdt_hard_tree_loss_ex(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz,
+                                      const int64_t* y, float smoothing, float w_xent, float w_node, float grad_scale,
+                                      float* row_loss, float* loss, float* gz, void* stream) {
   int rc = check_common(t, z, ztype, B, ldz);
   if (rc) return rc;
   NBDT_REQUIRE(y && row_loss && loss && gz, "null buffer");
+  NBDT_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "label smoothing must be in [0, 1)");
   NBDT_REQUIRE(B > 0, "empty batch has no mean loss");
   TreeView v = view_of(t);
   const float scale = grad_scale / (float)B;
-  NBDT_DISPATCH_RULES(hard_loss_kernel, false, 2 * t->C + 2 * t->R + 16, v, z, B, ldz, y, w_xent, w_node, scale,
-                      row_loss, gz);
+  NBDT_DISPATCH_RULES(hard_loss_kernel, false, 2 * t->C + 2 * t->R + 16, v, z, B, ldz, y, smoothing, w_xent, w_node,
+                      scale, row_loss, gz);
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, row_loss, B, loss);
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;

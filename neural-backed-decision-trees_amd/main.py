@@ -49,6 +49,12 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   (``nbdt.dist.epoch_indices(..., sharded=True)``), not across the whole set as the reference's sampler does: a global
   batch is ``batch / world`` samples from every rank's part.  That is the price of never moving an image between GPUs;
   the augmentation a sample gets is the same either way (it depends on seed, epoch and the sample's index alone).
+* ``--label-smoothing E`` wraps ``nn.CrossEntropyLoss(label_smoothing=E)``; the fused tree losses apply it in their one
+  launch.  ``--mixup-alpha A`` / ``--cutmix-alpha A`` mix every training batch with itself rolled by one
+  (torchvision v2's MixUp / CutMix, one draw per step: ``nbdt.data.draw_mix`` of (seed, epoch, step), the same on every
+  rank) in one launch that also writes the probability targets, whatever ``--augment`` made the batch; the step then takes
+  ``soft_target_loss_and_grad``.  A loss without it (``HardTreeSupLoss``: the reference's cannot take probability
+  targets either) is refused at argument time.  Evaluation is never mixed.
 """
 import argparse
 import json
@@ -67,7 +73,8 @@ from nbdt import diagnostics  # noqa: E402
 from nbdt import dist as ndist  # noqa: E402
 from nbdt import loss as losses  # noqa: E402
 from nbdt import models  # noqa: E402
-from nbdt.data import DATASET_STATS, RESIZED_CROP_STATS, DeviceDataset, ResizedCropDataset, shard_range  # noqa: E402
+from nbdt.data import (DATASET_STATS, RESIZED_CROP_STATS, DeviceDataset, ResizedCropDataset, draw_mix, mix_batch,  # noqa: E402
+                       shard_range)
 from nbdt.engine import train_step  # noqa: E402
 from nbdt.model import coerce_state_dict  # noqa: E402
 from nbdt.tree import Tree  # noqa: E402
@@ -138,6 +145,13 @@ def build_parser():
                    help="--augment reference | resized-crop: every rank keeps only its contiguous part of both splits on "
                         "its GPU (nbdt.data shard=(rank, world)), a --data-file is memory-mapped, and training shuffles "
                         "within each rank's part")
+    p.add_argument("--label-smoothing", type=float, default=0.0, metavar="E",
+                   help="label_smoothing of the wrapped nn.CrossEntropyLoss, 0 <= E < 1 (applied inside the fused tree loss)")
+    p.add_argument("--mixup-alpha", type=float, default=0.0, metavar="A",
+                   help="MixUp on every training batch, lam ~ Beta(A, A) per step (0: off); with --cutmix-alpha too, a fair "
+                        "coin per step picks one of the two")
+    p.add_argument("--cutmix-alpha", type=float, default=0.0, metavar="A",
+                   help="CutMix on every training batch, lam ~ Beta(A, A) per step (0: off)")
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible training steps, like the reference's CPU path: every cross-block reduction in "
                         "a fixed order instead of fp32 atomics (nbdt_set_deterministic; ResNet / WideResNet backbones)")
@@ -180,12 +194,14 @@ def multistep_lr(base_lr, epoch, epochs, gamma=0.1):
 
 
 def build_criterion(args, tree, net=None, checkpoint_path="./"):
-    """reference main.py:191-205: the LAST entry of --loss wraps nn.CrossEntropyLoss()."""
-    criterion = nn.CrossEntropyLoss()
+    """reference main.py:191-205: the LAST entry of --loss wraps nn.CrossEntropyLoss() (--label-smoothing: its
+    label_smoothing)."""
+    smoothing = float(getattr(args, "label_smoothing", 0.0))
+    criterion = nn.CrossEntropyLoss(label_smoothing=smoothing)
     for name in args.loss:
         cls = getattr(losses, name)
         if name == "CrossEntropyLoss":
-            criterion = cls()
+            criterion = cls(label_smoothing=smoothing)
             continue
         kwargs = {"dataset": args.dataset, "criterion": criterion, "tree": tree}
         for key in ("tree_supervision_weight", "tree_supervision_weight_end", "tree_supervision_weight_power",
@@ -204,15 +220,18 @@ def build_criterion(args, tree, net=None, checkpoint_path="./"):
 class _PlainCE:
     """--loss CrossEntropyLoss on the engine's fast path: the fused kernel with a zero tree weight."""
 
-    def __init__(self, tree):
-        self.inner = losses.SoftTreeSupLoss(dataset=None, criterion=nn.CrossEntropyLoss(), tree=tree,
-                                            tree_supervision_weight=0.0)
+    def __init__(self, tree, label_smoothing=0.0):
+        self.inner = losses.SoftTreeSupLoss(dataset=None, criterion=nn.CrossEntropyLoss(label_smoothing=label_smoothing),
+                                            tree=tree, tree_supervision_weight=0.0)
 
     def set_epoch(self, cur, total):
         pass
 
     def loss_and_grad(self, z, y, grad_scale=1.0):
         return self.inner.loss_and_grad(z, y, grad_scale)
+
+    def soft_target_loss_and_grad(self, z, target_probs, grad_scale=1.0):
+        return self.inner.soft_target_loss_and_grad(z, target_probs, grad_scale)
 
 
 def load_data(args, num_classes, device, raw=False):
@@ -320,6 +339,16 @@ def parse_args(argv=None):
     if args.shard_data and args.augment not in ("reference", "resized-crop"):
         parser.error("--shard-data shards the device-resident datasets: it needs --augment reference or --augment "
                      "resized-crop")
+    if not 0.0 <= args.label_smoothing < 1.0:
+        parser.error(f"--label-smoothing must be in [0, 1), got {args.label_smoothing}")
+    if args.mixup_alpha < 0 or args.cutmix_alpha < 0:
+        parser.error("--mixup-alpha and --cutmix-alpha must be >= 0")
+    if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
+        name = args.loss[-1]            # the loss the training step calls
+        if name != "CrossEntropyLoss" and not hasattr(getattr(losses, name), "soft_target_loss_and_grad"):
+            raise SystemExit(f"--mixup-alpha / --cutmix-alpha make probability targets, which --loss {name} cannot take "
+                             f"(it has no soft_target_loss_and_grad; the reference's {name} cannot either): use "
+                             "SoftTreeSupLoss, SoftTreeLoss or CrossEntropyLoss")
     return args
 
 
@@ -404,7 +433,7 @@ def main(argv=None):
                 log(f"==> Checkpoint found at {resume_path}")
 
     criterion = build_criterion(args, tree, net=net, checkpoint_path=checkpoint_path)
-    fast = criterion if hasattr(criterion, "loss_and_grad") else _PlainCE(tree)
+    fast = criterion if hasattr(criterion, "loss_and_grad") else _PlainCE(tree, args.label_smoothing)
     analyzer_cls = getattr(analysis, args.analysis or "Noop")
     analyzer = analyzer_cls(tree=tree, metric=args.metric) if args.analysis not in (None, "Noop") else analyzer_cls(tree.classes)
     extras = [build_diagnostic(name, tree) for name in args.diagnostics]
@@ -437,6 +466,9 @@ def main(argv=None):
                 xb, yb = train_x.batch(idx, epoch=epoch, seed=args.seed)
             else:
                 xb, yb = train_x[idx].to(device, non_blocking=True), train_y[idx].to(device, non_blocking=True)
+            mix = draw_mix(args.seed, epoch, i, xb.shape[2], xb.shape[3], args.mixup_alpha, args.cutmix_alpha)
+            if mix is not None:              # one launch: the mixed batch and its probability targets
+                xb, yb = mix_batch(xb, yb, num_classes, mix)
             total += train_step(engine, fast, xb, yb, lr, comm=comm, **decay)
         log("Loss: %.3f (%d steps of %d x %d images)" % (total.item() / max(steps, 1), steps, world, per_rank))
 

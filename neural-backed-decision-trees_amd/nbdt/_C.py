@@ -116,6 +116,12 @@ SIGNATURES = {
                                          _P, _P, _P, _P, _P, _P, _P]),
     "nbdt_hard_tree_loss": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, c_float, c_float, c_float,
                                     _P, _P, _P, _P]),
+    "nbdt_soft_tree_loss_ex": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, c_int64, c_float, c_float, c_float,
+                                       c_float, _P, _P, _P, _P]),
+    "nbdt_hard_tree_loss_ex": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, c_float, c_float, c_float, c_float,
+                                       _P, _P, _P, _P]),
+    "nbdt_mix_batch": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_float, c_float, c_int32, c_int32, c_int32, c_int32,
+                               c_float, c_float, _P, _P, c_int32, _P]),
     "nbdt_node_logits_backward": (c_int, [c_void_p, _P, c_int64, _P, _P]),
     "nbdt_hard_forward": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "nbdt_node_outputs": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, _P, _P, _P]),
@@ -351,19 +357,40 @@ def soft_backward(handle, z, gP):
     return gz
 
 
-def soft_tree_loss(handle, z, y, w_xent, w_tree, grad_scale=1.0):
-    """Returns (loss scalar tensor, gz [B,C] fp32)."""
+def _soft_tree_loss_ex(handle, z, B, ld, y, t, ldt, smoothing, w_xent, w_tree, grad_scale):
+    row = torch.empty((B,), dtype=torch.float32, device=z.device)
+    loss = torch.empty((), dtype=torch.float32, device=z.device)
+    gz = torch.empty((B, handle.flat.num_classes), dtype=torch.float32, device=z.device)
+    check(lib().nbdt_soft_tree_loss_ex(handle.h, ptr(z), ztype_of(z), B, ld, ptr(y), ptr(t), int(ldt), float(smoothing),
+                                       float(w_xent), float(w_tree), float(grad_scale), ptr(row), ptr(loss), ptr(gz),
+                                       stream_of(z)))
+    return loss, gz
+
+
+def soft_tree_loss(handle, z, y, w_xent, w_tree, grad_scale=1.0, smoothing=0.0):
+    """Returns (loss scalar tensor, gz [B,C] fp32).  smoothing: the criterion's label_smoothing (nbdt_soft_tree_loss_ex)."""
     require_gpu(z, "soft_tree_loss")
     handle.flat.require_single_path()
     z, B, ld = _rows(z, handle)
     y = _class_targets(y, z)
-    row = torch.empty((B,), dtype=torch.float32, device=z.device)
-    loss = torch.empty((), dtype=torch.float32, device=z.device)
-    gz = torch.empty((B, handle.flat.num_classes), dtype=torch.float32, device=z.device)
-    check(lib().nbdt_soft_tree_loss(handle.h, ptr(z), ztype_of(z), B, ld, ptr(y), float(w_xent),
-                                    float(w_tree), float(grad_scale), ptr(row), ptr(loss), ptr(gz),
-                                    stream_of(z)))
-    return loss, gz
+    return _soft_tree_loss_ex(handle, z, B, ld, y, None, 0, smoothing, w_xent, w_tree, grad_scale)
+
+
+def soft_tree_loss_dense(handle, z, t, w_xent, w_tree, grad_scale=1.0, smoothing=0.0):
+    """The same loss on probability targets t [B, C] fp32 (MixUp / CutMix, soft labels): (loss, gz [B,C] fp32).  The rows
+    are used as given -- not normalised, like torch's criterion."""
+    require_gpu(z, "soft_tree_loss_dense")
+    handle.flat.require_single_path()
+    z, B, ld = _rows(z, handle)
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 2 or tuple(t.shape) != tuple(z.shape):
+        raise NBDTHipError(f"probability targets must be fp32 [B, C] = {tuple(z.shape)}, got "
+                           f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    if t.device != z.device:
+        raise NBDTHipError(f"probability targets are on {t.device}, the logits on {z.device}")
+    if t.stride(1) != 1 or (B > 1 and t.stride(0) < t.shape[1]):
+        raise NBDTHipError(f"probability targets need unit column stride and non-overlapping rows, got strides {t.stride()}")
+    ldt = t.stride(0) if B > 1 else t.shape[1]
+    return _soft_tree_loss_ex(handle, z, B, ld, None, t, ldt, smoothing, w_xent, w_tree, grad_scale)
 
 
 def head_soft_tree_loss(handle, pooled, W, bias, y, w_xent, w_tree, grad_scale=1.0, gW=None, gb=None,
@@ -389,17 +416,17 @@ def head_soft_tree_loss(handle, pooled, W, bias, y, w_xent, w_tree, grad_scale=1
     return loss, gp, z
 
 
-def hard_tree_loss(handle, z, y, w_xent, w_node, grad_scale=1.0):
-    """HardTreeSupLoss fused: returns (loss scalar tensor, gz [B,C] fp32)."""
+def hard_tree_loss(handle, z, y, w_xent, w_node, grad_scale=1.0, smoothing=0.0):
+    """HardTreeSupLoss fused: returns (loss scalar tensor, gz [B,C] fp32).  smoothing: the criterion's label_smoothing."""
     require_gpu(z, "hard_tree_loss")
     z, B, ld = _rows(z, handle)
     y = _class_targets(y, z)
     row = torch.empty((B,), dtype=torch.float32, device=z.device)
     loss = torch.empty((), dtype=torch.float32, device=z.device)
     gz = torch.empty((B, handle.flat.num_classes), dtype=torch.float32, device=z.device)
-    check(lib().nbdt_hard_tree_loss(handle.h, ptr(z), ztype_of(z), B, ld, ptr(y), float(w_xent),
-                                    float(w_node), float(grad_scale), ptr(row), ptr(loss), ptr(gz),
-                                    stream_of(z)))
+    check(lib().nbdt_hard_tree_loss_ex(handle.h, ptr(z), ztype_of(z), B, ld, ptr(y), float(smoothing), float(w_xent),
+                                       float(w_node), float(grad_scale), ptr(row), ptr(loss), ptr(gz),
+                                       stream_of(z)))
     return loss, gz
 
 

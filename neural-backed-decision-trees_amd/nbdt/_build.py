@@ -23,6 +23,7 @@ COMMON = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno
 FLAGS = {
     "rules.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "augment.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],   # bit-exact vs torch's CPU normalise
+    "mix.hip": ["-ffp-contract=off"],          # torch's x.mul(lam).add(partner.mul(1 - lam)): two multiplies, one add
     "resample.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],  # PIL's bytes, torch's normalise
     "conv.hip": ["-munsafe-fp-atomics"],
     "conv_dma.hip": ["-munsafe-fp-atomics"],

@@ -457,3 +457,52 @@ class ResizedCropDataset:
                                params_in=params, params_out=used,
                                index_base=self.shard_range[0] if self.sharded else None)
         return (img, targets, used) if return_params else (img, targets)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# MixUp / CutMix (torchvision.transforms.v2.MixUp / CutMix; the soft-label transforms of the reference's ImageNet example):
+# one draw per step on the host, one launch (nbdt_mix_batch, csrc/mix.hip) for the images and the probability targets.
+
+def draw_mix(seed, epoch, step, H, W, mixup_alpha=0.0, cutmix_alpha=0.0):
+    """The mixing of one training step, or None when both alphas are 0: a dict with ``mode`` ("mixup" | "cutmix"),
+    ``lam`` (the draw, Beta(alpha, alpha), one per batch), ``box`` = (y1, y2, x1, x2) and ``lam_t``, the weight of a
+    sample's own label.  A pure function of its arguments (numpy's default_rng([seed, epoch, step])), so every rank of a
+    run draws the same mixing without talking to the others.
+
+    MixUp: an empty box, lam_t = lam.  CutMix, as in torchvision: the box's centre is uniform over the pixels, its half
+    sides are int(0.5*sqrt(1 - lam)*H) and int(0.5*sqrt(1 - lam)*W), it is clipped to the image and
+    lam_t = 1 - area / (H*W).  With both alphas > 0 one fair coin per step picks the mode."""
+    mixup_alpha, cutmix_alpha = float(mixup_alpha), float(cutmix_alpha)
+    if mixup_alpha < 0 or cutmix_alpha < 0:
+        raise ValueError(f"mixup_alpha and cutmix_alpha must be >= 0, got {mixup_alpha}, {cutmix_alpha}")
+    if mixup_alpha == 0 and cutmix_alpha == 0:
+        return None
+    H, W = int(H), int(W)
+    rng = np.random.default_rng([int(seed), int(epoch), int(step)])
+    if mixup_alpha > 0 and cutmix_alpha > 0:
+        cut = bool(rng.integers(2))
+    else:
+        cut = cutmix_alpha > 0
+    alpha = cutmix_alpha if cut else mixup_alpha
+    lam = float(rng.beta(alpha, alpha))
+    if not cut:
+        return {"mode": "mixup", "lam": lam, "box": (0, 0, 0, 0), "lam_t": lam}
+    r_y, r_x = int(rng.integers(H)), int(rng.integers(W))
+    r = 0.5 * math.sqrt(1.0 - lam)
+    half_h, half_w = int(r * H), int(r * W)
+    y1, y2 = max(r_y - half_h, 0), min(r_y + half_h, H)
+    x1, x2 = max(r_x - half_w, 0), min(r_x + half_w, W)
+    return {"mode": "cutmix", "lam": lam, "box": (y1, y2, x1, x2), "lam_t": 1.0 - (y2 - y1) * (x2 - x1) / float(H * W)}
+
+
+def mix_batch(img, targets, num_classes, draw):
+    """(mixed images [B,3,H,W], probability targets [B, num_classes] fp32) of a training batch under ``draw``
+    (draw_mix): every sample is paired with its predecessor in the batch (the batch rolled by one).  One launch, freshly
+    allocated outputs; ``img`` and ``targets`` are left as they are."""
+    out = torch.empty_like(img)
+    tgt = torch.empty((img.shape[0], int(num_classes)), dtype=torch.float32, device=img.device)
+    if draw["mode"] == "cutmix":
+        ops.mix_batch(img, targets, out, tgt, lam=1.0, box=draw["box"], lam_t=draw["lam_t"])
+    else:
+        ops.mix_batch(img, targets, out, tgt, lam=draw["lam"], box=(0, 0, 0, 0), lam_t=draw["lam_t"])
+    return out, tgt

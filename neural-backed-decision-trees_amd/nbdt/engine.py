@@ -1672,10 +1672,16 @@ def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5
     kernel -- with the classifier's forward and backward inside it when the criterion and the head's width allow,
     fused_head=False keeps linear -> loss -> linear-backward as three launches), backward, [gradient all-reduce],
     SGD.  Returns the loss tensor (device scalar).  zero_grad=False leaves the step's gradient in the flat gradient
-    buffer instead of having the SGD kernel clear it for the next step (tests that compare gradients)."""
+    buffer instead of having the SGD kernel clear it for the next step (tests that compare gradients).
+    Floating-point targets are probability rows [B, C] (MixUp / CutMix, nbdt.data.mix_batch): they skip the fused head
+    and go through criterion.soft_target_loss_and_grad, still one loss launch."""
     engine.zero_grad()
     names = getattr(engine, "classifier_names", None)
-    if (fused_head and names is not None and hasattr(criterion, "can_fuse_head")
+    if targets.is_floating_point():
+        z = engine.forward(img, training=True)
+        loss, gz = criterion.soft_target_loss_and_grad(z, targets)
+        engine.backward(gz, comm=comm)
+    elif (fused_head and names is not None and hasattr(criterion, "can_fuse_head")
             and criterion.can_fuse_head(engine.num_classes)):
         # classifier + rules + loss + their backward in ONE launch (nbdt_head_soft_tree_loss): logits stay on chip
         pooled = engine.forward(img, training=True, head=False)
@@ -1712,6 +1718,8 @@ class GraphedStep:
     def __init__(self, engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5e-4, warmup=2):
         if getattr(engine, "dropout_rate", 0.0) > 0.0:
             raise ValueError("the dropout seed is a kernel argument: a captured step would repeat one mask")
+        if targets.is_floating_point():
+            raise ValueError("GraphedStep captures class-index targets only; probability targets go through train_step")
         self.engine, self.criterion = engine, criterion
         self.img = img.clone()
         self.targets = targets.clone()

@@ -5,10 +5,11 @@ Drop-in surface of the reference's ``nbdt/loss.py``: ``TreeSupLoss`` (:97-209) a
 attributes (used by the reference's ``main.py`` flag plumbing), ``set_epoch`` / ``get_weight``
 weight schedule and the ``_nbdt_output_flag`` guard.
 
-When the wrapped criterion is a default ``nn.CrossEntropyLoss()`` the whole loss --
-``w_x*CE(z,y) + w_t*CE(rules(z), y)`` and its gradient -- is ONE fused HIP kernel
-(csrc/rules.hip: soft_loss_kernel).  Any other criterion composes the fused rules kernel
-(autograd-enabled) with the user's criterion, exactly like the reference.
+When the wrapped criterion is an ``nn.CrossEntropyLoss`` without class weights (mean reduction, default
+``ignore_index``, any ``label_smoothing`` in [0, 1)) the whole loss -- ``w_x*CE(z,y) + w_t*CE(rules(z), y)`` and its
+gradient -- is ONE fused HIP kernel (csrc/rules.hip: soft_loss_kernel / soft_target_loss_kernel), for class-index
+targets and, with the soft loss, for probability targets ``[B, C]`` (MixUp / CutMix, soft labels).  Any other
+criterion composes the fused rules kernel (autograd-enabled) with the user's criterion, exactly like the reference.
 
 ``HardTreeSupLoss`` (reference :212-257) gets the same treatment (hard_loss_kernel).  ``SoftTreeLoss``
 (:269-315) adds mid-training re-induction of the hierarchy (nbdt/graph.py, nbdt/hierarchy.py).
@@ -61,6 +62,43 @@ def _is_plain_cross_entropy(criterion):
             and getattr(criterion, "label_smoothing", 0.0) == 0.0)
 
 
+def _fusable_smoothing(criterion):
+    """The label_smoothing of a criterion the fused loss kernels implement -- an nn.CrossEntropyLoss without class
+    weights, with mean reduction and the default ignore_index -- or None for any other criterion."""
+    if not (type(criterion) is nn.CrossEntropyLoss and criterion.weight is None and criterion.reduction == "mean"
+            and criterion.ignore_index == -100):
+        return None
+    smoothing = float(getattr(criterion, "label_smoothing", 0.0))
+    return smoothing if 0.0 <= smoothing < 1.0 else None
+
+
+def _why_not_fusable(criterion):
+    if type(criterion) is not nn.CrossEntropyLoss:
+        return f"it is a {type(criterion).__name__}, not an nn.CrossEntropyLoss"
+    if criterion.weight is not None:
+        return "it has class weights"
+    if criterion.reduction != "mean":
+        return f"its reduction is {criterion.reduction!r}, not 'mean'"
+    if criterion.ignore_index != -100:
+        return f"its ignore_index is {criterion.ignore_index}"
+    return f"its label_smoothing {getattr(criterion, 'label_smoothing', 0.0)} is outside [0, 1)"
+
+
+def _require_fusable(criterion, what):
+    """The smoothing for loss_and_grad / soft_target_loss_and_grad, which have no composed path to fall back to."""
+    smoothing = _fusable_smoothing(criterion)
+    if smoothing is None:
+        raise _C.NBDTHipError(f"{what}: the fused tree loss cannot apply the wrapped criterion ({_why_not_fusable(criterion)}); "
+                              "call the loss module itself (forward + autograd) for such a criterion")
+    return smoothing
+
+
+def _is_dense_target(outputs, targets):
+    """Probability targets [B, C] the fused soft loss takes as they are (no gradient flows into them)."""
+    return (targets.is_floating_point() and targets.dim() == 2 and targets.shape == outputs.shape
+            and not targets.requires_grad)
+
+
 def _is_class_index(targets):
     """Soft / probability targets ([B, C] floats) take the composed path, as with the reference's criterion."""
     return targets.dim() == 1 and not targets.is_floating_point()
@@ -70,9 +108,14 @@ class _FusedSoftTreeLossFn(torch.autograd.Function):
     """loss, and dloss/dz computed in the same launch (saved for backward)."""
 
     @staticmethod
-    def forward(ctx, z, y, tree, w_xent, w_tree):
+    def forward(ctx, z, y, tree, w_xent, w_tree, smoothing=0.0):
         handle = tree.device_handle(z.device.index)
-        loss, gz = _C.soft_tree_loss(handle, z, y, w_xent, w_tree)
+        if y.is_floating_point():
+            t = y.to(device=z.device, dtype=torch.float32)
+            loss, gz = _C.soft_tree_loss_dense(handle, z, t if t.stride(1) == 1 else t.contiguous(), w_xent, w_tree,
+                                               smoothing=smoothing)
+        else:
+            loss, gz = _C.soft_tree_loss(handle, z, y, w_xent, w_tree, smoothing=smoothing)
         ctx.save_for_backward(gz)
         ctx.z_dtype = z.dtype
         return loss
@@ -80,7 +123,7 @@ class _FusedSoftTreeLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss):
         (gz,) = ctx.saved_tensors
-        return (gz * gloss).to(ctx.z_dtype), None, None, None, None
+        return (gz * gloss).to(ctx.z_dtype), None, None, None, None, None
 
 
 class TreeSupLoss(nn.Module):
@@ -161,21 +204,35 @@ class SoftTreeSupLoss(TreeSupLoss):
         return self.criterion(self.rules(outputs), targets)
 
     def forward(self, outputs, targets):
-        if _is_plain_cross_entropy(self.criterion) and outputs.dim() == 2 and _is_class_index(targets):
+        smoothing = _fusable_smoothing(self.criterion)
+        if smoothing is not None and outputs.dim() == 2 and (_is_class_index(targets)
+                                                             or _is_dense_target(outputs, targets)):
             self.assert_output_not_nbdt(outputs)
             _C.require_gpu(outputs, "SoftTreeSupLoss")
             xent_weight, tree_weight = self.current_weights()
             return _FusedSoftTreeLossFn.apply(outputs, targets, self.tree, float(xent_weight),
-                                              float(tree_weight))
+                                              float(tree_weight), smoothing)
         return super().forward(outputs, targets)
 
     def loss_and_grad(self, outputs, targets, grad_scale=1.0):
-        """Engine fast path: (loss, dloss/dz * grad_scale) from one launch, no autograd."""
+        """Engine fast path: (loss, dloss/dz * grad_scale) from one launch, no autograd.  Class-index targets; the
+        wrapped criterion's label_smoothing is applied (NBDTHipError for a criterion the kernel does not implement)."""
         self.assert_output_not_nbdt(outputs)
+        smoothing = _require_fusable(self.criterion, f"{type(self).__name__}.loss_and_grad")
         xent_weight, tree_weight = self.current_weights()
         handle = self.tree.device_handle(outputs.device.index)
         return _C.soft_tree_loss(handle, outputs, targets, float(xent_weight), float(tree_weight),
-                                 grad_scale)
+                                 grad_scale, smoothing)
+
+    def soft_target_loss_and_grad(self, outputs, target_probs, grad_scale=1.0):
+        """loss_and_grad for probability targets [B, C] fp32 (MixUp / CutMix, soft labels): the same launch, the rows
+        used as given."""
+        self.assert_output_not_nbdt(outputs)
+        smoothing = _require_fusable(self.criterion, f"{type(self).__name__}.soft_target_loss_and_grad")
+        xent_weight, tree_weight = self.current_weights()
+        handle = self.tree.device_handle(outputs.device.index)
+        return _C.soft_tree_loss_dense(handle, outputs, target_probs, float(xent_weight), float(tree_weight),
+                                       grad_scale, smoothing)
 
 
     def can_fuse_head(self, num_classes):
@@ -201,9 +258,9 @@ class _FusedHardTreeLossFn(torch.autograd.Function):
     """HardTreeSupLoss and dloss/dz from one launch (csrc/rules.hip: hard_loss_kernel)."""
 
     @staticmethod
-    def forward(ctx, z, y, tree, w_xent, w_node):
+    def forward(ctx, z, y, tree, w_xent, w_node, smoothing=0.0):
         handle = tree.device_handle(z.device.index)
-        loss, gz = _C.hard_tree_loss(handle, z, y, w_xent, w_node)
+        loss, gz = _C.hard_tree_loss(handle, z, y, w_xent, w_node, smoothing=smoothing)
         ctx.save_for_backward(gz)
         ctx.z_dtype = z.dtype
         return loss
@@ -211,7 +268,7 @@ class _FusedHardTreeLossFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gloss):
         (gz,) = ctx.saved_tensors
-        return (gz * gloss).to(ctx.z_dtype), None, None, None, None
+        return (gz * gloss).to(ctx.z_dtype), None, None, None, None, None
 
 
 class HardTreeSupLoss(TreeSupLoss):
@@ -259,21 +316,24 @@ class HardTreeSupLoss(TreeSupLoss):
         return loss
 
     def forward(self, outputs, targets):
-        if _is_plain_cross_entropy(self.criterion) and outputs.dim() == 2 and _is_class_index(targets):
+        smoothing = _fusable_smoothing(self.criterion)
+        if smoothing is not None and outputs.dim() == 2 and _is_class_index(targets):
             self.assert_output_not_nbdt(outputs)
             _C.require_gpu(outputs, "HardTreeSupLoss")
             xent_weight, tree_weight = self.current_weights()
             return _FusedHardTreeLossFn.apply(outputs, targets, self.tree, float(xent_weight),
-                                              self._node_weight(tree_weight))
+                                              self._node_weight(tree_weight), smoothing)
         return super().forward(outputs, targets)
 
     def loss_and_grad(self, outputs, targets, grad_scale=1.0):
-        """Engine fast path: (loss, dloss/dz * grad_scale) from one launch, no autograd."""
+        """Engine fast path: (loss, dloss/dz * grad_scale) from one launch, no autograd.  The wrapped criterion's
+        label_smoothing is applied (NBDTHipError for a criterion the kernel does not implement)."""
         self.assert_output_not_nbdt(outputs)
+        smoothing = _require_fusable(self.criterion, "HardTreeSupLoss.loss_and_grad")
         xent_weight, tree_weight = self.current_weights()
         handle = self.tree.device_handle(outputs.device.index)
         return _C.hard_tree_loss(handle, outputs, targets, float(xent_weight),
-                                 self._node_weight(tree_weight), grad_scale)
+                                 self._node_weight(tree_weight), grad_scale, smoothing)
 
 
 class SoftTreeLoss(SoftTreeSupLoss):
@@ -312,11 +372,22 @@ class SoftTreeLoss(SoftTreeSupLoss):
     def loss_and_grad(self, outputs, targets, grad_scale=1.0):
         if self.epochs < self.start_epochs:      # w_x*CE + w_t*CE through the same fused kernel
             self.assert_output_not_nbdt(outputs)
+            smoothing = _require_fusable(self.criterion, "SoftTreeLoss.loss_and_grad")
             xent_weight, tree_weight = self.current_weights()
             handle = self.tree.device_handle(outputs.device.index)
             return _C.soft_tree_loss(handle, outputs, targets, float(xent_weight) + float(tree_weight), 0.0,
-                                     grad_scale)
+                                     grad_scale, smoothing)
         return super().loss_and_grad(outputs, targets, grad_scale)
+
+    def soft_target_loss_and_grad(self, outputs, target_probs, grad_scale=1.0):
+        if self.epochs < self.start_epochs:      # as loss_and_grad: both weights on the cross-entropy term
+            self.assert_output_not_nbdt(outputs)
+            smoothing = _require_fusable(self.criterion, "SoftTreeLoss.soft_target_loss_and_grad")
+            xent_weight, tree_weight = self.current_weights()
+            handle = self.tree.device_handle(outputs.device.index)
+            return _C.soft_tree_loss_dense(handle, outputs, target_probs, float(xent_weight) + float(tree_weight), 0.0,
+                                           grad_scale, smoothing)
+        return super().soft_target_loss_and_grad(outputs, target_probs, grad_scale)
 
     def set_epoch(self, *args, **kwargs):
         super().set_epoch(*args, **kwargs)

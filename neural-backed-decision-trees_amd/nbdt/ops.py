@@ -663,6 +663,22 @@ def augment_batch(src, labels_src, index, out, labels_out, pad, flip, mean=None,
         check(lib().nbdt_augment_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
 
 
+def mix_batch(x, y, out, tgt, lam=1.0, box=(0, 0, 0, 0), lam_t=1.0):
+    """nbdt_mix_batch: MixUp / CutMix of the fp32 batch x [B,3,H,W] (labels y, int64 [B]) with itself rolled by one, into
+    out [B,3,H,W] (not x) and the probability targets tgt [B,C] fp32.  MixUp: lam, an empty box, lam_t = lam.  CutMix:
+    lam = 1, box = (y1, y2, x1, x2) taken from the partner, lam_t = 1 - box area / (H*W).  lam and 1 - lam (formed in double, as torchvision
+    forms it) are each rounded to fp32 once, which is what torch does with a Python scalar next to a float32 tensor."""
+    B, ch, H, W = x.shape
+    ok = lambda t, dt: t.is_cuda and t.dtype == dt and t.is_contiguous() and t.device == x.device
+    if ch != 3 or not (ok(x, torch.float32) and ok(out, torch.float32) and ok(tgt, torch.float32) and ok(y, torch.int64)):
+        raise _C.NBDTHipError("mix_batch takes contiguous device tensors: fp32 x / out [B,3,H,W], int64 y [B], fp32 tgt [B,C]")
+    if tuple(out.shape) != tuple(x.shape) or tuple(y.shape) != (B,) or tgt.dim() != 2 or tgt.shape[0] != B:
+        raise _C.NBDTHipError(f"mix_batch: x {tuple(x.shape)}, out {tuple(out.shape)}, y {tuple(y.shape)}, tgt {tuple(tgt.shape)}")
+    lam, lam_t = float(lam), float(lam_t)
+    check(lib().nbdt_mix_batch(ptr(x), ptr(y), B, H, W, lam, 1.0 - lam, int(box[0]), int(box[1]), int(box[2]), int(box[3]),
+                               lam_t, 1.0 - lam_t, ptr(out), ptr(tgt), tgt.shape[1], stream_ptr(x.device)))
+
+
 def resized_crop_batch(src, labels_src, index, out, labels_out, resize, window, flip, mean, std, scale=None, ratio=None,
                        ratio_table=None, seed=0, epoch=0, params_in=None, params_out=None, index_base=None):
     """nbdt_resized_crop_batch: out[B,3,out_h,out_w] fp32, labels_out[B] <- gather + crop box + PIL-bilinear resample to
