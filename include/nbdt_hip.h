@@ -695,6 +695,35 @@ int nbdt_linear_bwd(const float* x, const float* w, const float* gz, int32_t B, 
 int nbdt_sgd_step(float* p, float* g, float* buf, int64_t n, float lr, float momentum,
                   float weight_decay, float grad_scale, void* p_bf16, int32_t zero_grad, void* stream);
 
+/* ------------------------------------------------------------------ LARS (nbdt_version() >= 117) */
+/* Layer-wise adaptive rate scaling (You et al. 2017; apex's LARC(clip=False) around optim.SGD) over the same three flat
+ * fp32 buffers nbdt_sgd_step takes, for large global batches.  A plan holds a segment table of n_seg rows (offset, length,
+ * weight_decay, adapt) over an arena of n elements: rows sorted by offset, disjoint, every offset a multiple of 4
+ * elements, lengths arbitrary (>= 1).  Per segment s
+ *   gn = sqrt(sum (grad_scale g_i)^2),  wn = sqrt(sum p_i^2),
+ *   ratio_s = trust wn / (gn + wd_s wn + eps)  if adapt_s != 0 and wn > 0 and gn > 0, else 1
+ * and per element of it
+ *   u = ratio_s (grad_scale g_i + wd_s p_i);  buf_i = momentum buf_i + u;  p_i -= lr buf_i;  p_bf16_i = bf16(p_i)
+ * -- optim.SGD(momentum, weight_decay=0) on the gradient ratio (g + wd p).  Elements outside every segment (alignment
+ * gaps, the tail) are neither read for the norms nor written in p, buf or p_bf16; with zero_grad != 0 the whole of
+ * g[0, n) is zero afterwards.  nbdt_lars_create checks the table (unsorted, overlapping, misaligned or out-of-range rows
+ * and an empty table are NBDT_EINVAL before any device call), builds the wave -> (segment, range) tables on the host and
+ * copies them, once, to the CURRENT device, with the workspace of the partial sums.  nbdt_lars_step is at most three
+ * launches on `stream` (partial sums of squares, one fold per segment, the streaming update), no host synchronisation,
+ * no floating-point atomics: which wave sums what, in which order, depends on the table alone, so a step is
+ * bit-reproducible with nbdt_set_deterministic on or off.  p, g, buf: n fp32 elements each, 16-byte aligned; p_bf16: n
+ * bf16 elements, 8-byte aligned, or NULL.  nbdt_lars_ratios: device pointer of ratio[n_seg] as the plan's last step left it
+ * (1 before the first step), for tests and logging; owned by the plan. */
+int nbdt_lars_create(int64_t n, const int64_t* offsets, const int64_t* lengths, const float* weight_decays,
+                     const int32_t* adapt, int32_t n_seg, void** plan);
+int nbdt_lars_destroy(void* plan);
+int nbdt_lars_step(void* plan, float* p, float* g, float* buf, float lr, float momentum, float trust, float eps,
+                   float grad_scale, void* p_bf16, int32_t zero_grad, void* stream);
+const float* nbdt_lars_ratios(void* plan);
+/* ... and a host copy of them: waits for `stream` (the one the step was issued on), then copies n_seg floats to out.
+ * Synchronises the host: for tests and logging, never on the step path. */
+int nbdt_lars_ratios_to_host(void* plan, float* out, void* stream);
+
 /* ------------------------------------------------------------------ device-resident datasets (nbdt_version() >= 110) */
 /* One launch builds a training batch from a dataset that lives in device memory: gather by index, then the reference's
  * RandomCrop(size, padding) -> RandomHorizontalFlip -> ToTensor -> Normalize (nbdt/data/cifar.py:11-21 pads CIFAR by 4,

@@ -55,6 +55,13 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   rank) in one launch that also writes the probability targets, whatever ``--augment`` made the batch; the step then takes
   ``soft_target_loss_and_grad``.  A loss without it (``HardTreeSupLoss``: the reference's cannot take probability
   targets either) is refused at argument time.  Evaluation is never mixed.
+* ``--optimizer lars`` replaces the SGD pass with layer-wise adaptive rate scaling (You et al. 2017; apex's
+  ``LARC(clip=False)`` around ``optim.SGD``): ``engine.lars_step``, three launches over the flat parameter arena.
+  ``--lars-trust`` / ``--lars-eps`` are its coefficients; BatchNorm parameters and biases take plain SGD steps without decay
+  unless ``--lars-adapt-1d``.  ``--warmup-epochs W`` ramps the learning rate linearly over the first ``W`` epochs' steps and
+  ``--lr-schedule cosine | poly`` decays it per step afterwards (Goyal et al. 2017; ``lr_at``): the large-batch recipe for a
+  whole node, e.g. 8 ranks at ``--batch-size 4096``.  With the defaults (``sgd``, ``multistep``, no warm-up) the learning
+  rate is the reference's MultiStepLR, evaluated once per epoch, and the step is the SGD step.
 """
 import argparse
 import json
@@ -155,6 +162,16 @@ def build_parser():
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible training steps, like the reference's CPU path: every cross-block reduction in "
                         "a fixed order instead of fp32 atomics (nbdt_set_deterministic; ResNet / WideResNet backbones)")
+    p.add_argument("--optimizer", choices=("sgd", "lars"), default="sgd",
+                   help="lars: layer-wise adaptive rate scaling (engine.lars_step) for large global batches")
+    p.add_argument("--lars-trust", type=float, default=1e-3, help="--optimizer lars: trust coefficient")
+    p.add_argument("--lars-eps", type=float, default=1e-8, help="--optimizer lars: added to the trust ratio's denominator")
+    p.add_argument("--lars-adapt-1d", action="store_true",
+                   help="--optimizer lars: adapt and decay BatchNorm parameters and biases too (default: plain SGD, no decay)")
+    p.add_argument("--lr-schedule", choices=("multistep", "cosine", "poly"), default="multistep",
+                   help="multistep: the reference's MultiStepLR per epoch; cosine / poly: per-step decay to 0 after warm-up")
+    p.add_argument("--warmup-epochs", type=float, default=0.0, metavar="W",
+                   help="linear learning-rate warm-up over the first W epochs' steps (may be fractional)")
     return p
 
 
@@ -191,6 +208,26 @@ def multistep_lr(base_lr, epoch, epochs, gamma=0.1):
     """optim.lr_scheduler.MultiStepLR(milestones=[int(3/7*E), int(5/7*E)]) -- reference main.py:208-210."""
     milestones = (int(3 / 7.0 * epochs), int(5 / 7.0 * epochs))
     return base_lr * gamma ** sum(epoch >= m for m in milestones)
+
+
+def lr_at(base_lr, step, steps_per_epoch, epochs, schedule="multistep", warmup_epochs=0.0):
+    """Learning rate of global step `step` (0-based, `steps_per_epoch` per epoch).  T_w = round(W * steps_per_epoch)
+    warm-up steps ramp linearly, base * (step + 1) / T_w (Goyal et al. 2017); then `multistep` is multistep_lr of the
+    step's epoch, `cosine` is 0.5 * base * (1 + cos(pi * t)) and `poly` is base * (1 - t)^2 with
+    t = (step - T_w) / (T - T_w), T = epochs * steps_per_epoch: both start at base on step T_w and would reach 0 on step
+    T, one past the last step a run takes."""
+    t_w = int(round(warmup_epochs * steps_per_epoch))
+    total = epochs * steps_per_epoch
+    if step < t_w:
+        return base_lr * (step + 1) / t_w
+    if schedule == "multistep":
+        return multistep_lr(base_lr, step // steps_per_epoch, epochs)
+    t = (step - t_w) / float(max(total - t_w, 1))
+    if schedule == "cosine":
+        return 0.5 * base_lr * (1.0 + math.cos(math.pi * t))
+    if schedule == "poly":
+        return base_lr * (1.0 - t) ** 2
+    raise ValueError(f"unknown learning-rate schedule {schedule!r}")
 
 
 def build_criterion(args, tree, net=None, checkpoint_path="./"):
@@ -343,6 +380,10 @@ def parse_args(argv=None):
         parser.error(f"--label-smoothing must be in [0, 1), got {args.label_smoothing}")
     if args.mixup_alpha < 0 or args.cutmix_alpha < 0:
         parser.error("--mixup-alpha and --cutmix-alpha must be >= 0")
+    if args.warmup_epochs < 0 or args.warmup_epochs > args.epochs:
+        parser.error(f"--warmup-epochs must be in [0, --epochs], got {args.warmup_epochs}")
+    if args.lars_trust <= 0 or args.lars_eps < 0:
+        parser.error("--lars-trust must be > 0 and --lars-eps >= 0")
     if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
         name = args.loss[-1]            # the loss the training step calls
         if name != "CrossEntropyLoss" and not hasattr(getattr(losses, name), "soft_target_loss_and_grad"):
@@ -412,6 +453,8 @@ def main(argv=None):
     ck_args = dict(vars(args))
     ck_args["path_graph"] = tree.path_graph
     checkpoint_fname = generate_checkpoint_fname(**ck_args)
+    if args.optimizer == "lars":
+        checkpoint_fname += "-lars"
     checkpoint_path = f"./checkpoint/{checkpoint_fname}.pth"
     log(f"==> Checkpoints will be saved to: {checkpoint_path}")
 
@@ -444,19 +487,30 @@ def main(argv=None):
     per_rank = args.batch_size // world
     # --weight-decay: handed on only when it is not train_step's own default
     decay = {} if args.weight_decay == 5e-4 else {"weight_decay": args.weight_decay}
+    if args.optimizer == "lars":
+        from nbdt.engine import LarsConfig
+        decay["lars"] = LarsConfig(args.lars_trust, args.lars_eps, not args.lars_adapt_1d)
+    per_step_lr = args.lr_schedule != "multistep" or args.warmup_epochs > 0
 
     @analyzer.train_function
     def train(epoch):
         if hasattr(criterion, "set_epoch"):
             criterion.set_epoch(epoch, args.epochs)
         lr = multistep_lr(args.lr, epoch, args.epochs)
-        log("\nEpoch: %d / LR: %.04f" % (epoch, lr))
-        net.train()
         # unsharded: the same shuffle of the whole set on every rank, each takes its slice of every global batch;
         # --shard-data: every rank shuffles the part it holds
         plan = ndist.epoch_indices(n_train, args.batch_size, rank, world, args.seed, epoch,
                                    sharded=shard is not None)
         steps = plan.shape[0]
+        lrs = None
+        if per_step_lr:          # warm-up / per-step decay: one learning rate per step of this epoch
+            lrs = [lr_at(args.lr, epoch * steps + i, steps, args.epochs, args.lr_schedule, args.warmup_epochs)
+                   for i in range(steps)]
+        if lrs and lrs[0] != lrs[-1]:
+            log("\nEpoch: %d / LR: %.6f -> %.6f" % (epoch, lrs[0], lrs[-1]))
+        else:
+            log("\nEpoch: %d / LR: %.04f" % (epoch, lrs[0] if lrs else lr))
+        net.train()
         total = torch.zeros((), device=device)
         if on_device:
             plan = plan.to(device)           # once per epoch; every step takes a row of it there
@@ -469,7 +523,7 @@ def main(argv=None):
             mix = draw_mix(args.seed, epoch, i, xb.shape[2], xb.shape[3], args.mixup_alpha, args.cutmix_alpha)
             if mix is not None:              # one launch: the mixed batch and its probability targets
                 xb, yb = mix_batch(xb, yb, num_classes, mix)
-            total += train_step(engine, fast, xb, yb, lr, comm=comm, **decay)
+            total += train_step(engine, fast, xb, yb, lrs[i] if lrs else lr, comm=comm, **decay)
         log("Loss: %.3f (%d steps of %d x %d images)" % (total.item() / max(steps, 1), steps, world, per_rank))
 
     def test(epoch, checkpoint=True):

@@ -220,6 +220,12 @@ SIGNATURES = {
     "nbdt_linear_fwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_linear_bwd": (c_int, [_P, _P, _P, c_int32, c_int32, c_int32, _P, _P, _P, _P]),
     "nbdt_sgd_step": (c_int, [_P, _P, _P, c_int64, c_float, c_float, c_float, c_float, _P, c_int32, _P]),
+    "nbdt_lars_create": (c_int, [c_int64, POINTER(c_int64), POINTER(c_int64), POINTER(c_float), _I32P, c_int32,
+                                 POINTER(c_void_p)]),
+    "nbdt_lars_destroy": (c_int, [c_void_p]),
+    "nbdt_lars_step": (c_int, [c_void_p, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, _P, c_int32, _P]),
+    "nbdt_lars_ratios": (c_void_p, [c_void_p]),
+    "nbdt_lars_ratios_to_host": (c_int, [c_void_p, POINTER(c_float), _P]),
 }
 
 

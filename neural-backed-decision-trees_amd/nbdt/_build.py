@@ -36,6 +36,8 @@ FLAGS = {
     "bn.hip": ["-munsafe-fp-atomics"],
     "misc.hip": ["-munsafe-fp-atomics"],
     "effnet.hip": ["-munsafe-fp-atomics"],
+    # the two per-segment scalars (one sqrt, one division) are IEEE-correct, the element update is four separate roundings
+    "lars.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
 }
 
 

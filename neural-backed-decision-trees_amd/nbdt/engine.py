@@ -14,6 +14,7 @@ pre-planned launch sequence:
 Python here only sequences C-ABI launches on the current HIP stream (capturable in a hipGraph via
 torch.cuda.CUDAGraph); there is no CPU or PyTorch-op fallback for any tensor op on the path.
 """
+import collections
 import math
 
 import torch
@@ -40,6 +41,10 @@ def side_stream(device):
 
 def _pad32(c):
     return (c + 31) // 32 * 32
+
+
+# train_step(..., lars=LarsConfig(...)): the optimizer pass is engine.lars_step instead of engine.sgd_step
+LarsConfig = collections.namedtuple("LarsConfig", ("trust", "eps", "exclude_1d"), defaults=(1e-3, 1e-8, True))
 
 
 class ParamStore:
@@ -102,6 +107,22 @@ class ParamStore:
 
     def zero_grad(self):
         self.grad.zero_()            # one memset node
+
+    def segments(self, weight_decay, exclude_1d=True):
+        """The segment table of a layer-wise optimizer (ops.LarsPlan): one row (offset, length, weight_decay, adapt) per
+        entry, in offset order.  The length is the product of the INTERNAL shape: the zero padding inside an entry adds
+        nothing to either norm and stays zero under the update; the alignment gaps between entries and the tail belong to
+        no row.  exclude_1d: one-dimensional entries (BatchNorm gamma / beta, biases) are neither decayed nor adapted,
+        the published recipe; False gives every entry adapt = 1 and the decay."""
+        rows = []
+        for name, (off, shape) in sorted(self.entries.items(), key=lambda kv: kv[1][0]):
+            plain = exclude_1d and len(shape) <= 1
+            rows.append((off, math.prod(shape), 0.0 if plain else float(weight_decay), 0 if plain else 1))
+        return rows
+
+    def segment_names(self):
+        """Entry names in the row order of segments()."""
+        return [name for name, _ in sorted(self.entries.items(), key=lambda kv: kv[1][0])]
 
 
 class Conv:
@@ -408,6 +429,8 @@ class _Engine:
         self._partials = None     # conv-epilogue BatchNorm partial sums (partials)
         self._reserved_now = 0    # CUs the MFMA launches currently leave to in-flight all-reduces (_reserve_for)
         self._grad_is_zero = False   # the flat gradient buffer is known to be zero (sgd_step(zero_grad=True))
+        self._lars_plans = {}     # (weight_decay, exclude_1d) -> ops.LarsPlan (lars_step)
+        self._lars_last = None    # the plan of the last lars_step (last_trust_ratios)
         self._B = None            # batch of the last forward()
 
     def seg_op(self, key, build, sources, sources32, on_side=False):
@@ -890,6 +913,35 @@ class _Engine:
         ops.sgd_step(s.flat, s.grad, s.mom, lr, momentum, weight_decay, grad_scale, s.bf16, zero_grad=zero_grad)
         self._grad_is_zero = bool(zero_grad)
         self.refresh_derived_weights()
+
+    def _lars_plan(self, weight_decay, exclude_1d):
+        key = (float(weight_decay), bool(exclude_1d))
+        plan = self._lars_plans.get(key)
+        if plan is None:         # host tables built and copied to the device once per (decay, rule)
+            s = self.store
+            plan = self._lars_plans[key] = ops.LarsPlan(s.flat.numel(), s.segments(*key), device=self.device)
+        return plan
+
+    def lars_step(self, lr, momentum=0.9, weight_decay=5e-4, trust=1e-3, eps=1e-8, grad_scale=1.0, zero_grad=False,
+                  exclude_1d=True):
+        """LARS step over every parameter (You et al. 2017: SGD with momentum on ratio * (g + wd * p), the ratio per
+        ParamStore entry; nbdt_lars_step) + refresh of bf16 / dgrad weights.  Three launches whatever the number of
+        parameters, no host synchronisation; zero_grad as in sgd_step.  exclude_1d: BatchNorm parameters and biases take
+        plain SGD steps without decay."""
+        self.join_side_stream()
+        s = self.store
+        plan = self._lars_plan(weight_decay, exclude_1d)
+        plan.step(s.flat, s.grad, s.mom, lr, momentum, trust, eps, grad_scale, s.bf16, zero_grad=zero_grad)
+        self._lars_last = plan
+        self._grad_is_zero = bool(zero_grad)
+        self.refresh_derived_weights()
+
+    def last_trust_ratios(self):
+        """ParamStore entry name -> trust ratio of the last lars_step (1 for entries it did not adapt).  Copies from the
+        device and waits for it: for logging and tests, not for the step path."""
+        if self._lars_last is None:
+            raise RuntimeError("last_trust_ratios: no lars_step yet")
+        return dict(zip(self.store.segment_names(), self._lars_last.ratios().tolist()))
 
     def zero_grad(self):
         if not self._grad_is_zero:
@@ -1667,14 +1719,16 @@ class ImageNetBottleneckEngine(_TorchvisionFront, BottleneckEngine):
 
 
 def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5e-4, comm=None, fused_head=True,
-               zero_grad=True):
+               zero_grad=True, lars=None):
     """One full training step (main.py:233-239): zero_grad, forward, SoftTreeSupLoss fwd+bwd (one fused
     kernel -- with the classifier's forward and backward inside it when the criterion and the head's width allow,
     fused_head=False keeps linear -> loss -> linear-backward as three launches), backward, [gradient all-reduce],
     SGD.  Returns the loss tensor (device scalar).  zero_grad=False leaves the step's gradient in the flat gradient
     buffer instead of having the SGD kernel clear it for the next step (tests that compare gradients).
     Floating-point targets are probability rows [B, C] (MixUp / CutMix, nbdt.data.mix_batch): they skip the fused head
-    and go through criterion.soft_target_loss_and_grad, still one loss launch."""
+    and go through criterion.soft_target_loss_and_grad, still one loss launch.
+    lars: a LarsConfig (trust, eps, exclude_1d) makes the optimizer pass engine.lars_step; the 1 / world_size of a
+    data-parallel step enters its norms, so every rank computes the same trust ratios from the same reduced gradient."""
     engine.zero_grad()
     names = getattr(engine, "classifier_names", None)
     if targets.is_floating_point():
@@ -1694,6 +1748,10 @@ def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5
         loss, gz = criterion.loss_and_grad(z, targets)
         engine.backward(gz, comm=comm)
     scale = 1.0 / comm.world_size if comm is not None else 1.0
+    if lars is not None:
+        engine.lars_step(lr, momentum, weight_decay, lars.trust, lars.eps, grad_scale=scale, zero_grad=zero_grad,
+                         exclude_1d=lars.exclude_1d)
+        return loss
     engine.sgd_step(lr, momentum, weight_decay, grad_scale=scale, zero_grad=zero_grad)
     return loss
 
@@ -1710,7 +1768,8 @@ class GraphedStep:
     step), while the graph serialises the cross-stream edges the eager schedule overlaps.  So this is latency insurance
     for slower hosts, not a speed-up, and bench.py does not use it.  The learning rate and the dropout
     seed are kernel arguments baked into the graph: build one GraphedStep per learning rate, and do not use it
-    for models with dropout.  So are the loss weights and the device pointers of the hierarchy: a replay after
+    for models with dropout.  A per-step learning rate is such a baked argument too, so a GraphedStep cannot be used with
+    learning-rate warm-up or a per-iteration decay (main.py --warmup-epochs, --lr-schedule cosine | poly).  So are the loss weights and the device pointers of the hierarchy: a replay after
     ``criterion.set_epoch`` changed the weights (--tswe / --xwe schedules) or after the hierarchy was re-induced
     (SoftTreeLoss) raises instead of silently using the captured ones; the captured tree handle is kept alive
     by this object.  Gradient all-reduce (RCCL) is not captured: single-GPU steps only."""

@@ -769,6 +769,60 @@ def sgd_step(p, g, buf, lr, momentum, weight_decay, grad_scale=1.0, p_bf16=None,
                               ptr(p_bf16), 1 if zero_grad else 0, stream_ptr(p.device)))
 
 
+LARS_ITEM = 4096      # elements one wave of csrc/lars.hip reduces / updates (kItem); a block is four waves
+
+
+class LarsPlan:
+    """A plan of nbdt_lars_*: `segments` = rows (offset, length, weight_decay, adapt) over a flat arena of n fp32 elements
+    (sorted, disjoint, offsets multiples of 4: ParamStore.segments).  The table is checked on the host first (a bad one
+    raises without a GPU); a good one puts its block tables and its workspace on `device` once, here."""
+
+    def __init__(self, n, segments, device=None):
+        rows = [(int(o), int(l), float(w), int(bool(a))) for o, l, w, a in segments]
+        k = len(rows)
+        self.n, self.n_seg, self.segments = int(n), k, rows
+        self.device = torch.device(device) if device is not None else None
+        self.handle = ctypes.c_void_p()
+        offs = (ctypes.c_int64 * max(k, 1))(*[r[0] for r in rows])
+        lens = (ctypes.c_int64 * max(k, 1))(*[r[1] for r in rows])
+        wds = (ctypes.c_float * max(k, 1))(*[r[2] for r in rows])
+        adapt = (ctypes.c_int32 * max(k, 1))(*[r[3] for r in rows])
+        if self.device is not None and self.device.type == "cuda":
+            with torch.cuda.device(self.device):
+                check(lib().nbdt_lars_create(self.n, offs, lens, wds, adapt, k, ctypes.byref(self.handle)))
+        else:
+            check(lib().nbdt_lars_create(self.n, offs, lens, wds, adapt, k, ctypes.byref(self.handle)))
+
+    def step(self, p, g, buf, lr, momentum, trust, eps, grad_scale=1.0, p_bf16=None, zero_grad=False):
+        """Three launches on p's current stream; no host synchronisation."""
+        _C.require_gpu(p, "lars_step")
+        for t, what in ((p, "p"), (g, "g"), (buf, "buf")):
+            if t.dtype != torch.float32 or t.numel() != self.n or t.device != p.device or not t.is_contiguous():
+                raise _C.NBDTHipError(f"lars_step: {what} must be a contiguous fp32 tensor of {self.n} elements on {p.device}")
+        if p_bf16 is not None and (p_bf16.dtype != torch.bfloat16 or p_bf16.numel() != self.n or p_bf16.device != p.device
+                                   or not p_bf16.is_contiguous()):
+            raise _C.NBDTHipError(f"lars_step: the mirror must be a contiguous bf16 tensor of {self.n} elements on {p.device}")
+        check(lib().nbdt_lars_step(self.handle, ptr(p), ptr(g), ptr(buf), lr, momentum, trust, eps, grad_scale,
+                                   ptr(p_bf16), 1 if zero_grad else 0, stream_ptr(p.device)))
+
+    def ratios(self):
+        """ratio[n_seg] of the last step as a host tensor (1 before the first step).  Synchronises: not for the step path."""
+        out = torch.empty(self.n_seg, dtype=torch.float32)
+        with torch.cuda.device(self.device):
+            check(lib().nbdt_lars_ratios_to_host(self.handle, ctypes.cast(out.data_ptr(), ctypes.POINTER(ctypes.c_float)),
+                                                 stream_ptr(self.device)))
+        return out
+
+    def __del__(self):
+        try:
+            h = getattr(self, "handle", None)
+            if h is not None and h.value:
+                lib().nbdt_lars_destroy(h)
+                self.handle = None
+        except Exception:      # (interpreter shutdown: modules may already be gone)
+            pass
+
+
 # ------------------------------------------------------------------------------------------------
 # MBConv pieces (EfficientNet-B0, csrc/effnet.hip)
 
