@@ -724,6 +724,26 @@ const float* nbdt_lars_ratios(void* plan);
  * Synchronises the host: for tests and logging, never on the step path. */
 int nbdt_lars_ratios_to_host(void* plan, float* out, void* stream);
 
+/* ------------------------------------------------------------------ weight EMA (nbdt_version() >= 118) */
+/* An exponential moving average of the weights (the `ModelEma` / `ExponentialMovingAverage` of the timm and torchvision
+ * recipes) over the flat fp32 arena nbdt_sgd_step takes, and its in-place exchange with the live weights for evaluation.
+ *   nbdt_ema_update:  per element  t = p - e;  e = e + one_minus_decay * t  -- three separately rounded fp32 operations (one
+ *     subtract, one multiply, one add; never a fused multiply-add), the definition for every one_minus_decay in [0, 1], 0
+ *     and 1 included.  One streaming pass over [0, n) with 16-byte accesses; p is only read.  Alignment gaps and padding
+ *     that are zero in both buffers stay zero, so no segment table is taken.
+ *   nbdt_ema_swap:    per element p and ema exchange values; with p_bf16 != NULL, p_bf16[i] = bf16(new p[i]), round to nearest
+ *     even, what nbdt_sgd_step writes.  In place, because live tensors alias p: exchanging pointers would leave them behind.
+ *   _multi: the same for n_rows small tensors in one launch (the BatchNorm running statistics).  `table` is a DEVICE array
+ *     of n_rows rows (live pointer, shadow pointer, length) as int64, built once by the caller: pointers 16-byte
+ *     aligned, lengths positive multiples of 32 elements, no tensor in two rows.  The rows cannot be checked on the host.
+ * One launch each on `stream`, no host synchronisation, no atomics, nothing crosses a block: bit-reproducible by
+ * construction.  Checked on the host before any device call (NBDT_EINVAL): NULL pointers, n <= 0 or n % 4 != 0, p / ema not
+ * 16-byte aligned (p_bf16: 8-byte), p == ema, n_rows <= 0, one_minus_decay outside [0, 1] or NaN. */
+int nbdt_ema_update(const float* p, float* ema, int64_t n, float one_minus_decay, void* stream);
+int nbdt_ema_update_multi(const int64_t* table, int32_t n_rows, float one_minus_decay, void* stream);
+int nbdt_ema_swap(float* p, float* ema, void* p_bf16, int64_t n, void* stream);
+int nbdt_ema_swap_multi(const int64_t* table, int32_t n_rows, void* stream);
+
 /* ------------------------------------------------------------------ device-resident datasets (nbdt_version() >= 110) */
 /* One launch builds a training batch from a dataset that lives in device memory: gather by index, then the reference's
  * RandomCrop(size, padding) -> RandomHorizontalFlip -> ToTensor -> Normalize (nbdt/data/cifar.py:11-21 pads CIFAR by 4,

@@ -62,6 +62,13 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   ``--lr-schedule cosine | poly`` decays it per step afterwards (Goyal et al. 2017; ``lr_at``): the large-batch recipe for a
   whole node, e.g. 8 ranks at ``--batch-size 4096``.  With the defaults (``sgd``, ``multistep``, no warm-up) the learning
   rate is the reference's MultiStepLR, evaluated once per epoch, and the step is the SGD step.
+* ``--ema-decay D`` keeps an exponential moving average of the weights and the BatchNorm running statistics inside the
+  engine (``engine.ema_enable`` / ``ema_update``: two launches after every ``--ema-steps``-th optimizer step, with the
+  usual ``(1 + t) / (10 + t)`` warm-up of the decay unless ``--no-ema-warmup``).  Every evaluation still reports the live
+  weights exactly as before, then evaluates once more inside ``engine.ema_weights()`` and logs ``EMA Accuracy``; a saved
+  checkpoint gains ``net_ema``, ``acc_ema`` and ``ema_updates`` and its name ``-ema``.  ``--resume`` restores the average
+  when the checkpoint has one, else starts it from the loaded weights; ``--eval --resume --use-ema`` evaluates ``net_ema``.
+  ``SoftTreeLoss`` keeps inducing hierarchies from the live classifier.  Every rank keeps its own, bit-identical, average.
 """
 import argparse
 import json
@@ -172,6 +179,15 @@ def build_parser():
                    help="multistep: the reference's MultiStepLR per epoch; cosine / poly: per-step decay to 0 after warm-up")
     p.add_argument("--warmup-epochs", type=float, default=0.0, metavar="W",
                    help="linear learning-rate warm-up over the first W epochs' steps (may be fractional)")
+    p.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                   help="keep an exponential moving average of the weights with decay D, 0 < D < 1 (engine.ema_update), "
+                        "evaluate it after the live weights and save it as net_ema (default: off)")
+    p.add_argument("--ema-steps", type=int, default=1, metavar="K",
+                   help="--ema-decay: update the average after every K-th optimizer step, with D as given")
+    p.add_argument("--no-ema-warmup", action="store_true",
+                   help="--ema-decay: decay D from the first update on, instead of min(D, (1 + t) / (10 + t))")
+    p.add_argument("--use-ema", action="store_true",
+                   help="--eval --resume: evaluate the checkpoint's averaged weights (net_ema) instead of net")
     return p
 
 
@@ -228,6 +244,32 @@ def lr_at(base_lr, step, steps_per_epoch, epochs, schedule="multistep", warmup_e
     if schedule == "poly":
         return base_lr * (1.0 - t) ** 2
     raise ValueError(f"unknown learning-rate schedule {schedule!r}")
+
+
+def eval_state_of(checkpoint, use_ema, path="the checkpoint"):
+    """What --resume loads as the network's weights: the checkpoint itself, or with --use-ema its averaged weights."""
+    if not use_ema:
+        return checkpoint
+    if "net_ema" not in checkpoint:
+        raise SystemExit(f"--use-ema: {path} holds no averaged weights (no 'net_ema' key; it was not trained with "
+                         "--ema-decay)")
+    return {"net": checkpoint["net_ema"]}
+
+
+def restore_ema(engine, checkpoint, reference_state_dict):
+    """--resume with --ema-decay, after ema_enable started the average from the loaded weights: take the checkpoint's
+    average and update count when it has them.  Returns whether it had."""
+    if "net_ema" not in checkpoint:
+        return False
+    engine.load_ema_state_dict(coerce_state_dict({"net": checkpoint["net_ema"]}, reference_state_dict))
+    engine.ema_updates = int(checkpoint.get("ema_updates", 0))
+    return True
+
+
+def ema_checkpoint_fields(engine, acc_ema):
+    """The keys a checkpoint gains with --ema-decay."""
+    return {"net_ema": {k: v.cpu() for k, v in engine.ema_state_dict().items()}, "acc_ema": acc_ema,
+            "ema_updates": engine.ema_updates}
 
 
 def build_criterion(args, tree, net=None, checkpoint_path="./"):
@@ -384,6 +426,12 @@ def parse_args(argv=None):
         parser.error(f"--warmup-epochs must be in [0, --epochs], got {args.warmup_epochs}")
     if args.lars_trust <= 0 or args.lars_eps < 0:
         parser.error("--lars-trust must be > 0 and --lars-eps >= 0")
+    if args.ema_decay is not None and not 0.0 < args.ema_decay < 1.0:
+        parser.error(f"--ema-decay must be in (0, 1), got {args.ema_decay}")
+    if args.ema_steps < 1:
+        parser.error(f"--ema-steps must be >= 1, got {args.ema_steps}")
+    if args.use_ema and not (args.eval and args.resume):
+        parser.error("--use-ema evaluates a checkpoint's averaged weights: it needs --eval and --resume")
     if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
         name = args.loss[-1]            # the loss the training step calls
         if name != "CrossEntropyLoss" and not hasattr(getattr(losses, name), "soft_target_loss_and_grad"):
@@ -455,6 +503,9 @@ def main(argv=None):
     checkpoint_fname = generate_checkpoint_fname(**ck_args)
     if args.optimizer == "lars":
         checkpoint_fname += "-lars"
+    ema_on = args.ema_decay is not None
+    if ema_on or args.use_ema:
+        checkpoint_fname += "-ema"
     checkpoint_path = f"./checkpoint/{checkpoint_fname}.pth"
     log(f"==> Checkpoints will be saved to: {checkpoint_path}")
 
@@ -463,10 +514,13 @@ def main(argv=None):
     if args.resume:
         log("==> Resuming from checkpoint..")
         if not os.path.exists(resume_path):
+            if args.use_ema:
+                raise SystemExit(f"--use-ema: no checkpoint at {resume_path} to take the averaged weights from")
             log("==> No checkpoint found. Skipping...")
         else:
             checkpoint = torch.load(resume_path, map_location="cpu")
-            state = coerce_state_dict(checkpoint, net.state_dict())     # {"net": ...} and `module.` prefix
+            # {"net": ...} and `module.` prefix; --use-ema: the averaged weights are the ones to evaluate
+            state = coerce_state_dict(eval_state_of(checkpoint, args.use_ema, resume_path), net.state_dict())
             net.load_state_dict(state)
             net._sync_mirrors()          # the engine reads the bf16 mirror / dgrad copies: refresh them now
             if "net" in checkpoint:
@@ -474,6 +528,13 @@ def main(argv=None):
                 log(f"==> Checkpoint found for epoch {start_epoch} with accuracy {best_acc} at {resume_path}")
             else:
                 log(f"==> Checkpoint found at {resume_path}")
+            if ema_on:                   # the average starts from the loaded weights unless the checkpoint brings its own
+                engine.ema_enable(args.ema_decay, warmup=not args.no_ema_warmup)
+                if restore_ema(engine, checkpoint, net.state_dict()):
+                    log(f"==> Averaged weights restored after {engine.ema_updates} updates")
+    if ema_on and engine.store.ema is None:
+        engine.ema_enable(args.ema_decay, warmup=not args.no_ema_warmup)
+    ema_analyzer = analysis.Noop(tree.classes)      # the averaged pass reports accuracy only; --analysis sees the live weights
 
     criterion = build_criterion(args, tree, net=net, checkpoint_path=checkpoint_path)
     fast = criterion if hasattr(criterion, "loss_and_grad") else _PlainCE(tree, args.label_smoothing)
@@ -524,6 +585,8 @@ def main(argv=None):
             if mix is not None:              # one launch: the mixed batch and its probability targets
                 xb, yb = mix_batch(xb, yb, num_classes, mix)
             total += train_step(engine, fast, xb, yb, lrs[i] if lrs else lr, comm=comm, **decay)
+            if ema_on and (epoch * steps + i + 1) % args.ema_steps == 0:
+                engine.ema_update()          # two launches; every rank averages its own (bit-identical) replica
         log("Loss: %.3f (%d steps of %d x %d images)" % (total.item() / max(steps, 1), steps, world, per_rank))
 
     def test(epoch, checkpoint=True):
@@ -536,11 +599,19 @@ def main(argv=None):
         log("Loss: %.3f | Acc: %.3f%%%s" % (loss, acc, extra))
         analyzer.end_test(epoch)
         log(f"Accuracy: {acc} | Best Accuracy: {best_acc}")
+        acc_ema = None
+        if ema_on:       # every rank swaps: the evaluation is distributed.  Swapped back before anything is saved
+            with engine.ema_weights():
+                acc_ema, loss_ema = evaluate(net, criterion, ema_analyzer, METRICS[args.metric], test_x, test_y, 100,
+                                             device, rank=rank, world=world)
+            log(f"EMA Accuracy: {acc_ema} | EMA Loss: {loss_ema:.3f} | {engine.ema_updates} updates")
         if acc > best_acc and checkpoint and rank == 0:
             log(f"Saving to {checkpoint_fname} ({acc})..")
             os.makedirs("checkpoint", exist_ok=True)
-            torch.save({"net": {k: v.cpu() for k, v in net.state_dict().items()}, "acc": acc, "epoch": epoch},
-                       checkpoint_path)
+            blob = {"net": {k: v.cpu() for k, v in net.state_dict().items()}, "acc": acc, "epoch": epoch}
+            if ema_on:
+                blob.update(ema_checkpoint_fields(engine, acc_ema))
+            torch.save(blob, checkpoint_path)
         best_acc = max(best_acc, acc)
         if extras and args.diagnostics_out and rank == 0:
             with open(args.diagnostics_out, "w") as f:

@@ -226,6 +226,10 @@ SIGNATURES = {
     "nbdt_lars_step": (c_int, [c_void_p, _P, _P, _P, c_float, c_float, c_float, c_float, c_float, _P, c_int32, _P]),
     "nbdt_lars_ratios": (c_void_p, [c_void_p]),
     "nbdt_lars_ratios_to_host": (c_int, [c_void_p, POINTER(c_float), _P]),
+    "nbdt_ema_update": (c_int, [_P, _P, c_int64, c_float, _P]),
+    "nbdt_ema_update_multi": (c_int, [_P, c_int32, c_float, _P]),
+    "nbdt_ema_swap": (c_int, [_P, _P, _P, c_int64, _P]),
+    "nbdt_ema_swap_multi": (c_int, [_P, c_int32, _P]),
 }
 
 

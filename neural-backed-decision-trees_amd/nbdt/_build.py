@@ -38,6 +38,7 @@ FLAGS = {
     "effnet.hip": ["-munsafe-fp-atomics"],
     # the two per-segment scalars (one sqrt, one division) are IEEE-correct, the element update is four separate roundings
     "lars.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    "ema.hip": ["-ffp-contract=off"],          # e + omd * (p - e): a subtract, a multiply and an add, never a fused multiply-add
 }
 
 

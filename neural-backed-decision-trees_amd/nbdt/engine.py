@@ -15,6 +15,7 @@ Python here only sequences C-ABI launches on the current HIP stream (capturable 
 torch.cuda.CUDAGraph); there is no CPU or PyTorch-op fallback for any tensor op on the path.
 """
 import collections
+import contextlib
 import math
 
 import torch
@@ -46,6 +47,9 @@ def _pad32(c):
 # train_step(..., lars=LarsConfig(...)): the optimizer pass is engine.lars_step instead of engine.sgd_step
 LarsConfig = collections.namedtuple("LarsConfig", ("trust", "eps", "exclude_1d"), defaults=(1e-3, 1e-8, True))
 
+_EMA_SWAPPED = ("%s: the averaged weights are swapped in (ema_swap / ema_weights); stepping or averaging would train into "
+                "the average -- swap back first")
+
 
 class ParamStore:
     """Flat parameter / gradient / momentum / bf16-mirror buffers + named views."""
@@ -56,6 +60,7 @@ class ParamStore:
         self.inits = []     # (name, fn(view))
         self.n = 0
         self.flat = self.grad = self.mom = self.bf16 = None
+        self.ema = None     # the moving average of flat (or, while _Engine.ema_swapped, the live weights): ema_enable
         self._views = {}    # (which buffer, name) -> (view, the buffer it was made of)
 
     def add(self, name, shape, init):
@@ -431,6 +436,9 @@ class _Engine:
         self._grad_is_zero = False   # the flat gradient buffer is known to be zero (sgd_step(zero_grad=True))
         self._lars_plans = {}     # (weight_decay, exclude_1d) -> ops.LarsPlan (lars_step)
         self._lars_last = None    # the plan of the last lars_step (last_trust_ratios)
+        self.ema_swapped = False  # ema_swap(): the arena holds the average, store.ema the live weights; no optimizer step then
+        self.ema_updates = 0      # ema_update() calls since ema_enable (the t of ema_decay_at)
+        self._ema_table = None    # ops.EmaTable over (running statistic, its shadow) of every BatchNorm
         self._B = None            # batch of the last forward()
 
     def seg_op(self, key, build, sources, sources32, on_side=False):
@@ -908,6 +916,8 @@ class _Engine:
         """optim.SGD step over every parameter (main.py:207) + refresh of bf16 / dgrad weights.
         zero_grad: the same pass leaves the gradient buffer zeroed, and the next zero_grad() is then free (the separate
         146 MB fill took 108 us per WRN-28-10 step; train_step asks for it)."""
+        if self.ema_swapped:
+            raise RuntimeError(_EMA_SWAPPED % "sgd_step")
         self.join_side_stream()
         s = self.store
         ops.sgd_step(s.flat, s.grad, s.mom, lr, momentum, weight_decay, grad_scale, s.bf16, zero_grad=zero_grad)
@@ -928,6 +938,8 @@ class _Engine:
         ParamStore entry; nbdt_lars_step) + refresh of bf16 / dgrad weights.  Three launches whatever the number of
         parameters, no host synchronisation; zero_grad as in sgd_step.  exclude_1d: BatchNorm parameters and biases take
         plain SGD steps without decay."""
+        if self.ema_swapped:
+            raise RuntimeError(_EMA_SWAPPED % "lars_step")
         self.join_side_stream()
         s = self.store
         plan = self._lars_plan(weight_decay, exclude_1d)
@@ -943,6 +955,112 @@ class _Engine:
             raise RuntimeError("last_trust_ratios: no lars_step yet")
         return dict(zip(self.store.segment_names(), self._lars_last.ratios().tolist()))
 
+    # ---- exponential moving average of the weights
+    def ema_enable(self, decay=0.9999, warmup=True):
+        """Start averaging: the shadow of the parameter arena (store.ema) and ONE flat shadow of every BatchNorm's running
+        statistics begin as copies of the live values, ema_updates = 0.  Calling it again re-initialises the average.
+        decay, warmup: what ema_update hands to ema_decay_at."""
+        if self.ema_swapped:
+            raise RuntimeError("ema_enable: the average is swapped into the weights (ema_swap / ema_weights); swap back first")
+        s = self.store
+        s.ema = s.flat.clone()
+        self._ema_stats = torch.empty(sum(2 * b.C for b in self.bns), dtype=torch.float32, device=self.device)
+        pairs, off = [], 0
+        for b in self.bns:
+            for live in (b.running_mean, b.running_var):
+                shadow = self._ema_stats[off:off + b.C]
+                shadow.copy_(live)
+                pairs.append((live, shadow))
+                off += b.C
+        self._ema_table = ops.EmaTable(pairs, self.device) if pairs else None
+        self._ema_nbt = [b.num_batches_tracked for b in self.bns]    # host ints: the counters as of the last update
+        self.ema_decay, self.ema_warmup, self.ema_updates = float(decay), bool(warmup), 0
+
+    @staticmethod
+    def ema_decay_at(t, decay=0.9999, warmup=True):
+        """The decay of the update that follows t earlier ones, in double: min(decay, (1 + t) / (10 + t)) with warm-up (the
+        ramp of tf.train.ExponentialMovingAverage(num_updates=) and timm's ModelEmaV3), else `decay`.  Host only.  The
+        kernel takes float32(1 - d)."""
+        return min(float(decay), (1.0 + t) / (10.0 + t)) if warmup else float(decay)
+
+    def _ema_require(self, what):
+        if self.store.ema is None:
+            raise RuntimeError(f"{what}: no average is kept (call ema_enable first)")
+
+    def ema_update(self):
+        """e += (1 - d) * (p - e) over the parameter arena and over every running statistic, d = ema_decay_at(ema_updates):
+        two launches on the current stream, no host synchronisation.  They only read the live values, so nothing the
+        second stream still does with them has to be waited for.  The caller issues it after train_step / a GraphedStep."""
+        self._ema_require("ema_update")
+        if self.ema_swapped:
+            raise RuntimeError(_EMA_SWAPPED % "ema_update")
+        omd = 1.0 - self.ema_decay_at(self.ema_updates, self.ema_decay, self.ema_warmup)   # (ctypes rounds it to fp32)
+        ops.ema_update(self.store.flat, self.store.ema, omd)
+        if self._ema_table is not None:
+            self._ema_table.update(omd)
+        self._ema_nbt = [b.num_batches_tracked for b in self.bns]
+        self.ema_updates += 1
+
+    def ema_swap(self):
+        """Exchange the live weights and running statistics with their averages IN PLACE (the facade's parameters, the
+        named views and BatchNorm.running_mean / running_var alias the live tensors), write the bf16 mirror of what the
+        arena now holds in the same pass, exchange the host counters, and rebuild every derived weight copy.  Flips
+        ema_swapped; while it is set, the optimizer steps and ema_update raise."""
+        self._ema_require("ema_swap")
+        self.join_side_stream()          # the second stream may still be reading flat (the transposed copies)
+        s = self.store
+        ops.ema_swap(s.flat, s.ema, s.bf16)
+        if self._ema_table is not None:
+            self._ema_table.swap()
+        live = [b.num_batches_tracked for b in self.bns]
+        for b, k in zip(self.bns, self._ema_nbt):
+            b.num_batches_tracked = k
+        self._ema_nbt = live
+        self.ema_swapped = not self.ema_swapped
+        self.refresh_derived_weights()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """with engine.ema_weights(): forward() / the facade evaluate the averaged weights; swapped back on exit, also when
+        the body raises."""
+        self.ema_swap()
+        try:
+            yield self
+        finally:
+            self.ema_swap()
+
+    def _ema_stat_views(self):
+        out, off = {}, 0
+        for b, k in zip(self.bns, self._ema_nbt):
+            out[b.name + ".running_mean"] = self._ema_stats[off:off + b.c_real]
+            out[b.name + ".running_var"] = self._ema_stats[off + b.C:off + b.C + b.c_real]
+            out[b.name + ".num_batches_tracked"] = torch.tensor(k, dtype=torch.long)
+            off += 2 * b.C
+        return out
+
+    def ema_state_dict(self):
+        """The average under state_dict()'s keys and logical shapes, whichever side it currently lives on."""
+        self._ema_require("ema_state_dict")
+        if self.ema_swapped:
+            return self.state_dict()
+        out = {k: v.detach().clone().contiguous() for k, v in self.named_params("ema").items()}
+        out.update({k: v.detach().clone() for k, v in self._ema_stat_views().items()})
+        return out
+
+    def load_ema_state_dict(self, sd):
+        """Copy a reference-named state dict into the average, whichever side it currently lives on."""
+        self._ema_require("load_ema_state_dict")
+        if self.ema_swapped:
+            return self.load_state_dict(sd)
+        params, bufs = self.named_params("ema"), self._ema_stat_views()
+        missing = {m for m in (set(params) | set(bufs)) - set(sd) if not m.endswith("num_batches_tracked")}
+        if missing:
+            raise KeyError(f"state dict is missing {sorted(missing)[:5]} ...")
+        for name, view in list(params.items()) + list(bufs.items()):
+            if not name.endswith("num_batches_tracked"):
+                view.copy_(sd[name].to(self.device))
+        self._ema_nbt = [int(sd.get(b.name + ".num_batches_tracked", k)) for b, k in zip(self.bns, self._ema_nbt)]
+
     def zero_grad(self):
         if not self._grad_is_zero:
             self.store.zero_grad()
@@ -954,7 +1072,7 @@ class _Engine:
         return {}
 
     def named_params(self, which="flat"):
-        buf = {"flat": self.store.flat, "grad": self.store.grad, "bf16": self.store.bf16}[which]
+        buf = {"flat": self.store.flat, "grad": self.store.grad, "bf16": self.store.bf16, "ema": self.store.ema}[which]
         out = dict(self.extra_param_views(buf))
         for c in self.convs:
             out[c.name] = c.logical(buf)

@@ -823,6 +823,65 @@ class LarsPlan:
             pass
 
 
+def _ema_pair(p, ema, what):
+    _C.require_gpu(p, what)
+    for t, name in ((p, "p"), (ema, "ema")):
+        if t.dtype != torch.float32 or t.numel() != p.numel() or t.device != p.device or not t.is_contiguous():
+            raise _C.NBDTHipError(f"{what}: {name} must be a contiguous fp32 tensor of {p.numel()} elements on {p.device}")
+
+
+def ema_update(p, ema, one_minus_decay):
+    """ema += one_minus_decay * (p - ema) as a subtract, a multiply and an add per element (nbdt_ema_update): one launch on
+    p's current stream, p only read."""
+    _ema_pair(p, ema, "ema_update")
+    check(lib().nbdt_ema_update(ptr(p), ptr(ema), p.numel(), one_minus_decay, stream_ptr(p.device)))
+
+
+def ema_swap(p, ema, p_bf16=None):
+    """p and ema exchange their values in place; p_bf16 (optional) becomes the bf16 mirror of the new p (nbdt_ema_swap)."""
+    _ema_pair(p, ema, "ema_swap")
+    if p_bf16 is not None and (p_bf16.dtype != torch.bfloat16 or p_bf16.numel() != p.numel() or p_bf16.device != p.device
+                               or not p_bf16.is_contiguous()):
+        raise _C.NBDTHipError(f"ema_swap: the mirror must be a contiguous bf16 tensor of {p.numel()} elements on {p.device}")
+    check(lib().nbdt_ema_swap(ptr(p), ptr(ema), ptr(p_bf16), p.numel(), stream_ptr(p.device)))
+
+
+class EmaTable:
+    """The device table of nbdt_ema_update_multi / nbdt_ema_swap_multi: `pairs` = (live, shadow) fp32 tensors of equal
+    length, a positive multiple of 32 elements each (the BatchNorm running statistics and their views of one flat shadow).
+    The rows are checked here, on the host (the library sees only a device pointer), and copied to `device` once; the
+    table keeps the tensors alive, whose addresses it holds."""
+
+    def __init__(self, pairs, device):
+        self.pairs = [(a, b) for a, b in pairs]
+        self.device = torch.device(device)
+        rows = []
+        for live, shadow in self.pairs:
+            for t in (live, shadow):
+                if t.dtype != torch.float32 or not t.is_contiguous() or t.device != live.device:
+                    raise _C.NBDTHipError("EmaTable: rows are pairs of contiguous fp32 tensors on one device")
+                if t.data_ptr() % 16:
+                    raise _C.NBDTHipError("EmaTable: tensors must be 16-byte aligned")
+            n = live.numel()
+            if shadow.numel() != n or n <= 0 or n % 32:
+                raise _C.NBDTHipError(f"EmaTable: row lengths must be equal positive multiples of 32, got {n} / {shadow.numel()}")
+            if live.data_ptr() == shadow.data_ptr():
+                raise _C.NBDTHipError("EmaTable: a tensor cannot be its own shadow")
+            rows.append([live.data_ptr(), shadow.data_ptr(), n])
+        self.n_rows = len(rows)
+        if not rows:
+            raise _C.NBDTHipError("EmaTable: empty table")
+        self.table = torch.tensor(rows, dtype=torch.int64).to(self.device)
+
+    def update(self, one_minus_decay):
+        _C.require_gpu(self.table, "EmaTable.update")
+        check(lib().nbdt_ema_update_multi(ptr(self.table), self.n_rows, one_minus_decay, stream_ptr(self.device)))
+
+    def swap(self):
+        _C.require_gpu(self.table, "EmaTable.swap")
+        check(lib().nbdt_ema_swap_multi(ptr(self.table), self.n_rows, stream_ptr(self.device)))
+
+
 # ------------------------------------------------------------------------------------------------
 # MBConv pieces (EfficientNet-B0, csrc/effnet.hip)
 
