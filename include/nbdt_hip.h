@@ -942,6 +942,90 @@ int nbdt_mix_batch(const float* x, const int64_t* y, int32_t B, int32_t H, int32
                    int32_t y1, int32_t y2, int32_t x1, int32_t x2, float lam_t, float one_minus_lam_t, float* out,
                    float* tgt, int32_t C, void* stream);
 
+/* ------------------------------------------------------------------ augmentation policy (nbdt_version() >= 119) */
+/* nbdt_augment_batch with an augmentation policy, still ONE launch per batch: gather by index, zero-padded random crop,
+ * flip, then ONE TrivialAugmentWide operation on the uint8 image, then /255 and Normalize, then torchvision's
+ * RandomErasing(value=0) on the normalised output.  csrc/policy.hip.  The recipe of the TrivialAugment paper's CIFAR setup
+ * and of torchvision's ResNet reference (ta_wide, RandomErasing(0.1)).  nbdt_policy_batch_sharded is the entry for a rank
+ * that holds the samples [index_base, index_base + N) (see nbdt_augment_batch_sharded); nbdt_policy_batch is its base-0 form.
+ *
+ * src, src_dtype, labels_src, index, B, N, H, W, pad, flip, mean, std, seed, epoch, params_in, out, labels_out, params_out:
+ * as for nbdt_augment_batch, except that src_dtype must be NBDT_U8 and 3*H*W at most 49152 bytes (the image is staged in
+ * LDS twice); anything else is NBDT_EINVAL.  The crop / flip draw is nbdt_augment_batch's: a sample gets the same crop with
+ * and without the policy.  Further arguments:
+ *   policy        NBDT_POLICY_NONE (every sample gets Identity) | NBDT_POLICY_TA_WIDE
+ *   policy_table  int32 [NBDT_POLICY_OPS][NBDT_POLICY_BINS][2][6], DEVICE memory; needed unless policy is NBDT_POLICY_NONE
+ *                 and policy_in is NULL.  Per (op, bin, sign) the magnitude in the form the kernel consumes, formed by the
+ *                 caller in fp64 (nbdt/data.py policy_table), so that the device does no trigonometry:
+ *                   ShearX/Y, TranslateX/Y, Rotate   Pillow's 16.16 fixed-point affine coefficients a0 .. a5 (below)
+ *                   Brightness, Color, Contrast, Sharpness   word 0 = the bits of (float)factor
+ *                   Posterize  word 0 = the byte mask;   Solarize  word 0 = ceil(threshold);   other words 0
+ *   erase_prob    in [0, 1]: the probability that a sample is erased
+ *   erase_scale, erase_ratio  HOST double[2] each, as scale / ratio of nbdt_resized_crop_batch (torchvision's defaults are
+ *                 (0.02, 0.33) and (0.3, 3.3)); ratio_table: the NBDT_RESIZED_CROP_RATIOS log-spaced ratios, DEVICE memory.
+ *                 All three are needed only when erase_prob > 0 and policy_in is NULL.
+ *   policy_in     optional int32 [B,7] (op, bin, sign, top, left, h, w), device memory: REPLACES the policy and erase draw.
+ *                 Device data, so the kernel clamps: op to [0, 13], bin to [0, 30], sign is (value != 0), top to [0, H-1],
+ *                 left to [0, W-1], h to [0, H-top], w to [0, W-left]; h == 0 or w == 0 erases nothing.
+ *   policy_out    optional int32 [B,7]: the values actually used (an empty rectangle is reported as 0, 0, 0, 0)
+ *
+ * The operations, in the kernel's order (op = 0 .. 13), for bin b in 0 .. 30 and s = +1 (sign 0) or -1 (sign 1); the
+ * magnitudes are TrivialAugmentWide's, the pixel rules are Pillow's (what torchvision calls on PIL images), fill = byte 0:
+ *   Identity
+ *   ShearX, ShearY      m = s*0.99*b/30; Image.transform(AFFINE, NEAREST) with [1, m, 0, 0, 1, 0] / [1, 0, 0, m, 1, 0]
+ *   TranslateX, TranslateY   t = s*int(32*b/30) pixels: source x - t / y - t
+ *   Rotate              Image.rotate(s*135*b/30 degrees, NEAREST): centre (W/2, H/2), matrix entries round(cos, 15) and
+ *                       round(sin, 15) of -radians(angle % 360); angle 0 is a copy and +-90 on a square image the exact
+ *                       transpose (Pillow's special cases)
+ *   Brightness, Color, Contrast, Sharpness   ImageEnhance: blend(degenerate, image, 1 + s*0.99*b/30); the degenerate image
+ *                       is black / the grey image / the solid grey mean int(mean(grey) + 0.5) / ImageFilter.SMOOTH
+ *                       ((1 1 1; 1 5 1; 1 1 1)/13 as trunc(sum/13 + 0.5), the one-pixel border copied);
+ *                       grey = (19595 R + 38470 G + 7471 B + 32768) >> 16;  blend in fp32: t = d + a*(x - d), a separate
+ *                       multiply and add, then 0 for t <= 0, 255 for t >= 255, else truncated
+ *   Posterize           v & ~(2^(8-bits) - 1), bits = 8 - round(b/5)
+ *   Solarize            v if v < 255 - 255*b/30 else 255 - v
+ *   AutoContrast        ImageOps.autocontrast, per channel: lo, hi = min, max; unchanged if hi <= lo, else
+ *                       clip(int(v*scale + offset)) with scale = 255.0/(hi - lo), offset = -lo*scale in fp64
+ *   Equalize            ImageOps.equalize, per channel: histogram h; unchanged with at most one non-empty bin or
+ *                       step = (H*W - h[last non-empty]) / 255 == 0; else lut[i] = min(255, (step/2 + sum h[j<i]) / step)
+ * Nearest affine (Pillow's affine_fixed): output pixel (x, y) reads source ((a2 + a0*x + a1*y) >> 16,
+ * (a5 + a3*x + a4*y) >> 16) when that lies inside the image, else 0, with FIX(v) = floor-for-negative int(v*65536 + 0.5),
+ * a0, a1, a3, a4 = FIX of the matrix entries, a2 = FIX(m[2] + 0.5*m[0] + 0.5*m[1]), a5 = FIX(m[5] + 0.5*m[3] + 0.5*m[4]).
+ * Parity with torchvision's own float32 linspace magnitudes and its atan/tan shear round trip is NOT claimed.
+ *
+ * The draw.  With mix64 and key as for nbdt_augment_batch and G = 0x9E3779B97F4A7C15:
+ *   rp = mix64(key ^ (index * 0xA0761D6478BD642F)):   op = ((rp & 0xFFFFFF) * 14) >> 24;
+ *                                                      bin = (((rp >> 24) & 0xFFFFFF) * 31) >> 24;  sign = rp >> 63
+ *   re = mix64(key ^ (index * 0xE7037ED1A0B428DB)):   erased when (re >> 11) * 2^-53 < erase_prob; then
+ *   attempt t = 0 .. NBDT_RESIZED_CROP_ATTEMPTS-1:  ra = mix64(re + (2t+1) * G);  rb = mix64(re + (2t+2) * G)
+ *     target = (double)(H*W) * (scale[0] + (ra >> 11) * 2^-53 * (scale[1] - scale[0]))
+ *     r = ratio_table[rb & (NBDT_RESIZED_CROP_RATIOS-1)];  h = round(sqrt(target * r));  w = round(sqrt(target / r))
+ *     the first attempt with h < H and w < W is taken:  top = (((rb >> 12) & 0xFFFFFF) * (H-h+1)) >> 24,
+ *                                                       left = (((rb >> 36) & 0xFFFFFF) * (W-w+1)) >> 24
+ *   no such attempt: nothing is erased.
+ * A pure function of (seed, epoch, dataset index) and the settings -- not of the position in the batch, the batch size or
+ * the rank (nbdt/data.py draw_policy_params restates it).  Erased pixels are exactly 0.0f in the normalised output.
+ *
+ * The per-image statistics (grey sum, channel minima / maxima, histograms) are integer LDS atomics: the same inputs give
+ * the same bits.  Out-of-range indices: a zero image with label -1 and zero params, as for nbdt_augment_batch. */
+#define NBDT_POLICY_NONE 0
+#define NBDT_POLICY_TA_WIDE 1
+#define NBDT_POLICY_OPS 14
+#define NBDT_POLICY_BINS 31
+int nbdt_policy_batch(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index, int32_t B,
+                      int64_t N, int32_t H, int32_t W, int32_t pad, int32_t flip, const float* mean, const float* std,
+                      int32_t policy, const int32_t* policy_table, double erase_prob, const double* erase_scale,
+                      const double* erase_ratio, const double* ratio_table, uint64_t seed, uint64_t epoch,
+                      const int8_t* params_in, const int32_t* policy_in, float* out, int64_t* labels_out,
+                      int8_t* params_out, int32_t* policy_out, void* stream);
+int nbdt_policy_batch_sharded(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index,
+                              int64_t index_base, int32_t B, int64_t N, int32_t H, int32_t W, int32_t pad, int32_t flip,
+                              const float* mean, const float* std, int32_t policy, const int32_t* policy_table,
+                              double erase_prob, const double* erase_scale, const double* erase_ratio,
+                              const double* ratio_table, uint64_t seed, uint64_t epoch, const int8_t* params_in,
+                              const int32_t* policy_in, float* out, int64_t* labels_out, int8_t* params_out,
+                              int32_t* policy_out, void* stream);
+
 /* ------------------------------------------------------------------ measurement probe (not on the product path) */
 /* A register-only stream of independent v_mfma_f32_32x32x16_bf16 on `blocks` CUs (one 512-thread block each, two waves
  * per SIMD): every wave issues iters x 16 of them (x 32768 flop).  bench.py times the launch for `roofline.mfma_stream`

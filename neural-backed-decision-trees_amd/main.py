@@ -55,6 +55,11 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   rank) in one launch that also writes the probability targets, whatever ``--augment`` made the batch; the step then takes
   ``soft_target_loss_and_grad``.  A loss without it (``HardTreeSupLoss``: the reference's cannot take probability
   targets either) is refused at argument time.  Evaluation is never mixed.
+* ``--auto-augment ta_wide`` applies TrivialAugmentWide (one of 14 operations at one of 31 magnitudes per image, Pillow's
+  pixel rules) and ``--random-erase P`` torchvision's ``RandomErasing(P, value=0)`` to every training image, inside the
+  one batch-assembly launch of ``--augment reference`` (``nbdt.data.DeviceDataset(policy=, erase_prob=)``,
+  ``nbdt_policy_batch``): gather, padded crop, flip, the operation on the bytes, normalise, erase.  Both need a uint8
+  ``--data-file``; ``--augment resized-crop`` does not have them.  MixUp / CutMix still run on the assembled batch.
 * ``--optimizer lars`` replaces the SGD pass with layer-wise adaptive rate scaling (You et al. 2017; apex's
   ``LARC(clip=False)`` around ``optim.SGD``): ``engine.lars_step``, three launches over the flat parameter arena.
   ``--lars-trust`` / ``--lars-eps`` are its coefficients; BatchNorm parameters and biases take plain SGD steps without decay
@@ -159,6 +164,12 @@ def build_parser():
                    help="--augment reference | resized-crop: every rank keeps only its contiguous part of both splits on "
                         "its GPU (nbdt.data shard=(rank, world)), a --data-file is memory-mapped, and training shuffles "
                         "within each rank's part")
+    p.add_argument("--auto-augment", choices=("none", "ta_wide"), default="none",
+                   help="ta_wide: TrivialAugmentWide, one of 14 operations at one of 31 magnitudes per training image, inside "
+                        "the batch-assembly launch (--augment reference on a uint8 --data-file; nbdt.data policy='ta_wide')")
+    p.add_argument("--random-erase", type=float, default=0.0, metavar="P",
+                   help="torchvision's RandomErasing(P, value=0) on every training image after the normalisation, in the "
+                        "same launch (--augment reference on a uint8 --data-file); 0: off")
     p.add_argument("--label-smoothing", type=float, default=0.0, metavar="E",
                    help="label_smoothing of the wrapped nn.CrossEntropyLoss, 0 <= E < 1 (applied inside the fused tree loss)")
     p.add_argument("--mixup-alpha", type=float, default=0.0, metavar="A",
@@ -418,6 +429,16 @@ def parse_args(argv=None):
     if args.shard_data and args.augment not in ("reference", "resized-crop"):
         parser.error("--shard-data shards the device-resident datasets: it needs --augment reference or --augment "
                      "resized-crop")
+    if not 0.0 <= args.random_erase <= 1.0:
+        parser.error(f"--random-erase must be in [0, 1], got {args.random_erase}")
+    if args.auto_augment != "none" or args.random_erase > 0:
+        if args.augment == "resized-crop":
+            parser.error("--auto-augment / --random-erase on --augment resized-crop is not built: the policy runs in the "
+                         "padded-crop launch of --augment reference (images of at most 128 x 128); a 224 x 224 crop "
+                         "belongs in the resampling kernel's output stage")
+        if args.augment != "reference" or not args.data_file:
+            parser.error("--auto-augment / --random-erase work on the bytes of a device-resident dataset: they need "
+                         "--augment reference and a uint8 --data-file")
     if not 0.0 <= args.label_smoothing < 1.0:
         parser.error(f"--label-smoothing must be in [0, 1), got {args.label_smoothing}")
     if args.mixup_alpha < 0 or args.cutmix_alpha < 0:
@@ -470,7 +491,17 @@ def main(argv=None):
     if args.augment == "reference":
         stats = DATASET_STATS[args.dataset]
         kwargs = dict(flip=True, device=device, shard=shard)
-        train_x = DeviceDataset(train_x, train_y, stats["mean"], stats["std"], stats["pad"], **kwargs)
+        policy = None if args.auto_augment == "none" else args.auto_augment
+        if (policy or args.random_erase > 0) and train_x.dtype != torch.uint8:
+            raise SystemExit(f"--auto-augment / --random-erase work on bytes: train_x of {args.data_file} must be uint8, "
+                             f"not {train_x.dtype}")
+        try:           # only the training split is augmented; evaluation never applies a policy
+            train_x = DeviceDataset(train_x, train_y, stats["mean"], stats["std"], stats["pad"], policy=policy,
+                                    erase_prob=args.random_erase, **kwargs)
+        except ValueError as e:
+            if policy or args.random_erase > 0:        # e.g. images too large for the policy kernel
+                raise SystemExit(f"--auto-augment / --random-erase: {e}") from e
+            raise
         test_x = DeviceDataset(test_x, test_y, stats["mean"], stats["std"], stats["pad"], **kwargs)
     elif args.augment == "resized-crop":
         stats = RESIZED_CROP_STATS[args.dataset]

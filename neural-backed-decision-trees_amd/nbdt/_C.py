@@ -20,6 +20,9 @@ NBDT_U8 = 3                     # nbdt_augment_batch's src_dtype for a uint8 dat
 NBDT_AUGMENT_MAX_PAD = 32
 NBDT_RESIZED_CROP_RATIOS = 4096     # entries of nbdt_resized_crop_batch's aspect-ratio table
 NBDT_RESIZED_CROP_ATTEMPTS = 10
+NBDT_POLICY_NONE, NBDT_POLICY_TA_WIDE = 0, 1
+NBDT_POLICY_OPS = 14               # nbdt_policy_batch: TrivialAugmentWide's operations ...
+NBDT_POLICY_BINS = 31               # ... and magnitude bins
 _ZTYPE = {torch.float32: NBDT_F32, torch.bfloat16: NBDT_BF16, torch.float16: NBDT_F16}
 
 
@@ -214,6 +217,14 @@ SIGNATURES = {
     "nbdt_resized_crop_batch_sharded": (c_int, [_P, c_int32, _P, _P, c_int64, c_int32, c_int64] + [c_int32] * 9 +
                                         [POINTER(c_float), POINTER(c_float), POINTER(ctypes.c_double),
                                          POINTER(ctypes.c_double), _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P, _P]),
+    "nbdt_policy_batch": (c_int, [_P, c_int32, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                  POINTER(c_float), POINTER(c_float), c_int32, _P, ctypes.c_double,
+                                  POINTER(ctypes.c_double), POINTER(ctypes.c_double), _P, ctypes.c_uint64, ctypes.c_uint64,
+                                  _P, _P, _P, _P, _P, _P, _P]),
+    "nbdt_policy_batch_sharded": (c_int, [_P, c_int32, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32,
+                                          c_int32, POINTER(c_float), POINTER(c_float), c_int32, _P, ctypes.c_double,
+                                          POINTER(ctypes.c_double), POINTER(ctypes.c_double), _P, ctypes.c_uint64,
+                                          ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P]),
     "nbdt_stem_patches": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_maxpool3x3s2_fwd": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
     "nbdt_maxpool3x3s2_bwd": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),

@@ -12,6 +12,12 @@ form, ``nbdt_resized_crop_batch`` (csrc/resample.hip): the crop box is drawn in 
 restates the draw) and resampled with PIL's bilinear filter, byte for byte (``resample_reference`` restates the pixels; it
 is documentation and test infrastructure, never called on the training path).
 
+``DeviceDataset(policy="ta_wide", erase_prob=p)`` adds an augmentation policy to the padded-crop family without leaving the
+one launch: ``nbdt_policy_batch`` (csrc/policy.hip) applies one TrivialAugmentWide operation to the cropped and flipped
+bytes, with Pillow's pixel rules, before the normalisation, and torchvision's RandomErasing after it
+(``draw_policy_params`` restates the draw, ``policy_reference`` the pixels; like ``resample_reference`` it is never called on
+the training path).
+
 Both classes take ``shard=(rank, world)``: the rank then keeps only its contiguous part ``shard_range(N, rank, world)`` of
 the dataset on its GPU (ImageNet at 256 x 256 is 252 GB whole, 31.5 GB per rank at 8 ranks) and ``batch`` still takes
 indices into the whole dataset.  The kernels draw from that index and gather from ``index - lo``
@@ -109,6 +115,16 @@ def draw_params(seed, epoch, index, pad):
     return dy.astype(np.int64), dx.astype(np.int64), flip.astype(np.int64)
 
 
+def _check_policy_source(x):
+    """The policy kernel works on bytes staged in LDS: refuse anything else on the host, before any launch."""
+    if x.dtype != torch.uint8:
+        raise ValueError(f"the augmentation policy and random erasing work on a uint8 dataset, got {x.dtype} (an fp32 "
+                         "dataset is already normalised: there are no bytes left to posterize or equalize)")
+    if 3 * x.shape[2] * x.shape[3] > POLICY_MAX_BYTES:
+        raise ValueError(f"the augmentation policy and random erasing take images of at most {POLICY_MAX_BYTES} bytes "
+                         f"(128 x 128 x 3), got {tuple(x.shape[1:])}")
+
+
 class DeviceDataset:
     """A dataset held on the device, batched by `nbdt_augment_batch`.
 
@@ -118,15 +134,27 @@ class DeviceDataset:
     ``(0 - mean)/std`` -- a file normalised with the dataset's statistics then yields the same batches as its uint8
     original.  pad: pixels of zero padding before the random ``H x W`` crop; flip: random horizontal flip.
 
+    policy="ta_wide": every training sample gets one TrivialAugmentWide operation (POLICY_OPS, 31 magnitude bins) between the
+    flip and the normalisation; erase_prob > 0: torchvision's RandomErasing(p, erase_scale, erase_ratio, value=0) after the
+    normalisation.  Both need a uint8 `x` of at most 49152 bytes per image and run in ``nbdt_policy_batch``, still one launch
+    per batch (csrc/policy.hip); the crop and the flip of a sample are the same with and without them.
+
     shard=(rank, world): only the samples ``shard_range(N, rank, world)`` are moved to the device.  ``shape[0]`` and
     ``len()`` are then the number held, ``global_size`` is N, ``shard_range`` the owned [lo, hi); ``batch`` keeps taking
     indices into the whole dataset and returns, for an index it owns, the very batch the unsharded dataset returns.
     """
 
-    def __init__(self, x, y, mean, std, pad, flip=True, fill=None, device="cuda", shard=None):
+    def __init__(self, x, y, mean, std, pad, flip=True, fill=None, device="cuda", shard=None, policy=None, erase_prob=0.0,
+                 erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3)):
         device = torch.device(device)
         if device.type != "cuda":
             raise _C.NBDTHipError(f"DeviceDataset lives on an MI355X, not on {device} (no CPU fallback)")
+        if policy not in (None, "ta_wide"):
+            raise ValueError(f"policy must be None or 'ta_wide', got {policy!r}")
+        self.policy = policy
+        self.erase_prob = _check_erase(erase_prob, erase_scale, erase_ratio)
+        self.erase_scale = tuple(float(v) for v in erase_scale)
+        self.erase_ratio = tuple(float(v) for v in erase_ratio)
         if x.dim() != 4 or x.shape[1] != 3 or x.dtype not in (torch.uint8, torch.float32):
             raise ValueError(f"x must be uint8 or fp32 [N,3,H,W], got {x.dtype} {tuple(x.shape)}")
         if y.dim() != 1 or y.shape[0] != x.shape[0] or y.is_floating_point():
@@ -142,8 +170,11 @@ class DeviceDataset:
         self.fill = tuple(float(f) for f in fill)
         self.pad, self.flip = int(pad), bool(flip)
         self.sharded = shard is not None
+        if policy is not None or self.erase_prob > 0.0:
+            _check_policy_source(x)
         self.x, self.y, self.shard_range, self.global_size = _place("DeviceDataset", x, y, shard, device)
         self.device = self.x.device
+        self._policy_tables = None        # (policy table, ratio table) on the device, built by the first policy batch
 
     def __len__(self):
         return self.x.shape[0]
@@ -152,7 +183,16 @@ class DeviceDataset:
     def shape(self):
         return self.x.shape
 
-    def batch(self, index, epoch=0, seed=0, train=True, params=None, return_params=False):
+    def _tables(self):
+        if self._policy_tables is None:
+            _check_policy_source(self.x)
+            H, W = self.x.shape[2], self.x.shape[3]
+            self._policy_tables = (torch.from_numpy(policy_table(H, W).copy()).to(self.device),
+                                   torch.from_numpy(ratio_table(self.erase_ratio).copy()).to(self.device))
+        return self._policy_tables
+
+    def batch(self, index, epoch=0, seed=0, train=True, params=None, return_params=False, policy_params=None,
+              return_policy_params=False):
         """(img fp32 [B,3,H,W], targets int64 [B][, params int8 [B,3]]) for the samples `index`, in ONE launch on torch's
         current stream.
 
@@ -161,6 +201,14 @@ class DeviceDataset:
         index outside [0, N), or outside the owned range of a shard.  train=False is the evaluation transform (no crop, no
         flip).  params: int8 [B,3] of (dy, dx, flip) replaces the generator; a CPU tensor is
         range-checked and copied.  Without it the draw is ``draw_params(seed, epoch, index, pad)``.
+
+        With ``policy="ta_wide"`` or ``erase_prob > 0`` (or policy_params) a training batch is ONE launch of
+        nbdt_policy_batch instead: the same crop and flip, then one TrivialAugmentWide operation on the bytes, the
+        normalisation, then the erase rectangle set to 0.0.  policy_params: integer [B,7] of (op, bin, sign, top, left, h,
+        w) replaces that draw (h = w = 0: no erase); a CPU tensor is range-checked and copied, a device tensor is clamped by
+        the kernel.  Without it the draw is ``draw_policy_params(seed, epoch, index, H, W, erase_prob, erase_scale,
+        erase_ratio)`` (every op is Identity when policy is None).  return_policy_params appends the int32 [B,7] used.
+        train=False never applies a policy.  With neither setting nor argument the launch is nbdt_augment_batch, untouched.
 
         Every call returns freshly allocated tensors (torch's caching allocator): train_step is asynchronous and the engine
         keeps `img` until the stem's weight gradient, so nothing handed out is ever overwritten by a later call."""
@@ -187,13 +235,49 @@ class DeviceDataset:
                 params = params.to(self.device, non_blocking=True)
             _C.require_gpu(params, "DeviceDataset.batch")
             params = params.contiguous()
+        if policy_params is not None:
+            if not train:
+                raise ValueError("policy_params replace the training draw; train=False has none")
+            H, W = self.x.shape[2], self.x.shape[3]
+            if not isinstance(policy_params, torch.Tensor):
+                policy_params = torch.as_tensor(np.asarray(policy_params))
+            if tuple(policy_params.shape) != (B, 7) or policy_params.is_floating_point() \
+                    or policy_params.dtype == torch.bool:
+                raise ValueError(f"policy_params must be integer [{B},7], got {policy_params.dtype} "
+                                 f"{tuple(policy_params.shape)}")
+            _check_policy_source(self.x)
+            if not policy_params.is_cuda:
+                p = policy_params.long()
+                ok = (p[:, 0] >= 0) & (p[:, 0] < len(POLICY_OPS)) & (p[:, 1] >= 0) & (p[:, 1] < POLICY_BINS) \
+                    & (p[:, 2] >= 0) & (p[:, 2] <= 1) & (p[:, 3] >= 0) & (p[:, 4] >= 0) & (p[:, 5] >= 0) & (p[:, 6] >= 0) \
+                    & (p[:, 3] + p[:, 5] <= H) & (p[:, 4] + p[:, 6] <= W)
+                if not bool(ok.all()):
+                    raise ValueError(f"policy_params outside op in [0, {len(POLICY_OPS) - 1}], bin in [0, {POLICY_BINS - 1}], "
+                                     f"sign in {{0, 1}} or an erase rectangle outside the {H} x {W} image")
+                policy_params = policy_params.to(self.device, non_blocking=True)
+            _C.require_gpu(policy_params, "DeviceDataset.batch")
+            policy_params = policy_params.to(dtype=torch.int32).contiguous()
         img = torch.empty((B,) + tuple(self.x.shape[1:]), dtype=torch.float32, device=self.device)
         targets = torch.empty((B,), dtype=torch.int64, device=self.device)
         used = torch.empty((B, 3), dtype=torch.int8, device=self.device) if return_params else None
-        ops.augment_batch(self.x, self.y, index, img, targets, pad, flip, mean=self.mean, std=self.std, fill=self.fill,
-                          seed=seed, epoch=epoch, params_in=params, params_out=used,
-                          index_base=self.shard_range[0] if self.sharded else None)
-        return (img, targets, used) if return_params else (img, targets)
+        base = self.shard_range[0] if self.sharded else None
+        with_policy = train and (self.policy is not None or self.erase_prob > 0.0 or policy_params is not None)
+        if not with_policy:
+            ops.augment_batch(self.x, self.y, index, img, targets, pad, flip, mean=self.mean, std=self.std, fill=self.fill,
+                              seed=seed, epoch=epoch, params_in=params, params_out=used, index_base=base)
+            out = (img, targets, used) if return_params else (img, targets)
+            if return_policy_params:         # nothing was applied: Identity, no erase
+                out += (torch.zeros((B, 7), dtype=torch.int32, device=self.device),)
+            return out
+        table, ratios = self._tables()
+        pused = torch.empty((B, 7), dtype=torch.int32, device=self.device) if return_policy_params else None
+        ops.policy_batch(self.x, self.y, index, img, targets, pad, flip, self.mean, self.std,
+                         policy=self.policy is not None, policy_table=table, erase_prob=self.erase_prob,
+                         erase_scale=self.erase_scale, erase_ratio=self.erase_ratio, ratio_table=ratios, seed=seed,
+                         epoch=epoch, params_in=params, policy_in=policy_params, params_out=used, policy_out=pused,
+                         index_base=base)
+        out = (img, targets, used) if return_params else (img, targets)
+        return out + (pused,) if return_policy_params else out
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -457,6 +541,231 @@ class ResizedCropDataset:
                                params_in=params, params_out=used,
                                index_base=self.shard_range[0] if self.sharded else None)
         return (img, targets, used) if return_params else (img, targets)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# TrivialAugmentWide and random erasing (nbdt_policy_batch, csrc/policy.hip): one of 14 operations per image at one of 31
+# magnitudes, on the cropped and flipped uint8 image, with Pillow's pixel rules; then torchvision's RandomErasing(value=0)
+# on the normalised output.  DeviceDataset(policy="ta_wide", erase_prob=p) switches them on.
+
+POLICY_OPS = ("Identity", "ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast",
+              "Sharpness", "Posterize", "Solarize", "AutoContrast", "Equalize")        # the kernel's order
+POLICY_BINS = _C.NBDT_POLICY_BINS
+POLICY_SIGNED = frozenset(range(1, 10))           # ShearX .. Sharpness draw a sign, the others ignore it
+POLICY_MAX_BYTES = 49152                          # 3*H*W of a dataset the policy kernel takes (NBDT_AUGMENT_LDS_BYTES)
+ERASE_SCALE, ERASE_RATIO = (0.02, 0.33), (0.3, 3.3)          # torchvision's RandomErasing defaults
+_OP = {name: i for i, name in enumerate(POLICY_OPS)}
+_K_POLICY, _K_ERASE = 0xA0761D6478BD642F, 0xE7037ED1A0B428DB     # odd: the policy's and the erase's hash of the index
+
+
+def _fix(v):
+    """Pillow's FIX(): 16.16 fixed point, floor(v * 65536 + 0.5) for a negative argument, truncation otherwise."""
+    v = v * 65536.0 + 0.5
+    return int(math.floor(v)) if v < 0.0 else int(v)
+
+
+def _affine_fixed(a):
+    """The six int32 of Pillow's nearest-neighbour affine transform for the fp64 matrix a[0..5] (affine_fixed): output pixel
+    (x, y) reads source ((a2 + a0*x + a1*y) >> 16, (a5 + a3*x + a4*y) >> 16), returned in the order a0 .. a5."""
+    return [_fix(a[0]), _fix(a[1]), _fix(a[2] + a[0] * 0.5 + a[1] * 0.5),
+            _fix(a[3]), _fix(a[4]), _fix(a[5] + a[3] * 0.5 + a[4] * 0.5)]
+
+
+def _rotate_fixed(angle, H, W):
+    """Image.rotate(angle, NEAREST) as the six fixed-point coefficients: Pillow's matrix (entries rounded to 15 decimals,
+    centre (W/2, H/2)) for the general case; angle 0 and, on a square image, the quarter turns are exact copies /
+    transposes, which the same form expresses exactly."""
+    angle = angle % 360.0
+    if angle == 0.0:
+        return _affine_fixed([1.0, 0.0, 0.0, 0.0, 1.0, 0.0])
+    if H == W and angle == 90.0:        # Transpose.ROTATE_90: out[y][x] = in[x][W-1-y]
+        return [0, -65536, ((W - 1) << 16) + 32768, 65536, 0, 32768]
+    if H == W and angle == 270.0:       # Transpose.ROTATE_270: out[y][x] = in[H-1-x][y]
+        return [0, 65536, 32768, -65536, 0, ((H - 1) << 16) + 32768]
+    cx, cy = W / 2, H / 2
+    r = -math.radians(angle)
+    m = [round(math.cos(r), 15), round(math.sin(r), 15), 0.0, round(-math.sin(r), 15), round(math.cos(r), 15), 0.0]
+    x, y = -cx, -cy
+    m[2], m[5] = m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]
+    m[2] += cx
+    m[5] += cy
+    return _affine_fixed(m)
+
+
+@functools.lru_cache(maxsize=8)
+def _policy_table(H, W):
+    t = np.zeros((len(POLICY_OPS), POLICY_BINS, 2, 6), dtype=np.int32)
+    for b in range(POLICY_BINS):
+        for sg in (0, 1):
+            s = -1.0 if sg else 1.0
+            m = s * 0.99 * b / 30
+            t[_OP["ShearX"], b, sg] = _affine_fixed([1.0, m, 0.0, 0.0, 1.0, 0.0])
+            t[_OP["ShearY"], b, sg] = _affine_fixed([1.0, 0.0, 0.0, m, 1.0, 0.0])
+            px = int(s) * int(32 * b / 30)
+            t[_OP["TranslateX"], b, sg] = [65536, 0, 32768 - px * 65536, 0, 65536, 32768]
+            t[_OP["TranslateY"], b, sg] = [65536, 0, 32768, 0, 65536, 32768 - px * 65536]
+            t[_OP["Rotate"], b, sg] = _rotate_fixed(s * 135 * b / 30, H, W)
+            factor = np.array([1 + m], dtype=np.float64).astype(np.float32).view(np.int32)[0]
+            for name in ("Brightness", "Color", "Contrast", "Sharpness"):
+                t[_OP[name], b, sg, 0] = factor
+            bits = 8 - round(b / 5)
+            t[_OP["Posterize"], b, sg, 0] = 0xFF & ~((1 << (8 - bits)) - 1)
+            t[_OP["Solarize"], b, sg, 0] = math.ceil(255 - 255 * b / 30)      # v < threshold  <=>  v < ceil(threshold)
+    t.setflags(write=False)
+    return t
+
+
+def policy_table(H, W):
+    """The int32 ``[14, 31, 2, 6]`` table nbdt_policy_batch reads for an H x W dataset: per (op, bin, sign) the magnitude in
+    the form the kernel consumes, formed here in fp64 so that the device does no trigonometry and no rounding of its own.
+    Geometric ops (ShearX/Y, TranslateX/Y, Rotate): Pillow's six 16.16 fixed-point affine coefficients a0 .. a5.
+    Brightness / Color / Contrast / Sharpness: word 0 is the bits of float32(1 + s * 0.99 * b / 30).  Posterize: word 0 is
+    the byte mask.  Solarize: word 0 is ceil(255 - 255 * b / 30).  The other words, and the other ops' rows, are 0."""
+    H, W = int(H), int(W)
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"image sides must be 1..{MAX_SIDE}, got {H} x {W}")
+    return _policy_table(H, W)
+
+
+def _check_erase(erase_prob, erase_scale, erase_ratio):
+    p = float(erase_prob)
+    if not 0.0 <= p <= 1.0:            # (NaN fails both comparisons)
+        raise ValueError(f"erase_prob must be in [0, 1], got {erase_prob}")
+    _check_ranges(erase_scale, erase_ratio)
+    return p
+
+
+def draw_policy_params(seed, epoch, index, H, W, erase_prob=0.0, erase_scale=ERASE_SCALE, erase_ratio=ERASE_RATIO):
+    """The policy and erase draw of nbdt_policy_batch (include/nbdt_hip.h), restated with numpy: (op, bin, sign, top, left,
+    h, w) int64 arrays shaped like `index`; h = w = 0 means no erase.  A pure function of (seed, epoch, dataset index) and
+    the settings; the crop and flip of the same sample stay ``draw_params``.
+
+    TrivialAugmentWide: op uniform in 0..13 (POLICY_OPS), bin uniform in 0..30, sign in {0, 1} (1: negative magnitude).
+    RandomErasing: applied when a uniform [0, 1) draw is below erase_prob; then up to 10 attempts of (area fraction
+    uniform in erase_scale, aspect ratio from ``ratio_table(erase_ratio)``, h = round(sqrt(area * r)),
+    w = round(sqrt(area / r)), accepted if h < H and w < W, position uniform); nothing is erased if none is accepted."""
+    H, W = int(H), int(W)
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"image sides must be 1..{MAX_SIDE}, got {H} x {W}")
+    p = _check_erase(erase_prob, erase_scale, erase_ratio)
+    s0, s1 = float(erase_scale[0]), float(erase_scale[1])
+    table = ratio_table(erase_ratio)
+    if isinstance(index, torch.Tensor):
+        index = index.cpu().numpy()
+    idx = np.asarray(index).astype(np.int64).astype(np.uint64)
+    u64 = np.uint64
+    m24, golden = u64(0xFFFFFF), 0x9E3779B97F4A7C15
+    with np.errstate(over="ignore"):
+        key = _mix64(np.asarray([(int(seed) * golden + int(epoch)) & _M64], dtype=np.uint64))[0]
+        rp = _mix64(key ^ (idx * u64(_K_POLICY)))
+        re = _mix64(key ^ (idx * u64(_K_ERASE)))
+        op = (((rp & m24) * u64(len(POLICY_OPS))) >> u64(24)).astype(np.int64)
+        bin_ = ((((rp >> u64(24)) & m24) * u64(POLICY_BINS)) >> u64(24)).astype(np.int64)
+        sign = (rp >> u64(63)).astype(np.int64)
+        top, left = np.zeros(idx.shape, dtype=np.int64), np.zeros(idx.shape, dtype=np.int64)
+        h, w = np.zeros(idx.shape, dtype=np.int64), np.zeros(idx.shape, dtype=np.int64)
+        apply = (re >> u64(11)).astype(np.float64) * 2.0 ** -53 < p
+        for t in reversed(range(_C.NBDT_RESIZED_CROP_ATTEMPTS)):      # the earliest accepted attempt is written last
+            ra = _mix64(re + u64(((2 * t + 1) * golden) & _M64))
+            rb = _mix64(re + u64(((2 * t + 2) * golden) & _M64))
+            u = (ra >> u64(11)).astype(np.float64) * 2.0 ** -53
+            target = float(H * W) * (s0 + u * (s1 - s0))
+            r = table[(rb & u64(_C.NBDT_RESIZED_CROP_RATIOS - 1)).astype(np.int64)]
+            ch, cw = _round_sqrt(target * r), _round_sqrt(target / r)
+            ok = apply & (ch < H) & (cw < W)
+            ct = (((rb >> u64(12)) & m24) * np.clip(H - ch + 1, 0, None).astype(np.uint64)) >> u64(24)
+            cl = (((rb >> u64(36)) & m24) * np.clip(W - cw + 1, 0, None).astype(np.uint64)) >> u64(24)
+            top, left = np.where(ok, ct.astype(np.int64), top), np.where(ok, cl.astype(np.int64), left)
+            h, w = np.where(ok, ch, h), np.where(ok, cw, w)
+    empty = (h == 0) | (w == 0)                  # an accepted rectangle with a side that rounded to 0 erases nothing
+    zero = np.zeros_like(h)
+    return (op, bin_, sign, np.where(empty, zero, top), np.where(empty, zero, left), np.where(empty, zero, h),
+            np.where(empty, zero, w))
+
+
+def _grey(img):
+    i = img.astype(np.int64)
+    return (19595 * i[0] + 38470 * i[1] + 7471 * i[2] + 32768) >> 16
+
+
+def _blend(deg, img, factor):
+    """Pillow's Image.blend(degenerate, image, factor) on 8-bit data: fp32 d + a * (x - d), a separate multiply and add,
+    then 0 at or below 0, 255 at or above 255, else truncated."""
+    a = np.float32(factor)
+    d, x = deg.astype(np.float32), img.astype(np.float32)
+    t = d + a * (x - d)
+    return np.where(t <= 0, 0, np.where(t >= 255, 255, np.trunc(t))).astype(np.uint8)
+
+
+def policy_reference(img_u8_chw, op, bin, sign):
+    """One TrivialAugmentWide operation on one uint8 ``[3,H,W]`` image (an array or a CPU tensor), restated with numpy from
+    Pillow's rules (include/nbdt_hip.h lists them); returns a uint8 array.  op: an index into POLICY_OPS or a name; bin:
+    0..30; sign: 0 or 1 (1: negative magnitude; ignored by the unsigned ops).  What nbdt_policy_batch computes between the
+    flip and the normalisation.  Test infrastructure and documentation: it must not be called on the training path."""
+    if isinstance(img_u8_chw, torch.Tensor):
+        img_u8_chw = img_u8_chw.cpu().numpy()
+    img = np.asarray(img_u8_chw)
+    if img.ndim != 3 or img.shape[0] != 3 or img.dtype != np.uint8:
+        raise ValueError(f"img must be uint8 [3,H,W], got {img.dtype} {img.shape}")
+    op = _OP[op] if isinstance(op, str) else int(op)
+    b, sg = int(bin), int(sign)
+    if not (0 <= op < len(POLICY_OPS) and 0 <= b < POLICY_BINS and sg in (0, 1)):
+        raise ValueError(f"need op in 0..{len(POLICY_OPS) - 1}, bin in 0..{POLICY_BINS - 1}, sign in {{0, 1}}; got "
+                         f"({op}, {b}, {sg})")
+    _, H, W = img.shape
+    row = policy_table(H, W)[op, b, sg].astype(np.int64)
+    name = POLICY_OPS[op]
+    if name == "Identity":
+        return img.copy()
+    if name in ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate"):
+        y, x = np.mgrid[0:H, 0:W].astype(np.int64)
+        sx = (row[2] + row[0] * x + row[1] * y) >> 16
+        sy = (row[5] + row[3] * x + row[4] * y) >> 16
+        inside = (sx >= 0) & (sx < W) & (sy >= 0) & (sy < H)
+        out = img[:, np.clip(sy, 0, H - 1), np.clip(sx, 0, W - 1)]
+        return np.where(inside[None], out, 0).astype(np.uint8)
+    if name in ("Brightness", "Color", "Contrast", "Sharpness"):
+        factor = np.array([row[0]], dtype=np.int32).view(np.float32)[0]
+        if name == "Brightness":
+            deg = np.zeros_like(img)
+        elif name == "Color":
+            deg = np.broadcast_to(_grey(img)[None], img.shape)
+        elif name == "Contrast":
+            g = _grey(img)
+            deg = np.full_like(img, int(float(g.sum()) / g.size + 0.5))
+        else:       # ImageFilter.SMOOTH: (1 1 1; 1 5 1; 1 1 1) / 13, the one-pixel border copied
+            i = img.astype(np.int64)
+            deg = i.copy()
+            if H >= 3 and W >= 3:
+                s = 4 * i[:, 1:-1, 1:-1]
+                for dy in (0, 1, 2):
+                    for dx in (0, 1, 2):
+                        s = s + i[:, dy:H - 2 + dy, dx:W - 2 + dx]
+                deg[:, 1:-1, 1:-1] = (2 * s + 13) // 26              # trunc(s / 13 + 0.5)
+        return _blend(deg, img, factor)
+    if name == "Posterize":
+        return img & np.uint8(row[0])
+    if name == "Solarize":
+        return np.where(img.astype(np.int64) < row[0], img, 255 - img).astype(np.uint8)
+    out = img.copy()
+    for c in range(3):
+        ch = img[c]
+        hist = np.bincount(ch.ravel(), minlength=256).astype(np.int64)
+        lo, hi = int(ch.min()), int(ch.max())
+        if hi <= lo:
+            continue
+        if name == "AutoContrast":
+            scale = 255.0 / (hi - lo)
+            offset = -lo * scale
+            lut = np.clip((np.arange(256, dtype=np.float64) * scale + offset).astype(np.int64), 0, 255)
+        else:       # Equalize
+            step = (int(hist.sum()) - int(hist[hi])) // 255
+            if step == 0:
+                continue
+            before = np.concatenate([[0], np.cumsum(hist)[:-1]])
+            lut = np.minimum(255, (step // 2 + before) // step)
+        out[c] = lut[ch].astype(np.uint8)
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -663,6 +663,29 @@ def augment_batch(src, labels_src, index, out, labels_out, pad, flip, mean=None,
         check(lib().nbdt_augment_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
 
 
+def policy_batch(src, labels_src, index, out, labels_out, pad, flip, mean, std, policy=False, policy_table=None,
+                 erase_prob=0.0, erase_scale=None, erase_ratio=None, ratio_table=None, seed=0, epoch=0, params_in=None,
+                 policy_in=None, params_out=None, policy_out=None, index_base=None):
+    """nbdt_policy_batch: augment_batch for a uint8 `src` of at most 49152 bytes per image, with one TrivialAugmentWide
+    operation per image between the flip and the normalisation (policy=True; policy_table: int32 [14,31,2,6], device) and
+    RandomErasing(value=0) after it (erase_prob; erase_scale / erase_ratio: two host floats each; ratio_table: fp64 [4096],
+    device).  policy_in / policy_out: int32 [B,7] (op, bin, sign, top, left, h, w), device; policy_in replaces the policy
+    and erase draw.  index_base: nbdt_policy_batch_sharded, as for augment_batch."""
+    N, _, H, W = src.shape
+    f3 = lambda v: None if v is None else (ctypes.c_float * 3)(*[float(a) for a in v])
+    d2 = lambda v: None if v is None else (ctypes.c_double * 2)(*[float(a) for a in v])
+    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
+    mask = (1 << 64) - 1
+    tail = (index.shape[0], N, H, W, int(pad), 1 if flip else 0, f3(mean), f3(std),
+            _C.NBDT_POLICY_TA_WIDE if policy else _C.NBDT_POLICY_NONE, ptr(policy_table), float(erase_prob), d2(erase_scale),
+            d2(erase_ratio), ptr(ratio_table), int(seed) & mask, int(epoch) & mask, ptr(params_in), ptr(policy_in), ptr(out),
+            ptr(labels_out), ptr(params_out), ptr(policy_out), stream_ptr(src.device))
+    if index_base is None:
+        check(lib().nbdt_policy_batch(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
+    else:
+        check(lib().nbdt_policy_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
+
+
 def mix_batch(x, y, out, tgt, lam=1.0, box=(0, 0, 0, 0), lam_t=1.0):
     """nbdt_mix_batch: MixUp / CutMix of the fp32 batch x [B,3,H,W] (labels y, int64 [B]) with itself rolled by one, into
     out [B,3,H,W] (not x) and the probability targets tgt [B,C] fp32.  MixUp: lam, an empty box, lam_t = lam.  CutMix:
