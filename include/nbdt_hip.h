@@ -744,6 +744,58 @@ int nbdt_ema_update_multi(const int64_t* table, int32_t n_rows, float one_minus_
 int nbdt_ema_swap(float* p, float* ema, void* p_bf16, int64_t n, void* stream);
 int nbdt_ema_swap_multi(const int64_t* table, int32_t n_rows, void* stream);
 
+/* ------------------------------------------------------------------ AdamW and RMSprop (nbdt_version() >= 120) */
+/* The adaptive optimizers over the flat fp32 arena nbdt_sgd_step takes, with a second state arena.  A plan holds the
+ * segment table LARS takes without its adapt column: n_seg rows (offset, length, weight_decay) over n elements, sorted by
+ * offset, disjoint, every offset a multiple of 4 elements, lengths arbitrary (>= 1).  nbdt_arena_opt_create checks the
+ * table (an empty, unsorted, overlapping, misaligned or out-of-range one is NBDT_EINVAL before any device call), cuts
+ * every segment into wave items of at most 512 elements, makes the gaps between segments and the tail items that only
+ * zero g, and copies the item table, once, to the CURRENT device.  A step is ONE launch on `stream`, one wave per item,
+ * 16-byte accesses with a scalar tail for length % 4, no atomics, no host synchronisation, nothing crosses a lane: it is
+ * bit-reproducible with nbdt_set_deterministic on or off, and its result does not depend on where the items are cut.
+ * Elements outside every segment are never written in p, the two state arenas or p_bf16; with zero_grad != 0 the whole of
+ * g[0, n) is zero afterwards, else g is untouched.  p, g and the state arenas: n fp32 elements each (the plan's n),
+ * 16-byte aligned; p_bf16: n bf16 elements, 8-byte aligned, or NULL.
+ *
+ * Every element update is the sequence of single IEEE fp32 operations below: each product, sum, difference, quotient and
+ * square root is rounded once, to nearest even, in the order the parentheses give; nothing is fused, divisions and
+ * square roots are correctly rounded.  fl(x) is x rounded to fp32.  The float arguments are fp32 values already; the
+ * derived host scalars are formed in double from them and rounded ONCE:
+ *   omb1 = fl(1 - (double)beta1), omb2 = fl(1 - (double)beta2), oma = fl(1 - (double)alpha),
+ *   ss = fl((double)lr / (1 - pow((double)beta1, (double)t))),  c2 = fl(sqrt(1 - pow((double)beta2, (double)t))).
+ * gs = grad_scale * g_i, wd the decay of the element's segment.
+ *
+ * nbdt_adamw_step -- torch.optim.AdamW (decoupled decay, no amsgrad), t >= 1 the number of this step:
+ *   k = 1 - (lr * wd)                          (per segment, two fp32 operations)
+ *   p1 = p * k
+ *   m = (beta1 * m) + (omb1 * gs)
+ *   v = (beta2 * v) + ((omb2 * gs) * gs)
+ *   d = (sqrt(v) / c2) + eps
+ *   p = p1 - (ss * (m / d));   p_bf16 = bf16(p)
+ * nbdt_rmsprop_step, tf == 0 -- torch.optim.RMSprop (not centered):
+ *   gs = gs + (wd * p)
+ *   sq = (alpha * sq) + ((oma * gs) * gs)
+ *   a = sqrt(sq) + eps
+ *   momentum > 0:   buf = (momentum * buf) + (gs / a);   p = p - (lr * buf)
+ *   momentum == 0:  p = p - (lr * (gs / a));  buf is neither read nor written and may be NULL
+ * nbdt_rmsprop_step, tf != 0 -- TensorFlow's RMSprop, the one EfficientNet was trained with (epsilon inside the root, the
+ * learning rate inside the momentum buffer; the caller starts sq at 1 inside the segments):
+ *   gs = gs + (wd * p)
+ *   sq = sq + (oma * ((gs * gs) - sq))
+ *   a = sqrt(sq + eps)
+ *   buf = (momentum * buf) + (lr * (gs / a));   p = p - buf
+ * Checked on the host before any device call, in this order (NBDT_EINVAL): t < 1; beta1, beta2, alpha or momentum outside
+ * [0, 1) or NaN; eps < 0 or NaN; lr or grad_scale not finite; a NULL plan; NULL or misaligned pointers; one buffer passed twice.  The plan's n
+ * is the length of every buffer: the caller checks it (ops.ArenaOptPlan does). */
+int nbdt_arena_opt_create(int64_t n, const int64_t* offsets, const int64_t* lengths, const float* weight_decays,
+                          int32_t n_seg, void** plan);
+int nbdt_arena_opt_destroy(void* plan);
+int64_t nbdt_arena_opt_n(void* plan);            /* the n the plan was made for (0 for a NULL plan) */
+int nbdt_adamw_step(void* plan, float* p, float* g, float* m, float* v, float lr, float beta1, float beta2, float eps,
+                    int64_t t, float grad_scale, void* p_bf16, int32_t zero_grad, void* stream);
+int nbdt_rmsprop_step(void* plan, float* p, float* g, float* sq, float* buf, float lr, float alpha, float eps,
+                      float momentum, int32_t tf, float grad_scale, void* p_bf16, int32_t zero_grad, void* stream);
+
 /* ------------------------------------------------------------------ device-resident datasets (nbdt_version() >= 110) */
 /* One launch builds a training batch from a dataset that lives in device memory: gather by index, then the reference's
  * RandomCrop(size, padding) -> RandomHorizontalFlip -> ToTensor -> Normalize (nbdt/data/cifar.py:11-21 pads CIFAR by 4,

@@ -67,6 +67,14 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   ``--lr-schedule cosine | poly`` decays it per step afterwards (Goyal et al. 2017; ``lr_at``): the large-batch recipe for a
   whole node, e.g. 8 ranks at ``--batch-size 4096``.  With the defaults (``sgd``, ``multistep``, no warm-up) the learning
   rate is the reference's MultiStepLR, evaluated once per epoch, and the step is the SGD step.
+* ``--optimizer adamw | rmsprop`` make the optimizer pass ``engine.adamw_step`` (``torch.optim.AdamW``: ``--adam-betas``,
+  ``--opt-eps``, ``--weight-decay`` decoupled) or ``engine.rmsprop_step`` (``torch.optim.RMSprop`` with the driver's momentum
+  0.9, ``--rmsprop-alpha``, ``--opt-eps``; ``--rmsprop-tf`` is TensorFlow's form with its defaults alpha 0.9 and eps 1e-3, the
+  one EfficientNet was trained with): one launch over the flat parameter arena and a second state arena
+  (``ParamStore.sq``), BatchNorm parameters and biases undecayed unless ``--opt-decay-1d``.  ``--lr-schedule exp``
+  multiplies the learning rate by ``--lr-decay-rate`` every ``--lr-decay-epochs`` epochs after the warm-up (0.97 every 2.4
+  epochs: the EfficientNet recipe, with ``--ema-decay 0.9999``).  The checkpoint's name gains ``-adamw`` / ``-rmsprop``;
+  like the reference's, a checkpoint holds no optimizer state.
 * ``--ema-decay D`` keeps an exponential moving average of the weights and the BatchNorm running statistics inside the
   engine (``engine.ema_enable`` / ``ema_update``: two launches after every ``--ema-steps``-th optimizer step, with the
   usual ``(1 + t) / (10 + t)`` warm-up of the decay unless ``--no-ema-warmup``).  Every evaluation still reports the live
@@ -180,14 +188,32 @@ def build_parser():
     p.add_argument("--deterministic", action="store_true",
                    help="bit-reproducible training steps, like the reference's CPU path: every cross-block reduction in "
                         "a fixed order instead of fp32 atomics (nbdt_set_deterministic; ResNet / WideResNet backbones)")
-    p.add_argument("--optimizer", choices=("sgd", "lars"), default="sgd",
-                   help="lars: layer-wise adaptive rate scaling (engine.lars_step) for large global batches")
+    p.add_argument("--optimizer", choices=("sgd", "lars", "adamw", "rmsprop"), default="sgd",
+                   help="lars: layer-wise adaptive rate scaling (engine.lars_step) for large global batches; adamw: "
+                        "torch.optim.AdamW (engine.adamw_step), for fine-tuning; rmsprop: torch.optim.RMSprop or, with "
+                        "--rmsprop-tf, TensorFlow's (engine.rmsprop_step), momentum 0.9")
+    p.add_argument("--adam-betas", type=float, nargs=2, default=(0.9, 0.999), metavar=("B1", "B2"),
+                   help="--optimizer adamw: decay rates of the two moment estimates")
+    p.add_argument("--opt-eps", type=float, default=None, metavar="EPS",
+                   help="--optimizer adamw | rmsprop: the denominator's epsilon (default 1e-8; 1e-3 with --rmsprop-tf)")
+    p.add_argument("--rmsprop-alpha", type=float, default=None, metavar="A",
+                   help="--optimizer rmsprop: decay of the mean square (default 0.99; 0.9 with --rmsprop-tf)")
+    p.add_argument("--rmsprop-tf", action="store_true",
+                   help="--optimizer rmsprop: TensorFlow's form (epsilon inside the root, the learning rate inside the "
+                        "momentum buffer, the mean square started at 1): the one EfficientNet was trained with")
+    p.add_argument("--opt-decay-1d", action="store_true",
+                   help="--optimizer adamw | rmsprop: decay BatchNorm parameters and biases too (default: no decay on them)")
     p.add_argument("--lars-trust", type=float, default=1e-3, help="--optimizer lars: trust coefficient")
     p.add_argument("--lars-eps", type=float, default=1e-8, help="--optimizer lars: added to the trust ratio's denominator")
     p.add_argument("--lars-adapt-1d", action="store_true",
                    help="--optimizer lars: adapt and decay BatchNorm parameters and biases too (default: plain SGD, no decay)")
-    p.add_argument("--lr-schedule", choices=("multistep", "cosine", "poly"), default="multistep",
-                   help="multistep: the reference's MultiStepLR per epoch; cosine / poly: per-step decay to 0 after warm-up")
+    p.add_argument("--lr-schedule", choices=("multistep", "cosine", "poly", "exp"), default="multistep",
+                   help="multistep: the reference's MultiStepLR per epoch; cosine / poly: per-step decay to 0 after warm-up; "
+                        "exp: times --lr-decay-rate every --lr-decay-epochs epochs after warm-up (the RMSprop recipe)")
+    p.add_argument("--lr-decay-rate", type=float, default=0.97, metavar="G",
+                   help="--lr-schedule exp: the factor of each decay, 0 < G <= 1")
+    p.add_argument("--lr-decay-epochs", type=float, default=2.4, metavar="E",
+                   help="--lr-schedule exp: epochs between two decays (may be fractional), > 0")
     p.add_argument("--warmup-epochs", type=float, default=0.0, metavar="W",
                    help="linear learning-rate warm-up over the first W epochs' steps (may be fractional)")
     p.add_argument("--ema-decay", type=float, default=None, metavar="D",
@@ -237,18 +263,24 @@ def multistep_lr(base_lr, epoch, epochs, gamma=0.1):
     return base_lr * gamma ** sum(epoch >= m for m in milestones)
 
 
-def lr_at(base_lr, step, steps_per_epoch, epochs, schedule="multistep", warmup_epochs=0.0):
+def lr_at(base_lr, step, steps_per_epoch, epochs, schedule="multistep", warmup_epochs=0.0, decay_rate=0.97,
+          decay_epochs=2.4):
     """Learning rate of global step `step` (0-based, `steps_per_epoch` per epoch).  T_w = round(W * steps_per_epoch)
     warm-up steps ramp linearly, base * (step + 1) / T_w (Goyal et al. 2017); then `multistep` is multistep_lr of the
     step's epoch, `cosine` is 0.5 * base * (1 + cos(pi * t)) and `poly` is base * (1 - t)^2 with
     t = (step - T_w) / (T - T_w), T = epochs * steps_per_epoch: both start at base on step T_w and would reach 0 on step
-    T, one past the last step a run takes."""
+    T, one past the last step a run takes.  `exp` is base * decay_rate^floor((step - T_w) / S) with
+    S = round(decay_epochs * steps_per_epoch) steps (at least 1): optim.lr_scheduler.StepLR(S, decay_rate) stepped once
+    per optimizer step, the staircase of the RMSprop recipes (0.97 every 2.4 epochs)."""
     t_w = int(round(warmup_epochs * steps_per_epoch))
     total = epochs * steps_per_epoch
     if step < t_w:
         return base_lr * (step + 1) / t_w
     if schedule == "multistep":
         return multistep_lr(base_lr, step // steps_per_epoch, epochs)
+    if schedule == "exp":
+        every = max(int(round(decay_epochs * steps_per_epoch)), 1)
+        return base_lr * decay_rate ** ((step - t_w) // every)
     t = (step - t_w) / float(max(total - t_w, 1))
     if schedule == "cosine":
         return 0.5 * base_lr * (1.0 + math.cos(math.pi * t))
@@ -447,6 +479,23 @@ def parse_args(argv=None):
         parser.error(f"--warmup-epochs must be in [0, --epochs], got {args.warmup_epochs}")
     if args.lars_trust <= 0 or args.lars_eps < 0:
         parser.error("--lars-trust must be > 0 and --lars-eps >= 0")
+    if args.rmsprop_tf and args.optimizer != "rmsprop":
+        parser.error("--rmsprop-tf belongs to --optimizer rmsprop")
+    if args.opt_eps is None:             # the defaults of torch.optim.AdamW / RMSprop, or of the TensorFlow recipe
+        args.opt_eps = 1e-3 if args.rmsprop_tf else 1e-8
+    if args.rmsprop_alpha is None:
+        args.rmsprop_alpha = 0.9 if args.rmsprop_tf else 0.99
+    args.adam_betas = tuple(args.adam_betas)
+    if not all(0.0 <= b < 1.0 for b in args.adam_betas):
+        parser.error(f"--adam-betas must be in [0, 1), got {args.adam_betas}")
+    if not 0.0 <= args.rmsprop_alpha < 1.0:
+        parser.error(f"--rmsprop-alpha must be in [0, 1), got {args.rmsprop_alpha}")
+    if not args.opt_eps >= 0.0 or math.isinf(args.opt_eps):
+        parser.error(f"--opt-eps must be finite and >= 0, got {args.opt_eps}")
+    if not 0.0 < args.lr_decay_rate <= 1.0:
+        parser.error(f"--lr-decay-rate must be in (0, 1], got {args.lr_decay_rate}")
+    if not 0.0 < args.lr_decay_epochs < math.inf:
+        parser.error(f"--lr-decay-epochs must be > 0, got {args.lr_decay_epochs}")
     if args.ema_decay is not None and not 0.0 < args.ema_decay < 1.0:
         parser.error(f"--ema-decay must be in (0, 1), got {args.ema_decay}")
     if args.ema_steps < 1:
@@ -532,8 +581,8 @@ def main(argv=None):
     ck_args = dict(vars(args))
     ck_args["path_graph"] = tree.path_graph
     checkpoint_fname = generate_checkpoint_fname(**ck_args)
-    if args.optimizer == "lars":
-        checkpoint_fname += "-lars"
+    if args.optimizer != "sgd":
+        checkpoint_fname += "-" + args.optimizer
     ema_on = args.ema_decay is not None
     if ema_on or args.use_ema:
         checkpoint_fname += "-ema"
@@ -582,6 +631,12 @@ def main(argv=None):
     if args.optimizer == "lars":
         from nbdt.engine import LarsConfig
         decay["lars"] = LarsConfig(args.lars_trust, args.lars_eps, not args.lars_adapt_1d)
+    elif args.optimizer == "adamw":
+        from nbdt.engine import AdamWConfig
+        decay["optim"] = AdamWConfig(args.adam_betas, args.opt_eps, not args.opt_decay_1d)
+    elif args.optimizer == "rmsprop":
+        from nbdt.engine import RMSpropConfig
+        decay["optim"] = RMSpropConfig(args.rmsprop_alpha, args.opt_eps, args.rmsprop_tf, not args.opt_decay_1d)
     per_step_lr = args.lr_schedule != "multistep" or args.warmup_epochs > 0
 
     @analyzer.train_function
@@ -596,8 +651,8 @@ def main(argv=None):
         steps = plan.shape[0]
         lrs = None
         if per_step_lr:          # warm-up / per-step decay: one learning rate per step of this epoch
-            lrs = [lr_at(args.lr, epoch * steps + i, steps, args.epochs, args.lr_schedule, args.warmup_epochs)
-                   for i in range(steps)]
+            lrs = [lr_at(args.lr, epoch * steps + i, steps, args.epochs, args.lr_schedule, args.warmup_epochs,
+                         args.lr_decay_rate, args.lr_decay_epochs) for i in range(steps)]
         if lrs and lrs[0] != lrs[-1]:
             log("\nEpoch: %d / LR: %.6f -> %.6f" % (epoch, lrs[0], lrs[-1]))
         else:

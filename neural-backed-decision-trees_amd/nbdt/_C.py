@@ -241,6 +241,14 @@ SIGNATURES = {
     "nbdt_ema_update_multi": (c_int, [_P, c_int32, c_float, _P]),
     "nbdt_ema_swap": (c_int, [_P, _P, _P, c_int64, _P]),
     "nbdt_ema_swap_multi": (c_int, [_P, c_int32, _P]),
+    "nbdt_arena_opt_create": (c_int, [c_int64, POINTER(c_int64), POINTER(c_int64), POINTER(c_float), c_int32,
+                                      POINTER(c_void_p)]),
+    "nbdt_arena_opt_destroy": (c_int, [c_void_p]),
+    "nbdt_arena_opt_n": (c_int64, [c_void_p]),
+    "nbdt_adamw_step": (c_int, [c_void_p, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_int64, c_float, _P,
+                                c_int32, _P]),
+    "nbdt_rmsprop_step": (c_int, [c_void_p, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_int32, c_float, _P,
+                                  c_int32, _P]),
 }
 
 

@@ -40,6 +40,8 @@ FLAGS = {
     "effnet.hip": ["-munsafe-fp-atomics"],
     # the two per-segment scalars (one sqrt, one division) are IEEE-correct, the element update is four separate roundings
     "lars.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # AdamW / RMSprop: every element update a fixed sequence of single IEEE operations, the division and the root included
+    "adaptive.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "ema.hip": ["-ffp-contract=off"],          # e + omd * (p - e): a subtract, a multiply and an add, never a fused multiply-add
 }
 

@@ -46,6 +46,12 @@ def _pad32(c):
 
 # train_step(..., lars=LarsConfig(...)): the optimizer pass is engine.lars_step instead of engine.sgd_step
 LarsConfig = collections.namedtuple("LarsConfig", ("trust", "eps", "exclude_1d"), defaults=(1e-3, 1e-8, True))
+# train_step(..., optim=AdamWConfig(...) | RMSpropConfig(...)): engine.adamw_step / engine.rmsprop_step; lr, weight_decay and
+# (RMSprop) momentum are train_step's own arguments.  RMSpropConfig(tf=True) is TensorFlow's form, with its defaults given
+# explicitly by the caller (alpha 0.9, eps 1e-3 in the EfficientNet recipe).
+AdamWConfig = collections.namedtuple("AdamWConfig", ("betas", "eps", "exclude_1d"), defaults=((0.9, 0.999), 1e-8, True))
+RMSpropConfig = collections.namedtuple("RMSpropConfig", ("alpha", "eps", "tf", "exclude_1d"),
+                                       defaults=(0.99, 1e-8, False, True))
 
 _EMA_SWAPPED = ("%s: the averaged weights are swapped in (ema_swap / ema_weights); stepping or averaging would train into "
                 "the average -- swap back first")
@@ -61,6 +67,7 @@ class ParamStore:
         self.n = 0
         self.flat = self.grad = self.mom = self.bf16 = None
         self.ema = None     # the moving average of flat (or, while _Engine.ema_swapped, the live weights): ema_enable
+        self.sq = None      # second optimizer state (AdamW's v, RMSprop's mean square): init_sq, at the first adaptive step
         self._views = {}    # (which buffer, name) -> (view, the buffer it was made of)
 
     def add(self, name, shape, init):
@@ -112,6 +119,17 @@ class ParamStore:
 
     def zero_grad(self):
         self.grad.zero_()            # one memset node
+
+    def init_sq(self, ones=False):
+        """(Re-)initialise the second state arena, allocating it at first use (SGD and LARS runs never pay for it): zeros, or
+        with `ones` 1 inside every segment (TensorFlow's RMSprop starts its mean square there) and 0 in the gaps."""
+        if self.sq is None:
+            self.sq = torch.zeros_like(self.flat)
+        else:
+            self.sq.zero_()
+        if ones:
+            for off, length, _, _ in self.segments(0.0):
+                self.sq[off:off + length].fill_(1.0)
 
     def segments(self, weight_decay, exclude_1d=True):
         """The segment table of a layer-wise optimizer (ops.LarsPlan): one row (offset, length, weight_decay, adapt) per
@@ -436,6 +454,9 @@ class _Engine:
         self._grad_is_zero = False   # the flat gradient buffer is known to be zero (sgd_step(zero_grad=True))
         self._lars_plans = {}     # (weight_decay, exclude_1d) -> ops.LarsPlan (lars_step)
         self._lars_last = None    # the plan of the last lars_step (last_trust_ratios)
+        self._opt_plans = {}      # (weight_decay, exclude_1d) -> ops.ArenaOptPlan (adamw_step, rmsprop_step)
+        self._opt_owner = None    # "adamw" | "rmsprop" | "rmsprop_tf": whose state store.mom and store.sq hold
+        self.opt_steps = 0        # adaptive steps since the state was (re-)initialised: AdamW's t
         self.ema_swapped = False  # ema_swap(): the arena holds the average, store.ema the live weights; no optimizer step then
         self.ema_updates = 0      # ema_update() calls since ema_enable (the t of ema_decay_at)
         self._ema_table = None    # ops.EmaTable over (running statistic, its shadow) of every BatchNorm
@@ -947,6 +968,62 @@ class _Engine:
         self._lars_last = plan
         self._grad_is_zero = bool(zero_grad)
         self.refresh_derived_weights()
+
+    def _adaptive_begin(self, owner, what, weight_decay, exclude_1d):
+        """What adamw_step and rmsprop_step share before their launch: the refusals, the second state arena at first use,
+        the step count, the plan."""
+        if self.ema_swapped:
+            raise RuntimeError(_EMA_SWAPPED % what)
+        if self._opt_owner not in (None, owner):
+            raise RuntimeError(f"{what}: store.mom and store.sq hold the state of {self._opt_owner}; call "
+                               "reset_optimizer_state() before changing the optimizer")
+        s = self.store
+        if self._opt_owner is None:
+            s.init_sq(ones=owner == "rmsprop_tf")
+            self._opt_owner = owner
+        self.join_side_stream()
+        self.opt_steps += 1
+        key = (float(weight_decay), bool(exclude_1d))
+        plan = self._opt_plans.get(key)
+        if plan is None:         # host table built and copied to the device once per (decay, rule)
+            plan = self._opt_plans[key] = ops.ArenaOptPlan(s.flat.numel(), s.segments(*key), device=self.device)
+        return plan
+
+    def adamw_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, zero_grad=False,
+                   exclude_1d=True):
+        """torch.optim.AdamW step over every parameter (decoupled decay per ParamStore entry, no amsgrad; nbdt_adamw_step)
+        + refresh of bf16 / dgrad weights.  One launch, no host synchronisation; zero_grad as in sgd_step.  m lives in
+        store.mom, v in store.sq (allocated at the first adaptive step); the bias corrections take opt_steps.
+        exclude_1d: BatchNorm parameters and biases are not decayed.  A step after sgd_step / lars_step on the same engine
+        wants reset_optimizer_state() first: store.mom then still holds their momentum."""
+        plan = self._adaptive_begin("adamw", "adamw_step", weight_decay, exclude_1d)
+        s = self.store
+        plan.adamw(s.flat, s.grad, s.mom, s.sq, lr, betas, eps, self.opt_steps, grad_scale, s.bf16, zero_grad=zero_grad)
+        self._grad_is_zero = bool(zero_grad)
+        self.refresh_derived_weights()
+
+    def rmsprop_step(self, lr, alpha=0.99, eps=1e-8, momentum=0.9, weight_decay=5e-4, tf=False, grad_scale=1.0,
+                     zero_grad=False, exclude_1d=True):
+        """torch.optim.RMSprop step (not centered; the decay enters the gradient) or, with tf, TensorFlow's -- eps inside
+        the root, lr inside the momentum buffer, the mean square started at 1: the form EfficientNet was trained with
+        (alpha 0.9, momentum 0.9, eps 1e-3) -- over every parameter (nbdt_rmsprop_step) + refresh of bf16 / dgrad weights.
+        One launch, no host synchronisation.  The buffer lives in store.mom, the mean square in store.sq."""
+        plan = self._adaptive_begin("rmsprop_tf" if tf else "rmsprop", "rmsprop_step", weight_decay, exclude_1d)
+        s = self.store
+        plan.rmsprop(s.flat, s.grad, s.sq, s.mom, lr, alpha, eps, momentum, tf, grad_scale, s.bf16, zero_grad=zero_grad)
+        self._grad_is_zero = bool(zero_grad)
+        self.refresh_derived_weights()
+
+    def reset_optimizer_state(self):
+        """Forget every optimizer's state: store.mom and store.sq (if it exists) zeroed, opt_steps = 0; the next adaptive
+        step owns the state and gives store.sq its own start (ones inside the segments for TensorFlow's RMSprop).
+        Required between two different adaptive optimizers on one engine."""
+        self.join_side_stream()
+        self.store.mom.zero_()
+        if self.store.sq is not None:
+            self.store.sq.zero_()
+        self._opt_owner = None
+        self.opt_steps = 0
 
     def last_trust_ratios(self):
         """ParamStore entry name -> trust ratio of the last lars_step (1 for entries it did not adapt).  Copies from the
@@ -1837,7 +1914,7 @@ class ImageNetBottleneckEngine(_TorchvisionFront, BottleneckEngine):
 
 
 def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5e-4, comm=None, fused_head=True,
-               zero_grad=True, lars=None):
+               zero_grad=True, lars=None, optim=None):
     """One full training step (main.py:233-239): zero_grad, forward, SoftTreeSupLoss fwd+bwd (one fused
     kernel -- with the classifier's forward and backward inside it when the criterion and the head's width allow,
     fused_head=False keeps linear -> loss -> linear-backward as three launches), backward, [gradient all-reduce],
@@ -1846,7 +1923,13 @@ def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5
     Floating-point targets are probability rows [B, C] (MixUp / CutMix, nbdt.data.mix_batch): they skip the fused head
     and go through criterion.soft_target_loss_and_grad, still one loss launch.
     lars: a LarsConfig (trust, eps, exclude_1d) makes the optimizer pass engine.lars_step; the 1 / world_size of a
-    data-parallel step enters its norms, so every rank computes the same trust ratios from the same reduced gradient."""
+    data-parallel step enters its norms, so every rank computes the same trust ratios from the same reduced gradient.
+    optim: an AdamWConfig or RMSpropConfig makes it engine.adamw_step / engine.rmsprop_step with this call's lr,
+    weight_decay and (RMSprop) momentum; not together with lars."""
+    if lars is not None and optim is not None:
+        raise ValueError("train_step: lars= and optim= both name the optimizer pass; pass one of them")
+    if optim is not None and not isinstance(optim, (AdamWConfig, RMSpropConfig)):
+        raise TypeError(f"train_step: optim must be an AdamWConfig or an RMSpropConfig, got {type(optim).__name__}")
     engine.zero_grad()
     names = getattr(engine, "classifier_names", None)
     if targets.is_floating_point():
@@ -1869,6 +1952,14 @@ def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5
     if lars is not None:
         engine.lars_step(lr, momentum, weight_decay, lars.trust, lars.eps, grad_scale=scale, zero_grad=zero_grad,
                          exclude_1d=lars.exclude_1d)
+        return loss
+    if isinstance(optim, AdamWConfig):
+        engine.adamw_step(lr, optim.betas, optim.eps, weight_decay, grad_scale=scale, zero_grad=zero_grad,
+                          exclude_1d=optim.exclude_1d)
+        return loss
+    if isinstance(optim, RMSpropConfig):
+        engine.rmsprop_step(lr, optim.alpha, optim.eps, momentum, weight_decay, optim.tf, grad_scale=scale,
+                            zero_grad=zero_grad, exclude_1d=optim.exclude_1d)
         return loss
     engine.sgd_step(lr, momentum, weight_decay, grad_scale=scale, zero_grad=zero_grad)
     return loss

@@ -846,6 +846,65 @@ class LarsPlan:
             pass
 
 
+ARENA_OPT_ITEM = 512      # elements one wave of csrc/adaptive.hip updates (kItem); a block is four waves
+
+
+class ArenaOptPlan:
+    """A plan of nbdt_adamw_step / nbdt_rmsprop_step: `segments` = rows (offset, length, weight_decay) over a flat arena of n
+    fp32 elements (sorted, disjoint, offsets multiples of 4; a fourth column, as ParamStore.segments has, is ignored).
+    The table is checked on the host first (a bad one raises without a GPU); a good one puts its wave-item table on
+    `device` once, here.  Every step is one launch on p's current stream, no host synchronisation."""
+
+    def __init__(self, n, segments, device=None):
+        rows = [(int(r[0]), int(r[1]), float(r[2])) for r in segments]
+        k = len(rows)
+        self.n, self.n_seg, self.segments = int(n), k, rows
+        self.device = torch.device(device) if device is not None else None
+        self.handle = ctypes.c_void_p()
+        offs = (ctypes.c_int64 * max(k, 1))(*[r[0] for r in rows])
+        lens = (ctypes.c_int64 * max(k, 1))(*[r[1] for r in rows])
+        wds = (ctypes.c_float * max(k, 1))(*[r[2] for r in rows])
+        if self.device is not None and self.device.type == "cuda":
+            with torch.cuda.device(self.device):
+                check(lib().nbdt_arena_opt_create(self.n, offs, lens, wds, k, ctypes.byref(self.handle)))
+        else:
+            check(lib().nbdt_arena_opt_create(self.n, offs, lens, wds, k, ctypes.byref(self.handle)))
+
+    def _check(self, what, p, fp32, p_bf16):
+        _C.require_gpu(p, what)
+        for t, name in fp32:
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or t.numel() != self.n or t.device != p.device or not t.is_contiguous():
+                raise _C.NBDTHipError(f"{what}: {name} must be a contiguous fp32 tensor of {self.n} elements on {p.device}")
+        if p_bf16 is not None and (p_bf16.dtype != torch.bfloat16 or p_bf16.numel() != self.n or p_bf16.device != p.device
+                                   or not p_bf16.is_contiguous()):
+            raise _C.NBDTHipError(f"{what}: the mirror must be a contiguous bf16 tensor of {self.n} elements on {p.device}")
+
+    def adamw(self, p, g, m, v, lr, betas, eps, t, grad_scale=1.0, p_bf16=None, zero_grad=False):
+        """torch.optim.AdamW's step number t >= 1 (the decay of each row decoupled, no amsgrad)."""
+        self._check("adamw_step", p, ((p, "p"), (g, "g"), (m, "m"), (v, "v")), p_bf16)
+        check(lib().nbdt_adamw_step(self.handle, ptr(p), ptr(g), ptr(m), ptr(v), lr, betas[0], betas[1], eps, int(t),
+                                    grad_scale, ptr(p_bf16), 1 if zero_grad else 0, stream_ptr(p.device)))
+
+    def rmsprop(self, p, g, sq, buf, lr, alpha, eps, momentum, tf=False, grad_scale=1.0, p_bf16=None, zero_grad=False):
+        """torch.optim.RMSprop's step (not centered), or with tf TensorFlow's: eps inside the root, lr inside the buffer, sq
+        started at 1 by the caller.  buf may be None for the torch form with momentum 0, which does not touch it."""
+        self._check("rmsprop_step", p, ((p, "p"), (g, "g"), (sq, "sq"), (buf, "buf")), p_bf16)
+        check(lib().nbdt_rmsprop_step(self.handle, ptr(p), ptr(g), ptr(sq), ptr(buf), lr, alpha, eps, momentum,
+                                      1 if tf else 0, grad_scale, ptr(p_bf16), 1 if zero_grad else 0,
+                                      stream_ptr(p.device)))
+
+    def __del__(self):
+        try:
+            h = getattr(self, "handle", None)
+            if h is not None and h.value:
+                lib().nbdt_arena_opt_destroy(h)
+                self.handle = None
+        except Exception:      # (interpreter shutdown: modules may already be gone)
+            pass
+
+
 def _ema_pair(p, ema, what):
     _C.require_gpu(p, what)
     for t, name in ((p, "p"), (ema, "ema")):
