@@ -796,6 +796,44 @@ int nbdt_adamw_step(void* plan, float* p, float* g, float* m, float* v, float lr
 int nbdt_rmsprop_step(void* plan, float* p, float* g, float* sq, float* buf, float lr, float alpha, float eps,
                       float momentum, int32_t tf, float grad_scale, void* p_bf16, int32_t zero_grad, void* stream);
 
+/* ------------------------------------------------------------------ gradient clipping (nbdt_version() >= 121) */
+/* Clipping by the global norm (torch.nn.utils.clip_grad_norm_, norm_type 2) over the flat fp32 gradient arena
+ * nbdt_sgd_step takes, without a host read-back.  A plan holds the arena length n, a workspace of fp64 partial sums and a
+ * 32-byte device record, on the CURRENT device.  Every operation below is ONE IEEE operation, rounded to nearest even.
+ *
+ * nbdt_clip_norm, two launches on `stream`:
+ *   S = sum_{i<n} (double)g[i] * (double)g[i] over the whole arena g[0, n), in fp64 (each product of two floats is exact
+ *   there).  The partition is fixed by n alone: B = min(2048, max(1, ceil(floor(n / 4) / 1024))) blocks of 256 threads,
+ *   block b owning the 16-byte groups [b c, min((b + 1) c, floor(n / 4))), c = ceil(floor(n / 4) / B); thread t adds the
+ *   groups t, t + 256, ... of its block's chunk into one fp64 accumulator per component (x, y, z, w), combines them as
+ *   (x + y) + (z + w), and in the last block the threads t < n % 4 add element 4 floor(n / 4) + t; waves fold with the xor
+ *   butterfly (offsets 32, 16, ..., 1), the four wave sums are added as ((w0 + w1) + w2) + w3, and one fp64 partial per
+ *   block goes to the workspace.  The second launch is ONE block: thread t adds partials t, t + 256, ... in increasing
+ *   index, then the same butterfly and wave-order sum.  No floating-point atomics, no last-block-done counter: the same g
+ *   gives the same bits on every run, with nbdt_set_deterministic on or off.  Padding inside arena entries and the
+ *   alignment gaps hold +0 in g (ParamStore.segments), so S is the sum over the logical parameters.  Then, in fp32,
+ *     s32 = (float)S;  r = sqrtf(s32);  norm = fabsf(grad_scale) * r;  den = norm + 1e-6f;  coef = max_norm / den
+ *   -- with grad_scale == 1, clip_grad_norm_'s coefficient -- and the record
+ *     { float norm; float coef; int32 clipped; int32 steps; int32 nonfinite; int32 total_clipped; 8 bytes reserved }
+ *   is updated by the one thread that writes it: steps += 1 on every call; norm not finite (inf or NaN): coef = 1,
+ *   clipped = 0, nonfinite += 1; else coef < 1: clipped = 1, total_clipped += 1; else coef = 1, clipped = 0.  A new plan's
+ *   record is {0, 1, 0, 0, 0, 0}.
+ * nbdt_clip_apply, one launch on `stream`, the partition above: every wave reads coef from the record; coef == 1.0f: it
+ *   returns before it touches g (an unclipped step costs one near-empty launch and no traffic); else g[i] = g[i] * coef,
+ *   one fp32 multiply per element, 16-byte accesses and the scalar tail.  Elements at and beyond n are never written.
+ * nbdt_clip_record: device pointer of the record, owned by the plan.  nbdt_clip_record_to_host: waits for `stream` (the
+ *   one the launches were issued on), then copies the 32 bytes to out32.  Synchronises the host: for logging and tests,
+ *   never on the step path.
+ * Checked on the host before any device call, in this order (NBDT_EINVAL): max_norm not finite or <= 0; grad_scale not
+ * finite; g NULL; g not 16-byte aligned; a NULL plan.  nbdt_clip_create: a NULL plan pointer, n <= 0.  g holds the plan's
+ * n elements: the caller checks it (ops.ClipPlan does). */
+int nbdt_clip_create(int64_t n, void** plan);
+int nbdt_clip_destroy(void* plan);
+int nbdt_clip_norm(void* plan, const float* g, float grad_scale, float max_norm, void* stream);
+int nbdt_clip_apply(void* plan, float* g, void* stream);
+const void* nbdt_clip_record(void* plan);
+int nbdt_clip_record_to_host(void* plan, void* out32, void* stream);
+
 /* ------------------------------------------------------------------ device-resident datasets (nbdt_version() >= 110) */
 /* One launch builds a training batch from a dataset that lives in device memory: gather by index, then the reference's
  * RandomCrop(size, padding) -> RandomHorizontalFlip -> ToTensor -> Normalize (nbdt/data/cifar.py:11-21 pads CIFAR by 4,

@@ -225,6 +225,13 @@ def build_parser():
                    help="--ema-decay: decay D from the first update on, instead of min(D, (1 + t) / (10 + t))")
     p.add_argument("--use-ema", action="store_true",
                    help="--eval --resume: evaluate the checkpoint's averaged weights (net_ema) instead of net")
+    p.add_argument("--accum-steps", type=int, default=1, metavar="K",
+                   help="gradient accumulation: every rank runs its share of --batch-size (still the GLOBAL batch of one "
+                        "optimizer step) as K micro-batches of batch / (ranks * K) images; one all-reduce and one "
+                        "optimizer step per K (train_step micro_batches=K)")
+    p.add_argument("--clip-grad-norm", type=float, default=None, metavar="M",
+                   help="clip the gradient's global L2 norm to M before every optimizer step, on the device "
+                        "(engine.clip_grad_norm; torchvision's --clip-grad-norm).  Default: off")
     return p
 
 
@@ -500,6 +507,10 @@ def parse_args(argv=None):
         parser.error(f"--ema-decay must be in (0, 1), got {args.ema_decay}")
     if args.ema_steps < 1:
         parser.error(f"--ema-steps must be >= 1, got {args.ema_steps}")
+    if args.accum_steps < 1:
+        parser.error(f"--accum-steps must be >= 1, got {args.accum_steps}")
+    if args.clip_grad_norm is not None and not 0.0 < args.clip_grad_norm < math.inf:
+        parser.error(f"--clip-grad-norm must be finite and > 0, got {args.clip_grad_norm}")
     if args.use_ema and not (args.eval and args.resume):
         parser.error("--use-ema evaluates a checkpoint's averaged weights: it needs --eval and --resume")
     if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
@@ -532,6 +543,9 @@ def main(argv=None):
         raise SystemExit("--pretrained downloads release checkpoints; load a local file with --resume --path-resume")
     if args.batch_size % world:
         raise SystemExit(f"--batch-size {args.batch_size} must be divisible by the number of ranks ({world})")
+    if args.batch_size % (world * args.accum_steps):
+        raise SystemExit(f"--batch-size {args.batch_size} must be divisible by ranks x --accum-steps "
+                         f"({world} x {args.accum_steps})")
 
     num_classes = DATASET_TO_NUM_CLASSES[args.dataset]
     log("==> Preparing data..")
@@ -583,6 +597,10 @@ def main(argv=None):
     checkpoint_fname = generate_checkpoint_fname(**ck_args)
     if args.optimizer != "sgd":
         checkpoint_fname += "-" + args.optimizer
+    if args.accum_steps > 1:
+        checkpoint_fname += f"-acc{args.accum_steps}"
+    if args.clip_grad_norm is not None:
+        checkpoint_fname += f"-clip{args.clip_grad_norm}"
     ema_on = args.ema_decay is not None
     if ema_on or args.use_ema:
         checkpoint_fname += "-ema"
@@ -637,6 +655,11 @@ def main(argv=None):
     elif args.optimizer == "rmsprop":
         from nbdt.engine import RMSpropConfig
         decay["optim"] = RMSpropConfig(args.rmsprop_alpha, args.opt_eps, args.rmsprop_tf, not args.opt_decay_1d)
+    if args.accum_steps > 1:          # the mixed batch of a rank is cut into micro-batches inside train_step
+        decay["micro_batches"] = args.accum_steps
+    if args.clip_grad_norm is not None:
+        from nbdt.engine import ClipConfig
+        decay["clip"] = ClipConfig(args.clip_grad_norm)
     per_step_lr = args.lr_schedule != "multistep" or args.warmup_epochs > 0
 
     @analyzer.train_function
@@ -674,6 +697,10 @@ def main(argv=None):
             if ema_on and (epoch * steps + i + 1) % args.ema_steps == 0:
                 engine.ema_update()          # two launches; every rank averages its own (bit-identical) replica
         log("Loss: %.3f (%d steps of %d x %d images)" % (total.item() / max(steps, 1), steps, world, per_rank))
+        if args.clip_grad_norm is not None and rank == 0 and steps:      # one read-back per epoch, none per step
+            c = engine.clip_stats()
+            log("Clip: last norm %.4g, clipped %d of %d steps (max norm %g), %d non-finite"
+                % (c["norm"], c["total_clipped"], c["steps"], args.clip_grad_norm, c["nonfinite"]))
 
     def test(epoch, checkpoint=True):
         nonlocal best_acc

@@ -249,6 +249,12 @@ SIGNATURES = {
                                 c_int32, _P]),
     "nbdt_rmsprop_step": (c_int, [c_void_p, _P, _P, _P, _P, c_float, c_float, c_float, c_float, c_int32, c_float, _P,
                                   c_int32, _P]),
+    "nbdt_clip_create": (c_int, [c_int64, POINTER(c_void_p)]),
+    "nbdt_clip_destroy": (c_int, [c_void_p]),
+    "nbdt_clip_norm": (c_int, [c_void_p, _P, c_float, c_float, _P]),
+    "nbdt_clip_apply": (c_int, [c_void_p, _P, _P]),
+    "nbdt_clip_record": (c_void_p, [c_void_p]),
+    "nbdt_clip_record_to_host": (c_int, [c_void_p, _P, _P]),
 }
 
 

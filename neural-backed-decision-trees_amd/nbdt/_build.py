@@ -42,6 +42,8 @@ FLAGS = {
     "lars.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # AdamW / RMSprop: every element update a fixed sequence of single IEEE operations, the division and the root included
     "adaptive.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # global-norm clipping: the five fp32 operations behind norm and coef are single IEEE operations, root and division included
+    "clip.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "ema.hip": ["-ffp-contract=off"],          # e + omd * (p - e): a subtract, a multiply and an add, never a fused multiply-add
 }
 

@@ -52,6 +52,8 @@ LarsConfig = collections.namedtuple("LarsConfig", ("trust", "eps", "exclude_1d")
 AdamWConfig = collections.namedtuple("AdamWConfig", ("betas", "eps", "exclude_1d"), defaults=((0.9, 0.999), 1e-8, True))
 RMSpropConfig = collections.namedtuple("RMSpropConfig", ("alpha", "eps", "tf", "exclude_1d"),
                                        defaults=(0.99, 1e-8, False, True))
+# train_step(..., clip=ClipConfig(max_norm)): engine.clip_grad_norm between the last backward and the optimizer pass
+ClipConfig = collections.namedtuple("ClipConfig", ("max_norm",))
 
 _EMA_SWAPPED = ("%s: the averaged weights are swapped in (ema_swap / ema_weights); stepping or averaging would train into "
                 "the average -- swap back first")
@@ -457,6 +459,7 @@ class _Engine:
         self._opt_plans = {}      # (weight_decay, exclude_1d) -> ops.ArenaOptPlan (adamw_step, rmsprop_step)
         self._opt_owner = None    # "adamw" | "rmsprop" | "rmsprop_tf": whose state store.mom and store.sq hold
         self.opt_steps = 0        # adaptive steps since the state was (re-)initialised: AdamW's t
+        self._clip_plan = None    # ops.ClipPlan over store.grad (clip_grad_norm), made at first use
         self.ema_swapped = False  # ema_swap(): the arena holds the average, store.ema the live weights; no optimizer step then
         self.ema_updates = 0      # ema_update() calls since ema_enable (the t of ema_decay_at)
         self._ema_table = None    # ops.EmaTable over (running statistic, its shadow) of every BatchNorm
@@ -1013,6 +1016,35 @@ class _Engine:
         plan.rmsprop(s.flat, s.grad, s.sq, s.mom, lr, alpha, eps, momentum, tf, grad_scale, s.bf16, zero_grad=zero_grad)
         self._grad_is_zero = bool(zero_grad)
         self.refresh_derived_weights()
+
+    def clip_grad_norm(self, max_norm, grad_scale=1.0):
+        """torch.nn.utils.clip_grad_norm_ over every parameter's gradient, on the device: the global norm of grad_scale *
+        store.grad (nbdt_clip_norm, two launches) and, only where it exceeds max_norm, one scaling pass over store.grad
+        (nbdt_clip_apply).  No host synchronisation: the coefficient stays in the plan's device record (clip_stats reads
+        it).  Runs between backward() and the optimizer step, which takes the same grad_scale."""
+        if not (math.isfinite(max_norm) and max_norm > 0.0):
+            raise ValueError(f"clip_grad_norm: max_norm must be finite and > 0, got {max_norm}")
+        self.join_side_stream()      # weight gradients still running on the second stream write store.grad
+        g = self.store.grad
+        if self._clip_plan is None:
+            self._clip_plan = ops.ClipPlan(g.numel(), device=self.device)
+        self._clip_plan.norm(g, grad_scale, max_norm)
+        self._clip_plan.apply(g)
+
+    def clip_stats(self):
+        """{norm, coef, clipped, steps, nonfinite, total_clipped} of the clip_grad_norm calls so far: the last call's norm
+        and coefficient, the counts over all of them.  Copies from the device and waits for it: for logging and tests."""
+        if self._clip_plan is None:
+            raise RuntimeError("clip_stats: no clip_grad_norm yet")
+        return self._clip_plan.to_host()
+
+    def calibrate_pending(self, comm):
+        """Run the CU-sharing calibration now if the next backward() would: a caller whose first backward must not reduce
+        gradients (train_step's leading micro-batches) still hands the calibration its communicator, so every rank adopts
+        rank 0's schedule."""
+        if self._cu_share is not None and not self._share_calibrated:
+            self.join_side_stream()
+            self.calibrate_cu_share(comm)
 
     def reset_optimizer_state(self):
         """Forget every optimizer's state: store.mom and store.sq (if it exists) zeroed, opt_steps = 0; the next adaptive
@@ -1913,8 +1945,38 @@ class ImageNetBottleneckEngine(_TorchvisionFront, BottleneckEngine):
     """torchvision's resnet50 / 101 / 152 (Bottleneck v1.5: the stride is on the 3x3 conv, as in BottleneckEngine)."""
 
 
+def _loss_backward(engine, criterion, img, targets, comm, fused_head, calibrate_with=None):
+    """forward, loss and backward of one (micro-)batch on the head path its targets and the criterion select; the
+    gradients are ADDED to store.grad, all-reduced if comm is given.  Returns the loss (device scalar).
+    calibrate_with: the communicator of a step whose backward HERE does not reduce (a leading micro-batch).  A pending
+    CU-sharing calibration broadcasts rank 0's decision, so it runs with that communicator, after the forward it needs
+    and before backward() would run it without one."""
+    names = getattr(engine, "classifier_names", None)
+    gpool = None
+    if targets.is_floating_point():
+        z = engine.forward(img, training=True)
+        loss, gz = criterion.soft_target_loss_and_grad(z, targets)
+    elif (fused_head and names is not None and hasattr(criterion, "can_fuse_head")
+            and criterion.can_fuse_head(engine.num_classes)):
+        # classifier + rules + loss + their backward in ONE launch (nbdt_head_soft_tree_loss): logits stay on chip
+        pooled = engine.forward(img, training=True, head=False)
+        st = engine.store
+        loss, gpool, _ = criterion.head_loss_and_grad(pooled, st.p(names[0]), st.p(names[1]), targets,
+                                                      grad_weight=st.g(names[0]), grad_bias=st.g(names[1]))
+    else:
+        z = engine.forward(img, training=True)
+        loss, gz = criterion.loss_and_grad(z, targets)
+    if calibrate_with is not None and comm is None:
+        engine.calibrate_pending(calibrate_with)
+    if gpool is not None:
+        engine.backward(None, comm=comm, gpooled=gpool)
+    else:
+        engine.backward(gz, comm=comm)
+    return loss
+
+
 def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5e-4, comm=None, fused_head=True,
-               zero_grad=True, lars=None, optim=None):
+               zero_grad=True, lars=None, optim=None, clip=None, micro_batches=1):
     """One full training step (main.py:233-239): zero_grad, forward, SoftTreeSupLoss fwd+bwd (one fused
     kernel -- with the classifier's forward and backward inside it when the criterion and the head's width allow,
     fused_head=False keeps linear -> loss -> linear-backward as three launches), backward, [gradient all-reduce],
@@ -1925,30 +1987,40 @@ def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5
     lars: a LarsConfig (trust, eps, exclude_1d) makes the optimizer pass engine.lars_step; the 1 / world_size of a
     data-parallel step enters its norms, so every rank computes the same trust ratios from the same reduced gradient.
     optim: an AdamWConfig or RMSpropConfig makes it engine.adamw_step / engine.rmsprop_step with this call's lr,
-    weight_decay and (RMSprop) momentum; not together with lars."""
+    weight_decay and (RMSprop) momentum; not together with lars.
+    micro_batches=K > 1: gradient accumulation.  img / targets are cut into K equal chunks along dim 0 (B % K != 0
+    raises); the gradient buffer is zeroed once, every chunk runs forward + loss + backward into it -- each with its own
+    BatchNorm statistics and its own update of the running ones, as K PyTorch forward passes would -- only the last
+    chunk's backward all-reduces, and the optimizer takes grad_scale = 1 / (K * world_size): the step of the mean loss
+    over all K chunks.  Returns the mean of the chunk losses.
+    clip: a ClipConfig(max_norm) runs engine.clip_grad_norm(max_norm, grad_scale) on the complete (accumulated, reduced)
+    gradient before the optimizer pass, whichever it is.  With the defaults of both the launches are what they were."""
     if lars is not None and optim is not None:
         raise ValueError("train_step: lars= and optim= both name the optimizer pass; pass one of them")
     if optim is not None and not isinstance(optim, (AdamWConfig, RMSpropConfig)):
         raise TypeError(f"train_step: optim must be an AdamWConfig or an RMSpropConfig, got {type(optim).__name__}")
+    if clip is not None and not isinstance(clip, ClipConfig):
+        raise TypeError(f"train_step: clip must be a ClipConfig, got {type(clip).__name__}")
+    K = int(micro_batches)
+    if K != micro_batches or K < 1:
+        raise ValueError(f"train_step: micro_batches must be an integer >= 1, got {micro_batches!r}")
+    if img.shape[0] % K or targets.shape[0] != img.shape[0]:
+        raise ValueError(f"train_step: a batch of {img.shape[0]} images ({targets.shape[0]} targets) does not split into "
+                         f"{K} equal micro-batches")
     engine.zero_grad()
-    names = getattr(engine, "classifier_names", None)
-    if targets.is_floating_point():
-        z = engine.forward(img, training=True)
-        loss, gz = criterion.soft_target_loss_and_grad(z, targets)
-        engine.backward(gz, comm=comm)
-    elif (fused_head and names is not None and hasattr(criterion, "can_fuse_head")
-            and criterion.can_fuse_head(engine.num_classes)):
-        # classifier + rules + loss + their backward in ONE launch (nbdt_head_soft_tree_loss): logits stay on chip
-        pooled = engine.forward(img, training=True, head=False)
-        st = engine.store
-        loss, gpool, _ = criterion.head_loss_and_grad(pooled, st.p(names[0]), st.p(names[1]), targets,
-                                                      grad_weight=st.g(names[0]), grad_bias=st.g(names[1]))
-        engine.backward(None, comm=comm, gpooled=gpool)
+    if K == 1:
+        loss = _loss_backward(engine, criterion, img, targets, comm, fused_head)
     else:
-        z = engine.forward(img, training=True)
-        loss, gz = criterion.loss_and_grad(z, targets)
-        engine.backward(gz, comm=comm)
-    scale = 1.0 / comm.world_size if comm is not None else 1.0
+        # (chunks along dim 0 of contiguous tensors are contiguous views: nothing is copied)
+        total = None
+        for k, (x, y) in enumerate(zip(img.chunk(K), targets.chunk(K))):
+            last = k == K - 1
+            loss_k = _loss_backward(engine, criterion, x, y, comm if last else None, fused_head, calibrate_with=comm)
+            total = loss_k.clone() if total is None else total.add_(loss_k)
+        loss = total.div_(K)
+    scale = 1.0 / (K * (comm.world_size if comm is not None else 1))
+    if clip is not None:
+        engine.clip_grad_norm(clip.max_norm, grad_scale=scale)
     if lars is not None:
         engine.lars_step(lr, momentum, weight_decay, lars.trust, lars.eps, grad_scale=scale, zero_grad=zero_grad,
                          exclude_1d=lars.exclude_1d)

@@ -905,6 +905,70 @@ class ArenaOptPlan:
             pass
 
 
+class ClipRecord(ctypes.Structure):      # nbdt_clip_*'s 32-byte record
+    _fields_ = [("norm", ctypes.c_float), ("coef", ctypes.c_float), ("clipped", ctypes.c_int32), ("steps", ctypes.c_int32),
+                ("nonfinite", ctypes.c_int32), ("total_clipped", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
+
+
+class ClipPlan:
+    """A plan of nbdt_clip_*: global-norm clipping of a flat fp32 gradient arena of n elements on `device`, which gets the
+    fp64 partials and the 32-byte record once, here.  norm() is two launches and apply() one on g's current stream, no
+    host synchronisation; to_host() is the one place that waits."""
+
+    def __init__(self, n, device=None):
+        self.n = int(n)
+        self.device = torch.device(device) if device is not None else None
+        self.handle = ctypes.c_void_p()
+        if self.device is not None and self.device.type == "cuda":
+            with torch.cuda.device(self.device):
+                check(lib().nbdt_clip_create(self.n, ctypes.byref(self.handle)))
+        else:
+            check(lib().nbdt_clip_create(self.n, ctypes.byref(self.handle)))
+
+    def _check(self, what, g):
+        _C.require_gpu(g, what)
+        if g.dtype != torch.float32 or g.numel() != self.n or not g.is_contiguous():
+            raise _C.NBDTHipError(f"{what}: g must be a contiguous fp32 tensor of {self.n} elements, got {g.dtype} x {g.numel()}")
+        if self.device is not None and g.device != self.device:
+            raise _C.NBDTHipError(f"{what}: g is on {g.device}, the plan on {self.device}")
+
+    def norm(self, g, grad_scale, max_norm):
+        """The record after this call holds norm = |grad_scale| * ||g||_2 and coef = min(1, max_norm / (norm + 1e-6))."""
+        self._check("clip_norm", g)
+        check(lib().nbdt_clip_norm(self.handle, ptr(g), grad_scale, max_norm, stream_ptr(g.device)))
+
+    def apply(self, g):
+        """g *= coef of the record when that is below 1; nothing is read or written otherwise."""
+        self._check("clip_apply", g)
+        check(lib().nbdt_clip_apply(self.handle, ptr(g), stream_ptr(g.device)))
+
+    def record(self):
+        """The device record as an int32[8] tensor view (norm and coef are its first two words, as fp32 bits); owned by the
+        plan, valid while it lives.  Reading it in a kernel on the issuing stream costs no synchronisation."""
+        addr = lib().nbdt_clip_record(self.handle)
+        if not addr:
+            raise _C.NBDTHipError("clip_record: no plan")
+        iface = {"shape": (8,), "typestr": "<i4", "data": (int(addr), False), "version": 2, "strides": None}
+        holder = type("_ClipRecordView", (), {"__cuda_array_interface__": iface})()
+        return torch.as_tensor(holder, device=self.device)
+
+    def to_host(self):
+        """{norm, coef, clipped, steps, nonfinite, total_clipped} as the last norm() left them.  Synchronises."""
+        out = ClipRecord()
+        with torch.cuda.device(self.device):
+            check(lib().nbdt_clip_record_to_host(self.handle, ctypes.byref(out), stream_ptr(self.device)))
+        return {k: getattr(out, k) for k, _ in ClipRecord._fields_[:6]}
+
+    def __del__(self):
+        try:
+            h = getattr(self, "handle", None)
+            if h is not None and h.value:
+                lib().nbdt_clip_destroy(h)
+                self.handle = None
+        except Exception:      # (interpreter shutdown: modules may already be gone)
+            pass
+
+
 def _ema_pair(p, ema, what):
     _C.require_gpu(p, what)
     for t, name in ((p, "p"), (ema, "ema")):
