@@ -20,7 +20,7 @@
 // Which thread sums what, in which order, is fixed by n alone: the same g gives the same record bits on every run, with
 // nbdt_set_deterministic on or off.  The fp64 work of launch 1 is one convert and one fused multiply-add per element
 // beside a 4-byte read; whether that or the bytes bound the pass is a measurement.
-#include "common.h"
+#include "arena.h"
 
 #include <math.h>
 
@@ -38,10 +38,9 @@ struct ClipRecord {                  // include/nbdt_hip.h: 32 bytes
 };
 static_assert(sizeof(ClipRecord) == 32, "the clip record is 32 bytes by ABI");
 
-struct ClipPlan {
-  long long n = 0;
-  int blocks = 0, device = 0;
-  void* blob = nullptr;              // one allocation: the record, then the partials
+struct ClipPlan : ArenaPlan {        // the blob: the record, then the partials
+  using ArenaPlan::ArenaPlan;
+  int blocks = 0;
   ClipRecord* rec = nullptr;
   double* part = nullptr;
 };
@@ -55,12 +54,6 @@ inline int clip_blocks(long long n) {
   return (int)b;
 }
 inline long long clip_chunk(long long n, int blocks) { return ((n >> 2) + blocks - 1) / blocks; }
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // the block's sum in thread 0: butterfly per wave, then wave 0 + wave 1 + wave 2 + wave 3 in that order
 __device__ __forceinline__ double block_sum(double v, double* lds) {
@@ -153,7 +146,7 @@ int clip_check(void* plan, const float* g) {
   NBDT_REQUIRE(plan, "null plan");
   int dev = 0;
   NBDT_HIP_CHECK(hipGetDevice(&dev));
-  NBDT_REQUIRE(dev == ((ClipPlan*)plan)->device, "the plan's workspace lives on another device");
+  NBDT_REQUIRE(dev == ((ClipPlan*)plan)->blob.device, "the plan's workspace lives on another device");
   return NBDT_OK;
 }
 
@@ -167,29 +160,16 @@ extern "C" int nbdt_clip_create(int64_t n, void** plan) {
   NBDT_REQUIRE(plan, "null plan pointer");
   *plan = nullptr;
   NBDT_REQUIRE(n > 0, "empty arena");
-  ClipPlan* P = new ClipPlan();
-  P->n = n;
+  ClipPlan* P = new ClipPlan(n, sizeof(ClipRecord) + (size_t)nbdt::kMaxBlocks * sizeof(double));
   P->blocks = nbdt::clip_blocks(n);
   const ClipRecord start = {0.f, 1.f, 0, 0, 0, 0, {0, 0}};   // read before the first step: nothing clipped
-  hipError_t e = hipGetDevice(&P->device);
-  if (e == hipSuccess) e = hipMalloc(&P->blob, sizeof(ClipRecord) + (size_t)nbdt::kMaxBlocks * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpy(P->blob, &start, sizeof(start), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    if (P->blob) (void)hipFree(P->blob);
-    delete P;
-    return nbdt::fail(NBDT_EHIP, "%s: %s", "nbdt_clip_create: device workspace", hipGetErrorString(e));
-  }
-  P->rec = (ClipRecord*)P->blob;
-  P->part = (double*)((char*)P->blob + sizeof(ClipRecord));
-  *plan = P;
-  return NBDT_OK;
+  P->rec = (ClipRecord*)P->blob.put(0, &start, sizeof(start));
+  P->part = (double*)(P->blob.base + sizeof(ClipRecord));
+  return nbdt::finish_plan(P, "nbdt_clip_create: device workspace", plan);
 }
 
 extern "C" int nbdt_clip_destroy(void* plan) {
-  if (!plan) return NBDT_OK;
-  ClipPlan* P = (ClipPlan*)plan;
-  if (P->blob) (void)hipFree(P->blob);
-  delete P;
+  delete (ClipPlan*)plan;
   return NBDT_OK;
 }
 

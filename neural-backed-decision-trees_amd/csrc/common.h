@@ -114,6 +114,21 @@ __device__ __forceinline__ unsigned pack_bf16x2(float lo, float hi) {
   asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
   return r;
 }
+// four fp32 -> the 8 bytes of four bf16 (what the arena passes store to the mirror per 16 bytes of p)
+__device__ __forceinline__ uint2 bf16x4_of(const float4 v) {
+  uint2 o;
+  o.x = pack_bf16x2(v.x, v.y);
+  o.y = pack_bf16x2(v.z, v.w);
+  return o;
+}
+
+// the wave's sum in every lane (float or double): the xor butterfly from 32 down to 1, a fixed order
+template <class T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
 
 // exact n / d for 0 <= n < 2^31 with one mul-hi and one shift (host builds, device divides)
 struct FastDiv {

@@ -30,13 +30,6 @@ __device__ __forceinline__ float4 ema_of(const float4 p, const float4 e, const f
   return o;
 }
 
-__device__ __forceinline__ uint2 bf16x4_of(const float4 v) {
-  uint2 o;
-  o.x = pack_bf16x2(v.x, v.y);
-  o.y = pack_bf16x2(v.z, v.w);
-  return o;
-}
-
 __global__ __launch_bounds__(256) void ema_update_kernel(const float4* __restrict__ p, float4* __restrict__ e,
                                                          long long n4, float omd) {
   const long long base = (long long)blockIdx.x * kChunk + threadIdx.x;

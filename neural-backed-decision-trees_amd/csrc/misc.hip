@@ -586,12 +586,7 @@ __global__ __launch_bounds__(256) void sgd_kernel(float* __restrict__ p, float* 
     ((float4*)buf)[i] = bv;
     ((float4*)p)[i] = pv;
     if (zero_g) ((float4*)g)[i] = float4{0.f, 0.f, 0.f, 0.f};
-    if (pb) {
-      uint2 o;
-      o.x = pack_bf16x2(pv.x, pv.y);
-      o.y = pack_bf16x2(pv.z, pv.w);
-      ((uint2*)pb)[i] = o;
-    }
+    if (pb) ((uint2*)pb)[i] = bf16x4_of(pv);
   }
   // tail (n % 4)
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {

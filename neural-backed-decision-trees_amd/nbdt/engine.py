@@ -454,9 +454,8 @@ class _Engine:
         self._partials = None     # conv-epilogue BatchNorm partial sums (partials)
         self._reserved_now = 0    # CUs the MFMA launches currently leave to in-flight all-reduces (_reserve_for)
         self._grad_is_zero = False   # the flat gradient buffer is known to be zero (sgd_step(zero_grad=True))
-        self._lars_plans = {}     # (weight_decay, exclude_1d) -> ops.LarsPlan (lars_step)
+        self._plans = {}          # (ops.LarsPlan | ops.ArenaOptPlan, weight_decay, exclude_1d) -> that plan (optimizer_step)
         self._lars_last = None    # the plan of the last lars_step (last_trust_ratios)
-        self._opt_plans = {}      # (weight_decay, exclude_1d) -> ops.ArenaOptPlan (adamw_step, rmsprop_step)
         self._opt_owner = None    # "adamw" | "rmsprop" | "rmsprop_tf": whose state store.mom and store.sq hold
         self.opt_steps = 0        # adaptive steps since the state was (re-)initialised: AdamW's t
         self._clip_plan = None    # ops.ClipPlan over store.grad (clip_grad_norm), made at first use
@@ -936,86 +935,74 @@ class _Engine:
                 ops.weight_tile_batched(self._wd_flat, self._wt_dtable, self._wt_n, self._wt_dtotal, self._wt_dgrad)
             self._retile_seg(True)
 
-    def sgd_step(self, lr, momentum=0.9, weight_decay=5e-4, grad_scale=1.0, zero_grad=False):
-        """optim.SGD step over every parameter (main.py:207) + refresh of bf16 / dgrad weights.
-        zero_grad: the same pass leaves the gradient buffer zeroed, and the next zero_grad() is then free (the separate
-        146 MB fill took 108 us per WRN-28-10 step; train_step asks for it)."""
+    def optimizer_step(self, lr, momentum, weight_decay, config=None, grad_scale=1.0, zero_grad=False):
+        """The optimizer pass over every parameter + refresh of bf16 / dgrad weights: what sgd_step (config None),
+        lars_step (a LarsConfig), adamw_step (an AdamWConfig) and rmsprop_step (an RMSpropConfig) wrap and train_step
+        calls.  No host synchronisation.  zero_grad: the same pass leaves the gradient buffer zeroed, and the next
+        zero_grad() is then free (the separate 146 MB fill took 108 us per WRN-28-10 step; train_step asks for it)."""
+        adaptive = isinstance(config, (AdamWConfig, RMSpropConfig))
+        what = ("sgd_step" if config is None else "adamw_step" if isinstance(config, AdamWConfig) else
+                "rmsprop_step" if adaptive else "lars_step")
         if self.ema_swapped:
-            raise RuntimeError(_EMA_SWAPPED % "sgd_step")
-        self.join_side_stream()
+            raise RuntimeError(_EMA_SWAPPED % what)
         s = self.store
-        ops.sgd_step(s.flat, s.grad, s.mom, lr, momentum, weight_decay, grad_scale, s.bf16, zero_grad=zero_grad)
+        if adaptive:
+            owner = "adamw" if what == "adamw_step" else "rmsprop_tf" if config.tf else "rmsprop"
+            if self._opt_owner not in (None, owner):
+                raise RuntimeError(f"{what}: store.mom and store.sq hold the state of {self._opt_owner}; call "
+                                   "reset_optimizer_state() before changing the optimizer")
+            if self._opt_owner is None:      # the second state arena at first use
+                s.init_sq(ones=owner == "rmsprop_tf")
+                self._opt_owner = owner
+        self.join_side_stream()
+        if config is None:
+            ops.sgd_step(s.flat, s.grad, s.mom, lr, momentum, weight_decay, grad_scale, s.bf16, zero_grad=zero_grad)
+        else:
+            cls, wd, rule = ops.ArenaOptPlan if adaptive else ops.LarsPlan, float(weight_decay), bool(config.exclude_1d)
+            plan = self._plans.get((cls, wd, rule))
+            if plan is None:         # host tables built and copied to the device once per (pass, decay, rule)
+                plan = self._plans[cls, wd, rule] = cls(s.flat.numel(), s.segments(wd, rule), device=self.device)
+            if not adaptive:
+                plan.step(s.flat, s.grad, s.mom, lr, momentum, config.trust, config.eps, grad_scale, s.bf16,
+                          zero_grad=zero_grad)
+                self._lars_last = plan
+            else:
+                self.opt_steps += 1
+                if what == "adamw_step":
+                    plan.adamw(s.flat, s.grad, s.mom, s.sq, lr, config.betas, config.eps, self.opt_steps, grad_scale,
+                               s.bf16, zero_grad=zero_grad)
+                else:
+                    plan.rmsprop(s.flat, s.grad, s.sq, s.mom, lr, config.alpha, config.eps, momentum, config.tf,
+                                 grad_scale, s.bf16, zero_grad=zero_grad)
         self._grad_is_zero = bool(zero_grad)
         self.refresh_derived_weights()
 
-    def _lars_plan(self, weight_decay, exclude_1d):
-        key = (float(weight_decay), bool(exclude_1d))
-        plan = self._lars_plans.get(key)
-        if plan is None:         # host tables built and copied to the device once per (decay, rule)
-            s = self.store
-            plan = self._lars_plans[key] = ops.LarsPlan(s.flat.numel(), s.segments(*key), device=self.device)
-        return plan
+    def sgd_step(self, lr, momentum=0.9, weight_decay=5e-4, grad_scale=1.0, zero_grad=False):
+        """optim.SGD step over every parameter (main.py:207); zero_grad as in optimizer_step."""
+        self.optimizer_step(lr, momentum, weight_decay, None, grad_scale, zero_grad)
 
     def lars_step(self, lr, momentum=0.9, weight_decay=5e-4, trust=1e-3, eps=1e-8, grad_scale=1.0, zero_grad=False,
                   exclude_1d=True):
         """LARS step over every parameter (You et al. 2017: SGD with momentum on ratio * (g + wd * p), the ratio per
-        ParamStore entry; nbdt_lars_step) + refresh of bf16 / dgrad weights.  Three launches whatever the number of
-        parameters, no host synchronisation; zero_grad as in sgd_step.  exclude_1d: BatchNorm parameters and biases take
-        plain SGD steps without decay."""
-        if self.ema_swapped:
-            raise RuntimeError(_EMA_SWAPPED % "lars_step")
-        self.join_side_stream()
-        s = self.store
-        plan = self._lars_plan(weight_decay, exclude_1d)
-        plan.step(s.flat, s.grad, s.mom, lr, momentum, trust, eps, grad_scale, s.bf16, zero_grad=zero_grad)
-        self._lars_last = plan
-        self._grad_is_zero = bool(zero_grad)
-        self.refresh_derived_weights()
-
-    def _adaptive_begin(self, owner, what, weight_decay, exclude_1d):
-        """What adamw_step and rmsprop_step share before their launch: the refusals, the second state arena at first use,
-        the step count, the plan."""
-        if self.ema_swapped:
-            raise RuntimeError(_EMA_SWAPPED % what)
-        if self._opt_owner not in (None, owner):
-            raise RuntimeError(f"{what}: store.mom and store.sq hold the state of {self._opt_owner}; call "
-                               "reset_optimizer_state() before changing the optimizer")
-        s = self.store
-        if self._opt_owner is None:
-            s.init_sq(ones=owner == "rmsprop_tf")
-            self._opt_owner = owner
-        self.join_side_stream()
-        self.opt_steps += 1
-        key = (float(weight_decay), bool(exclude_1d))
-        plan = self._opt_plans.get(key)
-        if plan is None:         # host table built and copied to the device once per (decay, rule)
-            plan = self._opt_plans[key] = ops.ArenaOptPlan(s.flat.numel(), s.segments(*key), device=self.device)
-        return plan
+        ParamStore entry; nbdt_lars_step).  Three launches whatever the number of parameters.  exclude_1d: BatchNorm
+        parameters and biases take plain SGD steps without decay."""
+        self.optimizer_step(lr, momentum, weight_decay, LarsConfig(trust, eps, exclude_1d), grad_scale, zero_grad)
 
     def adamw_step(self, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, grad_scale=1.0, zero_grad=False,
                    exclude_1d=True):
-        """torch.optim.AdamW step over every parameter (decoupled decay per ParamStore entry, no amsgrad; nbdt_adamw_step)
-        + refresh of bf16 / dgrad weights.  One launch, no host synchronisation; zero_grad as in sgd_step.  m lives in
-        store.mom, v in store.sq (allocated at the first adaptive step); the bias corrections take opt_steps.
-        exclude_1d: BatchNorm parameters and biases are not decayed.  A step after sgd_step / lars_step on the same engine
-        wants reset_optimizer_state() first: store.mom then still holds their momentum."""
-        plan = self._adaptive_begin("adamw", "adamw_step", weight_decay, exclude_1d)
-        s = self.store
-        plan.adamw(s.flat, s.grad, s.mom, s.sq, lr, betas, eps, self.opt_steps, grad_scale, s.bf16, zero_grad=zero_grad)
-        self._grad_is_zero = bool(zero_grad)
-        self.refresh_derived_weights()
+        """torch.optim.AdamW step over every parameter (decoupled decay per ParamStore entry, no amsgrad; nbdt_adamw_step).
+        One launch.  m lives in store.mom, v in store.sq (allocated at the first adaptive step); the bias corrections
+        take opt_steps.  exclude_1d: BatchNorm parameters and biases are not decayed.  A step after sgd_step / lars_step
+        on the same engine wants reset_optimizer_state() first: store.mom then still holds their momentum."""
+        self.optimizer_step(lr, None, weight_decay, AdamWConfig(betas, eps, exclude_1d), grad_scale, zero_grad)
 
     def rmsprop_step(self, lr, alpha=0.99, eps=1e-8, momentum=0.9, weight_decay=5e-4, tf=False, grad_scale=1.0,
                      zero_grad=False, exclude_1d=True):
         """torch.optim.RMSprop step (not centered; the decay enters the gradient) or, with tf, TensorFlow's -- eps inside
         the root, lr inside the momentum buffer, the mean square started at 1: the form EfficientNet was trained with
-        (alpha 0.9, momentum 0.9, eps 1e-3) -- over every parameter (nbdt_rmsprop_step) + refresh of bf16 / dgrad weights.
-        One launch, no host synchronisation.  The buffer lives in store.mom, the mean square in store.sq."""
-        plan = self._adaptive_begin("rmsprop_tf" if tf else "rmsprop", "rmsprop_step", weight_decay, exclude_1d)
-        s = self.store
-        plan.rmsprop(s.flat, s.grad, s.sq, s.mom, lr, alpha, eps, momentum, tf, grad_scale, s.bf16, zero_grad=zero_grad)
-        self._grad_is_zero = bool(zero_grad)
-        self.refresh_derived_weights()
+        (alpha 0.9, momentum 0.9, eps 1e-3) -- over every parameter (nbdt_rmsprop_step).  One launch.  The buffer lives
+        in store.mom, the mean square in store.sq."""
+        self.optimizer_step(lr, momentum, weight_decay, RMSpropConfig(alpha, eps, tf, exclude_1d), grad_scale, zero_grad)
 
     def clip_grad_norm(self, max_norm, grad_scale=1.0):
         """torch.nn.utils.clip_grad_norm_ over every parameter's gradient, on the device: the global norm of grad_scale *
@@ -2021,19 +2008,8 @@ def train_step(engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5
     scale = 1.0 / (K * (comm.world_size if comm is not None else 1))
     if clip is not None:
         engine.clip_grad_norm(clip.max_norm, grad_scale=scale)
-    if lars is not None:
-        engine.lars_step(lr, momentum, weight_decay, lars.trust, lars.eps, grad_scale=scale, zero_grad=zero_grad,
-                         exclude_1d=lars.exclude_1d)
-        return loss
-    if isinstance(optim, AdamWConfig):
-        engine.adamw_step(lr, optim.betas, optim.eps, weight_decay, grad_scale=scale, zero_grad=zero_grad,
-                          exclude_1d=optim.exclude_1d)
-        return loss
-    if isinstance(optim, RMSpropConfig):
-        engine.rmsprop_step(lr, optim.alpha, optim.eps, momentum, weight_decay, optim.tf, grad_scale=scale,
-                            zero_grad=zero_grad, exclude_1d=optim.exclude_1d)
-        return loss
-    engine.sgd_step(lr, momentum, weight_decay, grad_scale=scale, zero_grad=zero_grad)
+    engine.optimizer_step(lr, momentum, weight_decay, lars if lars is not None else optim, grad_scale=scale,
+                          zero_grad=zero_grad)
     return loss
 
 

@@ -9,6 +9,7 @@ ever write interiors, so the border stays zero for the lifetime of the buffer).
 Weight layout: ``[cout][taps][cin]`` (fp32 master and bf16 copy); the data-gradient kernel reads
 the transposed, tap-reversed copy ``[cin][taps][cout]`` produced by ``weight_prep``.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -792,39 +793,72 @@ def sgd_step(p, g, buf, lr, momentum, weight_decay, grad_scale=1.0, p_bf16=None,
                               ptr(p_bf16), 1 if zero_grad else 0, stream_ptr(p.device)))
 
 
+def _check_fp32(what, n, p, named):
+    """Every (tensor, name) of `named` that is not None: contiguous fp32, n elements, on p's device."""
+    for t, name in named:
+        if t is None:
+            continue
+        if t.dtype != torch.float32 or t.numel() != n or t.device != p.device or not t.is_contiguous():
+            raise _C.NBDTHipError(f"{what}: {name} must be a contiguous fp32 tensor of {n} elements on {p.device}")
+
+
+def _check_mirror(what, n, p, p_bf16):
+    if p_bf16 is not None and (p_bf16.dtype != torch.bfloat16 or p_bf16.numel() != n or p_bf16.device != p.device
+                               or not p_bf16.is_contiguous()):
+        raise _C.NBDTHipError(f"{what}: the mirror must be a contiguous bf16 tensor of {n} elements on {p.device}")
+
+
+class _ArenaPlan:
+    """What the plans over a flat arena of n fp32 elements share (csrc/arena.h has the library's half): the segment rows
+    as ctypes columns, the create call with `device` current -- the table is checked on the host first (a bad one raises
+    without a GPU), a good one puts the plan's tables and workspace on `device` once -- the tensor checks of a step, and
+    the destroy call when the plan goes.  A subclass names its entry points and the ctypes type of each row column."""
+    _CREATE = _DESTROY = None
+    _COLUMNS = ()
+
+    def __init__(self, n, rows, device):
+        self.n = int(n)
+        self.device = torch.device(device) if device is not None else None
+        self.handle = ctypes.c_void_p()
+        args = [self.n]
+        if self._COLUMNS:
+            k = len(rows)
+            self.n_seg, self.segments = k, rows
+            args += [(ct * max(k, 1))(*[r[i] for r in rows]) for i, ct in enumerate(self._COLUMNS)] + [k]
+        on_device = self.device is not None and self.device.type == "cuda"
+        with torch.cuda.device(self.device) if on_device else contextlib.nullcontext():
+            check(getattr(lib(), self._CREATE)(*args, ctypes.byref(self.handle)))
+
+    def _check(self, what, p, named, p_bf16):
+        _C.require_gpu(p, what)
+        _check_fp32(what, self.n, p, named)
+        _check_mirror(what, self.n, p, p_bf16)
+
+    def __del__(self):
+        try:
+            h = getattr(self, "handle", None)
+            if h is not None and h.value:
+                getattr(lib(), self._DESTROY)(h)
+                self.handle = None
+        except Exception:      # (interpreter shutdown: modules may already be gone)
+            pass
+
+
 LARS_ITEM = 4096      # elements one wave of csrc/lars.hip reduces / updates (kItem); a block is four waves
 
 
-class LarsPlan:
+class LarsPlan(_ArenaPlan):
     """A plan of nbdt_lars_*: `segments` = rows (offset, length, weight_decay, adapt) over a flat arena of n fp32 elements
-    (sorted, disjoint, offsets multiples of 4: ParamStore.segments).  The table is checked on the host first (a bad one
-    raises without a GPU); a good one puts its block tables and its workspace on `device` once, here."""
+    (sorted, disjoint, offsets multiples of 4: ParamStore.segments)."""
+    _CREATE, _DESTROY = "nbdt_lars_create", "nbdt_lars_destroy"
+    _COLUMNS = (ctypes.c_int64, ctypes.c_int64, ctypes.c_float, ctypes.c_int32)
 
     def __init__(self, n, segments, device=None):
-        rows = [(int(o), int(l), float(w), int(bool(a))) for o, l, w, a in segments]
-        k = len(rows)
-        self.n, self.n_seg, self.segments = int(n), k, rows
-        self.device = torch.device(device) if device is not None else None
-        self.handle = ctypes.c_void_p()
-        offs = (ctypes.c_int64 * max(k, 1))(*[r[0] for r in rows])
-        lens = (ctypes.c_int64 * max(k, 1))(*[r[1] for r in rows])
-        wds = (ctypes.c_float * max(k, 1))(*[r[2] for r in rows])
-        adapt = (ctypes.c_int32 * max(k, 1))(*[r[3] for r in rows])
-        if self.device is not None and self.device.type == "cuda":
-            with torch.cuda.device(self.device):
-                check(lib().nbdt_lars_create(self.n, offs, lens, wds, adapt, k, ctypes.byref(self.handle)))
-        else:
-            check(lib().nbdt_lars_create(self.n, offs, lens, wds, adapt, k, ctypes.byref(self.handle)))
+        super().__init__(n, [(int(o), int(l), float(w), int(bool(a))) for o, l, w, a in segments], device)
 
     def step(self, p, g, buf, lr, momentum, trust, eps, grad_scale=1.0, p_bf16=None, zero_grad=False):
         """Three launches on p's current stream; no host synchronisation."""
-        _C.require_gpu(p, "lars_step")
-        for t, what in ((p, "p"), (g, "g"), (buf, "buf")):
-            if t.dtype != torch.float32 or t.numel() != self.n or t.device != p.device or not t.is_contiguous():
-                raise _C.NBDTHipError(f"lars_step: {what} must be a contiguous fp32 tensor of {self.n} elements on {p.device}")
-        if p_bf16 is not None and (p_bf16.dtype != torch.bfloat16 or p_bf16.numel() != self.n or p_bf16.device != p.device
-                                   or not p_bf16.is_contiguous()):
-            raise _C.NBDTHipError(f"lars_step: the mirror must be a contiguous bf16 tensor of {self.n} elements on {p.device}")
+        self._check("lars_step", p, ((p, "p"), (g, "g"), (buf, "buf")), p_bf16)
         check(lib().nbdt_lars_step(self.handle, ptr(p), ptr(g), ptr(buf), lr, momentum, trust, eps, grad_scale,
                                    ptr(p_bf16), 1 if zero_grad else 0, stream_ptr(p.device)))
 
@@ -836,50 +870,19 @@ class LarsPlan:
                                                  stream_ptr(self.device)))
         return out
 
-    def __del__(self):
-        try:
-            h = getattr(self, "handle", None)
-            if h is not None and h.value:
-                lib().nbdt_lars_destroy(h)
-                self.handle = None
-        except Exception:      # (interpreter shutdown: modules may already be gone)
-            pass
-
 
 ARENA_OPT_ITEM = 512      # elements one wave of csrc/adaptive.hip updates (kItem); a block is four waves
 
 
-class ArenaOptPlan:
+class ArenaOptPlan(_ArenaPlan):
     """A plan of nbdt_adamw_step / nbdt_rmsprop_step: `segments` = rows (offset, length, weight_decay) over a flat arena of n
     fp32 elements (sorted, disjoint, offsets multiples of 4; a fourth column, as ParamStore.segments has, is ignored).
-    The table is checked on the host first (a bad one raises without a GPU); a good one puts its wave-item table on
-    `device` once, here.  Every step is one launch on p's current stream, no host synchronisation."""
+    Every step is one launch on p's current stream, no host synchronisation."""
+    _CREATE, _DESTROY = "nbdt_arena_opt_create", "nbdt_arena_opt_destroy"
+    _COLUMNS = (ctypes.c_int64, ctypes.c_int64, ctypes.c_float)
 
     def __init__(self, n, segments, device=None):
-        rows = [(int(r[0]), int(r[1]), float(r[2])) for r in segments]
-        k = len(rows)
-        self.n, self.n_seg, self.segments = int(n), k, rows
-        self.device = torch.device(device) if device is not None else None
-        self.handle = ctypes.c_void_p()
-        offs = (ctypes.c_int64 * max(k, 1))(*[r[0] for r in rows])
-        lens = (ctypes.c_int64 * max(k, 1))(*[r[1] for r in rows])
-        wds = (ctypes.c_float * max(k, 1))(*[r[2] for r in rows])
-        if self.device is not None and self.device.type == "cuda":
-            with torch.cuda.device(self.device):
-                check(lib().nbdt_arena_opt_create(self.n, offs, lens, wds, k, ctypes.byref(self.handle)))
-        else:
-            check(lib().nbdt_arena_opt_create(self.n, offs, lens, wds, k, ctypes.byref(self.handle)))
-
-    def _check(self, what, p, fp32, p_bf16):
-        _C.require_gpu(p, what)
-        for t, name in fp32:
-            if t is None:
-                continue
-            if t.dtype != torch.float32 or t.numel() != self.n or t.device != p.device or not t.is_contiguous():
-                raise _C.NBDTHipError(f"{what}: {name} must be a contiguous fp32 tensor of {self.n} elements on {p.device}")
-        if p_bf16 is not None and (p_bf16.dtype != torch.bfloat16 or p_bf16.numel() != self.n or p_bf16.device != p.device
-                                   or not p_bf16.is_contiguous()):
-            raise _C.NBDTHipError(f"{what}: the mirror must be a contiguous bf16 tensor of {self.n} elements on {p.device}")
+        super().__init__(n, [(int(r[0]), int(r[1]), float(r[2])) for r in segments], device)
 
     def adamw(self, p, g, m, v, lr, betas, eps, t, grad_scale=1.0, p_bf16=None, zero_grad=False):
         """torch.optim.AdamW's step number t >= 1 (the decay of each row decoupled, no amsgrad)."""
@@ -895,35 +898,20 @@ class ArenaOptPlan:
                                       1 if tf else 0, grad_scale, ptr(p_bf16), 1 if zero_grad else 0,
                                       stream_ptr(p.device)))
 
-    def __del__(self):
-        try:
-            h = getattr(self, "handle", None)
-            if h is not None and h.value:
-                lib().nbdt_arena_opt_destroy(h)
-                self.handle = None
-        except Exception:      # (interpreter shutdown: modules may already be gone)
-            pass
-
 
 class ClipRecord(ctypes.Structure):      # nbdt_clip_*'s 32-byte record
     _fields_ = [("norm", ctypes.c_float), ("coef", ctypes.c_float), ("clipped", ctypes.c_int32), ("steps", ctypes.c_int32),
                 ("nonfinite", ctypes.c_int32), ("total_clipped", ctypes.c_int32), ("reserved", ctypes.c_int32 * 2)]
 
 
-class ClipPlan:
+class ClipPlan(_ArenaPlan):
     """A plan of nbdt_clip_*: global-norm clipping of a flat fp32 gradient arena of n elements on `device`, which gets the
     fp64 partials and the 32-byte record once, here.  norm() is two launches and apply() one on g's current stream, no
     host synchronisation; to_host() is the one place that waits."""
+    _CREATE, _DESTROY = "nbdt_clip_create", "nbdt_clip_destroy"
 
     def __init__(self, n, device=None):
-        self.n = int(n)
-        self.device = torch.device(device) if device is not None else None
-        self.handle = ctypes.c_void_p()
-        if self.device is not None and self.device.type == "cuda":
-            with torch.cuda.device(self.device):
-                check(lib().nbdt_clip_create(self.n, ctypes.byref(self.handle)))
-        else:
-            check(lib().nbdt_clip_create(self.n, ctypes.byref(self.handle)))
+        super().__init__(n, None, device)
 
     def _check(self, what, g):
         _C.require_gpu(g, what)
@@ -959,21 +947,10 @@ class ClipPlan:
             check(lib().nbdt_clip_record_to_host(self.handle, ctypes.byref(out), stream_ptr(self.device)))
         return {k: getattr(out, k) for k, _ in ClipRecord._fields_[:6]}
 
-    def __del__(self):
-        try:
-            h = getattr(self, "handle", None)
-            if h is not None and h.value:
-                lib().nbdt_clip_destroy(h)
-                self.handle = None
-        except Exception:      # (interpreter shutdown: modules may already be gone)
-            pass
-
 
 def _ema_pair(p, ema, what):
     _C.require_gpu(p, what)
-    for t, name in ((p, "p"), (ema, "ema")):
-        if t.dtype != torch.float32 or t.numel() != p.numel() or t.device != p.device or not t.is_contiguous():
-            raise _C.NBDTHipError(f"{what}: {name} must be a contiguous fp32 tensor of {p.numel()} elements on {p.device}")
+    _check_fp32(what, p.numel(), p, ((p, "p"), (ema, "ema")))
 
 
 def ema_update(p, ema, one_minus_decay):
@@ -986,9 +963,7 @@ def ema_update(p, ema, one_minus_decay):
 def ema_swap(p, ema, p_bf16=None):
     """p and ema exchange their values in place; p_bf16 (optional) becomes the bf16 mirror of the new p (nbdt_ema_swap)."""
     _ema_pair(p, ema, "ema_swap")
-    if p_bf16 is not None and (p_bf16.dtype != torch.bfloat16 or p_bf16.numel() != p.numel() or p_bf16.device != p.device
-                               or not p_bf16.is_contiguous()):
-        raise _C.NBDTHipError(f"ema_swap: the mirror must be a contiguous bf16 tensor of {p.numel()} elements on {p.device}")
+    _check_mirror("ema_swap", p.numel(), p, p_bf16)
     check(lib().nbdt_ema_swap(ptr(p), ptr(ema), ptr(p_bf16), p.numel(), stream_ptr(p.device)))
 
 

@@ -145,6 +145,37 @@ def test_ragged_table_matches_the_fp64_reference():
     assert int(torch.count_nonzero(g)) == 0                                             # zero_grad: all of g[0, n)
 
 
+def test_ragged_update_is_the_fp32_formula_bit_for_bit():
+    """The element update alone, exactly: with the kernel's own ratios (plan.ratios(), so the order of the norm sums does
+    not enter) u = r (gs g + wd p), buf = mu buf + u, p = p - lr buf evaluated in numpy float32 -- one rounding per
+    operation, which is what -ffp-contract=off makes of csrc/lars.hip -- gives the bytes of p, buf and the mirror inside
+    every segment of the ragged table (float4 bodies, length % 4 tails, items of every length), after each of three steps."""
+    n, segments, p0, b0, grads, _ = _ragged()
+    hp, f = _RAGGED_HP, np.float32
+    lr, mu, gs = f(hp["lr"]), f(hp["momentum"]), f(hp["gs"])
+    inside = _inside(n, segments)
+    want_p, want_b = p0.numpy().copy(), b0.numpy().copy()
+    p, buf, g = p0.to(DEV), b0.to(DEV), torch.empty(n, device=DEV)
+    mirror = torch.full((n,), 7.0, dtype=torch.bfloat16, device=DEV)
+    plan = ops.LarsPlan(n, segments, device=DEV)
+    for step, gk in enumerate(grads):
+        g.copy_(gk)
+        plan.step(p, g, buf, hp["lr"], hp["momentum"], hp["trust"], hp["eps"], hp["gs"], mirror, zero_grad=True)
+        ratios, gn = plan.ratios().numpy(), gk.numpy()
+        assert ratios.dtype == gn.dtype == want_p.dtype == np.float32
+        for (o, l, wd, _), r in zip(segments, ratios):
+            sl = slice(o, o + l)
+            u = r * (gs * gn[sl] + f(wd) * want_p[sl])
+            want_b[sl] = mu * want_b[sl] + u
+            want_p[sl] = want_p[sl] - lr * want_b[sl]
+        assert want_p.dtype == want_b.dtype == np.float32
+        got_p, got_b = p.cpu(), buf.cpu()
+        m = inside.numpy()
+        assert got_p.numpy()[m].tobytes() == want_p[m].tobytes(), f"p, step {step}"
+        assert got_b.numpy()[m].tobytes() == want_b[m].tobytes(), f"buf, step {step}"
+        assert torch.equal(mirror.cpu()[inside], torch.from_numpy(want_p).to(torch.bfloat16)[inside]), f"mirror, step {step}"
+
+
 # ------------------------------------------------------------------------------------------------ 3. degenerate norms
 def test_degenerate_norms_take_ratio_one():
     gen = torch.Generator().manual_seed(5)
