@@ -611,6 +611,39 @@ int nbdt_dropout_fwd(const float* x, int64_t n, float p, uint32_t seed, uint8_t*
                      void* stream);
 int nbdt_dropout_bwd(const float* gy, int64_t n, float p, const uint8_t* mask, float* gx, void* stream);
 
+/* ---- stochastic depth (nbdt_version() >= 122): torchvision's StochasticDepth(p, mode="row") on the branch of an MBConv
+ * residual add, inside the passes that exist already.  Replaces `stochastic_depth(...)` behind torchvision's
+ * efficientnet_b0 MBConv.forward; the reference's pytorchcv model has none.
+ *
+ * nbdt_bn_act_apply_rows: y = residual + row_scale[b] * act(bn(x)), row_scale fp32 [B] (device).  The statistics are the
+ * whole batch's: the scale comes after the BatchNorm.  A factor of exactly 0 copies the residual's bits; a factor of 1
+ * gives the bits of nbdt_bn_act_apply.  row_scale needs a residual and takes no gate: anything else is NBDT_EINVAL before
+ * any launch (gate is in the signature only to be refused).
+ *
+ * nbdt_bn_act_bwd_rows: nbdt_bn_act_bwd's plain form with g_a = gu * row_scale[b]: a dropped image adds exact zeros to
+ * the sums and still receives gx = gamma*rstd * (-mean(g_y) - xhat * mean(g_y*xhat)) [+ gx_add] through the batch
+ * statistics.  The skip gradient is the caller's (gu itself, unscaled).  gu == NULL, a gate or a gpool is NBDT_EINVAL
+ * before any launch.  scratch is left zero and deterministic mode holds as for nbdt_bn_act_bwd. */
+int nbdt_bn_act_apply_rows(const void* x, const float* save_mean, const float* save_rstd, const float* gamma,
+                           const float* beta, int32_t act, const float* gate, const void* residual,
+                           const float* row_scale, int32_t B, int32_t H, int32_t W, int32_t C, void* y, void* stream);
+int nbdt_bn_act_bwd_rows(const void* gu, const float* row_scale, const float* gate, const float* gpool, const void* x,
+                         const float* save_mean, const float* save_rstd, const float* gamma, const float* beta,
+                         int32_t act, const void* gx_add, int32_t B, int32_t H, int32_t W, int32_t C, float* scratch,
+                         float* dsum, float* dgamma, float* dbeta, void* gx, void* stream);
+/* The factors of one training forward in ONE launch: table[U][B] fp32 (device) = u < prob[unit] ? 0 : scale[unit].
+ * prob / scale: HOST fp32 [U], U <= NBDT_SD_MAX_UNITS, 0 <= prob < 1, scale finite and > 0 (the caller rounds
+ * 1 / (1 - prob) to fp32 once, so no bit depends on the device's division); they travel as kernel arguments.  A unit
+ * without a skip has prob 0 and scale 1: its row is all ones.  The draw is a pure function of
+ * (seed, stream_id, counter, unit, image) -- not of B.  With mix64 (splitmix64's finaliser) as for nbdt_augment_batch,
+ * G = 0x9E3779B97F4A7C15 and K = 0xD1342543DE82EF95, all arithmetic mod 2^64:
+ *   key = mix64(mix64(seed * G + counter) ^ (stream_id * K))
+ *   r   = mix64(key ^ ((unit << 32 | image) * K)),   u = (float)(r >> 40) * 2^-24   (exact, in [0, 1))
+ * nbdt/ops.py draw_stochastic_depth restates it with numpy, bit for bit. */
+#define NBDT_SD_MAX_UNITS 64
+int nbdt_stochastic_depth_draw(uint64_t seed, uint64_t stream_id, uint64_t counter, const float* prob,
+                               const float* scale, int32_t U, int32_t B, float* table, void* stream);
+
 /* ------------------------------------------------------------------ verification-only fp32-storage kernels
  * NOT the product path (csrc/ref_fp32.hip): the same operators as above on fp32 padded NHWC tensors, written to be
  * obviously right (one thread per output, plain loops, double accumulators), taking the SAME descriptors.  The engines'
@@ -664,6 +697,15 @@ int nbdt_ref_bn_act_bwd(const float* gu, const float* gate, const float* gpool, 
                         const float* save_rstd, const float* gamma, const float* beta, int32_t act, const float* gx_add,
                         int32_t B, int32_t H, int32_t W, int32_t C, float* dsum, float* dgamma, float* dbeta, float* gx,
                         void* stream);
+/* twins of nbdt_bn_act_apply_rows / nbdt_bn_act_bwd_rows (stochastic depth): same arguments, meaning and refusals */
+int nbdt_ref_bn_act_apply_rows(const float* x, const float* save_mean, const float* save_rstd, const float* gamma,
+                               const float* beta, int32_t act, const float* gate, const float* residual,
+                               const float* row_scale, int32_t B, int32_t H, int32_t W, int32_t C, float* y,
+                               void* stream);
+int nbdt_ref_bn_act_bwd_rows(const float* gu, const float* row_scale, const float* gate, const float* gpool,
+                             const float* x, const float* save_mean, const float* save_rstd, const float* gamma,
+                             const float* beta, int32_t act, const float* gx_add, int32_t B, int32_t H, int32_t W,
+                             int32_t C, float* dsum, float* dgamma, float* dbeta, float* gx, void* stream);
 int nbdt_ref_dwconv_fwd(const float* x, const float* w, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
                         int32_t stride, float* y, void* stream);
 int nbdt_ref_dwconv_bwd_data(const float* gy, const float* w, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,

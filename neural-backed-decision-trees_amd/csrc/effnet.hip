@@ -126,12 +126,16 @@ __device__ __forceinline__ void block_fold(float (&acc)[NQ][8], int cx, int py, 
 
 // ------------------------------------------------------------------------------------------
 // y = act(bn(x)) [* gate[b,c]] [+ residual]
-template <int ACT, bool GATE, bool RES>
+// ROWS (stochastic depth, residual form only): y = residual + row_scale[b] * act(bn(x)); an image is a block row, so its
+// factor is one register.  A factor of exactly 0 passes the residual's bits through whatever the branch holds.
+template <int ACT, bool GATE, bool RES, bool ROWS = false>
 __global__ __launch_bounds__(kThreads) void mb_apply_kernel(const bf16_t* __restrict__ x, const float* mean,
                                                             const float* rstd, const float* gamma,
                                                             const float* beta, const float* __restrict__ gate,
-                                                            const bf16_t* __restrict__ res, MbGeom g, int ppt,
+                                                            const bf16_t* __restrict__ res,
+                                                            const float* __restrict__ row_scale, MbGeom g, int ppt,
                                                             bf16_t* __restrict__ y) {
+  static_assert(!ROWS || (RES && !GATE), "row_scale: residual form without a gate");
   const int cx = threadIdx.x % g.c8, py = threadIdx.x / g.c8, b = blockIdx.y;
   BnRegs bn;
   load_bn(bn, mean, rstd, gamma, beta, cx);
@@ -139,6 +143,7 @@ __global__ __launch_bounds__(kThreads) void mb_apply_kernel(const bf16_t* __rest
   if (GATE)
 #pragma unroll
     for (int i = 0; i < 8; ++i) gt[i] = gate[(size_t)b * g.C + cx * 8 + i];
+  const float rsc = ROWS ? row_scale[b] : 1.f;
   const int p0 = blockIdx.x * g.PY * ppt + py;
   for (int k = 0; k < ppt; ++k) {
     const int p = p0 + k * g.PY;
@@ -151,7 +156,8 @@ __global__ __launch_bounds__(kThreads) void mb_apply_kernel(const bf16_t* __rest
     for (int i = 0; i < 8; ++i) {
       float v = act_fwd<ACT>(f[i] * bn.sc[i] + bn.sh[i]);
       if (GATE) v *= gt[i];
-      if (RES) v += r[i];
+      if (ROWS) v = rsc == 0.f ? r[i] : r[i] + rsc * v;
+      else if (RES) v += r[i];
       f[i] = v;
     }
     *(u32x4_t*)(y + o) = pack8(f);
@@ -194,14 +200,18 @@ __global__ __launch_bounds__(kThreads) void mb_pool_kernel(const bf16_t* __restr
 }
 
 // gradient entering the activation:  g_a = SE ? gu*gate[b,c] + gpool[b,c]/HW : (POOL ? gpooled[b,c]/HW : gu)
+// ROWS (plain form only): g_a = gu * row_scale[b], the backward of mb_apply_kernel's ROWS form (a dropped image adds
+// exact zeros to the sums and still receives the batch-statistics terms in pass 2)
 // backward pass 1: per-channel sums of g_y = g_a * act'(y) and g_y * xhat  -> 32-slot scratch
-template <int ACT, bool SE, bool POOL>
+template <int ACT, bool SE, bool POOL, bool ROWS = false>
 __global__ __launch_bounds__(kThreads) void mb_bwd_reduce_kernel(
     const bf16_t* __restrict__ gu, const float* __restrict__ gate, const float* __restrict__ gpool,
-    const bf16_t* __restrict__ x, const float* mean, const float* rstd, const float* gamma, const float* beta,
-    MbGeom g, int ppt, float* __restrict__ scratch, unsigned slot_mask) {
+    const float* __restrict__ row_scale, const bf16_t* __restrict__ x, const float* mean, const float* rstd,
+    const float* gamma, const float* beta, MbGeom g, int ppt, float* __restrict__ scratch, unsigned slot_mask) {
+  static_assert(!ROWS || (!SE && !POOL), "row_scale: plain form only");
   extern __shared__ float lds[];
   const int cx = threadIdx.x % g.c8, py = threadIdx.x / g.c8, b = blockIdx.y;
+  const float rsc = ROWS ? row_scale[b] : 1.f;
   BnRegs bn;
   load_bn(bn, mean, rstd, gamma, beta, cx);
   float mu[8], rs[8], gt[8], gp[8];
@@ -229,6 +239,7 @@ __global__ __launch_bounds__(kThreads) void mb_bwd_reduce_kernel(
     for (int i = 0; i < 8; ++i) {
       float ga = POOL ? gp[i] : fg[i];
       if (SE) ga = ga * gt[i] + gp[i];
+      if (ROWS) ga *= rsc;
       const float gy = ga * act_bwd<ACT>(fx[i] * bn.sc[i] + bn.sh[i]);
       acc[0][i] += gy;
       acc[1][i] += gy * ((fx[i] - mu[i]) * rs[i]);
@@ -241,13 +252,15 @@ __global__ __launch_bounds__(kThreads) void mb_bwd_reduce_kernel(
 }
 
 // backward pass 2: gx = gamma*rstd * (g_y - mean(g_y) - xhat * mean(g_y*xhat)) [+ gx_add]
-template <int ACT, bool SE, bool POOL, bool HAS_ADD>
+template <int ACT, bool SE, bool POOL, bool HAS_ADD, bool ROWS = false>
 __global__ __launch_bounds__(kThreads) void mb_bwd_apply_kernel(
     const bf16_t* __restrict__ gu, const float* __restrict__ gate, const float* __restrict__ gpool,
-    const bf16_t* __restrict__ x, const float* mean, const float* rstd, const float* gamma, const float* beta,
-    const float* __restrict__ dsum, const bf16_t* __restrict__ gx_add, MbGeom g, int ppt,
-    bf16_t* __restrict__ gx) {
+    const float* __restrict__ row_scale, const bf16_t* __restrict__ x, const float* mean, const float* rstd,
+    const float* gamma, const float* beta, const float* __restrict__ dsum, const bf16_t* __restrict__ gx_add, MbGeom g,
+    int ppt, bf16_t* __restrict__ gx) {
+  static_assert(!ROWS || (!SE && !POOL), "row_scale: plain form only");
   const int cx = threadIdx.x % g.c8, py = threadIdx.x / g.c8, b = blockIdx.y;
+  const float rsc = ROWS ? row_scale[b] : 1.f;
   BnRegs bn;
   load_bn(bn, mean, rstd, gamma, beta, cx);
   float mu[8], rs[8], gt[8], gp[8], k0[8], k1[8];
@@ -276,6 +289,7 @@ __global__ __launch_bounds__(kThreads) void mb_bwd_apply_kernel(
     for (int i = 0; i < 8; ++i) {
       float ga = POOL ? gp[i] : fg[i];
       if (SE) ga = ga * gt[i] + gp[i];
+      if (ROWS) ga *= rsc;
       const float gy = ga * act_bwd<ACT>(fx[i] * bn.sc[i] + bn.sh[i]);
       const float xh = (fx[i] - mu[i]) * rs[i];
       float v = bn.sc[i] * (gy - k0[i] - xh * k1[i]);
@@ -929,6 +943,32 @@ __global__ __launch_bounds__(256) void dropout_bwd_kernel(const float* __restric
   gx[i] = mask[i] ? gy[i] * inv_keep : 0.f;
 }
 
+// ------------------------------------------------------------------------------------------
+// stochastic depth: the per-(unit, image) factors of one training forward, table[U][B] = u < prob[unit] ? 0 : scale[unit].
+// The draw is the augmentation kernels' counter hash (splitmix64's finaliser; nbdt/data.py _mix64), a pure function of
+// (seed, stream, counter, unit, image): `key` folds the first three on the host, the element hashes (unit, image) -- not
+// the batch size.  u is the hash's top 24 bits as an fp32 in [0, 1); prob / scale come from the host by value, so the
+// kernel divides nothing.
+constexpr int kSdMaxUnits = NBDT_SD_MAX_UNITS;
+struct SdTables {
+  float prob[kSdMaxUnits], scale[kSdMaxUnits];
+};
+__host__ __device__ inline unsigned long long mix64(unsigned long long x) {
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+__global__ __launch_bounds__(256) void sd_draw_kernel(unsigned long long key, SdTables t, int U, int B,
+                                                      float* __restrict__ table) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= U * B) return;
+  const int unit = idx / B, b = idx - unit * B;
+  const unsigned long long r =
+      mix64(key ^ ((((unsigned long long)unit << 32) | (unsigned long long)b) * 0xD1342543DE82EF95ull));
+  const float u = (float)(unsigned)(r >> 40) * (1.f / 16777216.f);
+  table[idx] = u < t.prob[unit] ? 0.f : t.scale[unit];
+}
+
 constexpr int kPpt = 8;
 
 }  // namespace
@@ -943,27 +983,46 @@ constexpr int kPpt = 8;
   } while (0)
 
 
-extern "C" int nbdt_bn_act_apply(const void* x, const float* save_mean, const float* save_rstd, const float* gamma,
-                                 const float* beta, int32_t act, const float* gate, const void* residual, int32_t B,
-                                 int32_t H, int32_t W, int32_t C, void* y, void* stream) {
+static int bn_act_apply_impl(const void* x, const float* save_mean, const float* save_rstd, const float* gamma,
+                             const float* beta, int32_t act, const float* gate, const void* residual,
+                             const float* row_scale, int32_t B, int32_t H, int32_t W, int32_t C, void* y,
+                             void* stream) {
   NBDT_REQUIRE(x && save_mean && save_rstd && gamma && beta && y, "null argument");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
+  NBDT_REQUIRE(!row_scale || (residual && !gate), "row_scale scales the branch of a residual add: it needs a residual and takes no gate");
   int rc = check_mb(B, H, W, C);
   if (rc) return rc;
   const MbGeom g = mb_geom(B, H, W, C, kPpt);
   const dim3 grid(g.slices, B), blk(g.threads);
   hipStream_t st = (hipStream_t)stream;
-#define NBDT_GO(A)                                                                                              \
-  do {                                                                                                          \
-    if (gate && residual) hipLaunchKernelGGL((mb_apply_kernel<A, true, true>), grid, blk, 0, st, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, gate, (const bf16_t*)residual, g, kPpt, (bf16_t*)y); \
-    else if (gate) hipLaunchKernelGGL((mb_apply_kernel<A, true, false>), grid, blk, 0, st, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, gate, (const bf16_t*)residual, g, kPpt, (bf16_t*)y); \
-    else if (residual) hipLaunchKernelGGL((mb_apply_kernel<A, false, true>), grid, blk, 0, st, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, gate, (const bf16_t*)residual, g, kPpt, (bf16_t*)y); \
-    else hipLaunchKernelGGL((mb_apply_kernel<A, false, false>), grid, blk, 0, st, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, gate, (const bf16_t*)residual, g, kPpt, (bf16_t*)y); \
+#define NBDT_APPLY(A, GATE, RES, ROWS) hipLaunchKernelGGL((mb_apply_kernel<A, GATE, RES, ROWS>), grid, blk, 0, st, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, gate, (const bf16_t*)residual, row_scale, g, kPpt, (bf16_t*)y)
+#define NBDT_GO(A)                                  \
+  do {                                              \
+    if (row_scale) NBDT_APPLY(A, false, true, true);      \
+    else if (gate && residual) NBDT_APPLY(A, true, true, false);  \
+    else if (gate) NBDT_APPLY(A, true, false, false);     \
+    else if (residual) NBDT_APPLY(A, false, true, false); \
+    else NBDT_APPLY(A, false, false, false);              \
   } while (0)
   NBDT_ACT_SWITCH(act, NBDT_GO);
 #undef NBDT_GO
+#undef NBDT_APPLY
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;
+}
+
+extern "C" int nbdt_bn_act_apply(const void* x, const float* save_mean, const float* save_rstd, const float* gamma,
+                                 const float* beta, int32_t act, const float* gate, const void* residual, int32_t B,
+                                 int32_t H, int32_t W, int32_t C, void* y, void* stream) {
+  return bn_act_apply_impl(x, save_mean, save_rstd, gamma, beta, act, gate, residual, nullptr, B, H, W, C, y, stream);
+}
+
+extern "C" int nbdt_bn_act_apply_rows(const void* x, const float* save_mean, const float* save_rstd, const float* gamma,
+                                      const float* beta, int32_t act, const float* gate, const void* residual,
+                                      const float* row_scale, int32_t B, int32_t H, int32_t W, int32_t C, void* y,
+                                      void* stream) {
+  NBDT_REQUIRE(row_scale != nullptr, "null row_scale");
+  return bn_act_apply_impl(x, save_mean, save_rstd, gamma, beta, act, gate, residual, row_scale, B, H, W, C, y, stream);
 }
 
 extern "C" int nbdt_bn_act_pool(const void* x, const float* save_mean, const float* save_rstd, const float* gamma,
@@ -1003,8 +1062,10 @@ static int bn_act_bwd_impl(const void* gu, const float* gate, const float* gpool
                            const float* save_mean, const float* save_rstd, const float* gamma, const float* beta,
                            int32_t act, const void* gx_add, int32_t B, int32_t H, int32_t W, int32_t C,
                            float* scratch, float* dsum, float* dgamma, float* dbeta, void* gx, void* stream,
-                           bool sums_ready, bool dsum_ready = false) {
+                           bool sums_ready, bool dsum_ready = false, const float* row_scale = nullptr) {
   NBDT_REQUIRE(x && save_mean && save_rstd && gamma && beta && (scratch || dsum_ready) && dsum && gx, "null argument");
+  NBDT_REQUIRE(!row_scale || (gu && !gate && !gpool && !sums_ready && !dsum_ready),
+               "row_scale belongs to the plain form: an upstream gradient tensor, no gate, no pooled gradient, no precomputed sums");
   NBDT_REQUIRE(gu || (gpool && !gate), "need an upstream gradient tensor or a pooled gradient");
   NBDT_REQUIRE(!gate || (gu && gpool), "the SE form needs gu, gate and gpool");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
@@ -1021,14 +1082,17 @@ static int bn_act_bwd_impl(const void* gu, const float* gate, const float* gpool
     const int nblk = g.slices * B;
     rc = slot_target(st, scratch, nblk, 2 * (size_t)C, &tgt);
     if (rc) return rc;
-#define NBDT_GO(A)                                                                                              \
-  do {                                                                                                          \
-    if (se) hipLaunchKernelGGL((mb_bwd_reduce_kernel<A, true, false>), grid, blk, shmem, st, (const bf16_t*)gu, gate, gpool, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, g, 2 * kPpt, tgt.ptr, tgt.mask); \
-    else if (pool) hipLaunchKernelGGL((mb_bwd_reduce_kernel<A, false, true>), grid, blk, shmem, st, (const bf16_t*)gu, gate, gpool, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, g, 2 * kPpt, tgt.ptr, tgt.mask); \
-    else hipLaunchKernelGGL((mb_bwd_reduce_kernel<A, false, false>), grid, blk, shmem, st, (const bf16_t*)gu, gate, gpool, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, g, 2 * kPpt, tgt.ptr, tgt.mask); \
+#define NBDT_REDUCE(A, SE, POOL, ROWS) hipLaunchKernelGGL((mb_bwd_reduce_kernel<A, SE, POOL, ROWS>), grid, blk, shmem, st, (const bf16_t*)gu, gate, gpool, row_scale, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, g, 2 * kPpt, tgt.ptr, tgt.mask)
+#define NBDT_GO(A)                                        \
+  do {                                                    \
+    if (row_scale) NBDT_REDUCE(A, false, false, true);    \
+    else if (se) NBDT_REDUCE(A, true, false, false);      \
+    else if (pool) NBDT_REDUCE(A, false, true, false);    \
+    else NBDT_REDUCE(A, false, false, false);             \
   } while (0)
     NBDT_ACT_SWITCH(act, NBDT_GO);
 #undef NBDT_GO
+#undef NBDT_REDUCE
     NBDT_LAUNCH_CHECK();
     rc = slot_finish(st, tgt, nblk, 2 * (size_t)C, scratch);
     if (rc) return rc;
@@ -1040,19 +1104,30 @@ static int bn_act_bwd_impl(const void* gu, const float* gate, const float* gpool
   {
     const MbGeom g = mb_geom(B, H, W, C, kPpt);
     const dim3 grid(g.slices, B), blk(g.threads);
-#define NBDT_GO(A)                                                                                              \
-  do {                                                                                                          \
-    if (se) { if (gx_add) hipLaunchKernelGGL((mb_bwd_apply_kernel<A, true, false, true>), grid, blk, 0, st, (const bf16_t*)gu, gate, gpool, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, dsum, (const bf16_t*)gx_add, g, kPpt, (bf16_t*)gx); \
-              else hipLaunchKernelGGL((mb_bwd_apply_kernel<A, true, false, false>), grid, blk, 0, st, (const bf16_t*)gu, gate, gpool, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, dsum, (const bf16_t*)gx_add, g, kPpt, (bf16_t*)gx); } \
-    else if (pool) hipLaunchKernelGGL((mb_bwd_apply_kernel<A, false, true, false>), grid, blk, 0, st, (const bf16_t*)gu, gate, gpool, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, dsum, (const bf16_t*)gx_add, g, kPpt, (bf16_t*)gx); \
-    else { if (gx_add) hipLaunchKernelGGL((mb_bwd_apply_kernel<A, false, false, true>), grid, blk, 0, st, (const bf16_t*)gu, gate, gpool, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, dsum, (const bf16_t*)gx_add, g, kPpt, (bf16_t*)gx); \
-           else hipLaunchKernelGGL((mb_bwd_apply_kernel<A, false, false, false>), grid, blk, 0, st, (const bf16_t*)gu, gate, gpool, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, dsum, (const bf16_t*)gx_add, g, kPpt, (bf16_t*)gx); } \
+#define NBDT_BWD(A, SE, POOL, ADD, ROWS) hipLaunchKernelGGL((mb_bwd_apply_kernel<A, SE, POOL, ADD, ROWS>), grid, blk, 0, st, (const bf16_t*)gu, gate, gpool, row_scale, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, dsum, (const bf16_t*)gx_add, g, kPpt, (bf16_t*)gx)
+#define NBDT_GO(A)                                                                            \
+  do {                                                                                        \
+    if (row_scale) { if (gx_add) NBDT_BWD(A, false, false, true, true); else NBDT_BWD(A, false, false, false, true); } \
+    else if (se) { if (gx_add) NBDT_BWD(A, true, false, true, false); else NBDT_BWD(A, true, false, false, false); }   \
+    else if (pool) NBDT_BWD(A, false, true, false, false);                                    \
+    else { if (gx_add) NBDT_BWD(A, false, false, true, false); else NBDT_BWD(A, false, false, false, false); }         \
   } while (0)
     NBDT_ACT_SWITCH(act, NBDT_GO);
 #undef NBDT_GO
+#undef NBDT_BWD
     NBDT_LAUNCH_CHECK();
   }
   return NBDT_OK;
+}
+
+extern "C" int nbdt_bn_act_bwd_rows(const void* gu, const float* row_scale, const float* gate, const float* gpool,
+                                    const void* x, const float* save_mean, const float* save_rstd, const float* gamma,
+                                    const float* beta, int32_t act, const void* gx_add, int32_t B, int32_t H, int32_t W,
+                                    int32_t C, float* scratch, float* dsum, float* dgamma, float* dbeta, void* gx,
+                                    void* stream) {
+  NBDT_REQUIRE(row_scale != nullptr, "null row_scale");
+  return bn_act_bwd_impl(gu, gate, gpool, x, save_mean, save_rstd, gamma, beta, act, gx_add, B, H, W, C, scratch, dsum,
+                         dgamma, dbeta, gx, stream, false, false, row_scale);
 }
 
 extern "C" int nbdt_bn_act_bwd(const void* gu, const float* gate, const float* gpool, const void* x,
@@ -1290,6 +1365,24 @@ extern "C" int nbdt_dropout_bwd(const float* gy, int64_t n, float p, const uint8
   NBDT_REQUIRE(n > 0 && p >= 0.f && p < 1.f, "bad dropout arguments");
   hipLaunchKernelGGL(dropout_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gy,
                      (long long)n, 1.f / (1.f - p), mask, gx);
+  NBDT_LAUNCH_CHECK();
+  return NBDT_OK;
+}
+
+extern "C" int nbdt_stochastic_depth_draw(uint64_t seed, uint64_t stream_id, uint64_t counter, const float* prob,
+                                          const float* scale, int32_t U, int32_t B, float* table, void* stream) {
+  NBDT_REQUIRE(prob && scale && table, "null argument");
+  NBDT_REQUIRE(U > 0 && U <= kSdMaxUnits && B > 0 && (long long)U * B < (1ll << 31), "bad table size");
+  SdTables t = {};
+  for (int i = 0; i < U; ++i) {
+    NBDT_REQUIRE(prob[i] >= 0.f && prob[i] < 1.f && scale[i] > 0.f && scale[i] < INFINITY, "prob must be in [0, 1) and scale finite and positive");
+    t.prob[i] = prob[i];
+    t.scale[i] = scale[i];
+  }
+  unsigned long long key = mix64((unsigned long long)seed * 0x9E3779B97F4A7C15ull + (unsigned long long)counter);
+  key = mix64(key ^ ((unsigned long long)stream_id * 0xD1342543DE82EF95ull));
+  hipLaunchKernelGGL(sd_draw_kernel, dim3((unsigned)(((long long)U * B + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     key, t, U, B, table);
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;
 }

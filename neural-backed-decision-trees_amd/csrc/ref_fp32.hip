@@ -391,11 +391,13 @@ __device__ __forceinline__ float ref_act_grad(float v, int act) {
   return 1.f;
 }
 
-// y = act(bn(x)) [* gate[b][c]] [+ residual]
+// y = act(bn(x)) [* gate[b][c]] [+ residual]; rows (stochastic depth): y = residual + rows[b] * act(bn(x)), a factor of
+// exactly 0 copies the residual
 __global__ __launch_bounds__(256) void ref_bn_act_apply_kernel(const float* __restrict__ x, const float* mean,
                                                                const float* rstd, const float* gamma, const float* beta,
                                                                int act, const float* __restrict__ gate,
-                                                               const float* __restrict__ res, PadGeom g,
+                                                               const float* __restrict__ res,
+                                                               const float* __restrict__ rows, PadGeom g,
                                                                float* __restrict__ y) {
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long long)g.npix * g.C) return;
@@ -404,7 +406,8 @@ __global__ __launch_bounds__(256) void ref_bn_act_apply_kernel(const float* __re
   const float sc = gamma[c] * rstd[c];
   float v = ref_act(x[o] * sc + (beta[c] - mean[c] * sc), act);
   if (gate) v *= gate[(size_t)b * g.C + c];
-  if (res) v += res[o];
+  if (rows) v = rows[b] == 0.f ? res[o] : res[o] + rows[b] * v;
+  else if (res) v += res[o];
   y[o] = v;
 }
 
@@ -428,16 +431,18 @@ __global__ __launch_bounds__(256) void ref_bn_act_pool_kernel(const float* __res
 }
 
 // gradient entering the activation of element o of image b, channel c (include/nbdt_hip.h, nbdt_bn_act_bwd)
-__device__ __forceinline__ float ref_act_in_grad(const float* gu, const float* gate, const float* gpool, int o, int b,
-                                                 int c, int C, int hw) {
+__device__ __forceinline__ float ref_act_in_grad(const float* gu, const float* gate, const float* gpool,
+                                                 const float* rows, int o, int b, int c, int C, int hw) {
   if (!gu) return gpool[(size_t)b * C + c] / (float)hw;
   float ga = gu[o];
+  if (rows) ga *= rows[b];      // (plain form only: the launcher refuses rows with a gate or a pooled gradient)
   if (gate) ga = ga * gate[(size_t)b * C + c] + gpool[(size_t)b * C + c] / (float)hw;
   return ga;
 }
 
 __global__ __launch_bounds__(256) void ref_bn_act_bwd_sums_kernel(const float* __restrict__ gu, const float* gate,
-                                                                  const float* gpool, const float* __restrict__ x,
+                                                                  const float* gpool, const float* rows,
+                                                                  const float* __restrict__ x,
                                                                   const float* mean, const float* rstd,
                                                                   const float* gamma, const float* beta, int act,
                                                                   PadGeom g, float* dsum, float* dgamma, float* dbeta) {
@@ -449,7 +454,7 @@ __global__ __launch_bounds__(256) void ref_bn_act_bwd_sums_kernel(const float* _
   for (int p = threadIdx.x; p < g.npix; p += 256) {
     const int o = pad_offset(g, p) + c;
     const float xv = x[o];
-    const float gg = ref_act_in_grad(gu, gate, gpool, o, p / hw, c, g.C, hw) * ref_act_grad(xv * sc + sh, act);
+    const float gg = ref_act_in_grad(gu, gate, gpool, rows, o, p / hw, c, g.C, hw) * ref_act_grad(xv * sc + sh, act);
     s0 += gg; s1 += (double)gg * (double)((xv - mu) * rs);
   }
   red[0][threadIdx.x] = s0; red[1][threadIdx.x] = s1;
@@ -467,6 +472,7 @@ __global__ __launch_bounds__(256) void ref_bn_act_bwd_sums_kernel(const float* _
 
 // (gx may be gu: every element is read and written by the one thread that owns it)
 __global__ __launch_bounds__(256) void ref_bn_act_bwd_apply_kernel(const float* gu, const float* gate, const float* gpool,
+                                                                   const float* rows,
                                                                    const float* __restrict__ x, const float* mean,
                                                                    const float* rstd, const float* gamma,
                                                                    const float* beta, int act, const float* dsum,
@@ -479,7 +485,7 @@ __global__ __launch_bounds__(256) void ref_bn_act_bwd_apply_kernel(const float* 
   const float sc = gamma[c] * rs, sh = beta[c] - mu * sc;
   const float inv_n = 1.f / (float)g.npix;
   const float xv = x[o];
-  const float gg = ref_act_in_grad(gu, gate, gpool, o, p / hw, c, g.C, hw) * ref_act_grad(xv * sc + sh, act);
+  const float gg = ref_act_in_grad(gu, gate, gpool, rows, o, p / hw, c, g.C, hw) * ref_act_grad(xv * sc + sh, act);
   float v = sc * (gg - dsum[c] * inv_n - (xv - mu) * rs * dsum[g.C + c] * inv_n);
   if (gx_add) v += gx_add[o];
   gx[o] = v;
@@ -552,16 +558,33 @@ __global__ __launch_bounds__(256) void ref_dw_bwd_weight_kernel(const float* __r
   dw[idx] += (float)acc;
 }
 
-extern "C" int nbdt_ref_bn_act_apply(const float* x, const float* save_mean, const float* save_rstd, const float* gamma,
-                                     const float* beta, int32_t act, const float* gate, const float* residual, int32_t B,
-                                     int32_t H, int32_t W, int32_t C, float* y, void* stream) {
+static int ref_bn_act_apply_impl(const float* x, const float* save_mean, const float* save_rstd, const float* gamma,
+                                 const float* beta, int32_t act, const float* gate, const float* residual,
+                                 const float* row_scale, int32_t B, int32_t H, int32_t W, int32_t C, float* y,
+                                 void* stream) {
   NBDT_REQUIRE(x && save_mean && save_rstd && gamma && beta && y, "null argument");
+  NBDT_REQUIRE(!row_scale || (residual && !gate), "row_scale scales the branch of a residual add: it needs a residual and takes no gate");
   const PadGeom g = make_geom(B, H, W, C);
   const long long total = (long long)g.npix * C;
   hipLaunchKernelGGL(ref_bn_act_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
-                     save_mean, save_rstd, gamma, beta, act, gate, residual, g, y);
+                     save_mean, save_rstd, gamma, beta, act, gate, residual, row_scale, g, y);
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;
+}
+
+extern "C" int nbdt_ref_bn_act_apply(const float* x, const float* save_mean, const float* save_rstd, const float* gamma,
+                                     const float* beta, int32_t act, const float* gate, const float* residual, int32_t B,
+                                     int32_t H, int32_t W, int32_t C, float* y, void* stream) {
+  return ref_bn_act_apply_impl(x, save_mean, save_rstd, gamma, beta, act, gate, residual, nullptr, B, H, W, C, y, stream);
+}
+
+extern "C" int nbdt_ref_bn_act_apply_rows(const float* x, const float* save_mean, const float* save_rstd,
+                                          const float* gamma, const float* beta, int32_t act, const float* gate,
+                                          const float* residual, const float* row_scale, int32_t B, int32_t H, int32_t W,
+                                          int32_t C, float* y, void* stream) {
+  NBDT_REQUIRE(row_scale != nullptr, "null row_scale");
+  return ref_bn_act_apply_impl(x, save_mean, save_rstd, gamma, beta, act, gate, residual, row_scale, B, H, W, C, y,
+                               stream);
 }
 
 extern "C" int nbdt_ref_bn_act_pool(const float* x, const float* save_mean, const float* save_rstd, const float* gamma,
@@ -577,23 +600,43 @@ extern "C" int nbdt_ref_bn_act_pool(const float* x, const float* save_mean, cons
 
 /* nbdt_bn_act_bwd (sums + elementwise pass; reduce == 0: the pass only, with the caller's dsum -- not used by the engine:
  * its fused-sums form recomputes them here, see nbdt.ops.bn_act_bwd_apply) */
+static int ref_bn_act_bwd_impl(const float* gu, const float* row_scale, const float* gate, const float* gpool,
+                               const float* x, const float* save_mean, const float* save_rstd, const float* gamma,
+                               const float* beta, int32_t act, const float* gx_add, int32_t B, int32_t H, int32_t W,
+                               int32_t C, float* dsum, float* dgamma, float* dbeta, float* gx, void* stream) {
+  NBDT_REQUIRE(x && save_mean && save_rstd && gamma && beta && dsum && gx, "null argument");
+  NBDT_REQUIRE((gu && !gate && !gpool) || (gu && gate && gpool) || (!gu && !gate && gpool),
+               "gradient forms: gu | gu, gate, gpool | gpool");
+  NBDT_REQUIRE(!row_scale || (gu && !gate && !gpool),
+               "row_scale belongs to the plain form: an upstream gradient tensor, no gate, no pooled gradient");
+  hipStream_t st = (hipStream_t)stream;
+  const PadGeom g = make_geom(B, H, W, C);
+  hipLaunchKernelGGL(ref_bn_act_bwd_sums_kernel, dim3(C), dim3(256), 0, st, gu, gate, gpool, row_scale, x, save_mean,
+                     save_rstd, gamma, beta, act, g, dsum, dgamma, dbeta);
+  NBDT_LAUNCH_CHECK();
+  const long long total = (long long)g.npix * C;
+  hipLaunchKernelGGL(ref_bn_act_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, gu, gate, gpool,
+                     row_scale, x, save_mean, save_rstd, gamma, beta, act, dsum, gx_add, g, gx);
+  NBDT_LAUNCH_CHECK();
+  return NBDT_OK;
+}
+
 extern "C" int nbdt_ref_bn_act_bwd(const float* gu, const float* gate, const float* gpool, const float* x,
                                    const float* save_mean, const float* save_rstd, const float* gamma, const float* beta,
                                    int32_t act, const float* gx_add, int32_t B, int32_t H, int32_t W, int32_t C,
                                    float* dsum, float* dgamma, float* dbeta, float* gx, void* stream) {
-  NBDT_REQUIRE(x && save_mean && save_rstd && gamma && beta && dsum && gx, "null argument");
-  NBDT_REQUIRE((gu && !gate && !gpool) || (gu && gate && gpool) || (!gu && !gate && gpool),
-               "gradient forms: gu | gu, gate, gpool | gpool");
-  hipStream_t st = (hipStream_t)stream;
-  const PadGeom g = make_geom(B, H, W, C);
-  hipLaunchKernelGGL(ref_bn_act_bwd_sums_kernel, dim3(C), dim3(256), 0, st, gu, gate, gpool, x, save_mean, save_rstd,
-                     gamma, beta, act, g, dsum, dgamma, dbeta);
-  NBDT_LAUNCH_CHECK();
-  const long long total = (long long)g.npix * C;
-  hipLaunchKernelGGL(ref_bn_act_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, gu, gate, gpool,
-                     x, save_mean, save_rstd, gamma, beta, act, dsum, gx_add, g, gx);
-  NBDT_LAUNCH_CHECK();
-  return NBDT_OK;
+  return ref_bn_act_bwd_impl(gu, nullptr, gate, gpool, x, save_mean, save_rstd, gamma, beta, act, gx_add, B, H, W, C, dsum,
+                             dgamma, dbeta, gx, stream);
+}
+
+extern "C" int nbdt_ref_bn_act_bwd_rows(const float* gu, const float* row_scale, const float* gate, const float* gpool,
+                                        const float* x, const float* save_mean, const float* save_rstd,
+                                        const float* gamma, const float* beta, int32_t act, const float* gx_add, int32_t B,
+                                        int32_t H, int32_t W, int32_t C, float* dsum, float* dgamma, float* dbeta,
+                                        float* gx, void* stream) {
+  NBDT_REQUIRE(row_scale != nullptr, "null row_scale");
+  return ref_bn_act_bwd_impl(gu, row_scale, gate, gpool, x, save_mean, save_rstd, gamma, beta, act, gx_add, B, H, W, C,
+                             dsum, dgamma, dbeta, gx, stream);
 }
 
 static int ref_check_dw(int B, int H, int W, int C, int k, int stride) {

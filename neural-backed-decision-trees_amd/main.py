@@ -82,6 +82,12 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   checkpoint gains ``net_ema``, ``acc_ema`` and ``ema_updates`` and its name ``-ema``.  ``--resume`` restores the average
   when the checkpoint has one, else starts it from the loaded weights; ``--eval --resume --use-ema`` evaluates ``net_ema``.
   ``SoftTreeLoss`` keeps inducing hierarchies from the live classifier.  Every rank keeps its own, bit-identical, average.
+* ``--stochastic-depth P`` (``--arch efficientnet_b0``) is torchvision's ``StochasticDepth(p, mode="row")``: in training,
+  image ``b`` of MBConv unit ``i`` of 16 loses its branch with probability ``P * i / 16`` wherever the unit has a skip
+  connection, inside the residual add and the BatchNorm backward that run anyway, plus one launch per forward that
+  draws the factors (``engine.set_stochastic_depth(P, stream=rank)``: every rank and every micro-batch of
+  ``--accum-steps`` draws its own).  Evaluation and ``--eval`` ignore it.  The draw's counter is not saved: a resumed run
+  restarts it.
 """
 import argparse
 import json
@@ -232,6 +238,10 @@ def build_parser():
     p.add_argument("--clip-grad-norm", type=float, default=None, metavar="M",
                    help="clip the gradient's global L2 norm to M before every optimizer step, on the device "
                         "(engine.clip_grad_norm; torchvision's --clip-grad-norm).  Default: off")
+    p.add_argument("--stochastic-depth", type=float, default=0.0, metavar="P",
+                   help="stochastic depth (drop-connect) on the MBConv units with a skip connection, torchvision's "
+                        "StochasticDepth(P * i / 16, 'row') for unit i, in training only (--arch efficientnet_b0; the "
+                        "published recipe: 0.2).  Default 0: off")
     return p
 
 
@@ -511,6 +521,13 @@ def parse_args(argv=None):
         parser.error(f"--accum-steps must be >= 1, got {args.accum_steps}")
     if args.clip_grad_norm is not None and not 0.0 < args.clip_grad_norm < math.inf:
         parser.error(f"--clip-grad-norm must be finite and > 0, got {args.clip_grad_norm}")
+    if not 0.0 <= args.stochastic_depth < 1.0:
+        parser.error(f"--stochastic-depth must be in [0, 1), got {args.stochastic_depth}")
+    if args.stochastic_depth > 0 and not hasattr(getattr(getattr(models, args.arch), "engine_cls", None),
+                                                 "set_stochastic_depth"):
+        parser.error(f"--stochastic-depth is built into the MBConv residual passes: --arch {args.arch} has no "
+                     "set_stochastic_depth (the ResNet / WideResNet residual add lives inside conv epilogues); use "
+                     "--arch efficientnet_b0")
     if args.use_ema and not (args.eval and args.resume):
         parser.error("--use-ema evaluates a checkpoint's averaged weights: it needs --eval and --resume")
     if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
@@ -588,6 +605,8 @@ def main(argv=None):
         ops.set_deterministic(True)
     net = getattr(models, args.arch)(num_classes=num_classes, device=device, seed=args.seed)
     engine = net.engine
+    if args.stochastic_depth > 0 and not args.eval:      # every rank drops its own images; evaluation never drops any
+        engine.set_stochastic_depth(args.stochastic_depth, stream=rank)
 
     if not args.hierarchy and not args.path_graph and any("Tree" in l for l in args.loss) or args.analysis or args.diagnostics:
         args.hierarchy = args.hierarchy or f"induced-{args.arch}"       # reference nbdt/model.py:296-298 default

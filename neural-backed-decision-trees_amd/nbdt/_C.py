@@ -17,6 +17,7 @@ _lib = None
 
 NBDT_F32, NBDT_BF16, NBDT_F16 = 0, 1, 2
 NBDT_U8 = 3                     # nbdt_augment_batch's src_dtype for a uint8 dataset
+NBDT_SD_MAX_UNITS = 64          # nbdt_stochastic_depth_draw: the longest prob / scale table
 NBDT_AUGMENT_MAX_PAD = 32
 NBDT_RESIZED_CROP_RATIOS = 4096     # entries of nbdt_resized_crop_batch's aspect-ratio table
 NBDT_RESIZED_CROP_ATTEMPTS = 10
@@ -165,6 +166,10 @@ SIGNATURES = {
                                      _P]),
     "nbdt_ref_bn_act_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32, _P,
                                     _P, _P, _P, _P]),
+    "nbdt_ref_bn_act_apply_rows": (c_int, [_P, _P, _P, _P, _P, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P,
+                                           _P]),
+    "nbdt_ref_bn_act_bwd_rows": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32, c_int32, c_int32,
+                                         c_int32, _P, _P, _P, _P, _P]),
     "nbdt_ref_dwconv_fwd": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_ref_dwconv_bwd_data": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_ref_dwconv_bwd_weight": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
@@ -204,6 +209,12 @@ SIGNATURES = {
     "nbdt_se_param_grad": (c_int, [_P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P]),
     "nbdt_dropout_fwd": (c_int, [_P, c_int64, c_float, ctypes.c_uint32, _P, _P, _P]),
     "nbdt_dropout_bwd": (c_int, [_P, c_int64, c_float, _P, _P, _P]),
+    "nbdt_bn_act_apply_rows": (c_int, [_P, _P, _P, _P, _P, c_int32, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P,
+                                       _P]),
+    "nbdt_bn_act_bwd_rows": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32,
+                                     _P, _P, _P, _P, _P, _P]),
+    "nbdt_stochastic_depth_draw": (c_int, [ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint64, POINTER(c_float),
+                                           POINTER(c_float), c_int32, c_int32, _P, _P]),
     "nbdt_augment_batch": (c_int, [_P, c_int32, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
                                    POINTER(c_float), POINTER(c_float), POINTER(c_float), ctypes.c_uint64, ctypes.c_uint64,
                                    _P, _P, _P, _P, _P]),

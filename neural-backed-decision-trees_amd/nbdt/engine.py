@@ -2025,7 +2025,7 @@ class GraphedStep:
     step), while the graph serialises the cross-stream edges the eager schedule overlaps.  So this is latency insurance
     for slower hosts, not a speed-up, and bench.py does not use it.  The learning rate and the dropout
     seed are kernel arguments baked into the graph: build one GraphedStep per learning rate, and do not use it
-    for models with dropout.  A per-step learning rate is such a baked argument too, so a GraphedStep cannot be used with
+    for models with dropout or stochastic depth (its counter is such an argument too).  A per-step learning rate is such a baked argument too, so a GraphedStep cannot be used with
     learning-rate warm-up or a per-iteration decay (main.py --warmup-epochs, --lr-schedule cosine | poly).  So are the loss weights and the device pointers of the hierarchy: a replay after
     ``criterion.set_epoch`` changed the weights (--tswe / --xwe schedules) or after the hierarchy was re-induced
     (SoftTreeLoss) raises instead of silently using the captured ones; the captured tree handle is kept alive
@@ -2034,6 +2034,8 @@ class GraphedStep:
     def __init__(self, engine, criterion, img, targets, lr, momentum=0.9, weight_decay=5e-4, warmup=2):
         if getattr(engine, "dropout_rate", 0.0) > 0.0:
             raise ValueError("the dropout seed is a kernel argument: a captured step would repeat one mask")
+        if getattr(engine, "stochastic_depth_prob", 0.0) > 0.0:
+            raise ValueError("the stochastic depth counter is a kernel argument: a captured step would repeat one draw")
         if targets.is_floating_point():
             raise ValueError("GraphedStep captures class-index targets only; probability targets go through train_step")
         self.engine, self.criterion = engine, criterion

@@ -108,7 +108,7 @@ class SqueezeExcite:
 
 class EfficientNetEngine(_Engine):
     def __init__(self, num_classes=1000, dropout_rate=0.2, stages=B0_STAGES, init_channels=32,
-                 final_channels=1280, device="cuda", seed=0):
+                 final_channels=1280, device="cuda", seed=0, stochastic_depth_prob=0.0):
         super().__init__(device, seed)
         self.num_classes, self.dropout_rate = num_classes, float(dropout_rate)
         gen = self.gen
@@ -125,7 +125,8 @@ class EfficientNetEngine(_Engine):
                 pre = f"features.stage{i + 1}.unit{j + 1}."
                 mid = cin * exp
                 u = {"cin": cin, "cout": cout, "mid": mid, "k": k, "stride": stride, "exp": exp,
-                     "key": f"s{i + 1}u{j + 1}", "stage": i + 1, "residual": cin == cout and stride == 1}
+                     "key": f"s{i + 1}u{j + 1}", "stage": i + 1, "residual": cin == cout and stride == 1,
+                     "index": len(self.units)}
                 if i == 0:   # EffiDwsConvUnit: depthwise -> SE -> pointwise
                     u["conv1"] = u["bn1"] = None
                     u["dw"] = DepthwiseConv(self.store, pre + "dw_conv.conv.weight", mid, k, stride, gen)
@@ -158,6 +159,19 @@ class EfficientNetEngine(_Engine):
         self._side = side_stream(self.device)     # weight gradients on the process's second stream (see WRNEngine)
         for c in self.convs + self.dws:
             c.side_stream = self._side
+        self.sd_seed = seed            # stochastic depth: the draw hashes (sd_seed, sd_stream, sd_counter, unit, image)
+        self.sd_counter = 0            # the counter the NEXT training forward draws with; not saved: a resumed run restarts it
+        self._sd_rows = None           # the [units, B] table the last forward drew (None: it drew none) -- what backward reads
+        self.set_stochastic_depth(stochastic_depth_prob)
+
+    def set_stochastic_depth(self, prob, stream=0):
+        """torchvision's StochasticDepth(p, mode="row") on every unit with a skip connection: in training, image b of unit
+        i (0-based over ALL units) loses its branch with probability prob * i / len(units) and keeps it scaled by
+        1 / (1 - p_i) otherwise; evaluation never changes.  0 <= prob < 1, 0 switches it off.  stream: an id mixed into
+        the draw (main.py passes the rank, so the ranks of a data-parallel run drop different images)."""
+        flags = [u["residual"] for u in self.units]
+        self._sd_prob, self._sd_scale = ops.stochastic_depth_probs(prob, len(flags), flags)     # raises outside [0, 1)
+        self.stochastic_depth_prob, self.sd_stream = float(prob), int(stream)
 
     # ------------------------------------------------------------------ reference-named views
     def extra_param_views(self, buf):
@@ -239,6 +253,14 @@ class EfficientNetEngine(_Engine):
         self.bn0.stats(t0, training)
         bn = self.bn0
         ops.bn_act_apply(t0, bn.mean, bn.rstd, bn.gamma, bn.beta, x, act=ACT)
+        self._sd_rows = None
+        if training and self.stochastic_depth_prob > 0.0:
+            # ONE launch draws every unit's per-image factors; a unit's row rides in the residual add it already makes
+            # and in bn3's backward.  Like _mask, the table is what this forward's backward reads.
+            self._sd_rows = self._tensor("sd_rows", (len(self.units), B))
+            ops.stochastic_depth_draw(self._sd_rows, self._sd_prob, self._sd_scale, self.sd_seed, self.sd_stream,
+                                      self.sd_counter)
+            self.sd_counter += 1
         for u in self.units:
             k, s = u["key"], u["stride"]
             cin, mid, cout = _pad32(u["cin"]), _pad32(u["mid"]), _pad32(u["cout"])
@@ -279,8 +301,12 @@ class EfficientNetEngine(_Engine):
                 u["conv3"].forward(d_se, p_raw, bn_scratch=self.partials(p_raw) if fuse else None)
                 bn = u["bn3"]
                 bn.stats(p_raw, training, fused=fuse)
-                ops.bn_act_apply(p_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, out, act=ops.ACT_NONE,
-                                 residual=x if u["residual"] else None)
+                if u["residual"] and self._sd_rows is not None:
+                    ops.bn_act_apply(p_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, out, act=ops.ACT_NONE, residual=x,
+                                     row_scale=self._sd_rows[u["index"]])
+                else:
+                    ops.bn_act_apply(p_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, out, act=ops.ACT_NONE,
+                                     residual=x if u["residual"] else None)
             u["x_in"], u["hw_in"] = x, (h, w)
             x, h, w = out, ho, wo
         self._x_last, self._hw = x, (h, w)
@@ -343,8 +369,14 @@ class EfficientNetEngine(_Engine):
             gp = self.buf(f"gp_{cout}_{ho}_{par}{tag}", B, ho, wo, cout)
             gd = self.buf(f"gd_{mid}_{ho}_{par}{tag}", B, ho, wo, mid)
             bn = u["bn3"]
-            ops.bn_act_bwd(g, p_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
-                           st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), gp, act=ops.ACT_NONE)
+            if u["residual"] and self._sd_rows is not None:
+                # out = x_in + r[b] * bn3(p_raw): the branch gradient is g * r[b]; g itself stays the skip gradient
+                ops.bn_act_bwd(g, p_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
+                               st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), gp, act=ops.ACT_NONE,
+                               row_scale=self._sd_rows[u["index"]])
+            else:
+                ops.bn_act_bwd(g, p_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
+                               st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), gp, act=ops.ACT_NONE)
             u["conv3"].backward_weight(d_se, gp)
             u["conv3"].backward_data(gp, gd)
             # squeeze-and-excitation + BatchNorm/swish of the depthwise output (gd rewritten in place)

@@ -12,6 +12,7 @@ the transposed, tap-reversed copy ``[cin][taps][cout]`` produced by ``weight_pre
 import contextlib
 import ctypes
 
+import numpy as np
 import torch
 
 from nbdt import _C
@@ -1009,8 +1010,16 @@ class EmaTable:
 ACT_NONE, ACT_RELU, ACT_SWISH = 0, 1, 2
 
 
-def bn_act_apply(x, mean, rstd, gamma, beta, y, act=ACT_SWISH, gate=None, residual=None):
+def bn_act_apply(x, mean, rstd, gamma, beta, y, act=ACT_SWISH, gate=None, residual=None, row_scale=None):
+    """row_scale (fp32 [B], device; stochastic depth): y = residual + row_scale[b] * act(bn(x)) through
+    nbdt_bn_act_apply_rows, which needs a residual and refuses a gate.  None: the call made without it."""
     B, H, W, C = _dims(x)
+    if row_scale is not None:
+        _check_rows(row_scale, B, x.device)
+        fn = lib().nbdt_ref_bn_act_apply_rows if _ref(x) else lib().nbdt_bn_act_apply_rows
+        check(fn(ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), act, ptr(gate), ptr(residual), ptr(row_scale), B, H,
+                 W, C, ptr(y), stream_ptr(x.device)))
+        return
     if _ref(x):
         check(lib().nbdt_ref_bn_act_apply(ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), act, ptr(gate),
                                           ptr(residual), B, H, W, C, ptr(y), stream_ptr(x.device)))
@@ -1031,8 +1040,20 @@ def bn_act_pool(x, mean, rstd, gamma, beta, out, act=ACT_SWISH, mul=None, scale=
 
 
 def bn_act_bwd(gu, x, mean, rstd, gamma, beta, scratch, dsum, dgamma, dbeta, gx, act=ACT_SWISH, gate=None,
-               gpool=None, gx_add=None):
+               gpool=None, gx_add=None, row_scale=None):
+    """row_scale (fp32 [B], device; stochastic depth): the gradient entering the activation is gu * row_scale[b], through
+    nbdt_bn_act_bwd_rows -- the plain form only (gu given, no gate, no gpool).  None: the call made without it."""
     B, H, W, C = _dims(x)
+    if row_scale is not None:
+        _check_rows(row_scale, B, x.device)
+        head = (ptr(gu), ptr(row_scale), ptr(gate), ptr(gpool), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), act,
+                ptr(gx_add), B, H, W, C)
+        tail = (ptr(dsum), ptr(dgamma), ptr(dbeta), ptr(gx), stream_ptr(x.device))
+        if _ref(x):
+            check(lib().nbdt_ref_bn_act_bwd_rows(*head, *tail))
+        else:
+            check(lib().nbdt_bn_act_bwd_rows(*head, ptr(scratch), *tail))
+        return
     if _ref(x):
         check(lib().nbdt_ref_bn_act_bwd(ptr(gu), ptr(gate), ptr(gpool), ptr(x), ptr(mean), ptr(rstd), ptr(gamma),
                                         ptr(beta), act, ptr(gx_add), B, H, W, C, ptr(dsum), ptr(dgamma), ptr(dbeta),
@@ -1041,6 +1062,77 @@ def bn_act_bwd(gu, x, mean, rstd, gamma, beta, scratch, dsum, dgamma, dbeta, gx,
     check(lib().nbdt_bn_act_bwd(ptr(gu), ptr(gate), ptr(gpool), ptr(x), ptr(mean), ptr(rstd), ptr(gamma),
                                 ptr(beta), act, ptr(gx_add), B, H, W, C, ptr(scratch), ptr(dsum), ptr(dgamma),
                                 ptr(dbeta), ptr(gx), stream_ptr(x.device)))
+
+
+def _check_rows(row_scale, B, device):
+    if not (row_scale.is_cuda and row_scale.device == device and row_scale.dtype == torch.float32 and
+            row_scale.is_contiguous() and tuple(row_scale.shape) == (B,)):
+        raise _C.NBDTHipError(f"row_scale must be a contiguous fp32 [{B}] tensor on {device}, got {row_scale.dtype} "
+                              f"{tuple(row_scale.shape)} on {row_scale.device}")
+
+
+def stochastic_depth_probs(P, n_units, residual_flags):
+    """The host tables of nbdt_stochastic_depth_draw for torchvision's linear rule: unit i of n_units (0-based over ALL
+    units) drops with p_i = P * i / n_units where residual_flags[i], never elsewhere.  Returns (prob, scale), numpy fp32
+    [n_units]: prob = float32(p_i) is what the kernel compares its uniform with, scale = float32(1 / (1 - prob)), formed in
+    double from that fp32 prob and rounded once; (0, 1) for a unit without a skip."""
+    P = float(P)
+    if not 0.0 <= P < 1.0:
+        raise ValueError(f"the stochastic depth probability must be in [0, 1), got {P}")
+    flags = [bool(f) for f in residual_flags]
+    if len(flags) != int(n_units) or not 0 < len(flags) <= _C.NBDT_SD_MAX_UNITS:
+        raise ValueError(f"residual_flags must name each of the {n_units} units (at most {_C.NBDT_SD_MAX_UNITS})")
+    prob = np.asarray([P * i / len(flags) if f else 0.0 for i, f in enumerate(flags)], dtype=np.float64).astype(np.float32)
+    scale = (1.0 / (1.0 - prob.astype(np.float64))).astype(np.float32)
+    return prob, scale
+
+
+def _sd_host(v, what):
+    a = np.ascontiguousarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v)
+    if a.dtype != np.float32 or a.ndim != 1:
+        raise ValueError(f"{what} must be a one-dimensional fp32 host table, got {a.dtype} {a.shape}")
+    return a
+
+
+def stochastic_depth_draw(table, prob, scale, seed, stream, counter):
+    """nbdt_stochastic_depth_draw: ONE launch writes table [U, B] fp32 (device) = 0 where image b of unit i is dropped,
+    scale[i] where it is kept.  prob / scale: the host tables of stochastic_depth_probs; `stream` is the draw's stream
+    id (a rank), not a HIP stream."""
+    prob, scale = _sd_host(prob, "prob"), _sd_host(scale, "scale")
+    _C.require_gpu(table, "stochastic_depth_draw")
+    U, B = table.shape
+    if table.dtype != torch.float32 or not table.is_contiguous() or prob.shape != (U,) or scale.shape != (U,):
+        raise _C.NBDTHipError(f"stochastic_depth_draw: table must be contiguous fp32 [U, B] with prob / scale of length U, "
+                              f"got {table.dtype} {tuple(table.shape)}, prob {prob.shape}, scale {scale.shape}")
+    mask = (1 << 64) - 1
+    fp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    check(lib().nbdt_stochastic_depth_draw(int(seed) & mask, int(stream) & mask, int(counter) & mask, fp(prob), fp(scale),
+                                           U, B, ptr(table), stream_ptr(table.device)))
+
+
+_M64 = (1 << 64) - 1
+
+
+def _mix64(x):      # splitmix64's finaliser: nbdt/data.py _mix64, csrc/effnet.hip mix64
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def draw_stochastic_depth(seed, stream, counter, prob, scale, B):
+    """The generator of nbdt_stochastic_depth_draw (include/nbdt_hip.h), restated with numpy: the fp32 [U, B] table, bit
+    for bit.  A pure function of (seed, stream, counter, unit, image)."""
+    prob, scale = _sd_host(prob, "prob"), _sd_host(scale, "scale")
+    U = prob.shape[0]
+    u64 = np.uint64
+    golden, k = 0x9E3779B97F4A7C15, u64(0xD1342543DE82EF95)
+    with np.errstate(over="ignore"):
+        key = _mix64(np.asarray([(int(seed) * golden + int(counter)) & _M64], dtype=u64))
+        key = _mix64(key ^ (u64(int(stream) & _M64) * k))[0]
+        elem = (np.arange(U, dtype=u64)[:, None] << u64(32)) | np.arange(int(B), dtype=u64)[None, :]
+        r = _mix64(key ^ (elem * k))
+    u = (r >> u64(40)).astype(np.float32) * np.float32(2.0 ** -24)
+    return np.where(u < prob[:, None], np.float32(0.0), scale[:, None]).astype(np.float32)
 
 
 def dwconv_fwd(x, w, y, k, stride, bn_scratch=None):
