@@ -1158,6 +1158,73 @@ int nbdt_policy_batch_sharded(const void* src, int32_t src_dtype, const int64_t*
                               const int32_t* policy_in, float* out, int64_t* labels_out, int8_t* params_out,
                               int32_t* policy_out, void* stream);
 
+/* ------------------------------------------------------------------ policy chains (nbdt_version() >= 123) */
+/* RandAugment and AutoAugment: nbdt_policy_batch with up to NBDT_CHAIN_MAX_OPS operations per image, still ONE launch per
+ * batch (policy_chain_kernel, csrc/policy.hip).  Order: gather, zero-padded crop, flip, the chain on the bytes, /255 and
+ * Normalize, erase.  After the crop the source tile is free, so the chain ping-pongs between the two LDS tiles: every
+ * non-Identity slot but the last is one byte pass, the last one is evaluated inside the normalising output pass, the
+ * per-image statistics (grey sum, minima / maxima, histograms) are collected again on the tile an operation reads.  An
+ * Identity slot costs nothing.  The LDS budget, so the 3*H*W <= 49152 limit and the uint8-only source, are
+ * nbdt_policy_batch's, and so are the arguments src .. std, erase_prob .. epoch, params_in, out, labels_out, params_out.
+ *
+ * Pixel rules: those of nbdt_policy_batch for op 0 .. 13, fill byte 0, plus op 14 = Invert (255 - v): NBDT_CHAIN_OPS = 15.
+ * Magnitudes for a policy with n = nbins bins, bin b, s = +1 (sign 0) or -1 (sign 1), each formed in double as hi*b/(n-1)
+ * (torchvision's _augmentation_space of RandAugment, n = 31, and of AutoAugment, n = 10; nbdt/data.py chain_table):
+ *   ShearX, ShearY      m = s*0.3*b/(n-1)
+ *   TranslateX          t = s*int((150/331)*W*b/(n-1)) pixels, source x - t;   TranslateY: the same with H
+ *   Rotate              s*30*b/(n-1) degrees
+ *   Brightness, Color, Contrast, Sharpness   factor 1 + s*0.9*b/(n-1)
+ *   Posterize           bits = 8 - round(b / ((n-1)/4));   Solarize: threshold 255 - 255*b/(n-1)
+ *   Identity, AutoContrast, Equalize, Invert   none
+ * Pillow with these double magnitudes is the oracle; parity with torchvision's own float32 linspace magnitudes and its
+ * atan/tan shear round trip is NOT claimed.
+ *   mode          NBDT_CHAIN_RAND | NBDT_CHAIN_SUBPOLICY
+ *   nbins         1 .. NBDT_CHAIN_MAX_BINS
+ *   table         int32 [NBDT_CHAIN_OPS][nbins][2][6], DEVICE memory, rows in the form of policy_table
+ *   num_ops, magnitude   NBDT_CHAIN_RAND: 1 .. NBDT_CHAIN_MAX_OPS slots, each at bin `magnitude` < nbins (ignored otherwise)
+ *   subpolicies, P       NBDT_CHAIN_SUBPOLICY: int32 [P][NBDT_CHAIN_MAX_OPS][3] of (op, q = round(p * 2^24), bin), DEVICE
+ *                 memory, P in 1 .. NBDT_CHAIN_MAX_SUBPOLICIES; an unused slot is op 0 / q 0.  The host reads nothing from it:
+ *                 the kernel clamps op to [0, 14], q to [0, 2^24], bin to [0, nbins-1]
+ *   chain_in      optional int32 [B][NBDT_CHAIN_MAX_OPS][3] (op, bin, sign), device memory: REPLACES the chain's draw; clamped
+ *                 by the kernel: op to [0, 14], bin to [0, nbins-1], sign is (value != 0)
+ *   erase_in      optional int32 [B][4] (top, left, h, w), device memory: REPLACES the erase draw; clamped as policy_in's
+ *   chain_out, erase_out   optional, the values actually used; a skipped or unused slot is Identity (0, 0, 0)
+ *
+ * The draw.  The crop / flip word and the erase word `re` are nbdt_policy_batch's: a sample gets the same crop and the same
+ * erase rectangle under every policy setting.  The chain adds, with mix64, key and G as above:
+ *   rc = mix64(key ^ (index * 0x8EBC6AF09C88C6E3));   slot k = 0 .. 3:  rs = mix64(rc + (k+1) * G)
+ *   NBDT_CHAIN_RAND, k < num_ops:   op = ((rs & 0xFFFFFF) * 14) >> 24 (Invert is not in its space);  bin = magnitude;
+ *                                   sign = rs >> 63
+ *   NBDT_CHAIN_SUBPOLICY:   the sub-policy is ((rc & 0xFFFFFF) * P) >> 24; its slot k = (op, q, bin) is applied when
+ *                           (rs & 0xFFFFFF) < q (exact: p = 0 never, p = 1 always; it replaces torchvision's rand() <= p),
+ *                           with sign = 1 - (rs >> 63) (negative magnitude when the sign bit is 0, torchvision's
+ *                           signs[i] == 0); a slot that is not applied is Identity
+ * A pure function of (seed, epoch, dataset index) and the settings (nbdt/data.py draw_chain_params restates it).
+ * Integer statistics, as for nbdt_policy_batch: the same inputs give the same bits.  Out-of-range indices: a zero image,
+ * label -1, zero params.  nbdt_policy_batch itself is unchanged and keeps refusing policy = 2. */
+#define NBDT_CHAIN_OPS 15
+#define NBDT_CHAIN_MAX_OPS 4
+#define NBDT_CHAIN_MAX_BINS 31
+#define NBDT_CHAIN_MAX_SUBPOLICIES 1024
+#define NBDT_CHAIN_RAND 0
+#define NBDT_CHAIN_SUBPOLICY 1
+int nbdt_policy_chain_batch(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index, int32_t B,
+                            int64_t N, int32_t H, int32_t W, int32_t pad, int32_t flip, const float* mean,
+                            const float* std, int32_t mode, int32_t nbins, const int32_t* table, int32_t num_ops,
+                            int32_t magnitude, const int32_t* subpolicies, int32_t P, double erase_prob,
+                            const double* erase_scale, const double* erase_ratio, const double* ratio_table, uint64_t seed,
+                            uint64_t epoch, const int8_t* params_in, const int32_t* chain_in, const int32_t* erase_in,
+                            float* out, int64_t* labels_out, int8_t* params_out, int32_t* chain_out, int32_t* erase_out,
+                            void* stream);
+int nbdt_policy_chain_batch_sharded(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index,
+                                    int64_t index_base, int32_t B, int64_t N, int32_t H, int32_t W, int32_t pad,
+                                    int32_t flip, const float* mean, const float* std, int32_t mode, int32_t nbins,
+                                    const int32_t* table, int32_t num_ops, int32_t magnitude, const int32_t* subpolicies,
+                                    int32_t P, double erase_prob, const double* erase_scale, const double* erase_ratio,
+                                    const double* ratio_table, uint64_t seed, uint64_t epoch, const int8_t* params_in,
+                                    const int32_t* chain_in, const int32_t* erase_in, float* out, int64_t* labels_out,
+                                    int8_t* params_out, int32_t* chain_out, int32_t* erase_out, void* stream);
+
 /* ------------------------------------------------------------------ measurement probe (not on the product path) */
 /* A register-only stream of independent v_mfma_f32_32x32x16_bf16 on `blocks` CUs (one 512-thread block each, two waves
  * per SIMD): every wave issues iters x 16 of them (x 32768 flop).  bench.py times the launch for `roofline.mfma_stream`

@@ -60,6 +60,10 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   one batch-assembly launch of ``--augment reference`` (``nbdt.data.DeviceDataset(policy=, erase_prob=)``,
   ``nbdt_policy_batch``): gather, padded crop, flip, the operation on the bytes, normalise, erase.  Both need a uint8
   ``--data-file``; ``--augment resized-crop`` does not have them.  MixUp / CutMix still run on the assembled batch.
+* ``--auto-augment ra`` (RandAugment: ``--ra-num-ops`` N in 1..4 operations per image, each uniform among the 14, at bin
+  ``--ra-magnitude`` M in 0..30 with a random sign) and ``--auto-augment cifar10`` (AutoAugment's CIFAR-10 policy: one of 25
+  sub-policies of two (op, probability, magnitude) slots per image) run the whole chain in the same launch
+  (``nbdt_policy_chain_batch``; ``DeviceDataset(policy="ra" | "cifar10")``), under the preconditions of ``ta_wide``.
 * ``--optimizer lars`` replaces the SGD pass with layer-wise adaptive rate scaling (You et al. 2017; apex's
   ``LARC(clip=False)`` around ``optim.SGD``): ``engine.lars_step``, three launches over the flat parameter arena.
   ``--lars-trust`` / ``--lars-eps`` are its coefficients; BatchNorm parameters and biases take plain SGD steps without decay
@@ -178,9 +182,13 @@ def build_parser():
                    help="--augment reference | resized-crop: every rank keeps only its contiguous part of both splits on "
                         "its GPU (nbdt.data shard=(rank, world)), a --data-file is memory-mapped, and training shuffles "
                         "within each rank's part")
-    p.add_argument("--auto-augment", choices=("none", "ta_wide"), default="none",
-                   help="ta_wide: TrivialAugmentWide, one of 14 operations at one of 31 magnitudes per training image, inside "
-                        "the batch-assembly launch (--augment reference on a uint8 --data-file; nbdt.data policy='ta_wide')")
+    p.add_argument("--auto-augment", choices=("none", "ta_wide", "ra", "cifar10"), default="none",
+                   help="ta_wide: TrivialAugmentWide, one of 14 operations at one of 31 magnitudes per training image; ra: "
+                        "RandAugment, --ra-num-ops operations at magnitude --ra-magnitude; cifar10: AutoAugment's CIFAR-10 "
+                        "policy (25 sub-policies of two operations).  All inside the batch-assembly launch (--augment "
+                        "reference on a uint8 --data-file; nbdt.data DeviceDataset(policy=))")
+    p.add_argument("--ra-num-ops", type=int, default=2, metavar="N", help="RandAugment: operations per image, 1..4")
+    p.add_argument("--ra-magnitude", type=int, default=9, metavar="M", help="RandAugment: the magnitude bin, 0..30")
     p.add_argument("--random-erase", type=float, default=0.0, metavar="P",
                    help="torchvision's RandomErasing(P, value=0) on every training image after the normalisation, in the "
                         "same launch (--augment reference on a uint8 --data-file); 0: off")
@@ -480,6 +488,10 @@ def parse_args(argv=None):
                      "resized-crop")
     if not 0.0 <= args.random_erase <= 1.0:
         parser.error(f"--random-erase must be in [0, 1], got {args.random_erase}")
+    if not 1 <= args.ra_num_ops <= 4:
+        parser.error(f"--ra-num-ops must be 1..4, got {args.ra_num_ops}")
+    if not 0 <= args.ra_magnitude <= 30:
+        parser.error(f"--ra-magnitude must be 0..30, got {args.ra_magnitude}")
     if args.auto_augment != "none" or args.random_erase > 0:
         if args.augment == "resized-crop":
             parser.error("--auto-augment / --random-erase on --augment resized-crop is not built: the policy runs in the "
@@ -577,11 +589,17 @@ def main(argv=None):
                              f"not {train_x.dtype}")
         try:           # only the training split is augmented; evaluation never applies a policy
             train_x = DeviceDataset(train_x, train_y, stats["mean"], stats["std"], stats["pad"], policy=policy,
-                                    erase_prob=args.random_erase, **kwargs)
+                                    erase_prob=args.random_erase, policy_ops=args.ra_num_ops,
+                                    policy_magnitude=args.ra_magnitude, **kwargs)
         except ValueError as e:
             if policy or args.random_erase > 0:        # e.g. images too large for the policy kernel
                 raise SystemExit(f"--auto-augment / --random-erase: {e}") from e
             raise
+        if train_x.chain:
+            log("--auto-augment " + (f"ra: RandAugment, {args.ra_num_ops} operations at magnitude {args.ra_magnitude}"
+                                     if policy == "ra" else
+                                     f"{policy}: AutoAugment, {len(train_x._subpolicies)} sub-policies")
+                + " per training image, in the batch-assembly launch (nbdt_policy_chain_batch)")
         test_x = DeviceDataset(test_x, test_y, stats["mean"], stats["std"], stats["pad"], **kwargs)
     elif args.augment == "resized-crop":
         stats = RESIZED_CROP_STATS[args.dataset]

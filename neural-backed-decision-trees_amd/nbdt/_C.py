@@ -24,6 +24,11 @@ NBDT_RESIZED_CROP_ATTEMPTS = 10
 NBDT_POLICY_NONE, NBDT_POLICY_TA_WIDE = 0, 1
 NBDT_POLICY_OPS = 14               # nbdt_policy_batch: TrivialAugmentWide's operations ...
 NBDT_POLICY_BINS = 31               # ... and magnitude bins
+NBDT_CHAIN_OPS = 15                 # nbdt_policy_chain_batch: the 14 and Invert
+NBDT_CHAIN_MAX_OPS = 4              # slots of a chain
+NBDT_CHAIN_MAX_BINS = 31
+NBDT_CHAIN_MAX_SUBPOLICIES = 1024
+NBDT_CHAIN_RAND, NBDT_CHAIN_SUBPOLICY = 0, 1
 _ZTYPE = {torch.float32: NBDT_F32, torch.bfloat16: NBDT_BF16, torch.float16: NBDT_F16}
 
 
@@ -236,6 +241,15 @@ SIGNATURES = {
                                           c_int32, POINTER(c_float), POINTER(c_float), c_int32, _P, ctypes.c_double,
                                           POINTER(ctypes.c_double), POINTER(ctypes.c_double), _P, ctypes.c_uint64,
                                           ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P]),
+    "nbdt_policy_chain_batch": (c_int, [_P, c_int32, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                        POINTER(c_float), POINTER(c_float), c_int32, c_int32, _P, c_int32, c_int32, _P,
+                                        c_int32, ctypes.c_double, POINTER(ctypes.c_double), POINTER(ctypes.c_double), _P,
+                                        ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "nbdt_policy_chain_batch_sharded": (c_int, [_P, c_int32, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32, c_int32,
+                                                c_int32, POINTER(c_float), POINTER(c_float), c_int32, c_int32, _P, c_int32,
+                                                c_int32, _P, c_int32, ctypes.c_double, POINTER(ctypes.c_double),
+                                                POINTER(ctypes.c_double), _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P,
+                                                _P, _P, _P, _P, _P, _P]),
     "nbdt_stem_patches": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_maxpool3x3s2_fwd": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
     "nbdt_maxpool3x3s2_bwd": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),

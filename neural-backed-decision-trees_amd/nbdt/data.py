@@ -12,6 +12,8 @@ form, ``nbdt_resized_crop_batch`` (csrc/resample.hip): the crop box is drawn in 
 restates the draw) and resampled with PIL's bilinear filter, byte for byte (``resample_reference`` restates the pixels; it
 is documentation and test infrastructure, never called on the training path).
 
+``DeviceDataset(policy="ra" | "cifar10" | [sub-policies])`` chains up to four such operations per image (RandAugment,
+AutoAugment) in one launch of ``nbdt_policy_chain_batch`` (``draw_chain_params``, ``chain_reference``, ``chain_table``).
 ``DeviceDataset(policy="ta_wide", erase_prob=p)`` adds an augmentation policy to the padded-crop family without leaving the
 one launch: ``nbdt_policy_batch`` (csrc/policy.hip) applies one TrivialAugmentWide operation to the cropped and flipped
 bytes, with Pillow's pixel rules, before the normalisation, and torchvision's RandomErasing after it
@@ -134,6 +136,11 @@ class DeviceDataset:
     ``(0 - mean)/std`` -- a file normalised with the dataset's statistics then yields the same batches as its uint8
     original.  pad: pixels of zero padding before the random ``H x W`` crop; flip: random horizontal flip.
 
+    policy="ra": RandAugment -- `policy_ops` (1..4) operations per training sample, each uniform among POLICY_OPS at bin
+    `policy_magnitude` (0..30) with a random sign; policy="cifar10" or a list of sub-policies (``subpolicy_array``'s form):
+    AutoAugment -- one sub-policy per sample, each of its slots applied with its probability.  Both run the whole chain in
+    ``nbdt_policy_chain_batch``, one launch per batch, with the crop, flip and erase rectangle of every other setting.
+
     policy="ta_wide": every training sample gets one TrivialAugmentWide operation (POLICY_OPS, 31 magnitude bins) between the
     flip and the normalisation; erase_prob > 0: torchvision's RandomErasing(p, erase_scale, erase_ratio, value=0) after the
     normalisation.  Both need a uint8 `x` of at most 49152 bytes per image and run in ``nbdt_policy_batch``, still one launch
@@ -145,13 +152,20 @@ class DeviceDataset:
     """
 
     def __init__(self, x, y, mean, std, pad, flip=True, fill=None, device="cuda", shard=None, policy=None, erase_prob=0.0,
-                 erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3)):
+                 erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3), policy_ops=2, policy_magnitude=9):
         device = torch.device(device)
         if device.type != "cuda":
             raise _C.NBDTHipError(f"DeviceDataset lives on an MI355X, not on {device} (no CPU fallback)")
-        if policy not in (None, "ta_wide"):
-            raise ValueError(f"policy must be None or 'ta_wide', got {policy!r}")
+        self._subpolicies = None          # int32 [P,4,3] on the host: the policy is a list of sub-policies (AutoAugment)
+        if isinstance(policy, (list, tuple)) or policy == "cifar10":
+            self._subpolicies = subpolicy_array(policy)
+        elif policy == "ra":
+            policy_ops, policy_magnitude = _check_ra(policy_ops, policy_magnitude)
+        elif policy not in (None, "ta_wide"):
+            raise ValueError(f"policy must be None, 'ta_wide', 'ra', 'cifar10' or a list of sub-policies, got {policy!r}")
         self.policy = policy
+        self.chain = policy is not None and policy != "ta_wide"       # RandAugment / AutoAugment: nbdt_policy_chain_batch
+        self.policy_ops, self.policy_magnitude = policy_ops, policy_magnitude
         self.erase_prob = _check_erase(erase_prob, erase_scale, erase_ratio)
         self.erase_scale = tuple(float(v) for v in erase_scale)
         self.erase_ratio = tuple(float(v) for v in erase_ratio)
@@ -175,6 +189,7 @@ class DeviceDataset:
         self.x, self.y, self.shard_range, self.global_size = _place("DeviceDataset", x, y, shard, device)
         self.device = self.x.device
         self._policy_tables = None        # (policy table, ratio table) on the device, built by the first policy batch
+        self._chain_tables = None         # (chain table, sub-policies or None) on the device, likewise
 
     def __len__(self):
         return self.x.shape[0]
@@ -191,8 +206,55 @@ class DeviceDataset:
                                    torch.from_numpy(ratio_table(self.erase_ratio).copy()).to(self.device))
         return self._policy_tables
 
+    def _chain(self):
+        if self._chain_tables is None:
+            H, W = self.x.shape[2], self.x.shape[3]
+            table = chain_table("ra" if self.policy == "ra" else "cifar10", H, W)
+            subs = None if self._subpolicies is None else torch.from_numpy(self._subpolicies).to(self.device)
+            self._chain_tables = (torch.from_numpy(table.copy()).to(self.device), subs)
+        return self._chain_tables
+
+    def _batch_chain(self, index, img, targets, pad, flip, seed, epoch, params, used, base, chain_params, erase_params,
+                     return_chain_params, return_erase_params):
+        B, H, W = index.shape[0], self.x.shape[2], self.x.shape[3]
+        table, subs = self._chain()
+        nbins = table.shape[1]
+
+        def device_rows(v, name, shape, ok, what):
+            if not isinstance(v, torch.Tensor):
+                v = torch.as_tensor(np.asarray(v))
+            if tuple(v.shape) != shape or v.is_floating_point() or v.dtype == torch.bool:
+                raise ValueError(f"{name} must be integer {list(shape)}, got {v.dtype} {tuple(v.shape)}")
+            if not v.is_cuda:
+                if not bool(ok(v.long()).all()):
+                    raise ValueError(f"{name} outside {what}")
+                v = v.to(self.device, non_blocking=True)
+            _C.require_gpu(v, "DeviceDataset.batch")
+            return v.to(dtype=torch.int32).contiguous()
+        if chain_params is not None:
+            chain_params = device_rows(
+                chain_params, "chain_params", (B, CHAIN_MAX_OPS, 3),
+                lambda p: (p[..., 0] >= 0) & (p[..., 0] < len(CHAIN_OPS)) & (p[..., 1] >= 0) & (p[..., 1] < nbins)
+                & (p[..., 2] >= 0) & (p[..., 2] <= 1),
+                f"op in [0, {len(CHAIN_OPS) - 1}], bin in [0, {nbins - 1}], sign in {{0, 1}}")
+        if erase_params is not None:
+            erase_params = device_rows(
+                erase_params, "erase_params", (B, 4),
+                lambda p: (p >= 0).all(dim=1) & (p[:, 0] + p[:, 2] <= H) & (p[:, 1] + p[:, 3] <= W),
+                f"the {H} x {W} image")
+        ratios = self._tables()[1]
+        cused = torch.empty((B, CHAIN_MAX_OPS, 3), dtype=torch.int32, device=self.device) if return_chain_params else None
+        eused = torch.empty((B, 4), dtype=torch.int32, device=self.device) if return_erase_params else None
+        ops.policy_chain_batch(self.x, self.y, index, img, targets, pad, flip, self.mean, self.std, table, nbins,
+                               num_ops=self.policy_ops, magnitude=self.policy_magnitude, subpolicies=subs,
+                               erase_prob=self.erase_prob, erase_scale=self.erase_scale, erase_ratio=self.erase_ratio,
+                               ratio_table=ratios, seed=seed, epoch=epoch, params_in=params, chain_in=chain_params,
+                               erase_in=erase_params, params_out=used, chain_out=cused, erase_out=eused, index_base=base)
+        return cused, eused
+
     def batch(self, index, epoch=0, seed=0, train=True, params=None, return_params=False, policy_params=None,
-              return_policy_params=False):
+              return_policy_params=False, chain_params=None, return_chain_params=False, erase_params=None,
+              return_erase_params=False):
         """(img fp32 [B,3,H,W], targets int64 [B][, params int8 [B,3]]) for the samples `index`, in ONE launch on torch's
         current stream.
 
@@ -209,6 +271,15 @@ class DeviceDataset:
         the kernel.  Without it the draw is ``draw_policy_params(seed, epoch, index, H, W, erase_prob, erase_scale,
         erase_ratio)`` (every op is Identity when policy is None).  return_policy_params appends the int32 [B,7] used.
         train=False never applies a policy.  With neither setting nor argument the launch is nbdt_augment_batch, untouched.
+
+        With ``policy="ra"``, ``"cifar10"`` or a list of sub-policies a training batch is ONE launch of
+        nbdt_policy_chain_batch: the same crop, flip and erase rectangle, and between flip and normalisation the chain of
+        up to four operations ``draw_chain_params(seed, epoch, index, policy, policy_ops, policy_magnitude)`` draws.
+        chain_params: integer [B,4,3] of (op, bin, sign) per slot (op indexes CHAIN_OPS, Identity for an unused slot)
+        replaces that draw; erase_params: integer [B,4] of (top, left, h, w) replaces the erase draw; a CPU tensor is
+        range-checked and copied, a device tensor is clamped by the kernel.  return_chain_params / return_erase_params
+        append the int32 [B,4,3] / [B,4] used, in that order, after the other returns.  These four arguments belong to
+        the chain policies (policy_params / return_policy_params to None and "ta_wide"): the other kind is a ValueError.
 
         Every call returns freshly allocated tensors (torch's caching allocator): train_step is asynchronous and the engine
         keeps `img` until the stem's weight gradient, so nothing handed out is ever overwritten by a later call."""
@@ -257,10 +328,25 @@ class DeviceDataset:
                 policy_params = policy_params.to(self.device, non_blocking=True)
             _C.require_gpu(policy_params, "DeviceDataset.batch")
             policy_params = policy_params.to(dtype=torch.int32).contiguous()
+        chain_args = chain_params is not None or erase_params is not None or return_chain_params or return_erase_params
+        if chain_args and not self.chain:
+            raise ValueError("chain_params / erase_params and their returns belong to policy='ra', 'cifar10' or a list of "
+                             f"sub-policies; this dataset has policy={self.policy!r} (use policy_params)")
+        if self.chain and (policy_params is not None or return_policy_params):
+            raise ValueError(f"policy_params belong to policy=None or 'ta_wide'; policy={self.policy!r} takes chain_params "
+                             "and erase_params")
+        if not train and (chain_params is not None or erase_params is not None):
+            raise ValueError("chain_params / erase_params replace the training draw; train=False has none")
         img = torch.empty((B,) + tuple(self.x.shape[1:]), dtype=torch.float32, device=self.device)
         targets = torch.empty((B,), dtype=torch.int64, device=self.device)
         used = torch.empty((B, 3), dtype=torch.int8, device=self.device) if return_params else None
         base = self.shard_range[0] if self.sharded else None
+        if self.chain and train:
+            cused, eused = self._batch_chain(index, img, targets, pad, flip, seed, epoch, params, used, base, chain_params,
+                                             erase_params, return_chain_params, return_erase_params)
+            out = (img, targets, used) if return_params else (img, targets)
+            out += (cused,) if return_chain_params else ()
+            return out + ((eused,) if return_erase_params else ())
         with_policy = train and (self.policy is not None or self.erase_prob > 0.0 or policy_params is not None)
         if not with_policy:
             ops.augment_batch(self.x, self.y, index, img, targets, pad, flip, mean=self.mean, std=self.std, fill=self.fill,
@@ -268,6 +354,10 @@ class DeviceDataset:
             out = (img, targets, used) if return_params else (img, targets)
             if return_policy_params:         # nothing was applied: Identity, no erase
                 out += (torch.zeros((B, 7), dtype=torch.int32, device=self.device),)
+            if return_chain_params:
+                out += (torch.zeros((B, CHAIN_MAX_OPS, 3), dtype=torch.int32, device=self.device),)
+            if return_erase_params:
+                out += (torch.zeros((B, 4), dtype=torch.int32, device=self.device),)
             return out
         table, ratios = self._tables()
         pused = torch.empty((B, 7), dtype=torch.int32, device=self.device) if return_policy_params else None
@@ -592,27 +682,38 @@ def _rotate_fixed(angle, H, W):
     return _affine_fixed(m)
 
 
-@functools.lru_cache(maxsize=8)
-def _policy_table(H, W):
-    t = np.zeros((len(POLICY_OPS), POLICY_BINS, 2, 6), dtype=np.int32)
-    for b in range(POLICY_BINS):
+def _magnitude_table(nops, n, shear, tx, ty, rotate, enhance, posterize_steps, H, W):
+    """int32 [nops, n, 2, 6]: per (op, bin, sign) the magnitude hi * b / (n - 1), formed in fp64, in the form the kernels
+    consume.  shear, rotate (degrees), enhance: the `hi` of those ops; tx, ty: of TranslateX / TranslateY in pixels;
+    Posterize drops round(b / ((n - 1) / posterize_steps)) bits.  Rows past Equalize (Invert) have no magnitude."""
+    t = np.zeros((nops, n, 2, 6), dtype=np.int32)
+    for b in range(n):
         for sg in (0, 1):
             s = -1.0 if sg else 1.0
-            m = s * 0.99 * b / 30
+            m = s * shear * b / (n - 1)
             t[_OP["ShearX"], b, sg] = _affine_fixed([1.0, m, 0.0, 0.0, 1.0, 0.0])
             t[_OP["ShearY"], b, sg] = _affine_fixed([1.0, 0.0, 0.0, m, 1.0, 0.0])
-            px = int(s) * int(32 * b / 30)
+            px, py = int(s) * int(tx * b / (n - 1)), int(s) * int(ty * b / (n - 1))
             t[_OP["TranslateX"], b, sg] = [65536, 0, 32768 - px * 65536, 0, 65536, 32768]
-            t[_OP["TranslateY"], b, sg] = [65536, 0, 32768, 0, 65536, 32768 - px * 65536]
-            t[_OP["Rotate"], b, sg] = _rotate_fixed(s * 135 * b / 30, H, W)
-            factor = np.array([1 + m], dtype=np.float64).astype(np.float32).view(np.int32)[0]
+            t[_OP["TranslateY"], b, sg] = [65536, 0, 32768, 0, 65536, 32768 - py * 65536]
+            t[_OP["Rotate"], b, sg] = _rotate_fixed(s * rotate * b / (n - 1), H, W)
+            factor = np.array([1 + s * enhance * b / (n - 1)], dtype=np.float64).astype(np.float32).view(np.int32)[0]
             for name in ("Brightness", "Color", "Contrast", "Sharpness"):
                 t[_OP[name], b, sg, 0] = factor
-            bits = 8 - round(b / 5)
+            bits = 8 - round(b / ((n - 1) / posterize_steps))
             t[_OP["Posterize"], b, sg, 0] = 0xFF & ~((1 << (8 - bits)) - 1)
-            t[_OP["Solarize"], b, sg, 0] = math.ceil(255 - 255 * b / 30)      # v < threshold  <=>  v < ceil(threshold)
+            t[_OP["Solarize"], b, sg, 0] = math.ceil(255 - 255 * b / (n - 1))      # v < threshold  <=>  v < ceil(threshold)
     t.setflags(write=False)
     return t
+
+
+# TrivialAugmentWide's ranges over 31 bins
+_TA_WIDE = dict(n=31, shear=0.99, tx=32, ty=32, rotate=135, enhance=0.99, posterize_steps=6)
+
+
+@functools.lru_cache(maxsize=8)
+def _policy_table(H, W):
+    return _magnitude_table(len(POLICY_OPS), H=H, W=W, **_TA_WIDE)
 
 
 def policy_table(H, W):
@@ -713,10 +814,16 @@ def policy_reference(img_u8_chw, op, bin, sign):
         raise ValueError(f"need op in 0..{len(POLICY_OPS) - 1}, bin in 0..{POLICY_BINS - 1}, sign in {{0, 1}}; got "
                          f"({op}, {b}, {sg})")
     _, H, W = img.shape
-    row = policy_table(H, W)[op, b, sg].astype(np.int64)
-    name = POLICY_OPS[op]
+    return _apply_op(img, POLICY_OPS[op], policy_table(H, W)[op, b, sg].astype(np.int64))
+
+
+def _apply_op(img, name, row):
+    """Operation `name` on a uint8 [3,H,W] array under the six int64 words `row` of its magnitude table."""
+    _, H, W = img.shape
     if name == "Identity":
         return img.copy()
+    if name == "Invert":
+        return (255 - img).astype(np.uint8)
     if name in ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate"):
         y, x = np.mgrid[0:H, 0:W].astype(np.int64)
         sx = (row[2] + row[0] * x + row[1] * y) >> 16
@@ -765,6 +872,176 @@ def policy_reference(img_u8_chw, op, bin, sign):
             before = np.concatenate([[0], np.cumsum(hist)[:-1]])
             lut = np.minimum(255, (step // 2 + before) // step)
         out[c] = lut[ch].astype(np.uint8)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# RandAugment and AutoAugment (nbdt_policy_chain_batch, csrc/policy.hip): a chain of up to four operations per image, each
+# under the pixel rules above, plus Invert.  DeviceDataset(policy="ra" | "cifar10" | <list of sub-policies>).
+
+CHAIN_OPS = POLICY_OPS + ("Invert",)
+CHAIN_MAX_OPS = _C.NBDT_CHAIN_MAX_OPS
+CHAIN_SIGNED = POLICY_SIGNED
+_CHAIN_NO_MAGNITUDE = frozenset(("Identity", "AutoContrast", "Equalize", "Invert"))
+_CHAIN_OP = {name: i for i, name in enumerate(CHAIN_OPS)}
+_K_CHAIN = 0x8EBC6AF09C88C6E3           # odd: the chain's hash of the index
+RA_BINS, AA_BINS = 31, 10               # torchvision's RandAugment(num_magnitude_bins=31), AutoAugment's 10
+# torchvision's _augmentation_space of RandAugment and AutoAugment; the translations are fractions of the image side
+_RA_RANGES = dict(shear=0.3, rotate=30.0, enhance=0.9, posterize_steps=4)
+_TRANSLATE = 150.0 / 331.0
+
+# AutoAugment's CIFAR-10 policy (Cubuk et al. 2019, as torchvision lists it): 25 sub-policies of two (op, p, bin) slots
+CIFAR10_POLICY = (
+    (("Invert", 0.1, None), ("Contrast", 0.2, 6)), (("Rotate", 0.7, 2), ("TranslateX", 0.3, 9)),
+    (("Sharpness", 0.8, 1), ("Sharpness", 0.9, 3)), (("ShearY", 0.5, 8), ("TranslateY", 0.7, 9)),
+    (("AutoContrast", 0.5, None), ("Equalize", 0.9, None)), (("ShearY", 0.2, 7), ("Posterize", 0.3, 7)),
+    (("Color", 0.4, 3), ("Brightness", 0.6, 7)), (("Sharpness", 0.3, 9), ("Brightness", 0.7, 9)),
+    (("Equalize", 0.6, None), ("Equalize", 0.5, None)), (("Contrast", 0.6, 7), ("Sharpness", 0.6, 5)),
+    (("Color", 0.7, 7), ("TranslateX", 0.5, 8)), (("Equalize", 0.3, None), ("AutoContrast", 0.4, None)),
+    (("TranslateY", 0.4, 3), ("Sharpness", 0.2, 6)), (("Brightness", 0.9, 6), ("Color", 0.2, 8)),
+    (("Solarize", 0.5, 2), ("Invert", 0.0, None)), (("Equalize", 0.2, None), ("AutoContrast", 0.6, None)),
+    (("Equalize", 0.2, None), ("Equalize", 0.6, None)), (("Color", 0.9, 9), ("Equalize", 0.6, None)),
+    (("AutoContrast", 0.8, None), ("Solarize", 0.2, 8)), (("Brightness", 0.1, 3), ("Color", 0.7, 0)),
+    (("Solarize", 0.4, 5), ("AutoContrast", 0.9, None)), (("TranslateY", 0.9, 9), ("TranslateY", 0.7, 9)),
+    (("AutoContrast", 0.9, None), ("Solarize", 0.8, 3)), (("Equalize", 0.8, None), ("Invert", 0.1, None)),
+    (("TranslateY", 0.7, 9), ("AutoContrast", 0.9, None)),
+)
+
+
+def subpolicy_array(policy):
+    """The int32 ``[P, 4, 3]`` of (op, q = round(p * 2^24), bin) nbdt_policy_chain_batch reads for ``"cifar10"`` or a list
+    of sub-policies, each a sequence of 1..4 slots ``(op name, p, bin)`` with bin None (or 0) for an op without a magnitude;
+    an unused slot is (0, 0, 0).  ValueError naming the slot for an unknown op, p outside [0, 1], a bin outside 0..9 or a
+    sub-policy without slots or with more than four."""
+    subs = CIFAR10_POLICY if isinstance(policy, str) and policy == "cifar10" else policy
+    if isinstance(subs, str) or not isinstance(subs, (list, tuple)) or not 1 <= len(subs) <= _C.NBDT_CHAIN_MAX_SUBPOLICIES:
+        raise ValueError(f"a policy is 'cifar10' or a list of 1..{_C.NBDT_CHAIN_MAX_SUBPOLICIES} sub-policies, got {policy!r}")
+    out = np.zeros((len(subs), CHAIN_MAX_OPS, 3), dtype=np.int32)
+    for i, sub in enumerate(subs):
+        if not isinstance(sub, (list, tuple)) or not 1 <= len(sub) <= CHAIN_MAX_OPS:
+            raise ValueError(f"sub-policy {i} must have 1..{CHAIN_MAX_OPS} slots (op, p, bin), got {sub!r}")
+        for k, slot in enumerate(sub):
+            where = f"sub-policy {i} slot {k} {slot!r}"
+            if not isinstance(slot, (list, tuple)) or len(slot) != 3:
+                raise ValueError(f"{where}: a slot is (op name, p, bin)")
+            name, p, b = slot
+            if name not in _CHAIN_OP:
+                raise ValueError(f"{where}: unknown op {name!r} (one of {', '.join(CHAIN_OPS)})")
+            try:
+                p = float(p)
+            except (TypeError, ValueError):
+                p = float("nan")
+            if not 0.0 <= p <= 1.0:
+                raise ValueError(f"{where}: p must be in [0, 1]")
+            b = 0 if b is None else b
+            if not isinstance(b, (int, np.integer)) or isinstance(b, bool) or not 0 <= b < AA_BINS:
+                raise ValueError(f"{where}: bin must be an integer in 0..{AA_BINS - 1} (None for an op without a magnitude)")
+            if name in _CHAIN_NO_MAGNITUDE:
+                b = 0
+            out[i, k] = (_CHAIN_OP[name], round(p * 2 ** 24), int(b))
+    return out
+
+
+def _chain_bins(policy):
+    if isinstance(policy, str) and policy in ("ra", "ta_wide"):
+        return RA_BINS
+    if isinstance(policy, str) and policy != "cifar10":
+        raise ValueError(f"policy must be 'ra', 'cifar10', 'ta_wide' or a list of sub-policies, got {policy!r}")
+    return AA_BINS
+
+
+@functools.lru_cache(maxsize=16)
+def _chain_table(n, ta_wide, H, W):
+    if ta_wide:
+        return _magnitude_table(len(CHAIN_OPS), H=H, W=W, **_TA_WIDE)
+    return _magnitude_table(len(CHAIN_OPS), n, tx=_TRANSLATE * W, ty=_TRANSLATE * H, H=H, W=W, **_RA_RANGES)
+
+
+def chain_table(policy, H, W):
+    """The int32 ``[15, n, 2, 6]`` table nbdt_policy_chain_batch reads for an H x W dataset, rows in the form of
+    ``policy_table``.  policy "ra": RandAugment's space over n = 31 bins; "cifar10" or a list of sub-policies:
+    AutoAugment's over n = 10; each magnitude is hi * b / (n - 1) in fp64 with hi = 0.3 (shear), (150 / 331) * side
+    (translation, truncated to whole pixels), 30 degrees, 0.9 (the four enhancements), Posterize to
+    8 - round(b / ((n - 1) / 4)) bits, Solarize below 255 - 255 * b / (n - 1).  "ta_wide": TrivialAugmentWide's ranges
+    (``policy_table``'s rows, and Invert's) -- a chain of one op on it is nbdt_policy_batch."""
+    H, W = int(H), int(W)
+    if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
+        raise ValueError(f"image sides must be 1..{MAX_SIDE}, got {H} x {W}")
+    return _chain_table(_chain_bins(policy), isinstance(policy, str) and policy == "ta_wide", H, W)
+
+
+def _check_ra(num_ops, magnitude):
+    if not (isinstance(num_ops, (int, np.integer)) and 1 <= num_ops <= CHAIN_MAX_OPS):
+        raise ValueError(f"RandAugment's num_ops must be 1..{CHAIN_MAX_OPS}, got {num_ops!r}")
+    if not (isinstance(magnitude, (int, np.integer)) and 0 <= magnitude < RA_BINS):
+        raise ValueError(f"RandAugment's magnitude must be 0..{RA_BINS - 1}, got {magnitude!r}")
+    return int(num_ops), int(magnitude)
+
+
+def draw_chain_params(seed, epoch, index, policy="ra", num_ops=2, magnitude=9, return_subpolicy=False):
+    """The chain's draw of nbdt_policy_chain_batch (include/nbdt_hip.h), restated with numpy: int64 ``[B, 4, 3]`` of (op,
+    bin, sign) per slot, sign 1 meaning a negative magnitude; a skipped or unused slot is Identity (0, 0, 0).  A pure
+    function of (seed, epoch, dataset index) and the settings; the crop, the flip and the erase rectangle of the same
+    sample stay ``draw_params`` and ``draw_policy_params``.
+
+    policy "ra": each of `num_ops` slots gets an op uniform in 0..13, bin `magnitude` and a fresh sign.  "cifar10" or a
+    list of sub-policies: one sub-policy uniformly; its slot (op, p, bin) is applied when a 24-bit uniform is below
+    round(p * 2^24), with a fresh sign.  return_subpolicy appends the int64 [B] sub-policy chosen (0 for "ra")."""
+    if isinstance(index, torch.Tensor):
+        index = index.cpu().numpy()
+    idx = np.asarray(index).astype(np.int64).astype(np.uint64).reshape(-1)
+    u64 = np.uint64
+    m24, golden = u64(0xFFFFFF), 0x9E3779B97F4A7C15
+    out = np.zeros((idx.shape[0], CHAIN_MAX_OPS, 3), dtype=np.int64)
+    if isinstance(policy, str) and policy == "ra":
+        num_ops, magnitude = _check_ra(num_ops, magnitude)
+        subs = None
+    else:
+        subs = subpolicy_array(policy).astype(np.int64)
+    with np.errstate(over="ignore"):
+        key = _mix64(np.asarray([(int(seed) * golden + int(epoch)) & _M64], dtype=np.uint64))[0]
+        rc = _mix64(key ^ (idx * u64(_K_CHAIN)))
+        which = np.zeros(idx.shape, dtype=np.int64) if subs is None else \
+            (((rc & m24) * u64(len(subs))) >> u64(24)).astype(np.int64)
+        for k in range(CHAIN_MAX_OPS if subs is not None else num_ops):
+            rs = _mix64(rc + u64(((k + 1) * golden) & _M64))
+            bit = (rs >> u64(63)).astype(np.int64)
+            if subs is None:
+                out[:, k, 0] = (((rs & m24) * u64(len(POLICY_OPS))) >> u64(24)).astype(np.int64)
+                out[:, k, 1] = magnitude
+                out[:, k, 2] = bit
+            else:
+                slot = subs[which, k]                               # [B, 3] (op, q, bin)
+                applied = (rs & m24).astype(np.int64) < slot[:, 1]
+                out[:, k, 0] = np.where(applied, slot[:, 0], 0)
+                out[:, k, 1] = np.where(applied, slot[:, 2], 0)
+                out[:, k, 2] = np.where(applied, 1 - bit, 0)
+    return (out, which) if return_subpolicy else out
+
+
+def chain_reference(img_u8_chw, chain, table):
+    """The operations `chain` -- a sequence of (op, bin, sign), op an index into CHAIN_OPS or a name -- applied one after
+    the other to one uint8 ``[3,H,W]`` image under the magnitudes of `table` (``chain_table``), each by the rules
+    ``policy_reference`` restates from Pillow, Invert being 255 - v; returns a uint8 array.  What nbdt_policy_chain_batch
+    computes between the flip and the normalisation.  Test infrastructure and documentation: it must not be called on the
+    training path."""
+    if isinstance(img_u8_chw, torch.Tensor):
+        img_u8_chw = img_u8_chw.cpu().numpy()
+    img = np.asarray(img_u8_chw)
+    if img.ndim != 3 or img.shape[0] != 3 or img.dtype != np.uint8:
+        raise ValueError(f"img must be uint8 [3,H,W], got {img.dtype} {img.shape}")
+    table = np.asarray(table)
+    if table.ndim != 4 or table.shape[0] != len(CHAIN_OPS) or table.shape[2:] != (2, 6):
+        raise ValueError(f"table must be [15, n, 2, 6] (chain_table), got {table.shape}")
+    out = img.copy()
+    for slot in chain:
+        op, b, sg = slot
+        op = _CHAIN_OP[op] if isinstance(op, str) else int(op)
+        b, sg = int(b), int(sg)
+        if not (0 <= op < len(CHAIN_OPS) and 0 <= b < table.shape[1] and sg in (0, 1)):
+            raise ValueError(f"need op in 0..{len(CHAIN_OPS) - 1}, bin in 0..{table.shape[1] - 1}, sign in {{0, 1}}; got "
+                             f"({op}, {b}, {sg})")
+        out = _apply_op(np.ascontiguousarray(out), CHAIN_OPS[op], table[op, b, sg].astype(np.int64))
     return out
 
 

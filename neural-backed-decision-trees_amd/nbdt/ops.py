@@ -688,6 +688,32 @@ def policy_batch(src, labels_src, index, out, labels_out, pad, flip, mean, std, 
         check(lib().nbdt_policy_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
 
 
+def policy_chain_batch(src, labels_src, index, out, labels_out, pad, flip, mean, std, table, nbins, num_ops=0, magnitude=0,
+                       subpolicies=None, erase_prob=0.0, erase_scale=None, erase_ratio=None, ratio_table=None, seed=0,
+                       epoch=0, params_in=None, chain_in=None, erase_in=None, params_out=None, chain_out=None,
+                       erase_out=None, index_base=None):
+    """nbdt_policy_chain_batch: policy_batch with a chain of up to four operations per image (RandAugment, AutoAugment).
+    table: int32 [15, nbins, 2, 6], device.  subpolicies: int32 [P,4,3] of (op, round(p * 2^24), bin), device -- given:
+    NBDT_CHAIN_SUBPOLICY; None: NBDT_CHAIN_RAND with num_ops slots at bin `magnitude`.  chain_in / chain_out: int32 [B,4,3]
+    (op, bin, sign), erase_in / erase_out: int32 [B,4] (top, left, h, w), device; the *_in replace the draws.
+    index_base: nbdt_policy_chain_batch_sharded, as for augment_batch."""
+    N, _, H, W = src.shape
+    f3 = lambda v: None if v is None else (ctypes.c_float * 3)(*[float(a) for a in v])
+    d2 = lambda v: None if v is None else (ctypes.c_double * 2)(*[float(a) for a in v])
+    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
+    mask = (1 << 64) - 1
+    mode = _C.NBDT_CHAIN_RAND if subpolicies is None else _C.NBDT_CHAIN_SUBPOLICY
+    tail = (index.shape[0], N, H, W, int(pad), 1 if flip else 0, f3(mean), f3(std), mode, int(nbins), ptr(table),
+            int(num_ops), int(magnitude), ptr(subpolicies), 0 if subpolicies is None else subpolicies.shape[0],
+            float(erase_prob), d2(erase_scale), d2(erase_ratio), ptr(ratio_table), int(seed) & mask, int(epoch) & mask,
+            ptr(params_in), ptr(chain_in), ptr(erase_in), ptr(out), ptr(labels_out), ptr(params_out), ptr(chain_out),
+            ptr(erase_out), stream_ptr(src.device))
+    if index_base is None:
+        check(lib().nbdt_policy_chain_batch(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
+    else:
+        check(lib().nbdt_policy_chain_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
+
+
 def mix_batch(x, y, out, tgt, lam=1.0, box=(0, 0, 0, 0), lam_t=1.0):
     """nbdt_mix_batch: MixUp / CutMix of the fp32 batch x [B,3,H,W] (labels y, int64 [B]) with itself rolled by one, into
     out [B,3,H,W] (not x) and the probability targets tgt [B,C] fp32.  MixUp: lam, an empty box, lam_t = lam.  CutMix:
