@@ -1225,6 +1225,66 @@ int nbdt_policy_chain_batch_sharded(const void* src, int32_t src_dtype, const in
                                     const int32_t* chain_in, const int32_t* erase_in, float* out, int64_t* labels_out,
                                     int8_t* params_out, int32_t* chain_out, int32_t* erase_out, void* stream);
 
+/* ------------------------------------------------------------------ resized-crop policy (nbdt_version() >= 124) */
+/* The policy chains and the erase on the ImageNet-style path: gather, RandomResizedCrop(S), flip, a chain of up to
+ * NBDT_CHAIN_MAX_OPS of the 15 operations on the S x S bytes, /255 and Normalize, RandomErasing(value=0), into out
+ * [B,3,S,S] fp32.  torchvision's RandomResizedCrop -> RandomHorizontalFlip -> {TrivialAugmentWide | RandAugment |
+ * AutoAugment} -> ToTensor -> Normalize -> RandomErasing, on the device with no host read-back (csrc/resample.hip).
+ *
+ * Two launches inside the one entry, both on `stream`.  (1) nbdt_resized_crop_batch's kernels in their byte-output mode:
+ * the same boxes, the same resampling arithmetic, the resized and flipped uint8 image into stage_a; labels_out and
+ * params_out as ever.  (2) One block per image applies the chain, ping-ponging between the image's 3*S*S bytes of stage_a
+ * and of stage_b: a tile of 150 KB at S = 224 does not fit the LDS tiles of nbdt_policy_chain_batch (49152 bytes), so the
+ * two tiles live in global memory, written and re-read by one block on one CU (its L1, its XCD's L2), ordered by workgroup
+ * barriers; only the statistics (three histograms, grey sum, minima / maxima, AutoContrast's scale and offset) are in LDS.
+ * As there: an Identity slot costs no pass, statistics are collected again on the tile an operation reads, the last
+ * non-Identity operation is evaluated inside the normalising output pass, which also zeroes the erase rectangle.
+ *
+ * Pixel rules, magnitudes and draws are nbdt_policy_chain_batch's with H = W = S: `table` is built for the S x S crop
+ * (translations (150/331) * S, Rotate about (S/2, S/2)), the erase rectangle is drawn in the S x S output, and every draw
+ * hashes the GLOBAL dataset index, so a sample's box and flip are nbdt_resized_crop_batch's with and without a policy.
+ *   src .. ratio_table   as nbdt_resized_crop_batch (rs_h = rs_w = out_h = out_w = S, window (0, 0): training only)
+ *   S             1 .. NBDT_RESIZED_CROP_POLICY_MAX_SIDE.  Contrast's grey sum and its rounding (2*sum + S*S) / (2*S*S) are
+ *                 formed in 32 bits: at 512^2 the largest intermediate is 2*255*262144 + 262144 ~ 1.3e8; at 4096^2 it
+ *                 would overflow, so larger sides are refused
+ *   mode          NBDT_CHAIN_RAND | NBDT_CHAIN_SUBPOLICY as above, num_ops 0 .. NBDT_CHAIN_MAX_OPS (0: no operation, the erase
+ *                 only; `table` may then be NULL unless chain_in is given), or NBDT_CHAIN_TA_WIDE (this entry only): ONE slot
+ *                 whose (op, bin, sign) is nbdt_policy_batch's draw -- rp = mix64(key ^ (index * 0xA0761D6478BD642F)),
+ *                 op = ((rp & 0xFFFFFF) * 14) >> 24, bin = (((rp >> 24) & 0xFFFFFF) * 31) >> 24, sign = rp >> 63 -- on a table of
+ *                 TrivialAugmentWide's ranges: nbins must be NBDT_POLICY_BINS
+ *   nbins, table, num_ops, magnitude, subpolicies, P      as nbdt_policy_chain_batch
+ *   erase_prob, erase_scale, erase_ratio, erase_ratio_table   as nbdt_policy_chain_batch's erase_prob .. ratio_table
+ *   params_in / params_out   int32 [B][5] (top, left, h, w, flip) as nbdt_resized_crop_batch
+ *   chain_in, erase_in, chain_out, erase_out   as nbdt_policy_chain_batch, clamped the same way (op to [0, 14], bin to
+ *                 [0, nbins-1], sign != 0, the rectangle into the S x S output)
+ *   stage_a, stage_b   uint8 [B][3][S][S] each, device memory, 16-byte aligned, distinct: scratch, contents undefined after
+ * Every value read from device memory (index, params, chain slots, rectangles, sub-policy rows) is clamped or
+ * bounds-checked before an address is formed from it.  Out-of-range indices (index < index_base or >= index_base + N,
+ * compared unsigned): a zero image, label -1, zero params; no source address is formed.  Integer statistics: the same
+ * inputs give the same bits. */
+#define NBDT_CHAIN_TA_WIDE 2
+#define NBDT_RESIZED_CROP_POLICY_MAX_SIDE 512
+int nbdt_resized_crop_policy_batch(const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index,
+                                   int32_t B, int64_t N, int32_t H, int32_t W, int32_t S, int32_t flip, const float* mean,
+                                   const float* std, const double* scale, const double* ratio, const double* ratio_table,
+                                   int32_t mode, int32_t nbins, const int32_t* table, int32_t num_ops, int32_t magnitude,
+                                   const int32_t* subpolicies, int32_t P, double erase_prob, const double* erase_scale,
+                                   const double* erase_ratio, const double* erase_ratio_table, uint64_t seed, uint64_t epoch,
+                                   const int32_t* params_in, const int32_t* chain_in, const int32_t* erase_in, void* stage_a,
+                                   void* stage_b, float* out, int64_t* labels_out, int32_t* params_out, int32_t* chain_out,
+                                   int32_t* erase_out, void* stream);
+int nbdt_resized_crop_policy_batch_sharded(const void* src, int32_t src_dtype, const int64_t* labels_src,
+                                           const int64_t* index, int64_t index_base, int32_t B, int64_t N, int32_t H,
+                                           int32_t W, int32_t S, int32_t flip, const float* mean, const float* std,
+                                           const double* scale, const double* ratio, const double* ratio_table, int32_t mode,
+                                           int32_t nbins, const int32_t* table, int32_t num_ops, int32_t magnitude,
+                                           const int32_t* subpolicies, int32_t P, double erase_prob,
+                                           const double* erase_scale, const double* erase_ratio,
+                                           const double* erase_ratio_table, uint64_t seed, uint64_t epoch,
+                                           const int32_t* params_in, const int32_t* chain_in, const int32_t* erase_in,
+                                           void* stage_a, void* stage_b, float* out, int64_t* labels_out, int32_t* params_out,
+                                           int32_t* chain_out, int32_t* erase_out, void* stream);
+
 /* ------------------------------------------------------------------ measurement probe (not on the product path) */
 /* A register-only stream of independent v_mfma_f32_32x32x16_bf16 on `blocks` CUs (one 512-thread block each, two waves
  * per SIMD): every wave issues iters x 16 of them (x 32768 flop).  bench.py times the launch for `roofline.mfma_stream`

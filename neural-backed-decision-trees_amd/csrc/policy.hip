@@ -23,20 +23,19 @@
 // Built with -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt (nbdt/_build.py): the blend d + a * (x - d) is a
 // separate fp32 multiply and add (Pillow's C), AutoContrast's v * scale + offset a separate fp64 multiply and add
 // (Python's), and the normalisation is augment.hip's three IEEE operations.
+//
+// The rules themselves -- the draws, the statistics, the per-pixel operations, the byte pass and the output pass -- live in
+// policy_ops.h, which the resized-crop path (resample.hip) shares; here they run on LDS tiles with 256 lanes.
 #include "common.h"
+#include "policy_ops.h"
 
 using namespace nbdt;
+using namespace nbdt::pol;
 
 // 3*H*W of the images this kernel takes: both tiles and the statistics stay far below the 160 KB of LDS
 #define NBDT_AUGMENT_LDS_BYTES 49152
 
 namespace {
-
-enum {
-  OP_IDENTITY, OP_SHEAR_X, OP_SHEAR_Y, OP_TRANSLATE_X, OP_TRANSLATE_Y, OP_ROTATE, OP_BRIGHTNESS, OP_COLOR, OP_CONTRAST,
-  OP_SHARPNESS, OP_POSTERIZE, OP_SOLARIZE, OP_AUTOCONTRAST, OP_EQUALIZE,
-  OP_INVERT          // the policy chains' 15th operation (NBDT_CHAIN_OPS): policy_kernel clamps its op to 0..13
-};
 
 struct PolArgs {
   const unsigned char* src;
@@ -49,218 +48,13 @@ struct PolArgs {
   const signed char* params_in;      // int8 [B,3] (dy, dx, flip): replaces the crop / flip draw
   const int* policy_in;              // int32 [B,7] (op, bin, sign, top, left, h, w): replaces the policy and erase draw
   const int* table;                  // int32 [NBDT_POLICY_OPS][NBDT_POLICY_BINS][2][6] (device)
-  double erase_p, s0, s1;            // erase probability and area-fraction range
-  const double* ratio_table;         // NBDT_RESIZED_CROP_RATIOS log-spaced aspect ratios (device)
+  EraseDraw erase;                   // erase probability, area-fraction range and the aspect-ratio table
   int vec_in, vec_out;
   float* out;
   long long* labels_out;
   signed char* params_out;
   int* policy_out;
 };
-
-// the draw (include/nbdt_hip.h, nbdt/data.py): splitmix64's finaliser
-__host__ __device__ inline unsigned long long mix64(unsigned long long x) {
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ float pick3(const float* v, int c) { return c == 0 ? v[0] : (c == 1 ? v[1] : v[2]); }
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
-// round-half-to-even of sqrt(v), 0 < v <= 2^30, decided by exact comparisons (resample.hip's): the result does not depend
-// on how sqrt() itself is rounded
-__device__ inline int round_sqrt(double v) {
-  long long c = (long long)sqrt(v);
-  if ((double)(c * c) > v) --c;
-  if ((double)((c + 1) * (c + 1)) <= v) ++c;
-  const double half = ((double)c + 0.5) * ((double)c + 0.5);
-  if (v > half) return (int)c + 1;
-  if (v < half) return (int)c;
-  return (int)(c + (c & 1));
-}
-
-// torchvision's RandomErasing.get_params with the project's counter hash (nbdt/data.py draw_policy_params): the first
-// attempt with h < H and w < W is taken; a side that rounded to 0 erases nothing
-__device__ inline void draw_erase(const PolArgs& a, unsigned long long re, int& top, int& left, int& h, int& w) {
-  top = left = h = w = 0;
-  if (!((double)(re >> 11) * 0x1p-53 < a.erase_p)) return;
-  const int H = a.H, W = a.W;
-  const double area = (double)(H * W);
-  for (int t = 0; t < NBDT_RESIZED_CROP_ATTEMPTS; ++t) {
-    const unsigned long long ra = mix64(re + (unsigned long long)(2 * t + 1) * 0x9E3779B97F4A7C15ull);
-    const unsigned long long rb = mix64(re + (unsigned long long)(2 * t + 2) * 0x9E3779B97F4A7C15ull);
-    const double u = (double)(ra >> 11) * 0x1p-53;
-    const double target = area * (a.s0 + u * (a.s1 - a.s0));
-    const double rt = a.ratio_table[rb & (NBDT_RESIZED_CROP_RATIOS - 1)];
-    const int ch = round_sqrt(target * rt), cw = round_sqrt(target / rt);
-    if (ch < H && cw < W) {
-      if (ch > 0 && cw > 0) {
-        h = ch;
-        w = cw;
-        top = (int)((((rb >> 12) & 0xFFFFFFull) * (unsigned long long)(H - ch + 1)) >> 24);
-        left = (int)((((rb >> 36) & 0xFFFFFFull) * (unsigned long long)(W - cw + 1)) >> 24);
-      }
-      return;
-    }
-  }
-}
-
-// integer reductions over the 64 lanes of a wave (every lane gets the result): order-independent, like the LDS atomics
-// that combine the four waves
-__device__ __forceinline__ unsigned wave_sum(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += (unsigned)__shfl_xor((int)v, o);
-  return v;
-}
-__device__ __forceinline__ unsigned wave_min(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = (unsigned)__shfl_xor((int)v, o);
-    v = t < v ? t : v;
-  }
-  return v;
-}
-__device__ __forceinline__ unsigned wave_max(unsigned v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = (unsigned)__shfl_xor((int)v, o);
-    v = t > v ? t : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ unsigned grey_of(unsigned r, unsigned g, unsigned b) {
-  return (19595u * r + 38470u * g + 7471u * b + 32768u) >> 16;
-}
-
-// Pillow's Image.blend on 8-bit data: fp32, a separate multiply and add
-__device__ __forceinline__ unsigned blend(unsigned d, unsigned x, float a) {
-  const float fd = (float)d;
-  const float t = fd + a * ((float)x - fd);
-  return t <= 0.f ? 0u : (t >= 255.f ? 255u : (unsigned)(int)t);
-}
-
-// what an operation needs beyond the tile, block-uniform
-struct OpCtx {
-  int op;
-  unsigned a[6];        // the table row: affine coefficients | factor bits | mask | threshold
-  float factor;
-  unsigned mean;        // Contrast: the grey mean
-};
-
-// the byte of output pixel (c, y, x) under the operation; T is the cropped and flipped image, lut the equalisation tables
-// [3][256], ac AutoContrast's (scale, offset) per channel -- scale 0 for a channel that stays as it is
-__device__ __forceinline__ unsigned op_pixel(const OpCtx& k, const unsigned char* T, const unsigned* lut, const double* ac,
-                                              int H, int W, int c, int y, int x) {
-  const int HW = H * W, p = y * W + x;
-  switch (k.op) {
-    case OP_SHEAR_X: case OP_SHEAR_Y: case OP_TRANSLATE_X: case OP_TRANSLATE_Y: case OP_ROTATE: {
-      // (unsigned arithmetic: whatever the table holds wraps instead of overflowing; the result is bounds-checked)
-      const int sx = (int)(k.a[2] + k.a[0] * (unsigned)x + k.a[1] * (unsigned)y) >> 16;
-      const int sy = (int)(k.a[5] + k.a[3] * (unsigned)x + k.a[4] * (unsigned)y) >> 16;
-      return (sx >= 0 && sx < W && sy >= 0 && sy < H) ? T[(c * H + sy) * W + sx] : 0u;
-    }
-    case OP_BRIGHTNESS: return blend(0u, T[c * HW + p], k.factor);
-    case OP_COLOR: return blend(grey_of(T[p], T[HW + p], T[2 * HW + p]), T[c * HW + p], k.factor);
-    case OP_CONTRAST: return blend(k.mean, T[c * HW + p], k.factor);
-    case OP_SHARPNESS: {
-      const unsigned char* q = T + c * HW + p;
-      const unsigned v = q[0];
-      if (x == 0 || y == 0 || x == W - 1 || y == H - 1) return v;        // ImageFilter.SMOOTH copies the border
-      const unsigned s = q[-W - 1] + q[-W] + q[-W + 1] + q[-1] + 5u * v + q[1] + q[W - 1] + q[W] + q[W + 1];
-      return blend((2u * s + 13u) / 26u, v, k.factor);                    // trunc(s / 13 + 0.5)
-    }
-    case OP_POSTERIZE: return T[c * HW + p] & k.a[0] & 0xFFu;
-    case OP_SOLARIZE: {
-      const int v = T[c * HW + p];
-      return (unsigned)(v < (int)k.a[0] ? v : 255 - v);
-    }
-    case OP_AUTOCONTRAST: {
-      const unsigned v = T[c * HW + p];
-      const double scale = ac[2 * c], offset = ac[2 * c + 1];
-      if (scale == 0.0) return v;          // hi <= lo
-      return (unsigned)clampi((int)((double)v * scale + offset), 0, 255);
-    }
-    case OP_EQUALIZE: return lut[c * 256 + T[c * HW + p]] & 0xFFu;
-    case OP_INVERT: return 255u - T[c * HW + p];
-    default: return T[c * HW + p];
-  }
-}
-
-// the per-image statistics an operation needs, collected over the tile T (block-uniform in k.op: so is every barrier):
-// Contrast's grey mean into k.mean, AutoContrast's (scale, offset) into ac, Equalize's tables into hist.  hist / stat must
-// hold their initial values (zeros, minima 255) and a barrier must lie between that and this call.
-__device__ __forceinline__ void op_statistics(OpCtx& k, const unsigned char* T, unsigned* hist, unsigned* stat, double* ac,
-                                               int HW, int tid) {
-  const int op = k.op;
-  if (op == OP_CONTRAST) {
-    unsigned sum = 0;
-    for (int p = tid; p < HW; p += 256) sum += grey_of(T[p], T[HW + p], T[2 * HW + p]);
-    sum = wave_sum(sum);
-    if ((tid & 63) == 0) atomicAdd(&stat[0], sum);            // at most 255 * 16384: no overflow
-    __syncthreads();
-    k.mean = (2u * stat[0] + (unsigned)HW) / (2u * (unsigned)HW);         // int(sum / HW + 0.5)
-  } else if (op == OP_AUTOCONTRAST || op == OP_EQUALIZE) {
-    for (int c = 0; c < 3; ++c) {
-      unsigned lo = 255u, hi = 0u;
-      for (int p = tid; p < HW; p += 256) {
-        const unsigned v = T[c * HW + p];
-        lo = v < lo ? v : lo;
-        hi = v > hi ? v : hi;
-        if (op == OP_EQUALIZE) atomicAdd(&hist[c * 256 + v], 1u);
-      }
-      lo = wave_min(lo);
-      hi = wave_max(hi);
-      if ((tid & 63) == 0) {             // one atomic per wave and address, not 64 contending ones
-        atomicMin(&stat[1 + c], lo);
-        atomicMax(&stat[4 + c], hi);
-      }
-    }
-    __syncthreads();
-    if (op == OP_AUTOCONTRAST) {
-      if (tid < 3) {
-        const int lo = (int)stat[1 + tid], hi = (int)stat[4 + tid];
-        const double scale = hi > lo ? 255.0 / (double)(hi - lo) : 0.0;
-        ac[2 * tid] = scale;
-        ac[2 * tid + 1] = -(double)lo * scale;
-      }
-      __syncthreads();
-    } else {
-      // ImageOps.equalize: lut[i] = min(255, (step / 2 + sum of h[j], j < i) / step), step = (H*W - h[last non-empty]) / 255
-      unsigned own[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) own[c] = hist[c * 256 + tid];
-      for (int off = 1; off < 256; off <<= 1) {            // inclusive prefix sums, all three channels at once
-        unsigned add[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) add[c] = tid >= off ? hist[c * 256 + tid - off] : 0u;
-        __syncthreads();
-#pragma unroll
-        for (int c = 0; c < 3; ++c) hist[c * 256 + tid] += add[c];
-        __syncthreads();
-      }
-      unsigned lutv[3];
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        lutv[c] = (unsigned)tid;
-        const int lo = (int)stat[1 + c], hi = (int)stat[4 + c];
-        if (hi > lo) {                    // (then hi >= 1) more than one non-empty bin
-          const unsigned last = hist[c * 256 + hi] - hist[c * 256 + hi - 1];
-          const unsigned step = ((unsigned)HW - last) / 255u;
-          if (step != 0u) {
-            const unsigned q = (step / 2u + hist[c * 256 + tid] - own[c]) / step;
-            lutv[c] = q > 255u ? 255u : q;
-          }
-        }
-      }
-      __syncthreads();
-#pragma unroll
-      for (int c = 0; c < 3; ++c) hist[c * 256 + tid] = lutv[c];
-      __syncthreads();
-    }
-  }
-}
 
 // the crop / flip of sample b (nbdt_augment_batch's draw, or params_in clamped)
 __device__ __forceinline__ void draw_crop(const PolArgs& a, int b, long long gidx, int& dy, int& dx, int& fl) {
@@ -314,43 +108,16 @@ __device__ __forceinline__ void stage_and_crop(const PolArgs& a, const unsigned 
   __syncthreads();
 }
 
-// the output: operation k on the tile T, /255 and the normalisation, the erase rectangle set to 0.0; four consecutive x of
-// one row per lane
+// the output pass on an LDS tile (byte reads: an LDS word read buys nothing here)
 __device__ __forceinline__ void write_output(const PolArgs& a, const OpCtx& k, const unsigned char* T, const unsigned* hist,
                                               const double* ac, float* o, int et, int el, int eh, int ew, int tid) {
-  const int H = a.H, W = a.W;
-  const int G = (W + 3) >> 2;
-  const int items = 3 * H * G;
-  for (int it = tid; it < items; it += 256) {
-    const int row = it / G, g = it - row * G;     // row = c * H + y
-    const int c = row / H, y = row - c * H;
-    const float mean = pick3(a.mean, c), sd = pick3(a.std, c);
-    const bool yer = y >= et && y < et + eh;
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int x = g * 4 + j;
-      v[j] = 0.f;
-      if (x < W && !(yer && x >= el && x < el + ew)) {
-        const unsigned u = op_pixel(k, T, hist, ac, H, W, c, y, x);
-        v[j] = ((float)u / 255.0f - mean) / sd;
-      }
-    }
-    float* dst = o + (size_t)row * W + g * 4;
-    if (a.vec_out) {
-      *(float4*)dst = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (g * 4 + j < W) dst[j] = v[j];
-    }
-  }
+  output_pass<256, false>(a.mean, a.std, a.H, a.W, a.vec_out, k, T, hist, ac, o, et, el, eh, ew, tid);
 }
 
 __global__ __launch_bounds__(256) void policy_kernel(const PolArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   const int b = blockIdx.x, tid = threadIdx.x;
-  const int H = a.H, W = a.W, pad = a.pad, HW = H * W, n = 3 * HW;
+  const int H = a.H, W = a.W, HW = H * W, n = 3 * HW;
   const int npad = (n + 15) & ~15;
   unsigned char* S = lds;                                   // [3][H][W] the source image
   unsigned char* T = lds + npad;                            // [3][H][W] cropped and flipped
@@ -371,11 +138,7 @@ __global__ __launch_bounds__(256) void policy_kernel(const PolArgs a) {
       op = clampi(q[0], 0, NBDT_POLICY_OPS - 1);
       bin = clampi(q[1], 0, NBDT_POLICY_BINS - 1);
       sg = q[2] != 0;
-      et = clampi(q[3], 0, H - 1);
-      el = clampi(q[4], 0, W - 1);
-      eh = clampi(q[5], 0, H - et);
-      ew = clampi(q[6], 0, W - el);
-      if (eh == 0 || ew == 0) et = el = eh = ew = 0;
+      clamp_erase(q + 3, H, W, et, el, eh, ew);
     } else {
       if (a.policy_on) {
         const unsigned long long rp = mix64(a.key ^ ((unsigned long long)gidx * 0xA0761D6478BD642Full));
@@ -383,7 +146,7 @@ __global__ __launch_bounds__(256) void policy_kernel(const PolArgs a) {
         bin = (int)((((unsigned)(rp >> 24) & 0xFFFFFFu) * (unsigned)NBDT_POLICY_BINS) >> 24);
         sg = (int)(rp >> 63);
       }
-      draw_erase(a, mix64(a.key ^ ((unsigned long long)gidx * 0xE7037ED1A0B428DBull)), et, el, eh, ew);
+      draw_erase(a.erase, H, W, erase_word(a.key, gidx), et, el, eh, ew);
     }
   }
   if (tid == 0) {
@@ -404,7 +167,7 @@ __global__ __launch_bounds__(256) void policy_kernel(const PolArgs a) {
   }
 
   // ---- stage the source, then crop and flip it into T
-  for (int i = tid; i < 776; i += 256) hist[i] = (i >= 769 && i <= 771) ? 255u : 0u;
+  reset_statistics<256>(hist, tid);
   stage_and_crop(a, a.src + (size_t)idx * n, S, T, dy, dx, fl, tid);
 
   // ---- the operation's constants and per-image statistics (op is block-uniform: so is every barrier below)
@@ -416,7 +179,7 @@ __global__ __launch_bounds__(256) void policy_kernel(const PolArgs a) {
     for (int i = 0; i < 6; ++i) k.a[i] = row ? (unsigned)row[i] : 0u;
     k.factor = __uint_as_float(k.a[0]);
   }
-  op_statistics(k, T, hist, stat, ac, HW, tid);
+  op_statistics<256>(k, T, hist, stat, ac, HW, tid);
 
   write_output(a, k, T, hist, ac, o, et, el, eh, ew, tid);
 }
@@ -435,19 +198,6 @@ struct ChainArgs {
   int* chain_out;
   int* erase_out;
 };
-
-__device__ __forceinline__ unsigned long long pack_slot(int op, int bin, int sg) {
-  return (unsigned long long)(unsigned)(op | (bin << 4) | (sg << 9));
-}
-
-__device__ __forceinline__ void load_op(OpCtx& k, const int* table, int nbins, int op, int bin, int sg) {
-  const int* row = table + (size_t)(((op * nbins + bin) * 2 + sg) * 6);
-  k.op = op;
-#pragma unroll
-  for (int i = 0; i < 6; ++i) k.a[i] = (unsigned)row[i];
-  k.factor = __uint_as_float(k.a[0]);
-  k.mean = 0u;
-}
 
 __global__ __launch_bounds__(256) void policy_chain_kernel(const ChainArgs ca) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
@@ -470,46 +220,14 @@ __global__ __launch_bounds__(256) void policy_chain_kernel(const ChainArgs ca) {
   unsigned long long chain = 0;      // 16 bits per slot: op | bin << 4 | sign << 9 (all zero: Identity)
   if (valid) {
     draw_crop(a, b, gidx, dy, dx, fl);
-    if (ca.chain_in) {
-      const int* q = ca.chain_in + (size_t)b * (NBDT_CHAIN_MAX_OPS * 3);
-#pragma unroll
-      for (int s = 0; s < NBDT_CHAIN_MAX_OPS; ++s) {
-        chain |= pack_slot(clampi(q[3 * s], 0, NBDT_CHAIN_OPS - 1), clampi(q[3 * s + 1], 0, ca.nbins - 1),
-                           q[3 * s + 2] != 0) << (16 * s);
-      }
-    } else {
-      const unsigned long long rc = mix64(a.key ^ ((unsigned long long)gidx * 0x8EBC6AF09C88C6E3ull));
-      const int* sub = nullptr;
-      int slots = ca.num_ops;
-      if (ca.mode == NBDT_CHAIN_SUBPOLICY) {
-        sub = ca.subpolicies + (size_t)(((rc & 0xFFFFFFull) * (unsigned long long)ca.P) >> 24) * (NBDT_CHAIN_MAX_OPS * 3);
-        slots = NBDT_CHAIN_MAX_OPS;
-      }
-#pragma unroll
-      for (int s = 0; s < NBDT_CHAIN_MAX_OPS; ++s) {
-        if (s >= slots) continue;
-        const unsigned long long rs = mix64(rc + (unsigned long long)(s + 1) * 0x9E3779B97F4A7C15ull);
-        if (sub) {
-          // applied when the 24-bit uniform lies below q = round(p * 2^24); negative magnitude when the sign bit is 0
-          if ((int)((unsigned)rs & 0xFFFFFFu) < clampi(sub[3 * s + 1], 0, 1 << 24))
-            chain |= pack_slot(clampi(sub[3 * s], 0, NBDT_CHAIN_OPS - 1), clampi(sub[3 * s + 2], 0, ca.nbins - 1),
-                               (int)(rs >> 63) ^ 1) << (16 * s);
-        } else {          // (Invert is not in RandAugment's space)
-          chain |= pack_slot((int)((((unsigned)rs & 0xFFFFFFu) * (unsigned)NBDT_POLICY_OPS) >> 24), ca.magnitude,
-                             (int)(rs >> 63)) << (16 * s);
-        }
-      }
-    }
-    if (ca.erase_in) {
-      const int* q = ca.erase_in + (size_t)b * 4;
-      et = clampi(q[0], 0, H - 1);
-      el = clampi(q[1], 0, W - 1);
-      eh = clampi(q[2], 0, H - et);
-      ew = clampi(q[3], 0, W - el);
-      if (eh == 0 || ew == 0) et = el = eh = ew = 0;
-    } else {
-      draw_erase(a, mix64(a.key ^ ((unsigned long long)gidx * 0xE7037ED1A0B428DBull)), et, el, eh, ew);
-    }
+    if (ca.chain_in)
+      chain = clamp_chain(ca.chain_in + (size_t)b * (NBDT_CHAIN_MAX_OPS * 3), ca.nbins);
+    else
+      chain = draw_chain(a.key, gidx, ca.mode, ca.nbins, ca.num_ops, ca.magnitude, ca.subpolicies, ca.P);
+    if (ca.erase_in)
+      clamp_erase(ca.erase_in + (size_t)b * 4, H, W, et, el, eh, ew);
+    else
+      draw_erase(a.erase, H, W, erase_word(a.key, gidx), et, el, eh, ew);
   }
   if (tid == 0) {
     a.labels_out[b] = valid ? a.labels_src[idx] : -1ll;
@@ -518,14 +236,7 @@ __global__ __launch_bounds__(256) void policy_chain_kernel(const ChainArgs ca) {
       a.params_out[b * 3 + 1] = (signed char)dx;
       a.params_out[b * 3 + 2] = (signed char)fl;
     }
-    if (ca.chain_out) {
-      int* q = ca.chain_out + (size_t)b * (NBDT_CHAIN_MAX_OPS * 3);
-#pragma unroll
-      for (int s = 0; s < NBDT_CHAIN_MAX_OPS; ++s) {
-        const unsigned w = (unsigned)(chain >> (16 * s));
-        q[3 * s] = (int)(w & 15u); q[3 * s + 1] = (int)((w >> 4) & 31u); q[3 * s + 2] = (int)((w >> 9) & 1u);
-      }
-    }
+    if (ca.chain_out) store_chain(ca.chain_out + (size_t)b * (NBDT_CHAIN_MAX_OPS * 3), chain);
     if (ca.erase_out) {
       int* q = ca.erase_out + (size_t)b * 4;
       q[0] = et; q[1] = el; q[2] = eh; q[3] = ew;
@@ -539,47 +250,23 @@ __global__ __launch_bounds__(256) void policy_chain_kernel(const ChainArgs ca) {
   stage_and_crop(a, a.src + (size_t)idx * n, S, T, dy, dx, fl, tid);
 
   // ---- the chain: `cur` holds the image so far, `oth` is free
-  int last = -1;
-#pragma unroll
-  for (int s = 0; s < NBDT_CHAIN_MAX_OPS; ++s)
-    if ((chain >> (16 * s)) & 15ull) last = s;
+  const int last = last_slot(chain);
   unsigned char* cur = T;
   unsigned char* oth = S;
   OpCtx k = {};            // all slots Identity: the output is read straight from T
-  const int G = (W + 3) >> 2;
-  const int items = 3 * H * G;
   for (int s = 0; s <= last; ++s) {             // (one copy of the passes, not four: the slot is a run-time shift)
-    const unsigned w = (unsigned)(chain >> (16 * s));
-    const int op = (int)(w & 15u);
+    const int op = load_slot(k, a.table, ca.nbins, chain, s);
     if (op == OP_IDENTITY) continue;            // costs nothing: no pass, no barrier
-    load_op(k, a.table, ca.nbins, op, (int)((w >> 4) & 31u), (int)((w >> 9) & 1u));
-    if (op == OP_CONTRAST || op == OP_AUTOCONTRAST || op == OP_EQUALIZE) {
+    if (op_needs_statistics(op)) {
       // the statistics of an earlier operation are stale: start again, a barrier on both sides (the first one also keeps
       // this slot's writes behind every read of the previous LUT)
       __syncthreads();
-      for (int i = tid; i < 776; i += 256) hist[i] = (i >= 769 && i <= 771) ? 255u : 0u;
+      reset_statistics<256>(hist, tid);
       __syncthreads();
-      op_statistics(k, cur, hist, stat, ac, HW, tid);
+      op_statistics<256>(k, cur, hist, stat, ac, HW, tid);
     }
     if (s == last) break;
-    for (int it = tid; it < items; it += 256) {
-      const int row = it / G, g = it - row * G;     // row = c * H + y
-      const int c = row / H, y = row - c * H;
-      unsigned u[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int x = g * 4 + j;
-        u[j] = x < W ? op_pixel(k, cur, hist, ac, H, W, c, y, x) : 0u;
-      }
-      unsigned char* dst = oth + row * W + g * 4;
-      if ((W & 3) == 0) {                  // (both tiles and the row pitch are multiples of four bytes)
-        *(unsigned*)dst = u[0] | (u[1] << 8) | (u[2] << 16) | (u[3] << 24);
-      } else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          if (g * 4 + j < W) dst[j] = (unsigned char)u[j];
-      }
-    }
+    byte_pass<256, false>(k, cur, oth, hist, ac, H, W, tid);
     __syncthreads();
     unsigned char* t = cur;
     cur = oth;
@@ -621,10 +308,10 @@ static int check_erase(PolArgs& a, double erase_prob, const double* erase_scale,
                  "erase_scale must satisfy 0 < lo <= hi <= 1");
     NBDT_REQUIRE(erase_ratio[0] >= 1.0 / 64.0 && erase_ratio[0] <= erase_ratio[1] && erase_ratio[1] <= 64.0,
                  "erase_ratio must satisfy 1/64 <= lo <= hi <= 64");
-    a.erase_p = erase_prob;
-    a.s0 = erase_scale[0];
-    a.s1 = erase_scale[1];
-    a.ratio_table = ratio_table;
+    a.erase.p = erase_prob;
+    a.erase.s0 = erase_scale[0];
+    a.erase.s1 = erase_scale[1];
+    a.erase.ratio_table = ratio_table;
   }
   return NBDT_OK;
 }

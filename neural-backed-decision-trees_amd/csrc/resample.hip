@@ -20,12 +20,19 @@
 // image) fits 64 KB.  resized_crop_global: a source too wide for that; one lane per output pixel, coefficients recomputed
 // per tap, every source byte a global read.  Slow, and the same bytes.
 //
+// nbdt_resized_crop_policy_batch (further down) adds an augmentation policy and random erasing to the training transform:
+// both kernels have a byte-output mode (template parameter BYTES) that writes the resized and flipped uint8 image to a
+// staging buffer, and resized_crop_policy_kernel runs the chain of policy_ops.h's operations on it, one block per image,
+// between two tiles in global memory, normalises and erases.  The float mode is the code it was.
+//
 // Built with -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt (nbdt/_build.py), like augment.hip: the fp64
 // coefficient arithmetic is a sequence of single IEEE operations, and (u / 255 - mean) / std is the three fp32 operations
 // of torch's CPU x.float().div(255).sub(mean).div(std).
 #include "common.h"
+#include "policy_ops.h"
 
 using namespace nbdt;
+using namespace nbdt::pol;      // mix64, pick3, round_sqrt: the draws' arithmetic is the policies'
 
 #define NBDT_RESAMPLE_LDS_BYTES 65536
 #define NBDT_RESAMPLE_PRECISION 22
@@ -49,31 +56,12 @@ struct RcArgs {
   unsigned long long key;
   const int* params_in;
   float* out;
+  unsigned char* out_u8;       // the byte-output mode (BYTES): the resized, flipped uint8 image instead of `out`
   long long* labels_out;
   int* params_out;
   // LDS kernel only: band height, taps per axis, source rows per band, pitches
   int band, kx, ky, srows, spitch, opitch;
 };
-
-__host__ __device__ inline unsigned long long mix64(unsigned long long x) {
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
-__device__ __forceinline__ float pick3(const float* v, int c) { return c == 0 ? v[0] : (c == 1 ? v[1] : v[2]); }
-
-// round-half-to-even of sqrt(v), 0 < v <= 2^30 (4096^2 pixels x ratio 64), decided by exact comparisons: c * c and
-// (c + 1/2)^2 are exact in fp64 for c < 2^25, so the result does not depend on how sqrt() itself is rounded
-__device__ inline int round_sqrt(double v) {
-  long long c = (long long)sqrt(v);
-  if ((double)(c * c) > v) --c;
-  if ((double)((c + 1) * (c + 1)) <= v) ++c;
-  const double half = ((double)c + 0.5) * ((double)c + 0.5);
-  if (v > half) return (int)c + 1;
-  if (v < half) return (int)c;
-  return (int)(c + (c & 1));
-}
 
 // torchvision's RandomResizedCrop.get_params with the project's counter hash (include/nbdt_hip.h, nbdt/data.py
 // draw_resized_crop_params)
@@ -171,6 +159,10 @@ __device__ __forceinline__ void write_header(const RcArgs& a, int b, bool valid,
 // image (sample_params), taps against the box (Axis::bounds), LDS rows against a.srows.  idx is index[b] - index_base mod
 // 2^64, compared unsigned (nbdt_resized_crop_batch_sharded; base 0 is the whole dataset): the draw hashes index[b], rows
 // and labels are read at idx.
+// BYTES: the byte-output mode of nbdt_resized_crop_policy_batch -- the same boxes and resampling, the uint8 result to
+// a.out_u8 [B,3,out_h,out_w] (four packed bytes per lane where out_w % 4 == 0; the host has checked the alignment) and
+// nothing to a.out; an invalid sample's tile is left as it is, nobody reads it.
+template <bool BYTES>
 __global__ __launch_bounds__(256) void resized_crop_lds(const RcArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
   __shared__ int hdr[8];
@@ -183,6 +175,7 @@ __global__ __launch_bounds__(256) void resized_crop_lds(const RcArgs a) {
   float* o = a.out + (size_t)b * 3 * n_out;
   if (!valid) {      // (block-uniform) a zero image, label -1, no source address formed
     if (tid == 0 && blockIdx.x == 0) write_header(a, b, false, idx, hdr);
+    if (BYTES) return;
     for (int it = tid; it < 3 * rows * a.out_w; it += 256) {
       const int cy = it / a.out_w, x = it - cy * a.out_w;
       const int c = cy / rows, y = cy - c * rows;
@@ -279,6 +272,7 @@ __global__ __launch_bounds__(256) void resized_crop_lds(const RcArgs a) {
     const int ymin = (yb[y] & 0xFFFF) - ys0, cnt = yb[y] >> 16;
     const float mean = pick3(a.mean, c), sd = pick3(a.std, c);
     float v[4];
+    unsigned u8[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int x = g * 4 + k;
@@ -289,7 +283,19 @@ __global__ __launch_bounds__(256) void resized_crop_lds(const RcArgs a) {
         const int u = r < nrows ? hts[((size_t)c * a.srows + r) * a.opitch + j] : 0;
         acc += u * cyv[y * a.ky + t];
       }
+      u8[k] = (unsigned)clip8(acc);
       v[k] = ((float)clip8(acc) / 255.0f - mean) / sd;
+    }
+    if (BYTES) {
+      unsigned char* d8 = a.out_u8 + (size_t)b * 3 * n_out + (size_t)c * n_out + (size_t)(y0 + y) * a.out_w + g * 4;
+      if ((a.out_w & 3) == 0) {
+        *(unsigned*)d8 = u8[0] | (u8[1] << 8) | (u8[2] << 16) | (u8[3] << 24);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (g * 4 + k < a.out_w) d8[k] = (unsigned char)u8[k];
+      }
+      continue;
     }
     float* dst = o + (size_t)c * n_out + (size_t)(y0 + y) * a.out_w + g * 4;
     if (vec_out) {
@@ -303,6 +309,7 @@ __global__ __launch_bounds__(256) void resized_crop_lds(const RcArgs a) {
 }
 
 // grid (ceil(3 * out_h * out_w / 256), B): one lane per output pixel, nothing staged
+template <bool BYTES>
 __global__ __launch_bounds__(256) void resized_crop_global(const RcArgs a) {
   __shared__ int hdr[8];
   const int tid = threadIdx.x, b = blockIdx.y;
@@ -314,7 +321,7 @@ __global__ __launch_bounds__(256) void resized_crop_global(const RcArgs a) {
   float* o = a.out + (size_t)b * 3 * n_out;
   if (!valid) {
     if (tid == 0 && blockIdx.x == 0) write_header(a, b, false, idx, hdr);
-    if (e < 3 * n_out) o[e] = 0.f;
+    if (!BYTES && e < 3 * n_out) o[e] = 0.f;
     return;
   }
   if (tid == 0) {
@@ -340,7 +347,112 @@ __global__ __launch_bounds__(256) void resized_crop_global(const RcArgs a) {
     for (int tx = 0; tx < xcnt; ++tx) hacc += (int)s[tx] * ax.coef(xmin + tx, xc, xww);
     acc += clip8(hacc) * ay.coef(ymin + ty, yc, yww);
   }
-  o[e] = ((float)clip8(acc) / 255.0f - pick3(a.mean, c)) / pick3(a.std, c);
+  if (BYTES) a.out_u8[(size_t)b * 3 * n_out + e] = (unsigned char)clip8(acc);
+  else o[e] = ((float)clip8(acc) / 255.0f - pick3(a.mean, c)) / pick3(a.std, c);
+}
+
+// ---- the policy chain and the erase on the resized crop (nbdt_resized_crop_policy_batch's second launch).  One block per
+// image.  The chain ping-pongs between the image's tile of the staging buffer A (what the byte-output mode above wrote) and
+// its tile of B, both in GLOBAL memory: 3 * S * S bytes are 150 KB at S = 224 and two of them fit no LDS.  A tile is
+// written and re-read by this block alone, on one CU, so __syncthreads() (workgroup scope) is all the ordering the passes
+// need; plain loads and stores, so the tile stays in that CU's L1 and the XCD's L2.  Only the statistics live in LDS.  The
+// structure is policy_chain_kernel's (policy.hip) and the rules are the same functions (policy_ops.h): an Identity slot
+// costs no pass, statistics are collected again on the tile an operation reads, the last non-Identity operation is
+// evaluated inside the output pass.  The chain is block-uniform, so every barrier is.
+struct RcpArgs {
+  const long long* index;
+  long long index_base, N;
+  int S;
+  float mean[3], std[3];
+  unsigned long long key;
+  unsigned char* A;                  // uint8 [B,3,S,S]: the resized and flipped image, then scratch
+  unsigned char* Bt;                 // uint8 [B,3,S,S]: scratch
+  const int* table;                  // int32 [NBDT_CHAIN_OPS][nbins][2][6] (device), built for S x S
+  int mode, nbins, num_ops, magnitude, P;
+  const int* subpolicies;            // int32 [P][NBDT_CHAIN_MAX_OPS][3] (op, q, bin), device: clamped by draw_chain
+  const int* chain_in;               // int32 [B][NBDT_CHAIN_MAX_OPS][3] (op, bin, sign): replaces the chain's draw
+  const int* erase_in;               // int32 [B][4] (top, left, h, w): replaces the erase draw
+  EraseDraw erase;
+  int vec_out;                       // S % 4 == 0 and `out` 16-byte aligned (the tiles always are when S % 4 == 0)
+  float* out;
+  int* chain_out;
+  int* erase_out;
+};
+
+// Lanes per image.  Measured at 512 images of 224 x 224 (two blocks per CU; profiles/resized_crop_policy_launch.txt): 256
+// lanes 1150 - 1200 us per call, 512 lanes 861 - 890, 1024 lanes 848 - 897 -- a pass is a stream of dependent byte loads
+// that wants waves to hide behind, and at 73 VGPRs two blocks of 16 waves still share a CU.  512 and 1024 tie at this batch
+// within the spread of the rounds; 1024 was ahead in every fixed-chain timing (1 - 3 %) and is the wider one when a
+// smaller batch leaves a block per CU or fewer.  Reading a point operation's four bytes with one load (WORD) instead of
+// four: 850 - 890 against 899 - 925 us, and 685 against 961 us for four Brightness passes.
+constexpr int kPolicyBlock = 1024;
+
+template <int BLOCK, bool WORD>
+__device__ __forceinline__ void chain_on_tiles(const RcpArgs& a, unsigned long long chain, unsigned char* cur,
+                                                unsigned char* oth, unsigned* hist, double* ac, float* o, int et, int el,
+                                                int eh, int ew, int tid) {
+  const int S = a.S, HW = S * S;
+  unsigned* stat = hist + 768;
+  const int last = last_slot(chain);
+  OpCtx k = {};            // all slots Identity: the output is read straight from A
+  for (int s = 0; s <= last; ++s) {
+    const int op = load_slot(k, a.table, a.nbins, chain, s);
+    if (op == OP_IDENTITY) continue;
+    if (op_needs_statistics(op)) {
+      __syncthreads();     // (also keeps this slot's writes behind every read of the previous LUT)
+      reset_statistics<BLOCK>(hist, tid);
+      __syncthreads();
+      op_statistics<BLOCK>(k, cur, hist, stat, ac, HW, tid);
+    }
+    if (s == last) break;
+    byte_pass<BLOCK, WORD>(k, cur, oth, hist, ac, S, S, tid);
+    __syncthreads();       // the pass's stores before the next pass's loads, its loads before the next pass's stores
+    unsigned char* t = cur;
+    cur = oth;
+    oth = t;
+  }
+  output_pass<BLOCK, WORD>(a.mean, a.std, S, S, a.vec_out, k, cur, hist, ac, o, et, el, eh, ew, tid);
+}
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void resized_crop_policy_kernel(const RcpArgs a) {
+  __shared__ unsigned hist[kStatWords];      // [3][256] histogram, then prefix sums, then the LUT; then stat[8]
+  __shared__ double ac[6];                   // [3][2] AutoContrast's (scale, offset)
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int S = a.S, n = 3 * S * S;
+  const long long gidx = a.index[b];               // the dataset's index: what the draws hash
+  const unsigned long long idx = (unsigned long long)gidx - (unsigned long long)a.index_base;
+  const bool valid = idx < (unsigned long long)a.N;
+  float* o = a.out + (size_t)b * n;
+
+  // ---- the sample's chain and rectangle (block-uniform; every lane computes them)
+  int et = 0, el = 0, eh = 0, ew = 0;
+  unsigned long long chain = 0;
+  if (valid) {
+    if (a.chain_in)
+      chain = clamp_chain(a.chain_in + (size_t)b * (NBDT_CHAIN_MAX_OPS * 3), a.nbins);
+    else
+      chain = draw_chain(a.key, gidx, a.mode, a.nbins, a.num_ops, a.magnitude, a.subpolicies, a.P);
+    if (a.erase_in)
+      clamp_erase(a.erase_in + (size_t)b * 4, S, S, et, el, eh, ew);
+    else
+      draw_erase(a.erase, S, S, erase_word(a.key, gidx), et, el, eh, ew);
+  }
+  if (tid == 0) {          // (the label and the box are the first launch's)
+    if (a.chain_out) store_chain(a.chain_out + (size_t)b * (NBDT_CHAIN_MAX_OPS * 3), chain);
+    if (a.erase_out) {
+      int* q = a.erase_out + (size_t)b * 4;
+      q[0] = et; q[1] = el; q[2] = eh; q[3] = ew;
+    }
+  }
+  if (!valid) {      // (block-uniform) an index the host could not check: a zero image, no tile read
+    for (int i = tid; i < n; i += BLOCK) o[i] = 0.f;
+    return;
+  }
+  unsigned char* cur = a.A + (size_t)b * n;
+  unsigned char* oth = a.Bt + (size_t)b * n;
+  if ((S & 3) == 0) chain_on_tiles<BLOCK, true>(a, chain, cur, oth, hist, ac, o, et, el, eh, ew, tid);
+  else chain_on_tiles<BLOCK, false>(a, chain, cur, oth, hist, ac, o, et, el, eh, ew, tid);
 }
 
 // taps of one axis for the widest box (the whole side): PIL's ksize
@@ -391,14 +503,12 @@ extern "C" int nbdt_resized_crop_band_rows(int32_t H, int32_t W, int32_t rs_h, i
   return plan_band(H, W, rs_h, rs_w, out_h, out_w, nullptr);
 }
 
-extern "C" int nbdt_resized_crop_batch_sharded(const void* src, int32_t src_dtype, const int64_t* labels_src,
-                                               const int64_t* index, int64_t index_base, int32_t B, int64_t N, int32_t H,
-                                               int32_t W, int32_t rs_h, int32_t rs_w, int32_t win_top, int32_t win_left,
-                                               int32_t out_h, int32_t out_w, int32_t flip, const float* mean,
-                                               const float* std, const double* scale, const double* ratio,
-                                               const double* ratio_table, uint64_t seed, uint64_t epoch,
-                                               const int32_t* params_in, float* out, int64_t* labels_out,
-                                               int32_t* params_out, void* stream) {
+// the arguments of both entries, checked before the first device call, into `a` (out / out_u8 are the caller's)
+static int fill_args(RcArgs& a, const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index,
+                     int64_t index_base, int32_t B, int64_t N, int32_t H, int32_t W, int32_t rs_h, int32_t rs_w,
+                     int32_t win_top, int32_t win_left, int32_t out_h, int32_t out_w, int32_t flip, const float* mean,
+                     const float* std, const double* scale, const double* ratio, const double* ratio_table, uint64_t seed,
+                     uint64_t epoch, const int32_t* params_in, const void* out, int64_t* labels_out, int32_t* params_out) {
   NBDT_REQUIRE(src && labels_src && index && out && labels_out, "null argument");
   NBDT_REQUIRE(N <= 0 || (index_base >= 0 && index_base <= INT64_MAX - N),
                "index_base must be >= 0 and index_base + N must fit int64");
@@ -409,7 +519,6 @@ extern "C" int nbdt_resized_crop_batch_sharded(const void* src, int32_t src_dtyp
   NBDT_REQUIRE(flip == 0 || flip == 1, "flip is 0 or 1");
   NBDT_REQUIRE(mean && std, "a uint8 dataset needs mean[3] and std[3]");
   NBDT_REQUIRE(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "std must be non-zero");
-  RcArgs a = {};
   if (!params_in) {
     NBDT_REQUIRE(scale && ratio && ratio_table, "the draw needs scale[2], ratio[2] and the ratio table");
     NBDT_REQUIRE(scale[0] > 0.0 && scale[0] <= scale[1] && scale[1] <= 1.0, "scale must satisfy 0 < lo <= hi <= 1");
@@ -428,20 +537,128 @@ extern "C" int nbdt_resized_crop_batch_sharded(const void* src, int32_t src_dtyp
   for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.std[c] = std[c]; }
   a.key = mix64((unsigned long long)seed * 0x9E3779B97F4A7C15ull + (unsigned long long)epoch);
   a.params_in = (const int*)params_in;
-  a.out = out;
   a.labels_out = (long long*)labels_out;
   a.params_out = (int*)params_out;
-  hipStream_t s = (hipStream_t)stream;
-  const int band = plan_band(H, W, rs_h, rs_w, out_h, out_w, &a);
+  return NBDT_OK;
+}
+
+// the resampling launch: the LDS kernel with the largest band that fits, else the global-memory kernel
+template <bool BYTES>
+static void launch_resample(RcArgs& a, int32_t B, hipStream_t s) {
+  const int band = plan_band(a.H, a.W, a.rs_h, a.rs_w, a.out_h, a.out_w, &a);
   if (band > 0) {
-    const size_t bytes = lds_bytes(H, W, rs_h, rs_w, out_w, band, nullptr);
-    hipLaunchKernelGGL(resized_crop_lds, dim3((out_h + band - 1) / band, B), dim3(256), bytes, s, a);
+    const size_t bytes = lds_bytes(a.H, a.W, a.rs_h, a.rs_w, a.out_w, band, nullptr);
+    hipLaunchKernelGGL(resized_crop_lds<BYTES>, dim3((a.out_h + band - 1) / band, B), dim3(256), bytes, s, a);
   } else {
-    const long long blocks = ((long long)3 * out_h * out_w + 255) / 256;
-    hipLaunchKernelGGL(resized_crop_global, dim3((unsigned)blocks, B), dim3(256), 0, s, a);
+    const long long blocks = ((long long)3 * a.out_h * a.out_w + 255) / 256;
+    hipLaunchKernelGGL(resized_crop_global<BYTES>, dim3((unsigned)blocks, B), dim3(256), 0, s, a);
   }
+}
+
+extern "C" int nbdt_resized_crop_batch_sharded(const void* src, int32_t src_dtype, const int64_t* labels_src,
+                                               const int64_t* index, int64_t index_base, int32_t B, int64_t N, int32_t H,
+                                               int32_t W, int32_t rs_h, int32_t rs_w, int32_t win_top, int32_t win_left,
+                                               int32_t out_h, int32_t out_w, int32_t flip, const float* mean,
+                                               const float* std, const double* scale, const double* ratio,
+                                               const double* ratio_table, uint64_t seed, uint64_t epoch,
+                                               const int32_t* params_in, float* out, int64_t* labels_out,
+                                               int32_t* params_out, void* stream) {
+  RcArgs a = {};
+  if (int rc = fill_args(a, src, src_dtype, labels_src, index, index_base, B, N, H, W, rs_h, rs_w, win_top, win_left, out_h,
+                         out_w, flip, mean, std, scale, ratio, ratio_table, seed, epoch, params_in, out, labels_out,
+                         params_out))
+    return rc;
+  a.out = out;
+  launch_resample<false>(a, B, (hipStream_t)stream);
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;
+}
+
+// ---- the policy chain and the erase on the resized crop: the byte-output resampling into stage_a, then
+// resized_crop_policy_kernel, both on the caller's stream
+extern "C" int nbdt_resized_crop_policy_batch_sharded(
+    const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index, int64_t index_base, int32_t B,
+    int64_t N, int32_t H, int32_t W, int32_t S, int32_t flip, const float* mean, const float* std, const double* scale,
+    const double* ratio, const double* ratio_table, int32_t mode, int32_t nbins, const int32_t* table, int32_t num_ops,
+    int32_t magnitude, const int32_t* subpolicies, int32_t P, double erase_prob, const double* erase_scale,
+    const double* erase_ratio, const double* erase_ratio_table, uint64_t seed, uint64_t epoch, const int32_t* params_in,
+    const int32_t* chain_in, const int32_t* erase_in, void* stage_a, void* stage_b, float* out, int64_t* labels_out,
+    int32_t* params_out, int32_t* chain_out, int32_t* erase_out, void* stream) {
+  NBDT_REQUIRE(S >= 1 && S <= NBDT_RESIZED_CROP_POLICY_MAX_SIDE,
+               "the crop side S must be 1..NBDT_RESIZED_CROP_POLICY_MAX_SIDE (512): Contrast's grey sum and its rounding "
+               "(2*sum + S*S) / (2*S*S) are formed in 32 bits, which a 4096 x 4096 crop would overflow");
+  RcArgs a = {};
+  if (int rc = fill_args(a, src, src_dtype, labels_src, index, index_base, B, N, H, W, S, S, 0, 0, S, S, flip, mean, std,
+                         scale, ratio, ratio_table, seed, epoch, params_in, out, labels_out, params_out))
+    return rc;
+  NBDT_REQUIRE(stage_a && stage_b && stage_a != stage_b, "null argument: the chain needs two distinct staging buffers");
+  NBDT_REQUIRE((uintptr_t)stage_a % 16 == 0 && (uintptr_t)stage_b % 16 == 0, "the staging buffers must be 16-byte aligned");
+  NBDT_REQUIRE(mode == NBDT_CHAIN_RAND || mode == NBDT_CHAIN_SUBPOLICY || mode == NBDT_CHAIN_TA_WIDE,
+               "mode is NBDT_CHAIN_RAND, NBDT_CHAIN_SUBPOLICY or NBDT_CHAIN_TA_WIDE");
+  NBDT_REQUIRE(nbins >= 1 && nbins <= NBDT_CHAIN_MAX_BINS, "nbins must be 1..NBDT_CHAIN_MAX_BINS");
+  RcpArgs p = {};
+  if (mode == NBDT_CHAIN_RAND) {
+    NBDT_REQUIRE(num_ops >= 0 && num_ops <= NBDT_CHAIN_MAX_OPS, "num_ops must be 0..NBDT_CHAIN_MAX_OPS");
+    NBDT_REQUIRE(magnitude >= 0 && magnitude < nbins, "magnitude must be a bin: 0 <= magnitude < nbins");
+    p.num_ops = num_ops;
+    p.magnitude = magnitude;
+  } else if (mode == NBDT_CHAIN_SUBPOLICY) {
+    NBDT_REQUIRE(subpolicies, "null argument: NBDT_CHAIN_SUBPOLICY needs the sub-policies");
+    NBDT_REQUIRE(P >= 1 && P <= NBDT_CHAIN_MAX_SUBPOLICIES, "P (the number of sub-policies) must be 1..NBDT_CHAIN_MAX_SUBPOLICIES");
+    p.subpolicies = subpolicies;
+    p.P = P;
+  } else {
+    NBDT_REQUIRE(nbins == NBDT_POLICY_BINS, "NBDT_CHAIN_TA_WIDE draws among NBDT_POLICY_BINS bins: nbins must be 31");
+  }
+  NBDT_REQUIRE(table || (mode == NBDT_CHAIN_RAND && num_ops == 0 && !chain_in),
+               "null argument: the chain needs its magnitude table");
+  NBDT_REQUIRE(erase_prob >= 0.0 && erase_prob <= 1.0, "erase_prob must be in [0, 1]");       // (NaN fails both)
+  if (erase_prob > 0.0 && !erase_in) {
+    NBDT_REQUIRE(erase_scale && erase_ratio && erase_ratio_table,
+                 "the erase draw needs erase_scale[2], erase_ratio[2] and the ratio table");
+    NBDT_REQUIRE(erase_scale[0] > 0.0 && erase_scale[0] <= erase_scale[1] && erase_scale[1] <= 1.0,
+                 "erase_scale must satisfy 0 < lo <= hi <= 1");
+    NBDT_REQUIRE(erase_ratio[0] >= 1.0 / 64.0 && erase_ratio[0] <= erase_ratio[1] && erase_ratio[1] <= 64.0,
+                 "erase_ratio must satisfy 1/64 <= lo <= hi <= 64");
+    p.erase.p = erase_prob;
+    p.erase.s0 = erase_scale[0];
+    p.erase.s1 = erase_scale[1];
+    p.erase.ratio_table = erase_ratio_table;
+  }
+  a.out_u8 = (unsigned char*)stage_a;
+  p.index = a.index; p.index_base = index_base; p.N = N;
+  p.S = S;
+  for (int c = 0; c < 3; ++c) { p.mean[c] = mean[c]; p.std[c] = std[c]; }
+  p.key = a.key;
+  p.A = (unsigned char*)stage_a;
+  p.Bt = (unsigned char*)stage_b;
+  p.table = table;
+  p.mode = mode; p.nbins = nbins;
+  p.chain_in = chain_in; p.erase_in = erase_in;
+  p.vec_out = (S % 4 == 0 && (uintptr_t)out % 16 == 0) ? 1 : 0;
+  p.out = out;
+  p.chain_out = chain_out; p.erase_out = erase_out;
+  hipStream_t s = (hipStream_t)stream;
+  launch_resample<true>(a, B, s);
+  NBDT_LAUNCH_CHECK();
+  hipLaunchKernelGGL(resized_crop_policy_kernel<kPolicyBlock>, dim3(B), dim3(kPolicyBlock), 0, s, p);
+  NBDT_LAUNCH_CHECK();
+  return NBDT_OK;
+}
+
+extern "C" int nbdt_resized_crop_policy_batch(
+    const void* src, int32_t src_dtype, const int64_t* labels_src, const int64_t* index, int32_t B, int64_t N, int32_t H,
+    int32_t W, int32_t S, int32_t flip, const float* mean, const float* std, const double* scale, const double* ratio,
+    const double* ratio_table, int32_t mode, int32_t nbins, const int32_t* table, int32_t num_ops, int32_t magnitude,
+    const int32_t* subpolicies, int32_t P, double erase_prob, const double* erase_scale, const double* erase_ratio,
+    const double* erase_ratio_table, uint64_t seed, uint64_t epoch, const int32_t* params_in, const int32_t* chain_in,
+    const int32_t* erase_in, void* stage_a, void* stage_b, float* out, int64_t* labels_out, int32_t* params_out,
+    int32_t* chain_out, int32_t* erase_out, void* stream) {
+  return nbdt_resized_crop_policy_batch_sharded(src, src_dtype, labels_src, index, 0, B, N, H, W, S, flip, mean, std, scale,
+                                                ratio, ratio_table, mode, nbins, table, num_ops, magnitude, subpolicies, P,
+                                                erase_prob, erase_scale, erase_ratio, erase_ratio_table, seed, epoch,
+                                                params_in, chain_in, erase_in, stage_a, stage_b, out, labels_out, params_out,
+                                                chain_out, erase_out, stream);
 }
 
 // the whole dataset is the shard at base 0: the same kernels, the same bits

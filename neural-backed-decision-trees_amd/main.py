@@ -59,7 +59,13 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   pixel rules) and ``--random-erase P`` torchvision's ``RandomErasing(P, value=0)`` to every training image, inside the
   one batch-assembly launch of ``--augment reference`` (``nbdt.data.DeviceDataset(policy=, erase_prob=)``,
   ``nbdt_policy_batch``): gather, padded crop, flip, the operation on the bytes, normalise, erase.  Both need a uint8
-  ``--data-file``; ``--augment resized-crop`` does not have them.  MixUp / CutMix still run on the assembled batch.
+  ``--data-file``; ``--augment resized-crop`` does not have them in its one launch.  MixUp / CutMix still run on the
+  assembled batch.
+* ``--augment resized-crop-policy`` is ``resized-crop`` with them: ``--auto-augment ta_wide | ra | cifar10 | imagenet`` and
+  ``--random-erase`` on the ``S x S`` crop (at most 512 x 512), between the flip and the normalisation and after it
+  (``nbdt.data.ResizedCropDataset(policy=, erase_prob=)``, ``nbdt_resized_crop_policy_batch``: the resampling launch
+  writes bytes, a second launch runs the chain between two global-memory tiles per image).  ``--crop-size``,
+  ``--shard-data`` and the evaluation transform are ``resized-crop``'s; it needs a uint8 ``--data-file``.
 * ``--auto-augment ra`` (RandAugment: ``--ra-num-ops`` N in 1..4 operations per image, each uniform among the 14, at bin
   ``--ra-magnitude`` M in 0..30 with a random sign) and ``--auto-augment cifar10`` (AutoAugment's CIFAR-10 policy: one of 25
   sub-policies of two (op, probability, magnitude) slots per image) run the whole chain in the same launch
@@ -171,27 +177,30 @@ def build_parser():
     p.add_argument("--synthetic", type=int, default=0, help="number of synthetic training samples")
     p.add_argument("--image-size", type=int, default=0, help="synthetic image size (default: dataset's)")
     p.add_argument("--seed", type=int, default=0)
-    p.add_argument("--augment", choices=("none", "reference", "resized-crop"), default="none",
+    p.add_argument("--augment", choices=("none", "reference", "resized-crop", "resized-crop-policy"), default="none",
                    help="reference: the reference's RandomCrop(padding) + RandomHorizontalFlip + Normalize on a "
                         "device-resident dataset, one launch per step (nbdt.data); resized-crop: its ImageNet recipe, "
                         "RandomResizedCrop + RandomHorizontalFlip + Normalize for training and Resize + CenterCrop for "
-                        "evaluation, on a device-resident uint8 dataset; none: samples as they are")
+                        "evaluation, on a device-resident uint8 dataset; resized-crop-policy: resized-crop with "
+                        "--auto-augment / --random-erase on the crop (a second launch per step); none: samples as they are")
     p.add_argument("--crop-size", type=int, default=0,
-                   help="--augment resized-crop: output side S (default: the dataset's, 224); evaluation resizes to S + 32")
+                   help="--augment resized-crop | resized-crop-policy: output side S (default: the dataset's, 224); evaluation "
+                        "resizes to S + 32")
     p.add_argument("--shard-data", action="store_true",
                    help="--augment reference | resized-crop: every rank keeps only its contiguous part of both splits on "
                         "its GPU (nbdt.data shard=(rank, world)), a --data-file is memory-mapped, and training shuffles "
                         "within each rank's part")
-    p.add_argument("--auto-augment", choices=("none", "ta_wide", "ra", "cifar10"), default="none",
+    p.add_argument("--auto-augment", choices=("none", "ta_wide", "ra", "cifar10", "imagenet"), default="none",
                    help="ta_wide: TrivialAugmentWide, one of 14 operations at one of 31 magnitudes per training image; ra: "
-                        "RandAugment, --ra-num-ops operations at magnitude --ra-magnitude; cifar10: AutoAugment's CIFAR-10 "
-                        "policy (25 sub-policies of two operations).  All inside the batch-assembly launch (--augment "
-                        "reference on a uint8 --data-file; nbdt.data DeviceDataset(policy=))")
+                        "RandAugment, --ra-num-ops operations at magnitude --ra-magnitude; cifar10 / imagenet: AutoAugment's "
+                        "CIFAR-10 / ImageNet policy (25 sub-policies of two operations).  Inside the batch-assembly launch "
+                        "of --augment reference (nbdt.data DeviceDataset(policy=)), or on the crop of --augment "
+                        "resized-crop-policy (ResizedCropDataset(policy=)); both on a uint8 --data-file")
     p.add_argument("--ra-num-ops", type=int, default=2, metavar="N", help="RandAugment: operations per image, 1..4")
     p.add_argument("--ra-magnitude", type=int, default=9, metavar="M", help="RandAugment: the magnitude bin, 0..30")
     p.add_argument("--random-erase", type=float, default=0.0, metavar="P",
                    help="torchvision's RandomErasing(P, value=0) on every training image after the normalisation, in the "
-                        "same launch (--augment reference on a uint8 --data-file); 0: off")
+                        "same launch (--augment reference | resized-crop-policy on a uint8 --data-file); 0: off")
     p.add_argument("--label-smoothing", type=float, default=0.0, metavar="E",
                    help="label_smoothing of the wrapped nn.CrossEntropyLoss, 0 <= E < 1 (applied inside the fused tree loss)")
     p.add_argument("--mixup-alpha", type=float, default=0.0, metavar="A",
@@ -381,6 +390,11 @@ class _PlainCE:
         return self.inner.soft_target_loss_and_grad(z, target_probs, grad_scale)
 
 
+def resized_crop_family(args):
+    """--augment resized-crop or resized-crop-policy: ResizedCropDataset, --crop-size, the Resize + CenterCrop evaluation."""
+    return args.augment in ("resized-crop", "resized-crop-policy")
+
+
 def load_data(args, num_classes, device, raw=False):
     """train_x, train_y, test_x, test_y on the host.  raw: a uint8 --data-file stays uint8 (the augmentation kernel
     normalises it).  --shard-data memory-maps the file: the datasets slice their rank's part out of it, and only that part
@@ -394,8 +408,8 @@ def load_data(args, num_classes, device, raw=False):
             if raw and x.dtype == torch.uint8:
                 out += [x.contiguous(), y]
                 continue
-            if args.augment == "resized-crop":
-                raise SystemExit(f"--augment resized-crop resamples bytes: {split}_x of {args.data_file} must be uint8, "
+            if resized_crop_family(args):
+                raise SystemExit(f"--augment {args.augment} resamples bytes: {split}_x of {args.data_file} must be uint8, "
                                  f"not {x.dtype}")
             if x.dtype == torch.uint8:
                 x = x.float().div_(255.0)
@@ -412,7 +426,7 @@ def load_data(args, num_classes, device, raw=False):
     def make(m):
         y = torch.randint(0, num_classes, (m,), generator=g)
         x = proto[y] + torch.randn(m, 3, size, size, generator=g)
-        if args.augment == "resized-crop":       # the resized crop reads bytes: the same signal around mid-grey
+        if resized_crop_family(args):            # the resized crop reads bytes: the same signal around mid-grey
             x = (128.0 + 40.0 * x).round_().clamp_(0, 255).to(torch.uint8)
         return x.contiguous(), y
     return [*make(n), *make(max(n // 4, args.batch_size))]
@@ -483,9 +497,9 @@ def parse_args(argv=None):
                      "pass (its start_train raises NotImplementedError)")
     if args.diagnostics_out and not args.diagnostics:
         parser.error("--diagnostics-out needs --diagnostics")
-    if args.shard_data and args.augment not in ("reference", "resized-crop"):
-        parser.error("--shard-data shards the device-resident datasets: it needs --augment reference or --augment "
-                     "resized-crop")
+    if args.shard_data and not (args.augment == "reference" or resized_crop_family(args)):
+        parser.error("--shard-data shards the device-resident datasets: it needs --augment reference, resized-crop or "
+                     "resized-crop-policy")
     if not 0.0 <= args.random_erase <= 1.0:
         parser.error(f"--random-erase must be in [0, 1], got {args.random_erase}")
     if not 1 <= args.ra_num_ops <= 4:
@@ -494,12 +508,14 @@ def parse_args(argv=None):
         parser.error(f"--ra-magnitude must be 0..30, got {args.ra_magnitude}")
     if args.auto_augment != "none" or args.random_erase > 0:
         if args.augment == "resized-crop":
-            parser.error("--auto-augment / --random-erase on --augment resized-crop is not built: the policy runs in the "
-                         "padded-crop launch of --augment reference (images of at most 128 x 128); a 224 x 224 crop "
-                         "belongs in the resampling kernel's output stage")
-        if args.augment != "reference" or not args.data_file:
+            parser.error("--auto-augment / --random-erase on --augment resized-crop is not built into that launch: use "
+                         "--augment resized-crop-policy, which runs the policy on the crop in a second launch")
+        if args.augment not in ("reference", "resized-crop-policy") or not args.data_file:
             parser.error("--auto-augment / --random-erase work on the bytes of a device-resident dataset: they need "
-                         "--augment reference and a uint8 --data-file")
+                         "--augment reference or --augment resized-crop-policy, and a uint8 --data-file")
+    if args.augment == "resized-crop-policy" and not args.data_file:
+        parser.error("--augment resized-crop-policy applies --auto-augment / --random-erase to the bytes of a uint8 "
+                     "--data-file: it needs one")
     if not 0.0 <= args.label_smoothing < 1.0:
         parser.error(f"--label-smoothing must be in [0, 1), got {args.label_smoothing}")
     if args.mixup_alpha < 0 or args.cutmix_alpha < 0:
@@ -556,12 +572,12 @@ def main(argv=None):
     if args.augment == "reference" and args.dataset not in DATASET_STATS:
         raise SystemExit(f"--augment reference: {args.dataset} trains with RandomResizedCrop in the reference, a different "
                          f"transform (--augment resized-crop); supported: {', '.join(sorted(DATASET_STATS))}")
-    if args.augment == "resized-crop" and args.dataset not in RESIZED_CROP_STATS:
-        raise SystemExit(f"--augment resized-crop: {args.dataset} trains with RandomCrop(padding) in the reference "
+    if resized_crop_family(args) and args.dataset not in RESIZED_CROP_STATS:
+        raise SystemExit(f"--augment {args.augment}: {args.dataset} trains with RandomCrop(padding) in the reference "
                          f"(--augment reference); supported: {', '.join(sorted(RESIZED_CROP_STATS))}")
-    if args.crop_size and args.augment != "resized-crop":
-        raise SystemExit("--crop-size belongs to --augment resized-crop")
-    on_device = args.augment in ("reference", "resized-crop")      # both splits are datasets held on the GPU
+    if args.crop_size and not resized_crop_family(args):
+        raise SystemExit("--crop-size belongs to --augment resized-crop | resized-crop-policy")
+    on_device = args.augment == "reference" or resized_crop_family(args)      # both splits are datasets held on the GPU
     rank, world, local = ndist.init_from_env()
     if not torch.cuda.is_available():
         raise SystemExit("main.py needs an MI355X: the NBDT hot path has no CPU fallback")
@@ -601,13 +617,28 @@ def main(argv=None):
                                      f"{policy}: AutoAugment, {len(train_x._subpolicies)} sub-policies")
                 + " per training image, in the batch-assembly launch (nbdt_policy_chain_batch)")
         test_x = DeviceDataset(test_x, test_y, stats["mean"], stats["std"], stats["pad"], **kwargs)
-    elif args.augment == "resized-crop":
+    elif resized_crop_family(args):
         stats = RESIZED_CROP_STATS[args.dataset]
         size = args.crop_size or stats["size"]
         resize = size + 32 if args.crop_size else stats["resize"]       # reference: Resize(input_size + 32)
         kwargs = dict(size=size, resize=resize, scale=stats["scale"], ratio=stats["ratio"], flip=True, device=device,
                       shard=shard)
-        train_x = ResizedCropDataset(train_x, train_y, stats["mean"], stats["std"], **kwargs)
+        policy = None if args.auto_augment == "none" else args.auto_augment        # (resized-crop-policy only: parse_args)
+        try:           # only the training split is augmented; evaluation never applies a policy
+            train_x = ResizedCropDataset(train_x, train_y, stats["mean"], stats["std"], policy=policy,
+                                         erase_prob=args.random_erase, policy_ops=args.ra_num_ops,
+                                         policy_magnitude=args.ra_magnitude, **kwargs)
+        except ValueError as e:
+            if policy or args.random_erase > 0:        # e.g. a crop too large for the policy kernel
+                raise SystemExit(f"--auto-augment / --random-erase: {e}") from e
+            raise
+        if policy or args.random_erase > 0:
+            what = {"ta_wide": "ta_wide: TrivialAugmentWide, one operation",
+                    "ra": f"ra: RandAugment, {args.ra_num_ops} operations at magnitude {args.ra_magnitude}",
+                    None: "none: no operation"}.get(policy) or \
+                f"{policy}: AutoAugment, {len(train_x._subpolicies)} sub-policies"
+            log(f"--auto-augment {what} per training image, --random-erase {args.random_erase:g}, on the {size} x {size} "
+                "crop (nbdt_resized_crop_policy_batch)")
         test_x = ResizedCropDataset(test_x, test_y, stats["mean"], stats["std"], **kwargs)
     n_train = train_x.global_size if on_device else train_x.shape[0]
     n_test = test_x.global_size if on_device else test_x.shape[0]

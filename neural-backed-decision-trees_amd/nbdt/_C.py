@@ -29,6 +29,8 @@ NBDT_CHAIN_MAX_OPS = 4              # slots of a chain
 NBDT_CHAIN_MAX_BINS = 31
 NBDT_CHAIN_MAX_SUBPOLICIES = 1024
 NBDT_CHAIN_RAND, NBDT_CHAIN_SUBPOLICY = 0, 1
+NBDT_CHAIN_TA_WIDE = 2              # nbdt_resized_crop_policy_batch only: one slot, nbdt_policy_batch's draw
+NBDT_RESIZED_CROP_POLICY_MAX_SIDE = 512
 _ZTYPE = {torch.float32: NBDT_F32, torch.bfloat16: NBDT_BF16, torch.float16: NBDT_F16}
 
 
@@ -250,6 +252,17 @@ SIGNATURES = {
                                                 c_int32, _P, c_int32, ctypes.c_double, POINTER(ctypes.c_double),
                                                 POINTER(ctypes.c_double), _P, ctypes.c_uint64, ctypes.c_uint64, _P, _P, _P,
                                                 _P, _P, _P, _P, _P, _P]),
+    "nbdt_resized_crop_policy_batch": (c_int, [_P, c_int32, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32, c_int32,
+                                               POINTER(c_float), POINTER(c_float), POINTER(ctypes.c_double),
+                                               POINTER(ctypes.c_double), _P, c_int32, c_int32, _P, c_int32, c_int32, _P,
+                                               c_int32, ctypes.c_double, POINTER(ctypes.c_double), POINTER(ctypes.c_double),
+                                               _P, ctypes.c_uint64, ctypes.c_uint64] + [_P] * 11),
+    "nbdt_resized_crop_policy_batch_sharded": (c_int, [_P, c_int32, _P, _P, c_int64, c_int32, c_int64, c_int32, c_int32,
+                                                       c_int32, c_int32, POINTER(c_float), POINTER(c_float),
+                                                       POINTER(ctypes.c_double), POINTER(ctypes.c_double), _P, c_int32,
+                                                       c_int32, _P, c_int32, c_int32, _P, c_int32, ctypes.c_double,
+                                                       POINTER(ctypes.c_double), POINTER(ctypes.c_double), _P,
+                                                       ctypes.c_uint64, ctypes.c_uint64] + [_P] * 11),
     "nbdt_stem_patches": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_maxpool3x3s2_fwd": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
     "nbdt_maxpool3x3s2_bwd": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),

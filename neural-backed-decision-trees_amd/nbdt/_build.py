@@ -24,7 +24,8 @@ FLAGS = {
     "rules.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "augment.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],   # bit-exact vs torch's CPU normalise
     "mix.hip": ["-ffp-contract=off"],          # torch's x.mul(lam).add(partner.mul(1 - lam)): two multiplies, one add
-    "resample.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],  # PIL's bytes, torch's normalise
+    # PIL's bytes, torch's normalise; and, for nbdt_resized_crop_policy_batch, policy.hip's reasons (both include policy_ops.h)
+    "resample.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # Pillow's fp32 blend d + a * (x - d) and fp64 v * scale + offset as separate operations, augment.hip's normalise
     "policy.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "conv.hip": ["-munsafe-fp-atomics"],

@@ -20,6 +20,10 @@ bytes, with Pillow's pixel rules, before the normalisation, and torchvision's Ra
 (``draw_policy_params`` restates the draw, ``policy_reference`` the pixels; like ``resample_reference`` it is never called on
 the training path).
 
+``ResizedCropDataset(policy=, erase_prob=)`` has the same policies and the erase on the ``size x size`` crop:
+``nbdt_resized_crop_policy_batch`` (csrc/resample.hip) resamples to bytes and runs the chain between two global-memory tiles
+per image, since a 224 x 224 crop fits no LDS tile (``resized_crop_policy_reference`` restates the pixels).
+
 Both classes take ``shard=(rank, world)``: the rank then keeps only its contiguous part ``shard_range(N, rank, world)`` of
 the dataset on its GPU (ImageNet at 256 x 256 is 252 GB whole, 31.5 GB per rank at 8 ranks) and ``batch`` still takes
 indices into the whole dataset.  The kernels draw from that index and gather from ``index - lo``
@@ -50,6 +54,7 @@ RESIZED_CROP_STATS = {
 
 MAX_PAD = _C.NBDT_AUGMENT_MAX_PAD
 MAX_SIDE = 4096                      # nbdt_resized_crop_batch: image and resized sides
+RESIZED_CROP_POLICY_MAX_SIDE = _C.NBDT_RESIZED_CROP_POLICY_MAX_SIDE      # nbdt_resized_crop_policy_batch: the crop's side
 _M64 = (1 << 64) - 1
 
 
@@ -127,6 +132,51 @@ def _check_policy_source(x):
                          f"(128 x 128 x 3), got {tuple(x.shape[1:])}")
 
 
+def _check_policy(policy, policy_ops, policy_magnitude):
+    """The `policy` setting of both dataset classes, checked on the host: (sub-policies int32 [P,4,3] or None, policy_ops,
+    policy_magnitude)."""
+    subs = None
+    if isinstance(policy, (list, tuple)) or policy in ("cifar10", "imagenet"):
+        subs = subpolicy_array(policy)
+    elif policy == "ra":
+        policy_ops, policy_magnitude = _check_ra(policy_ops, policy_magnitude)
+    elif policy not in (None, "ta_wide"):
+        raise ValueError("policy must be None, 'ta_wide', 'ra', 'cifar10', 'imagenet' or a list of sub-policies, got "
+                         f"{policy!r}")
+    return subs, policy_ops, policy_magnitude
+
+
+def _device_rows(v, name, shape, ok, what, device, who):
+    """An integer parameter tensor of `shape` for a batch launch, int32 on the device: a host tensor is checked with
+    `ok` (ValueError naming `what`) and copied, a device tensor goes to the kernel, which clamps it."""
+    if not isinstance(v, torch.Tensor):
+        v = torch.as_tensor(np.asarray(v))
+    if tuple(v.shape) != shape or v.is_floating_point() or v.dtype == torch.bool:
+        raise ValueError(f"{name} must be integer {list(shape)}, got {v.dtype} {tuple(v.shape)}")
+    if not v.is_cuda:
+        if not bool(ok(v.long()).all()):
+            raise ValueError(f"{name} outside {what}")
+        v = v.to(device, non_blocking=True)
+    _C.require_gpu(v, who)
+    return v.to(dtype=torch.int32).contiguous()
+
+
+def _chain_rows(chain_params, erase_params, B, nbins, H, W, device, who):
+    """chain_params [B,4,3] and erase_params [B,4] (either may be None) through ``_device_rows``."""
+    if chain_params is not None:
+        chain_params = _device_rows(
+            chain_params, "chain_params", (B, CHAIN_MAX_OPS, 3),
+            lambda p: (p[..., 0] >= 0) & (p[..., 0] < len(CHAIN_OPS)) & (p[..., 1] >= 0) & (p[..., 1] < nbins)
+            & (p[..., 2] >= 0) & (p[..., 2] <= 1),
+            f"op in [0, {len(CHAIN_OPS) - 1}], bin in [0, {nbins - 1}], sign in {{0, 1}}", device, who)
+    if erase_params is not None:
+        erase_params = _device_rows(
+            erase_params, "erase_params", (B, 4),
+            lambda p: (p >= 0).all(dim=1) & (p[:, 0] + p[:, 2] <= H) & (p[:, 1] + p[:, 3] <= W),
+            f"the {H} x {W} image", device, who)
+    return chain_params, erase_params
+
+
 class DeviceDataset:
     """A dataset held on the device, batched by `nbdt_augment_batch`.
 
@@ -137,8 +187,8 @@ class DeviceDataset:
     original.  pad: pixels of zero padding before the random ``H x W`` crop; flip: random horizontal flip.
 
     policy="ra": RandAugment -- `policy_ops` (1..4) operations per training sample, each uniform among POLICY_OPS at bin
-    `policy_magnitude` (0..30) with a random sign; policy="cifar10" or a list of sub-policies (``subpolicy_array``'s form):
-    AutoAugment -- one sub-policy per sample, each of its slots applied with its probability.  Both run the whole chain in
+    `policy_magnitude` (0..30) with a random sign; policy="cifar10", "imagenet" or a list of sub-policies
+    (``subpolicy_array``'s form): AutoAugment -- one sub-policy per sample, each of its slots applied with its probability.  Both run the whole chain in
     ``nbdt_policy_chain_batch``, one launch per batch, with the crop, flip and erase rectangle of every other setting.
 
     policy="ta_wide": every training sample gets one TrivialAugmentWide operation (POLICY_OPS, 31 magnitude bins) between the
@@ -156,13 +206,8 @@ class DeviceDataset:
         device = torch.device(device)
         if device.type != "cuda":
             raise _C.NBDTHipError(f"DeviceDataset lives on an MI355X, not on {device} (no CPU fallback)")
-        self._subpolicies = None          # int32 [P,4,3] on the host: the policy is a list of sub-policies (AutoAugment)
-        if isinstance(policy, (list, tuple)) or policy == "cifar10":
-            self._subpolicies = subpolicy_array(policy)
-        elif policy == "ra":
-            policy_ops, policy_magnitude = _check_ra(policy_ops, policy_magnitude)
-        elif policy not in (None, "ta_wide"):
-            raise ValueError(f"policy must be None, 'ta_wide', 'ra', 'cifar10' or a list of sub-policies, got {policy!r}")
+        # int32 [P,4,3] on the host when the policy is a list of sub-policies (AutoAugment), else None
+        self._subpolicies, policy_ops, policy_magnitude = _check_policy(policy, policy_ops, policy_magnitude)
         self.policy = policy
         self.chain = policy is not None and policy != "ta_wide"       # RandAugment / AutoAugment: nbdt_policy_chain_batch
         self.policy_ops, self.policy_magnitude = policy_ops, policy_magnitude
@@ -219,29 +264,8 @@ class DeviceDataset:
         B, H, W = index.shape[0], self.x.shape[2], self.x.shape[3]
         table, subs = self._chain()
         nbins = table.shape[1]
-
-        def device_rows(v, name, shape, ok, what):
-            if not isinstance(v, torch.Tensor):
-                v = torch.as_tensor(np.asarray(v))
-            if tuple(v.shape) != shape or v.is_floating_point() or v.dtype == torch.bool:
-                raise ValueError(f"{name} must be integer {list(shape)}, got {v.dtype} {tuple(v.shape)}")
-            if not v.is_cuda:
-                if not bool(ok(v.long()).all()):
-                    raise ValueError(f"{name} outside {what}")
-                v = v.to(self.device, non_blocking=True)
-            _C.require_gpu(v, "DeviceDataset.batch")
-            return v.to(dtype=torch.int32).contiguous()
-        if chain_params is not None:
-            chain_params = device_rows(
-                chain_params, "chain_params", (B, CHAIN_MAX_OPS, 3),
-                lambda p: (p[..., 0] >= 0) & (p[..., 0] < len(CHAIN_OPS)) & (p[..., 1] >= 0) & (p[..., 1] < nbins)
-                & (p[..., 2] >= 0) & (p[..., 2] <= 1),
-                f"op in [0, {len(CHAIN_OPS) - 1}], bin in [0, {nbins - 1}], sign in {{0, 1}}")
-        if erase_params is not None:
-            erase_params = device_rows(
-                erase_params, "erase_params", (B, 4),
-                lambda p: (p >= 0).all(dim=1) & (p[:, 0] + p[:, 2] <= H) & (p[:, 1] + p[:, 3] <= W),
-                f"the {H} x {W} image")
+        chain_params, erase_params = _chain_rows(chain_params, erase_params, B, nbins, H, W, self.device,
+                                                 "DeviceDataset.batch")
         ratios = self._tables()[1]
         cused = torch.empty((B, CHAIN_MAX_OPS, 3), dtype=torch.int32, device=self.device) if return_chain_params else None
         eused = torch.empty((B, 4), dtype=torch.int32, device=self.device) if return_erase_params else None
@@ -531,15 +555,31 @@ class ResizedCropDataset:
     RandomHorizontalFlip -> ToTensor -> Normalize(mean, std)``; evaluation batches are ``Resize(resize) -> CenterCrop(size)
     -> ToTensor -> Normalize`` (resize defaults to size + 32, as in the reference).  The resampling is PIL's bilinear filter.
 
+    policy / erase_prob / erase_scale / erase_ratio / policy_ops / policy_magnitude: DeviceDataset's settings, here on the
+    ``size x size`` crop (at most 512 x 512): policy="ta_wide" (one TrivialAugmentWide operation), "ra" (RandAugment),
+    "cifar10" / "imagenet" / a list of sub-policies (AutoAugment) apply a chain of up to four operations to the resized and
+    flipped bytes, before the normalisation; erase_prob > 0 is torchvision's RandomErasing(value=0) after it.  Such a
+    training batch is ``nbdt_resized_crop_policy_batch`` (two launches, no host read-back); the magnitude tables are built
+    for the crop (translations (150/331) * size, Rotate about its centre), and a sample's box and flip are the same with and
+    without a policy.  With policy=None and erase_prob == 0 nothing changes: one launch, the same bits.
+
     shard=(rank, world): as for DeviceDataset -- only ``shard_range(N, rank, world)`` is held, ``batch`` takes indices into
     the whole dataset; ``global_size`` and ``shard_range`` say what is where.
     """
 
     def __init__(self, x, y, mean, std, size=224, resize=None, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip=True,
-                 device="cuda", shard=None):
+                 device="cuda", shard=None, policy=None, erase_prob=0.0, erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3),
+                 policy_ops=2, policy_magnitude=9):
         device = torch.device(device)
         if device.type != "cuda":
             raise _C.NBDTHipError(f"ResizedCropDataset lives on an MI355X, not on {device} (no CPU fallback)")
+        self._subpolicies, policy_ops, policy_magnitude = _check_policy(policy, policy_ops, policy_magnitude)
+        self.policy = policy
+        self.chain = policy is not None          # every policy is a chain here: nbdt_resized_crop_policy_batch
+        self.policy_ops, self.policy_magnitude = policy_ops, policy_magnitude
+        self.erase_prob = _check_erase(erase_prob, erase_scale, erase_ratio)
+        self.erase_scale = tuple(float(v) for v in erase_scale)
+        self.erase_ratio = tuple(float(v) for v in erase_ratio)
         if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.uint8:
             raise ValueError(f"x must be uint8 [N,3,H,W], got {x.dtype} {tuple(x.shape)}")
         if y.dim() != 1 or y.shape[0] != x.shape[0] or y.is_floating_point():
@@ -555,6 +595,9 @@ class ResizedCropDataset:
         self.resize = self.size + 32 if resize is None else int(resize)
         if not 1 <= self.size <= self.resize <= MAX_SIDE:
             raise ValueError(f"need 1 <= size <= resize <= {MAX_SIDE}, got size {size}, resize {self.resize}")
+        if (policy is not None or self.erase_prob > 0.0) and self.size > RESIZED_CROP_POLICY_MAX_SIDE:
+            raise ValueError(f"the augmentation policy and random erasing take crops of at most "
+                             f"{RESIZED_CROP_POLICY_MAX_SIDE} x {RESIZED_CROP_POLICY_MAX_SIDE}, got size {self.size}")
         self.scale = tuple(float(v) for v in scale)
         self.ratio = tuple(float(v) for v in ratio)
         self.flip = bool(flip)
@@ -566,6 +609,7 @@ class ResizedCropDataset:
         self.device = self.x.device
         self._table = torch.from_numpy(ratio_table(self.ratio).copy()).to(self.device)
         self._whole = torch.empty((0, 5), dtype=torch.int32, device=self.device)     # evaluation boxes, grown on demand
+        self._chain_tables = None         # (chain table, sub-policies or None, erase ratios) on the device, built on demand
 
     def __len__(self):
         return self.x.shape[0]
@@ -580,7 +624,21 @@ class ResizedCropDataset:
             self._whole = row.repeat(B, 1).to(self.device)
         return self._whole[:B]
 
-    def batch(self, index, epoch=0, seed=0, train=True, params=None, return_params=False):
+    def _chain(self):
+        if self._chain_tables is None:
+            S = self.size
+            if self.policy is None:               # the erase alone: no operation reads a table
+                table = None
+            else:
+                name = self.policy if self.policy in ("ra", "ta_wide") else "cifar10"      # (AutoAugment's 10 bins)
+                table = torch.from_numpy(chain_table(name, S, S).copy()).to(self.device)
+            subs = None if self._subpolicies is None else torch.from_numpy(self._subpolicies).to(self.device)
+            ratios = torch.from_numpy(ratio_table(self.erase_ratio).copy()).to(self.device)
+            self._chain_tables = (table, subs, ratios)
+        return self._chain_tables
+
+    def batch(self, index, epoch=0, seed=0, train=True, params=None, return_params=False, chain_params=None,
+              return_chain_params=False, erase_params=None, return_erase_params=False):
         """(img fp32 [B,3,size,size], targets int64 [B][, params int32 [B,5]]) for the samples `index`, in ONE launch on
         torch's current stream.
 
@@ -591,6 +649,16 @@ class ResizedCropDataset:
         params: int32 [B,5] of (top, left, h, w, flip) replaces the generator; a CPU tensor is range-checked and copied, a
         device tensor is clamped into the image by the kernel.  Without it the draw is
         ``draw_resized_crop_params(seed, epoch, index, H, W, scale, ratio)``.
+
+        With a policy or ``erase_prob > 0`` a training batch is nbdt_resized_crop_policy_batch instead (two launches, two
+        uint8 staging buffers from torch's caching allocator, stream-ordered): the same box and flip, then the chain
+        ``draw_chain_params(seed, epoch, index, policy, policy_ops, policy_magnitude)`` draws -- for "ta_wide" one slot,
+        (op, bin, sign) of ``draw_policy_params`` -- then the normalisation, then the erase rectangle of
+        ``draw_policy_params(seed, epoch, index, size, size, erase_prob, erase_scale, erase_ratio)`` set to 0.0.
+        chain_params (integer [B,4,3] of (op, bin, sign), needs a policy) and erase_params (integer [B,4] of (top, left, h,
+        w)) replace those draws; a CPU tensor is range-checked and copied, a device tensor is clamped by the kernel.
+        return_chain_params / return_erase_params append the int32 [B,4,3] / [B,4] used, in that order.  train=False
+        never applies a policy or an erase.
 
         Every call returns freshly allocated tensors, as DeviceDataset.batch does."""
         H, W = self.x.shape[2], self.x.shape[3]
@@ -619,18 +687,76 @@ class ResizedCropDataset:
                 params = params.to(self.device, non_blocking=True)
             _C.require_gpu(params, "ResizedCropDataset.batch")
             params = params.contiguous()
+        if chain_params is not None and not self.chain:
+            raise ValueError("chain_params belong to policy='ta_wide', 'ra', 'cifar10', 'imagenet' or a list of "
+                             f"sub-policies; this dataset has policy={self.policy!r}")
+        if not train and (chain_params is not None or erase_params is not None):
+            raise ValueError("chain_params / erase_params replace the training draw; train=False has none")
+        S = self.size
+        with_policy = train and (self.chain or self.erase_prob > 0.0 or erase_params is not None)
+        if with_policy and S > RESIZED_CROP_POLICY_MAX_SIDE:
+            raise ValueError(f"the augmentation policy and random erasing take crops of at most "
+                             f"{RESIZED_CROP_POLICY_MAX_SIDE} x {RESIZED_CROP_POLICY_MAX_SIDE}, got size {S}")
         if train:
-            resize, window = (self.size, self.size), (0, 0)
+            resize, window = (S, S), (0, 0)
         else:
             resize, window, params = self.eval_resize, self.eval_window, self._whole_image(B)
-        img = torch.empty((B, 3, self.size, self.size), dtype=torch.float32, device=self.device)
+        img = torch.empty((B, 3, S, S), dtype=torch.float32, device=self.device)
         targets = torch.empty((B,), dtype=torch.int64, device=self.device)
         used = torch.empty((B, 5), dtype=torch.int32, device=self.device) if return_params else None
-        ops.resized_crop_batch(self.x, self.y, index, img, targets, resize, window, self.flip and train, self.mean, self.std,
-                               scale=self.scale, ratio=self.ratio, ratio_table=self._table, seed=seed, epoch=epoch,
-                               params_in=params, params_out=used,
-                               index_base=self.shard_range[0] if self.sharded else None)
-        return (img, targets, used) if return_params else (img, targets)
+        base = self.shard_range[0] if self.sharded else None
+        out = (img, targets, used) if return_params else (img, targets)
+        if not with_policy:
+            ops.resized_crop_batch(self.x, self.y, index, img, targets, resize, window, self.flip and train, self.mean, self.std,
+                                   scale=self.scale, ratio=self.ratio, ratio_table=self._table, seed=seed, epoch=epoch,
+                                   params_in=params, params_out=used, index_base=base)
+            if return_chain_params:          # nothing was applied: Identity, no erase
+                out += (torch.zeros((B, CHAIN_MAX_OPS, 3), dtype=torch.int32, device=self.device),)
+            if return_erase_params:
+                out += (torch.zeros((B, 4), dtype=torch.int32, device=self.device),)
+            return out
+        table, subs, ratios = self._chain()
+        nbins = 1 if table is None else table.shape[1]
+        chain_params, erase_params = _chain_rows(chain_params, erase_params, B, nbins, S, S, self.device,
+                                                 "ResizedCropDataset.batch")
+        cused = torch.empty((B, CHAIN_MAX_OPS, 3), dtype=torch.int32, device=self.device) if return_chain_params else None
+        eused = torch.empty((B, 4), dtype=torch.int32, device=self.device) if return_erase_params else None
+        # the chain's two tiles per image: scratch of this call (the caching allocator reuses it in stream order)
+        stage_a = torch.empty((B, 3, S, S), dtype=torch.uint8, device=self.device)
+        stage_b = torch.empty((B, 3, S, S), dtype=torch.uint8, device=self.device)
+        ra = self.policy == "ra"
+        ops.resized_crop_policy_batch(self.x, self.y, index, img, targets, self.flip, self.mean, self.std, stage_a, stage_b,
+                                      scale=self.scale, ratio=self.ratio, ratio_table=self._table, table=table, nbins=nbins,
+                                      num_ops=self.policy_ops if ra else 0, magnitude=self.policy_magnitude if ra else 0,
+                                      subpolicies=subs, ta_wide=self.policy == "ta_wide", erase_prob=self.erase_prob,
+                                      erase_scale=self.erase_scale, erase_ratio=self.erase_ratio, erase_ratio_table=ratios,
+                                      seed=seed, epoch=epoch, params_in=params, chain_in=chain_params,
+                                      erase_in=erase_params, params_out=used, chain_out=cused, erase_out=eused,
+                                      index_base=base)
+        out += (cused,) if return_chain_params else ()
+        return out + ((eused,) if return_erase_params else ())
+
+
+def resized_crop_policy_reference(img_u8, box, flip, size, chain, table, erase, mean, std):
+    """One training sample of ``ResizedCropDataset(policy=, erase_prob=)`` restated on the CPU: fp32 ``[3,size,size]`` (a
+    tensor).  It composes ``resample_reference(img_u8, box, (size, size))``, the horizontal flip, ``chain_reference`` under
+    `chain` (a sequence of (op, bin, sign); Identity slots may be left in) and `table` (``chain_table(..., size, size)``),
+    torch's CPU ``x.float().div(255).sub(mean).div(std)``, and the rectangle `erase` = (top, left, h, w) set to 0.0.  What
+    nbdt_resized_crop_policy_batch computes.  Test infrastructure and documentation: it must not be called on the training
+    path."""
+    size = int(size)
+    out = resample_reference(img_u8, box, (size, size))
+    if flip:
+        out = out[:, :, ::-1]
+    out = chain_reference(np.ascontiguousarray(out), chain, table)
+    mean = torch.tensor([float(m) for m in mean], dtype=torch.float32).view(3, 1, 1)
+    std = torch.tensor([float(s) for s in std], dtype=torch.float32).view(3, 1, 1)
+    f = torch.from_numpy(np.ascontiguousarray(out)).float().div(255).sub(mean).div(std)
+    t, l, h, w = (int(v) for v in erase)
+    if not (0 <= t and 0 <= l and h >= 0 and w >= 0 and t + h <= size and l + w <= size):
+        raise ValueError(f"erase {tuple(erase)} is not inside the {size} x {size} crop")
+    f[:, t:t + h, l:l + w] = 0.0
+    return f
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -907,15 +1033,35 @@ CIFAR10_POLICY = (
     (("TranslateY", 0.7, 9), ("AutoContrast", 0.9, None)),
 )
 
+# AutoAugment's ImageNet policy: 25 sub-policies in the order torchvision lists them.  Written down from memory; no copy of
+# torchvision or of the paper's table was at hand to check it against (DESIGN.md section 20 says so too).
+IMAGENET_POLICY = (
+    (("Posterize", 0.4, 8), ("Rotate", 0.6, 9)), (("Solarize", 0.6, 5), ("AutoContrast", 0.6, None)),
+    (("Equalize", 0.8, None), ("Equalize", 0.6, None)), (("Posterize", 0.6, 7), ("Posterize", 0.6, 6)),
+    (("Equalize", 0.4, None), ("Solarize", 0.2, 4)), (("Equalize", 0.4, None), ("Rotate", 0.8, 8)),
+    (("Solarize", 0.6, 3), ("Equalize", 0.6, None)), (("Posterize", 0.8, 5), ("Equalize", 1.0, None)),
+    (("Rotate", 0.2, 3), ("Solarize", 0.6, 8)), (("Equalize", 0.6, None), ("Posterize", 0.4, 6)),
+    (("Rotate", 0.8, 8), ("Color", 0.4, 0)), (("Rotate", 0.4, 9), ("Equalize", 0.6, None)),
+    (("Equalize", 0.0, None), ("Equalize", 0.8, None)), (("Invert", 0.6, None), ("Equalize", 1.0, None)),
+    (("Color", 0.6, 4), ("Contrast", 1.0, 8)), (("Rotate", 0.8, 8), ("Color", 1.0, 2)),
+    (("Color", 0.8, 8), ("Solarize", 0.8, 7)), (("Sharpness", 0.4, 7), ("Invert", 0.6, None)),
+    (("ShearX", 0.6, 5), ("Equalize", 1.0, None)), (("Color", 0.4, 0), ("Equalize", 0.6, None)),
+    (("Equalize", 0.4, None), ("Solarize", 0.2, 4)), (("Solarize", 0.6, 5), ("AutoContrast", 0.6, None)),
+    (("Invert", 0.6, None), ("Equalize", 1.0, None)), (("Color", 0.6, 4), ("Contrast", 1.0, 8)),
+    (("Equalize", 0.8, None), ("Equalize", 0.6, None)),
+)
+_NAMED_POLICIES = {"cifar10": CIFAR10_POLICY, "imagenet": IMAGENET_POLICY}
+
 
 def subpolicy_array(policy):
-    """The int32 ``[P, 4, 3]`` of (op, q = round(p * 2^24), bin) nbdt_policy_chain_batch reads for ``"cifar10"`` or a list
-    of sub-policies, each a sequence of 1..4 slots ``(op name, p, bin)`` with bin None (or 0) for an op without a magnitude;
-    an unused slot is (0, 0, 0).  ValueError naming the slot for an unknown op, p outside [0, 1], a bin outside 0..9 or a
-    sub-policy without slots or with more than four."""
-    subs = CIFAR10_POLICY if isinstance(policy, str) and policy == "cifar10" else policy
+    """The int32 ``[P, 4, 3]`` of (op, q = round(p * 2^24), bin) nbdt_policy_chain_batch reads for ``"cifar10"``,
+    ``"imagenet"`` or a list of sub-policies, each a sequence of 1..4 slots ``(op name, p, bin)`` with bin None (or 0) for an
+    op without a magnitude; an unused slot is (0, 0, 0).  ValueError naming the slot for an unknown op, p outside [0, 1], a
+    bin outside 0..9 or a sub-policy without slots or with more than four."""
+    subs = _NAMED_POLICIES.get(policy, policy) if isinstance(policy, str) else policy
     if isinstance(subs, str) or not isinstance(subs, (list, tuple)) or not 1 <= len(subs) <= _C.NBDT_CHAIN_MAX_SUBPOLICIES:
-        raise ValueError(f"a policy is 'cifar10' or a list of 1..{_C.NBDT_CHAIN_MAX_SUBPOLICIES} sub-policies, got {policy!r}")
+        raise ValueError(f"a policy is 'cifar10', 'imagenet' or a list of 1..{_C.NBDT_CHAIN_MAX_SUBPOLICIES} sub-policies, "
+                         f"got {policy!r}")
     out = np.zeros((len(subs), CHAIN_MAX_OPS, 3), dtype=np.int32)
     for i, sub in enumerate(subs):
         if not isinstance(sub, (list, tuple)) or not 1 <= len(sub) <= CHAIN_MAX_OPS:
@@ -945,8 +1091,8 @@ def subpolicy_array(policy):
 def _chain_bins(policy):
     if isinstance(policy, str) and policy in ("ra", "ta_wide"):
         return RA_BINS
-    if isinstance(policy, str) and policy != "cifar10":
-        raise ValueError(f"policy must be 'ra', 'cifar10', 'ta_wide' or a list of sub-policies, got {policy!r}")
+    if isinstance(policy, str) and policy not in _NAMED_POLICIES:
+        raise ValueError(f"policy must be 'ra', 'cifar10', 'imagenet', 'ta_wide' or a list of sub-policies, got {policy!r}")
     return AA_BINS
 
 
@@ -963,7 +1109,12 @@ def chain_table(policy, H, W):
     AutoAugment's over n = 10; each magnitude is hi * b / (n - 1) in fp64 with hi = 0.3 (shear), (150 / 331) * side
     (translation, truncated to whole pixels), 30 degrees, 0.9 (the four enhancements), Posterize to
     8 - round(b / ((n - 1) / 4)) bits, Solarize below 255 - 255 * b / (n - 1).  "ta_wide": TrivialAugmentWide's ranges
-    (``policy_table``'s rows, and Invert's) -- a chain of one op on it is nbdt_policy_batch."""
+    (``policy_table``'s rows, and Invert's) -- a chain of one op on it is nbdt_policy_batch.  A table belongs to a space of
+    magnitudes, not to a list of sub-policies: AutoAugment's ImageNet policy reads the table "cifar10" names, and
+    ``chain_table("imagenet", ...)`` is a ValueError saying so."""
+    if isinstance(policy, str) and policy == "imagenet":
+        raise ValueError("AutoAugment has one magnitude space for all its policies: the table of policy 'imagenet' is "
+                         "chain_table('cifar10', H, W)")
     H, W = int(H), int(W)
     if not (1 <= H <= MAX_SIDE and 1 <= W <= MAX_SIDE):
         raise ValueError(f"image sides must be 1..{MAX_SIDE}, got {H} x {W}")

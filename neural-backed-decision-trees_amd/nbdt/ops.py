@@ -752,6 +752,45 @@ def resized_crop_batch(src, labels_src, index, out, labels_out, resize, window, 
         check(lib().nbdt_resized_crop_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
 
 
+def resized_crop_policy_batch(src, labels_src, index, out, labels_out, flip, mean, std, stage_a, stage_b, scale=None,
+                              ratio=None, ratio_table=None, table=None, nbins=1, num_ops=0, magnitude=0, subpolicies=None,
+                              ta_wide=False, erase_prob=0.0, erase_scale=None, erase_ratio=None, erase_ratio_table=None,
+                              seed=0, epoch=0, params_in=None, chain_in=None, erase_in=None, params_out=None,
+                              chain_out=None, erase_out=None, index_base=None):
+    """nbdt_resized_crop_policy_batch: resized_crop_batch's training transform to out[B,3,S,S] (S = out.shape[2]) with a
+    chain of up to four operations on the S x S bytes between the flip and the normalisation, and RandomErasing(value=0)
+    after it.  Two launches on the current stream; stage_a / stage_b: uint8 [B,3,S,S] scratch, device.  table: int32
+    [15, nbins, 2, 6] built for S x S, device.  subpolicies given: NBDT_CHAIN_SUBPOLICY; ta_wide: NBDT_CHAIN_TA_WIDE (one
+    slot, policy_batch's draw); else NBDT_CHAIN_RAND with num_ops (0..4; 0: the erase only) slots at bin `magnitude`.
+    params_in / params_out: int32 [B,5] as resized_crop_batch; chain_in / chain_out: int32 [B,4,3]; erase_in / erase_out:
+    int32 [B,4]; the *_in replace the draws.  index_base: the _sharded entry, as for resized_crop_batch."""
+    N, _, H, W = src.shape
+    if out.shape[2] != out.shape[3] or tuple(stage_a.shape) != tuple(out.shape) or tuple(stage_b.shape) != tuple(out.shape) \
+            or stage_a.dtype != torch.uint8 or stage_b.dtype != torch.uint8:
+        raise _C.NBDTHipError(f"resized_crop_policy_batch: out must be [B,3,S,S] and both staging buffers uint8 of that "
+                              f"shape, got out {tuple(out.shape)}, stage_a {stage_a.dtype} {tuple(stage_a.shape)}, stage_b "
+                              f"{stage_b.dtype} {tuple(stage_b.shape)}")
+    f3 = lambda v: (ctypes.c_float * 3)(*[float(a) for a in v])
+    d2 = lambda v: None if v is None else (ctypes.c_double * 2)(*[float(a) for a in v])
+    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
+    mask = (1 << 64) - 1
+    if subpolicies is not None:
+        mode = _C.NBDT_CHAIN_SUBPOLICY
+    else:
+        mode = _C.NBDT_CHAIN_TA_WIDE if ta_wide else _C.NBDT_CHAIN_RAND
+    tail = (index.shape[0], N, H, W, out.shape[2], 1 if flip else 0, f3(mean), f3(std), d2(scale), d2(ratio),
+            ptr(ratio_table), mode, int(nbins), ptr(table), int(num_ops), int(magnitude), ptr(subpolicies),
+            0 if subpolicies is None else subpolicies.shape[0], float(erase_prob), d2(erase_scale), d2(erase_ratio),
+            ptr(erase_ratio_table), int(seed) & mask, int(epoch) & mask, ptr(params_in), ptr(chain_in), ptr(erase_in),
+            ptr(stage_a), ptr(stage_b), ptr(out), ptr(labels_out), ptr(params_out), ptr(chain_out), ptr(erase_out),
+            stream_ptr(src.device))
+    if index_base is None:
+        check(lib().nbdt_resized_crop_policy_batch(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
+    else:
+        check(lib().nbdt_resized_crop_policy_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base),
+                                                           *tail))
+
+
 def resized_crop_band_rows(H, W, resize, window, out_size):
     """nbdt_resized_crop_band_rows (host only): output rows per block of the LDS-staged kernel, 0 = the global-memory
     kernel runs for this geometry."""
