@@ -401,6 +401,50 @@ int nbdt_conv_igemm_affine(const nbdt_conv_desc* d, const void* in, const void* 
 int nbdt_conv_pw(const nbdt_conv_desc* d, const void* in, const void* w, void* out,
                  float* bn_partials /* nullable */, void* stream);
 
+/* ------------------------------------------------------------------ grouped 3x3 convolution (nbdt_version() >= 125)
+ * conv2 of torchvision's ResNeXt Bottleneck (nn.Conv2d(width, width, 3, stride, 1, groups=groups, bias=False)) and its
+ * autograd: cin == cout == width, width % 32 == 0, cg = width / groups channels per group with cg in {4, 8, 16, 32}.
+ * cg divides 32, so the conv is width / 32 independent dense 32 -> 32 convolutions with block-diagonal weights
+ * (csrc/conv_group.hip).  Every tensor is padded NHWC [B][H+2][W+2][width] with a zero ring, B, H, W the conv's INPUT
+ * batch and sides (the output is [B][H/stride+2][W/stride+2][width]); stride 1 or 2 with pad 1, even sides at stride 2.
+ * Only interior pixels are written: the ring of every output keeps its bytes.  Every argument is checked before the
+ * first HIP call (NBDT_EINVAL and a message): null pointers, width % 32 != 0, any other cg (cg = 64 -- layer4 of
+ * resnext101_32x8d -- included), any other stride, an odd side at stride 2, an empty batch.
+ *
+ * nbdt_conv_group_weight_prep: fp32 master w[width][9][cg] ([cout][taps][cin in group]) -> bf16 blocks
+ *   wf[width/32][32 co][9][32 ci], explicit zeros off the group diagonal (nullable), and the data-gradient blocks
+ *   wd[width/32][32 ci][9][32 co] with the tap order reversed, wd[n][ci][t][co] = wf[n][co][8 - t][ci] (nullable).
+ * nbdt_conv_group_weight_prep_batched: the same for n_layers convs in one launch; table (device, int64 [n_layers][5])
+ *   rows are {master offset in flat, offset of the layer's blocks in wf_flat / wd_flat, width, cg, index of the
+ *   layer's first block}, first blocks ascending from 0, total_blocks = sum of width / 32 (rows are not validated). */
+int nbdt_conv_group_weight_prep(const float* w, int32_t width, int32_t cg, void* wf_bf16, void* wd_bf16, void* stream);
+int nbdt_conv_group_weight_prep_batched(const float* flat, const int64_t* table, int32_t n_layers, int64_t total_blocks,
+                                        void* wf_flat, void* wd_flat, void* stream);
+/* out = conv3x3(in), bf16 operands, fp32 accumulation in tap order, one round-to-nearest-even at the store.  scale and
+ * shift (both or neither; fp32 [width]): out = act(acc * scale[c] + shift[c]) with the meaning of
+ * nbdt_conv_igemm_affine (act: NBDT_ACT_NONE | RELU | SWISH; without scale / shift only NBDT_ACT_NONE).  No residual
+ * operand and no statistics epilogue. */
+int nbdt_conv_group_fwd(const void* in, const void* wf, void* out, int32_t B, int32_t H, int32_t W, int32_t width,
+                        int32_t cg, int32_t stride, const float* scale, const float* shift, int32_t act, void* stream);
+/* gin[B][H+2][W+2] = data gradient of the above from gout[B][H/stride+2][W/stride+2], gather form over wd: at stride 2
+ * an input pixel sums only the taps its parity allows (4 / 2 / 2 / 1).  accumulate must be 0: there is no
+ * accumulating form (NBDT_EINVAL). */
+int nbdt_conv_group_dgrad(const void* gout, const void* wd, void* gin, int32_t B, int32_t H, int32_t W, int32_t width,
+                          int32_t cg, int32_t stride, int32_t accumulate, void* stream);
+/* dw[width][9][cg] fp32 += sum over pixels of gout[p][co] * x[stride p + tap][ci], ci in co's group.  No fp32 atomics:
+ * per-pixel-split sums in plain stores to a per-(device, stream) workspace (NBDT_ENOMEM if it cannot be had), then one
+ * fold that adds them in split order ONTO what dw holds.  Two runs leave identical bits. */
+int nbdt_conv_group_wgrad(const void* x, const void* gout, float* dw, int32_t B, int32_t H, int32_t W, int32_t width,
+                          int32_t cg, int32_t stride, void* stream);
+/* verification-only fp32-storage twins of the three (see nbdt_ref_conv below): fp32 tensors, w = the fp32 MASTER
+ * [width][9][cg] itself (no expansion), one thread per output, direct loops */
+int nbdt_ref_conv_group_fwd(const float* in, const float* w, float* out, int32_t B, int32_t H, int32_t W, int32_t width,
+                            int32_t cg, int32_t stride, void* stream);
+int nbdt_ref_conv_group_dgrad(const float* gout, const float* w, float* gin, int32_t B, int32_t H, int32_t W,
+                              int32_t width, int32_t cg, int32_t stride, int32_t accumulate, void* stream);
+int nbdt_ref_conv_group_wgrad(const float* x, const float* gout, float* dw, int32_t B, int32_t H, int32_t W,
+                              int32_t width, int32_t cg, int32_t stride, void* stream);
+
 /* weight gradient (replaces cuDNN wgrad): dw[cout][w_ntaps][cin] fp32 += sum over the pixel grid
  * of gy[pix_g(m)][co] * x[pix_x(m) + tap_off[t]][ci]; split over pixels with fp32 atomics, so dw
  * must be zeroed (or hold the running .grad) before the call. */

@@ -161,6 +161,14 @@ SIGNATURES = {
     "nbdt_conv_wgrad": (c_int, [POINTER(WgradDesc), _P, _P, _P, _P]),
     "nbdt_ref_conv": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "nbdt_ref_wgrad": (c_int, [POINTER(WgradDesc), _P, _P, _P, _P]),
+    "nbdt_conv_group_weight_prep": (c_int, [_P, c_int32, c_int32, _P, _P, _P]),
+    "nbdt_conv_group_weight_prep_batched": (c_int, [_P, _P, c_int32, c_int64, _P, _P, _P]),
+    "nbdt_conv_group_fwd": (c_int, [_P, _P, _P] + [c_int32] * 6 + [_P, _P, c_int32, _P]),
+    "nbdt_conv_group_dgrad": (c_int, [_P, _P, _P] + [c_int32] * 7 + [_P]),
+    "nbdt_conv_group_wgrad": (c_int, [_P, _P, _P] + [c_int32] * 6 + [_P]),
+    "nbdt_ref_conv_group_fwd": (c_int, [_P, _P, _P] + [c_int32] * 6 + [_P]),
+    "nbdt_ref_conv_group_dgrad": (c_int, [_P, _P, _P] + [c_int32] * 7 + [_P]),
+    "nbdt_ref_conv_group_wgrad": (c_int, [_P, _P, _P] + [c_int32] * 6 + [_P]),
     "nbdt_ref_bn_stats": (c_int, [_P, c_int32, c_int32, c_int32, c_int32, c_float, c_float, _P, _P, _P, _P, _P, _P]),
     "nbdt_ref_bn_apply": (c_int, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_ref_bn_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_int32, _P, c_int32, c_int32, c_int32, c_int32,

@@ -181,6 +181,8 @@ class Conv:
         self.side_stream = None              # the engine's second stream for weight gradients, or None: the caller's
         self.pointwise = False               # stride-1 1x1 launches go to ops.conv_pw (BottleneckEngine.pointwise)
 
+    fused_stats = True     # forward(bn_scratch=...) leaves the next BatchNorm's partial sums (ResNetEngine.forward asks)
+
     def logical(self, buf):
         """[cout_real, cin_real, k, k] view (OIHW semantics, channels_last memory) of a flat buffer."""
         v = self.store._view(buf, self.name).view(self.cout, self.k, self.k, self.cin)
@@ -311,6 +313,67 @@ class Conv:
             ops.conv_wgrad(desc, x, gout, self.store.g(self.name), cu_budget)
 
 
+class GroupedConv:
+    """Grouped 3x3 convolution (bias-free) of a ResNeXt bottleneck: cin == cout == width, cg = width / groups channels per
+    group with cg in ops.GROUP_CG -- width / 32 block-diagonal 32 x 32 convolutions (csrc/conv_group.hip).  The four
+    launches the block walker calls; NOT in _Engine.convs (whose batched tables assume dense [cout][taps][cin] masters):
+    _Engine.gconvs, with its own derived-weight tables (_Engine.finalize / refresh_derived_weights).
+
+    Master parameter [width][9][cg] (project order [cout][taps][cin in group]); init is torchvision's
+    kaiming_normal_(mode="fan_out") of the [width, cg, 3, 3] weight, whose fan_out is width * 9 (torch takes it from the
+    tensor's shape: the group count does not enter)."""
+
+    k, taps = 3, 9
+    fused_stats = False    # no statistics epilogue: the following BatchNorm takes its separate bn.stats pass
+    pointwise = False
+
+    def __init__(self, store, name, width, groups, stride, gen):
+        cg = width // groups if groups > 0 else 0
+        if groups <= 0 or width % groups or width % 32 or cg not in ops.GROUP_CG:
+            raise ValueError(f"{name}: a grouped 3x3 conv takes width % 32 == 0 and width / groups in {ops.GROUP_CG}, got "
+                             f"width {width}, groups {groups} (cg = 64, as in resnext101_32x8d, is not supported)")
+        self.store, self.name = store, name
+        self.cin_real = self.cout_real = self.cin = self.cout = self.width = width
+        self.groups, self.cg, self.stride = groups, cg, stride
+        std = math.sqrt(2.0 / (width * 9))
+        store.add(name, (width, 9, cg), lambda v: v.normal_(0.0, std, generator=gen))
+        self.wf = self.wd = None             # expanded bf16 blocks [width/32][32][9][32]: views of the engine's flat buffers
+        self.side_stream = None
+
+    def logical(self, buf):
+        """[width, cg, 3, 3] view (OIHW semantics: torchvision's shape of a grouped weight) of a flat buffer."""
+        return self.store._view(buf, self.name).view(self.width, 3, 3, self.cg).permute(0, 3, 1, 2)
+
+    def numel(self):
+        return self.width * 9 * 32
+
+    def _master_or(self, t, blocks):
+        """fp32 tensors (verification-only reference mode) take the fp32 master itself, bf16 ones the expanded blocks."""
+        return self.store.p(self.name) if t.dtype == torch.float32 else blocks
+
+    def forward(self, x, out, residual=None, bn_scratch=None):
+        assert residual is None and bn_scratch is None, "the grouped conv has no residual operand and no statistics epilogue"
+        ops.conv_group_fwd(x, self._master_or(x, self.wf), out, self.cg, self.stride)
+
+    def forward_affine(self, x, out, bn, act=1, residual=None):
+        assert residual is None, "the grouped conv has no residual operand"
+        scale, shift = bn.eval_affine()
+        ops.conv_group_fwd(x, self.wf, out, self.cg, self.stride, scale, shift, act)
+
+    def backward_data(self, gout, gin, accumulate=False):
+        ops.conv_group_dgrad(gout, self._master_or(gout, self.wd), gin, self.cg, self.stride, accumulate)
+
+    def backward_weight(self, x, gout, cu_budget=0):
+        """On the engine's second stream, as Conv._wgrad (cu_budget: ignored, the launch is not a one-block-per-CU kernel)."""
+        side = self.side_stream
+        if side is None:
+            ops.conv_group_wgrad(x, gout, self.store.g(self.name), self.cg, self.stride)
+            return
+        side.wait_stream(torch.cuda.current_stream(x.device))
+        with torch.cuda.stream(side):
+            ops.conv_group_wgrad(x, gout, self.store.g(self.name), self.cg, self.stride)
+
+
 class PatchConv(Conv):
     """A k x k convolution of the 3-colour image as the 1x1 convolution of its patch tensor (ops.stem_patches): cin_real =
     3 * k * k channels in (r, s, ci) order.  Always on nbdt_conv_igemm, whatever the engine routes its pointwise convs to."""
@@ -431,6 +494,7 @@ class _Engine:
         self._scratch = None
         self._bufs = {}
         self.convs, self.bns = [], []
+        self.gconvs = []          # GroupedConv: not in convs (finalize's dense tables); own tables, same refresh points
         self.training = True
         self.act_dtype = torch.bfloat16   # storage of activations / activation gradients (fp32: set_reference_fp32)
         self.debug_keep = False   # tests: give every unit its own gradient buffers (no reuse)
@@ -562,6 +626,13 @@ class _Engine:
         self.convs.append(c)
         return c
 
+    def grouped_conv(self, name, width, groups, stride):
+        c = GroupedConv(self.store, name, width, groups, stride, self.gen)
+        if self._side is not None:
+            c.side_stream = self._side
+        self.gconvs.append(c)
+        return c
+
     def set_reference_fp32(self, on=True):
         """VERIFICATION ONLY.  Switch the storage of every activation / activation-gradient buffer to fp32: nbdt.ops then
         routes each launch on such a buffer to the plain fp32 kernel of the same meaning (csrc/ref_fp32.hip) while this
@@ -587,7 +658,7 @@ class _Engine:
         """Turn the second (weight-gradient) stream on/off at run time; off = every launch on the caller's stream,
         so a kernel's event-bracketed duration is its own (bench.py's roofline pass)."""
         self.join_side_stream()
-        for c in self.convs + list(getattr(self, "dws", [])):
+        for c in self.convs + self.gconvs + list(getattr(self, "dws", [])):
             c.side_stream = self._side if on else None
         self._overlap = bool(on)
 
@@ -877,8 +948,14 @@ class _Engine:
             c.wd = self._wd_flat[off:off + c.numel()].view(c.cin, c.taps, c.cout)
             off += c.numel()
             tiles += c.taps * ((c.cout + 63) // 64) * (c.cin // 32)
-        self._wd_table = torch.tensor(rows, dtype=torch.int64, device=self.device)
-        self._wd_total = tiles
+        # nbdt_weight_prep_batched takes at most 64 layers per launch: one launch up to there (ResNet50: 53 convs), one per 64
+        # layers beyond (the 101-layer nets: 71 .. 155), each with its own first-tile numbering
+        self._wd_chunks = []
+        for i in range(0, len(rows), self.WD_CHUNK):
+            part = rows[i:i + self.WD_CHUNK]
+            end = rows[i + self.WD_CHUNK][5] if i + self.WD_CHUNK < len(rows) else tiles
+            table = torch.tensor([r[:5] + [r[5] - part[0][5]] for r in part], dtype=torch.int64, device=self.device)
+            self._wd_chunks.append((table, len(part), end - part[0][5]))
         # DMA-ordered weight tiles for the dense 3x3 / stride-1 kernel (forward weights from the bf16 mirror, data-
         # gradient weights from the transposed copy): one 1-KiB LDS-DMA instruction then reads one contiguous KiB
         dense = [c for c in self.convs if c.k == 3 and c.stride == 1]
@@ -909,7 +986,35 @@ class _Engine:
             self._wt_ftable = torch.tensor(frows, dtype=torch.int64, device=self.device)
             self._wt_dtable = torch.tensor(drows, dtype=torch.int64, device=self.device)
             self._wt_ftotal, self._wt_dtotal = tf, td
+        # grouped 3x3 convs: the expanded block-diagonal forward / data-gradient blocks of all of them, one table
+        if self.gconvs:
+            n_el = sum(c.numel() for c in self.gconvs)
+            self._gw_fwd = torch.empty(n_el, dtype=torch.bfloat16, device=self.device)
+            self._gw_dgrad = torch.empty(n_el, dtype=torch.bfloat16, device=self.device)
+            rows, off, first = [], 0, 0
+            for c in self.gconvs:
+                rows.append([self.store.entries[c.name][0], off, c.width, c.cg, first])
+                c.wf = self._gw_fwd[off:off + c.numel()]
+                c.wd = self._gw_dgrad[off:off + c.numel()]
+                off += c.numel()
+                first += c.width // 32
+            self._gw_table = torch.tensor(rows, dtype=torch.int64, device=self.device)
+            self._gw_total = first
         self.refresh_derived_weights()
+
+    WD_CHUNK = 64     # layers per nbdt_weight_prep_batched launch (the entry's limit)
+
+    def _prep_dgrad_copies(self):
+        for table, n, tiles in self._wd_chunks:
+            ops.weight_prep_batched(self.store.flat, table, n, tiles, self._wd_flat)
+
+    def _prep_grouped(self, dgrad):
+        """The grouped convs' forward blocks (needed by the very next forward: caller's stream) or data-gradient blocks
+        (wherever the dense data-gradient copies are built)."""
+        if self.gconvs:
+            ops.conv_group_weight_prep_batched(self.store.flat, self._gw_table, len(self.gconvs), self._gw_total,
+                                               wf_flat=None if dgrad else self._gw_fwd,
+                                               wd_flat=self._gw_dgrad if dgrad else None)
 
     def refresh_derived_weights(self):
         for b in self.bns:             # gamma / beta may have changed: drop the folded eval transforms
@@ -920,20 +1025,23 @@ class _Engine:
         if self._wt_n:     # forward tiles are needed by the very next forward: caller's stream
             ops.weight_tile_batched(self.store.bf16, self._wt_ftable, self._wt_n, self._wt_ftotal, self._wt_fwd)
         self._retile_seg(False)
+        self._prep_grouped(False)
         if self._side is None or not self._overlap:
-            ops.weight_prep_batched(self.store.flat, self._wd_table, len(self.convs), self._wd_total, self._wd_flat)
+            self._prep_dgrad_copies()
             if self._wt_n:
                 ops.weight_tile_batched(self._wd_flat, self._wt_dtable, self._wt_n, self._wt_dtotal, self._wt_dgrad)
             self._retile_seg(True)
+            self._prep_grouped(True)
             return
         # the transposed copies are only read by data-gradient launches: build them on the second stream while
         # the next forward runs (backward() joins the stream before its first dgrad)
         self._side.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(self._side):
-            ops.weight_prep_batched(self.store.flat, self._wd_table, len(self.convs), self._wd_total, self._wd_flat)
+            self._prep_dgrad_copies()
             if self._wt_n:
                 ops.weight_tile_batched(self._wd_flat, self._wt_dtable, self._wt_n, self._wt_dtotal, self._wt_dgrad)
             self._retile_seg(True)
+            self._prep_grouped(True)
 
     def optimizer_step(self, lr, momentum, weight_decay, config=None, grad_scale=1.0, zero_grad=False):
         """The optimizer pass over every parameter + refresh of bf16 / dgrad weights: what sgd_step (config None),
@@ -1170,7 +1278,7 @@ class _Engine:
     def named_params(self, which="flat"):
         buf = {"flat": self.store.flat, "grad": self.store.grad, "bf16": self.store.bf16, "ema": self.store.ema}[which]
         out = dict(self.extra_param_views(buf))
-        for c in self.convs:
+        for c in self.convs + self.gconvs:
             out[c.name] = c.logical(buf)
         for b in self.bns:
             out[b.name + ".weight"] = self.store._view(buf, b.name + ".weight")[:b.c_real]
@@ -1607,7 +1715,7 @@ class ResNetEngine(_Engine):
         self.store.add(b, (num_classes,), lambda v: v.uniform_(-kb, kb, generator=gen))
         self.finalize()
         self._side = side_stream(self.device)     # weight gradients on a second stream (see WRNEngine)
-        for c in self.convs:
+        for c in self.convs + self.gconvs:
             c.side_stream = self._side
         dev = self.device
         # identity "BN" for the plain average-pool head (features are already post-ReLU)
@@ -1635,10 +1743,14 @@ class ResNetEngine(_Engine):
         measured for this block's (conv2, bn1) only."""
         return [self._stage(pre, 1, cin, planes, 3, stride), self._stage(pre, 2, planes, planes, 3, 1, fusable=True)]
 
-    def _stage(self, pre, m, cin, cout, k, stride, fusable=False):
+    def _stage(self, pre, m, cin, cout, k, stride, fusable=False, groups=1):
         gamma = 0.0 if self.zero_init_residual and m == self.block_convs else 1.0
-        return (self.conv(f"{pre}conv{m}.weight", cin, cout, k, stride, init=self.conv_init),
-                self.bn(f"{pre}bn{m}", cout, gamma), fusable)
+        if groups > 1:       # (a ResNeXt conv2: cin == cout, 3x3)
+            assert cin == cout and k == 3
+            conv = self.grouped_conv(f"{pre}conv{m}.weight", cout, groups, stride)
+        else:
+            conv = self.conv(f"{pre}conv{m}.weight", cin, cout, k, stride, init=self.conv_init)
+        return (conv, self.bn(f"{pre}bn{m}", cout, gamma), fusable)
 
     def extra_param_views(self, buf):
         w, b = self.classifier_names
@@ -1707,8 +1819,9 @@ class ResNetEngine(_Engine):
             for conv, bn, c, tk, ak in blk["head"]:
                 h, w = h // conv.stride, w // conv.stride
                 t = self.buf(tk, B, h, w, c)              # raw conv outputs: only the training path keeps them
-                conv.forward(y, t, bn_scratch=self.partials(t) if fuse else None)
-                bn.stats(t, training, fused=fuse)
+                f = fuse and conv.fused_stats             # (a grouped conv has no statistics epilogue: separate pass)
+                conv.forward(y, t, bn_scratch=self.partials(t) if f else None)
+                bn.stats(t, training, fused=f)
                 y = self.buf(ak, B, h, w, c)
                 bn.apply(t, y, relu=True)
             conv, bn, tk, _ = blk["last"]
@@ -1827,15 +1940,21 @@ class BottleneckEngine(ResNetEngine):
     # BasicBlocks; nothing has been measured for these blocks, so every launch gets the whole chip.
     res_share = None
 
-    def __init__(self, num_classes=10, num_blocks=(3, 4, 6, 3), device="cuda", seed=0):
+    def __init__(self, num_classes=10, num_blocks=(3, 4, 6, 3), device="cuda", seed=0, groups=1, width_per_group=64):
+        self.groups, self.width_per_group = int(groups), int(width_per_group)
+        if self.groups < 1 or self.width_per_group < 1:
+            raise ValueError(f"groups and width_per_group are positive, got {groups} and {width_per_group}")
         super().__init__(num_classes, num_blocks, device, seed)
         self.pointwise = True
 
     def _block_stages(self, pre, cin, planes, stride):
-        """1x1 (cin -> planes) -> 3x3 (stride s) -> 1x1 (-> 4 planes); every pair's backward in the plain form (nothing
-        else has been measured for these blocks)."""
-        return [self._stage(pre, 1, cin, planes, 1, 1), self._stage(pre, 2, planes, planes, 3, stride),
-                self._stage(pre, 3, planes, self.expansion * planes, 1, 1)]
+        """1x1 (cin -> width) -> 3x3 (stride s) -> 1x1 (-> 4 planes), width = planes * width_per_group / 64 * groups as in
+        torchvision's Bottleneck: planes with the defaults, 2 planes for the wide ResNets (dense convs, the entries every
+        other 3x3 takes), and for a ResNeXt (groups > 1) conv2 is a GroupedConv.  Every pair's backward in the plain form
+        (nothing else has been measured for these blocks)."""
+        width = int(planes * self.width_per_group / 64) * self.groups
+        return [self._stage(pre, 1, cin, width, 1, 1), self._stage(pre, 2, width, width, 3, stride, groups=self.groups),
+                self._stage(pre, 3, width, self.expansion * planes, 1, 1)]
 
     @property
     def pointwise(self):
@@ -1868,12 +1987,12 @@ class _TorchvisionFront:
     res_share = None        # the CU-sharing plan was measured on CIFAR grids: nothing is assumed to carry over
     PATCH_K = 7
 
-    def __init__(self, num_classes=1000, num_blocks=None, zero_init_residual=False, device="cuda", seed=0):
+    def __init__(self, num_classes=1000, num_blocks=None, zero_init_residual=False, device="cuda", seed=0, **block_kw):
+        """block_kw: what the block engine behind this front takes besides (BottleneckEngine: groups, width_per_group)."""
         self.zero_init_residual = bool(zero_init_residual)
-        if num_blocks is None:
-            super().__init__(num_classes=num_classes, device=device, seed=seed)
-        else:
-            super().__init__(num_classes=num_classes, num_blocks=num_blocks, device=device, seed=seed)
+        if num_blocks is not None:
+            block_kw["num_blocks"] = num_blocks
+        super().__init__(num_classes=num_classes, device=device, seed=seed, **block_kw)
 
     def _make_stem(self):
         self.conv0 = PatchConv(self.store, "conv1.weight", 64, self.PATCH_K, self.gen, self.conv_init)
@@ -1929,7 +2048,10 @@ class ImageNetResNetEngine(_TorchvisionFront, ResNetEngine):
 
 
 class ImageNetBottleneckEngine(_TorchvisionFront, BottleneckEngine):
-    """torchvision's resnet50 / 101 / 152 (Bottleneck v1.5: the stride is on the 3x3 conv, as in BottleneckEngine)."""
+    """torchvision's resnet50 / 101 / 152 (Bottleneck v1.5: the stride is on the 3x3 conv, as in BottleneckEngine), and with
+    torchvision's ``groups`` / ``width_per_group`` keywords its resnext50_32x4d / resnext101_64x4d (groups = 32 / 64,
+    width_per_group = 4: conv2 is a GroupedConv) and wide_resnet50_2 / wide_resnet101_2 (width_per_group = 128: dense convs
+    at twice the width).  With the defaults nothing differs from before the keywords existed."""
 
 
 def _loss_backward(engine, criterion, img, targets, comm, fused_head, calibrate_with=None):

@@ -1,6 +1,7 @@
 """CIFAR ResNets -- reference nbdt/models/resnet.py: BasicBlock variants (:42-74, 115-149, 161-199) on ResNetEngine,
 Bottleneck variants (:77-112, 193-223) on BottleneckEngine -- and the ImageNet-style ResNets the reference takes from
-torchvision.models (nbdt/models/__init__.py: resnet18 ... resnet152, lower-case) on the ImageNet* engines."""
+torchvision.models (nbdt/models/__init__.py: resnet18 ... resnet152, resnext50_32x4d, resnext101_64x4d, wide_resnet50_2,
+wide_resnet101_2, lower-case) on the ImageNet* engines."""
 from nbdt.engine import BottleneckEngine, ImageNetBottleneckEngine, ImageNetResNetEngine, ResNetEngine
 from nbdt.models._hip_module import HipBackbone
 
@@ -37,11 +38,11 @@ def ResNet152(**kwargs):
 
 
 def _tv_resnet(engine, num_blocks, pretrained=False, progress=True, num_classes=1000, zero_init_residual=False,
-               dataset="Imagenet1000", device="cuda", seed=0):
+               dataset="Imagenet1000", device="cuda", seed=0, **block_kw):
     if pretrained:
         raise NotImplementedError("pretrained checkpoints need network access; use load_state_dict")
     return HipBackbone(engine(num_classes=num_classes, num_blocks=num_blocks, zero_init_residual=zero_init_residual,
-                              device=device, seed=seed))
+                              device=device, seed=seed, **block_kw))
 
 
 def resnet18(pretrained=False, **kwargs):
@@ -62,3 +63,21 @@ def resnet101(pretrained=False, **kwargs):
 
 def resnet152(pretrained=False, **kwargs):
     return _tv_resnet(ImageNetBottleneckEngine, (3, 8, 36, 3), pretrained, **kwargs)
+
+
+# torchvision.models.resnet's other half: the Bottleneck with groups / width_per_group (torchvision fixes the two per
+# factory and takes the remaining keywords; resnext101_32x8d -- 64 channels per group in layer4 -- is not offered)
+def resnext50_32x4d(pretrained=False, **kwargs):
+    return _tv_resnet(ImageNetBottleneckEngine, (3, 4, 6, 3), pretrained, groups=32, width_per_group=4, **kwargs)
+
+
+def resnext101_64x4d(pretrained=False, **kwargs):
+    return _tv_resnet(ImageNetBottleneckEngine, (3, 4, 23, 3), pretrained, groups=64, width_per_group=4, **kwargs)
+
+
+def wide_resnet50_2(pretrained=False, **kwargs):
+    return _tv_resnet(ImageNetBottleneckEngine, (3, 4, 6, 3), pretrained, width_per_group=128, **kwargs)
+
+
+def wide_resnet101_2(pretrained=False, **kwargs):
+    return _tv_resnet(ImageNetBottleneckEngine, (3, 4, 23, 3), pretrained, width_per_group=128, **kwargs)

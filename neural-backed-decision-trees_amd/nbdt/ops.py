@@ -517,6 +517,53 @@ def _dims(t):
     return B, Hp - 2, Wp - 2, C
 
 
+# ------------------------------------------------------------------------------------------------
+# grouped 3x3 convolution (csrc/conv_group.hip): B, H, W below are always the conv's INPUT batch and sides
+
+GROUP_CG = (4, 8, 16, 32)      # channels per group the kernels take (each divides the 32-channel MFMA block)
+
+
+def conv_group_weight_prep(w_fp32, width, cg, wf_bf16=None, wd_bf16=None):
+    """fp32 master [width][9][cg] -> block-diagonal bf16 blocks: forward wf[width/32][32][9][32] and / or the transposed,
+    tap-reversed data-gradient blocks wd (nbdt_conv_group_weight_prep)."""
+    check(lib().nbdt_conv_group_weight_prep(ptr(w_fp32), width, cg, ptr(wf_bf16), ptr(wd_bf16),
+                                            stream_ptr(w_fp32.device)))
+
+
+def conv_group_weight_prep_batched(flat, table, n_layers, total_blocks, wf_flat=None, wd_flat=None):
+    check(lib().nbdt_conv_group_weight_prep_batched(ptr(flat), ptr(table), n_layers, total_blocks, ptr(wf_flat),
+                                                    ptr(wd_flat), stream_ptr(flat.device)))
+
+
+def conv_group_fwd(x, w, out, cg, stride, scale=None, shift=None, act=0):
+    """out = conv3x3(x, groups = width / cg).  bf16 tensors: w = the expanded forward blocks; scale / shift / act: the eval
+    epilogue act(acc * scale[c] + shift[c]).  fp32 tensors (the engines' reference mode): w = the fp32 master."""
+    B, H, W, C = _dims(x)
+    st = stream_ptr(x.device)
+    if _ref(x):
+        if scale is not None:
+            _no_ref(x, "conv_group_fwd's eval epilogue: engine.fuse_eval is off in reference mode")
+        check(lib().nbdt_ref_conv_group_fwd(ptr(x), ptr(w), ptr(out), B, H, W, C, cg, stride, st))
+        return
+    check(lib().nbdt_conv_group_fwd(ptr(x), ptr(w), ptr(out), B, H, W, C, cg, stride, ptr(scale), ptr(shift), act, st))
+
+
+def conv_group_dgrad(gout, w, gin, cg, stride, accumulate=False):
+    """gin = data gradient of conv_group_fwd.  bf16: w = the expanded data-gradient blocks; fp32: the fp32 master.  The
+    entry has no accumulate form and refuses the request."""
+    B, H, W, C = _dims(gin)
+    st = stream_ptr(gin.device)
+    fn = lib().nbdt_ref_conv_group_dgrad if _ref(gout) else lib().nbdt_conv_group_dgrad
+    check(fn(ptr(gout), ptr(w), ptr(gin), B, H, W, C, cg, stride, 1 if accumulate else 0, st))
+
+
+def conv_group_wgrad(x, gout, dw, cg, stride):
+    """dw[width][9][cg] fp32 += the pixel sum, in a fixed order (no atomics)."""
+    B, H, W, C = _dims(x)
+    fn = lib().nbdt_ref_conv_group_wgrad if _ref(x) else lib().nbdt_conv_group_wgrad
+    check(fn(ptr(x), ptr(gout), ptr(dw), B, H, W, C, cg, stride, stream_ptr(x.device)))
+
+
 def bn_stats(x, scratch, save_mean, save_rstd, running_mean=None, running_var=None,
              eps=BN_EPS, momentum=BN_MOMENTUM, slots_filled=False):
     """slots_filled: the producing kernel already accumulated the sums into `scratch` (fold only)."""
