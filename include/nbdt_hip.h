@@ -1121,7 +1121,8 @@ int nbdt_mix_batch(const float* x, const int64_t* y, int32_t B, int32_t H, int32
 /* ------------------------------------------------------------------ augmentation policy (nbdt_version() >= 119) */
 /* nbdt_augment_batch with an augmentation policy, still ONE launch per batch: gather by index, zero-padded random crop,
  * flip, then ONE TrivialAugmentWide operation on the uint8 image, then /255 and Normalize, then torchvision's
- * RandomErasing(value=0) on the normalised output.  csrc/policy.hip.  The recipe of the TrivialAugment paper's CIFAR setup
+ * RandomErasing(value=0) on the normalised output.  csrc/policy.hip, policy_kernel: its own single-operation kernel, on the
+ * draw, statistics and output functions of the chain kernel below.  The recipe of the TrivialAugment paper's CIFAR setup
  * and of torchvision's ResNet reference (ta_wide, RandomErasing(0.1)).  nbdt_policy_batch_sharded is the entry for a rank
  * that holds the samples [index_base, index_base + N) (see nbdt_augment_batch_sharded); nbdt_policy_batch is its base-0 form.
  *

@@ -1,8 +1,9 @@
 // The rules of the augmentation policies, shared by the kernels that apply them: policy.hip (the padded-crop path, both
 // tiles in LDS, 256 lanes) and resample.hip (the resized-crop path, both tiles in global memory, a wider block).  The draw
 // of the chain and of the erase rectangle, the per-image statistics, the per-pixel rule of each of the 15 operations, the
-// byte pass from one tile into the other and the normalising output pass.  Pillow's pixel rules, byte for byte
-// (include/nbdt_hip.h states them, nbdt/data.py policy_reference / chain_reference restate them).
+// byte pass from one tile into the other, the normalising output pass, the loop that runs a chain through them (run_chain),
+// a sample's parameters (ChainSpec, chain_params, store_chain_params) and the host checks that fill them.  Pillow's pixel
+// rules, byte for byte (include/nbdt_hip.h states them, nbdt/data.py policy_reference / chain_reference restate them).
 //
 // A tile is a plain `unsigned char*`: after inlining the compiler knows whether it is LDS or global.  BLOCK is the number of
 // lanes of the block (a multiple of 64, at least 256: Equalize's prefix sums give every bin a lane).  Every statistic is an
@@ -363,6 +364,102 @@ __device__ __forceinline__ unsigned long long draw_chain(unsigned long long key,
   return chain;
 }
 
+// ---- what a chain launch needs beyond its tiles: how a sample's chain and erase rectangle are drawn or read, and where
+// what was used is reported.  The host checks below fill it; ChainArgs (policy.hip) and RcpArgs (resample.hip) embed it.
+struct ChainSpec {
+  int mode, nbins, num_ops, magnitude, P;
+  const int* table;                  // int32 [NBDT_CHAIN_OPS][nbins][2][6] (device); [NBDT_POLICY_OPS][31][2][6] indexes alike
+  const int* subpolicies;            // int32 [P][NBDT_CHAIN_MAX_OPS][3] (op, q, bin), device: clamped by draw_chain
+  const int* chain_in;               // int32 [B][NBDT_CHAIN_MAX_OPS][3] (op, bin, sign): replaces the chain's draw
+  const int* erase_in;               // int32 [B][4] (top, left, h, w): replaces the erase draw
+  int* chain_out;
+  int* erase_out;
+  EraseDraw erase;                   // erase probability, area-fraction range and the aspect-ratio table
+};
+
+// the chain and the erase rectangle of sample b (dataset index gidx) of an H x W image: read from device memory and
+// clamped, or drawn; an invalid index gets the chain of none and no rectangle.  Block-uniform; every lane computes it.
+__device__ __forceinline__ void chain_params(const ChainSpec& c, unsigned long long key, long long gidx, int b, int H, int W,
+                                               bool valid, unsigned long long& chain, int& et, int& el, int& eh, int& ew) {
+  chain = 0;                         // 16 bits per slot: op | bin << 4 | sign << 9 (all zero: Identity)
+  et = el = eh = ew = 0;
+  if (!valid) return;
+  if (c.chain_in)
+    chain = clamp_chain(c.chain_in + (size_t)b * (NBDT_CHAIN_MAX_OPS * 3), c.nbins);
+  else
+    chain = draw_chain(key, gidx, c.mode, c.nbins, c.num_ops, c.magnitude, c.subpolicies, c.P);
+  if (c.erase_in)
+    clamp_erase(c.erase_in + (size_t)b * 4, H, W, et, el, eh, ew);
+  else
+    draw_erase(c.erase, H, W, erase_word(key, gidx), et, el, eh, ew);
+}
+
+// what sample b used, into the outputs that were asked for (one lane calls this)
+__device__ __forceinline__ void store_chain_params(const ChainSpec& c, int b, unsigned long long chain, int et, int el, int eh,
+                                              int ew) {
+  if (c.chain_out) store_chain(c.chain_out + (size_t)b * (NBDT_CHAIN_MAX_OPS * 3), chain);
+  if (c.erase_out) {
+    int* q = c.erase_out + (size_t)b * 4;
+    q[0] = et; q[1] = el; q[2] = eh; q[3] = ew;
+  }
+}
+
+// the mode and its arguments into c, as both chain entries check them.  zero_ops: NBDT_CHAIN_RAND may have no slot (the
+// erase alone), and then, without chain_in, no table; ta_wide: NBDT_CHAIN_TA_WIDE is a mode of this entry.
+inline int check_chain(ChainSpec& c, int32_t mode, int32_t nbins, const int32_t* table, int32_t num_ops, int32_t magnitude,
+                       const int32_t* subpolicies, int32_t P, const int32_t* chain_in, bool zero_ops, bool ta_wide) {
+  if (ta_wide)
+    NBDT_REQUIRE(mode == NBDT_CHAIN_RAND || mode == NBDT_CHAIN_SUBPOLICY || mode == NBDT_CHAIN_TA_WIDE,
+                 "mode is NBDT_CHAIN_RAND, NBDT_CHAIN_SUBPOLICY or NBDT_CHAIN_TA_WIDE");
+  else
+    NBDT_REQUIRE(mode == NBDT_CHAIN_RAND || mode == NBDT_CHAIN_SUBPOLICY, "mode is NBDT_CHAIN_RAND or NBDT_CHAIN_SUBPOLICY");
+  NBDT_REQUIRE(nbins >= 1 && nbins <= NBDT_CHAIN_MAX_BINS, "nbins must be 1..NBDT_CHAIN_MAX_BINS");
+  if (!zero_ops) NBDT_REQUIRE(table, "null argument: the chain needs its magnitude table");      // (each entry's own order)
+  if (mode == NBDT_CHAIN_RAND) {
+    if (zero_ops)
+      NBDT_REQUIRE(num_ops >= 0 && num_ops <= NBDT_CHAIN_MAX_OPS, "num_ops must be 0..NBDT_CHAIN_MAX_OPS");
+    else
+      NBDT_REQUIRE(num_ops >= 1 && num_ops <= NBDT_CHAIN_MAX_OPS, "num_ops must be 1..NBDT_CHAIN_MAX_OPS");
+    NBDT_REQUIRE(magnitude >= 0 && magnitude < nbins, "magnitude must be a bin: 0 <= magnitude < nbins");
+    c.num_ops = num_ops;
+    c.magnitude = magnitude;
+  } else if (mode == NBDT_CHAIN_SUBPOLICY) {
+    NBDT_REQUIRE(subpolicies, "null argument: NBDT_CHAIN_SUBPOLICY needs the sub-policies");
+    NBDT_REQUIRE(P >= 1 && P <= NBDT_CHAIN_MAX_SUBPOLICIES, "P (the number of sub-policies) must be 1..NBDT_CHAIN_MAX_SUBPOLICIES");
+    c.subpolicies = subpolicies;
+    c.P = P;
+  } else {
+    NBDT_REQUIRE(nbins == NBDT_POLICY_BINS, "NBDT_CHAIN_TA_WIDE draws among NBDT_POLICY_BINS bins: nbins must be 31");
+  }
+  if (zero_ops)
+    NBDT_REQUIRE(table || (mode == NBDT_CHAIN_RAND && num_ops == 0 && !chain_in),
+                 "null argument: the chain needs its magnitude table");
+  c.mode = mode;
+  c.nbins = nbins;
+  c.table = table;
+  c.chain_in = chain_in;
+  return NBDT_OK;
+}
+
+// erase_prob, and what the erase draw needs when it is made (`drawn`: no rectangle is given), into c.erase
+inline int check_erase(ChainSpec& c, double erase_prob, const double* erase_scale, const double* erase_ratio,
+                       const double* ratio_table, bool drawn) {
+  NBDT_REQUIRE(erase_prob >= 0.0 && erase_prob <= 1.0, "erase_prob must be in [0, 1]");       // (NaN fails both)
+  if (erase_prob > 0.0 && drawn) {
+    NBDT_REQUIRE(erase_scale && erase_ratio && ratio_table,
+                 "the erase draw needs erase_scale[2], erase_ratio[2] and the ratio table");
+    NBDT_REQUIRE(erase_scale[0] > 0.0 && erase_scale[0] <= erase_scale[1] && erase_scale[1] <= 1.0,
+                 "erase_scale must satisfy 0 < lo <= hi <= 1");
+    NBDT_REQUIRE(erase_ratio[0] >= 1.0 / 64.0 && erase_ratio[0] <= erase_ratio[1] && erase_ratio[1] <= 64.0,
+                 "erase_ratio must satisfy 1/64 <= lo <= hi <= 64");
+    c.erase.p = erase_prob;
+    c.erase.s0 = erase_scale[0];
+    c.erase.s1 = erase_scale[1];
+    c.erase.ratio_table = ratio_table;
+  }
+  return NBDT_OK;
+}
+
 // ---- the two passes over a tile; four consecutive x of one row per lane.  WORD: the tiles and the row pitch are
 // multiples of four bytes (the caller has checked it) and a point operation reads its four bytes with one load.
 
@@ -434,6 +531,39 @@ __device__ __forceinline__ void output_pass(const float* mean3, const float* std
         if (g * 4 + j < W) dst[j] = v[j];
     }
   }
+}
+
+// ---- the chain on two tiles, then the output.  `cur` holds the image so far, `oth` is free: every non-Identity slot but
+// the last is a byte pass from `cur` into `oth`, the last is evaluated inside the normalising output pass, and the
+// statistics an operation needs are collected again on the tile it reads.  The chain is block-uniform, so every barrier is.
+// A tile is written and re-read by this block alone, so __syncthreads() (workgroup scope) orders global tiles as it does
+// LDS ones.  hist: kStatWords words of LDS, ac: six doubles of LDS.
+template <int BLOCK, bool WORD>
+__device__ __forceinline__ void run_chain(const ChainSpec& c, unsigned long long chain, unsigned char* cur,
+                                           unsigned char* oth, unsigned* hist, double* ac, int H, int W, const float* mean,
+                                           const float* std, int vec_out, float* o, int et, int el, int eh, int ew, int tid) {
+  unsigned* stat = hist + 768;
+  const int last = last_slot(chain);
+  OpCtx k = {};            // all slots Identity: the output is read straight from `cur`
+  for (int s = 0; s <= last; ++s) {             // (one copy of the passes, not four: the slot is a run-time shift)
+    const int op = load_slot(k, c.table, c.nbins, chain, s);
+    if (op == OP_IDENTITY) continue;            // costs nothing: no pass, no barrier
+    if (op_needs_statistics(op)) {
+      // the statistics of an earlier operation are stale: start again, a barrier on both sides (the first one also keeps
+      // this slot's writes behind every read of the previous LUT)
+      __syncthreads();
+      reset_statistics<BLOCK>(hist, tid);
+      __syncthreads();
+      op_statistics<BLOCK>(k, cur, hist, stat, ac, H * W, tid);
+    }
+    if (s == last) break;
+    byte_pass<BLOCK, WORD>(k, cur, oth, hist, ac, H, W, tid);
+    __syncthreads();       // the pass's stores before the next pass's loads, its loads before the next pass's stores
+    unsigned char* t = cur;
+    cur = oth;
+    oth = t;
+  }
+  output_pass<BLOCK, WORD>(mean, std, H, W, vec_out, k, cur, hist, ac, o, et, el, eh, ew, tid);
 }
 
 }  // namespace pol

@@ -356,9 +356,9 @@ __global__ __launch_bounds__(256) void resized_crop_global(const RcArgs a) {
 // its tile of B, both in GLOBAL memory: 3 * S * S bytes are 150 KB at S = 224 and two of them fit no LDS.  A tile is
 // written and re-read by this block alone, on one CU, so __syncthreads() (workgroup scope) is all the ordering the passes
 // need; plain loads and stores, so the tile stays in that CU's L1 and the XCD's L2.  Only the statistics live in LDS.  The
-// structure is policy_chain_kernel's (policy.hip) and the rules are the same functions (policy_ops.h): an Identity slot
-// costs no pass, statistics are collected again on the tile an operation reads, the last non-Identity operation is
-// evaluated inside the output pass.  The chain is block-uniform, so every barrier is.
+// loop is the one policy_chain_kernel (policy.hip) runs, run_chain, and the rules are the same functions (policy_ops.h): an
+// Identity slot costs no pass, statistics are collected again on the tile an operation reads, the last non-Identity
+// operation is evaluated inside the output pass.  The chain is block-uniform, so every barrier is.
 struct RcpArgs {
   const long long* index;
   long long index_base, N;
@@ -367,16 +367,9 @@ struct RcpArgs {
   unsigned long long key;
   unsigned char* A;                  // uint8 [B,3,S,S]: the resized and flipped image, then scratch
   unsigned char* Bt;                 // uint8 [B,3,S,S]: scratch
-  const int* table;                  // int32 [NBDT_CHAIN_OPS][nbins][2][6] (device), built for S x S
-  int mode, nbins, num_ops, magnitude, P;
-  const int* subpolicies;            // int32 [P][NBDT_CHAIN_MAX_OPS][3] (op, q, bin), device: clamped by draw_chain
-  const int* chain_in;               // int32 [B][NBDT_CHAIN_MAX_OPS][3] (op, bin, sign): replaces the chain's draw
-  const int* erase_in;               // int32 [B][4] (top, left, h, w): replaces the erase draw
-  EraseDraw erase;
+  ChainSpec c;                       // the chain and the erase (policy_ops.h); the table is built for S x S
   int vec_out;                       // S % 4 == 0 and `out` 16-byte aligned (the tiles always are when S % 4 == 0)
   float* out;
-  int* chain_out;
-  int* erase_out;
 };
 
 // Lanes per image.  Measured at 512 images of 224 x 224 (two blocks per CU; profiles/resized_crop_policy_launch.txt): 256
@@ -386,33 +379,6 @@ struct RcpArgs {
 // smaller batch leaves a block per CU or fewer.  Reading a point operation's four bytes with one load (WORD) instead of
 // four: 850 - 890 against 899 - 925 us, and 685 against 961 us for four Brightness passes.
 constexpr int kPolicyBlock = 1024;
-
-template <int BLOCK, bool WORD>
-__device__ __forceinline__ void chain_on_tiles(const RcpArgs& a, unsigned long long chain, unsigned char* cur,
-                                                unsigned char* oth, unsigned* hist, double* ac, float* o, int et, int el,
-                                                int eh, int ew, int tid) {
-  const int S = a.S, HW = S * S;
-  unsigned* stat = hist + 768;
-  const int last = last_slot(chain);
-  OpCtx k = {};            // all slots Identity: the output is read straight from A
-  for (int s = 0; s <= last; ++s) {
-    const int op = load_slot(k, a.table, a.nbins, chain, s);
-    if (op == OP_IDENTITY) continue;
-    if (op_needs_statistics(op)) {
-      __syncthreads();     // (also keeps this slot's writes behind every read of the previous LUT)
-      reset_statistics<BLOCK>(hist, tid);
-      __syncthreads();
-      op_statistics<BLOCK>(k, cur, hist, stat, ac, HW, tid);
-    }
-    if (s == last) break;
-    byte_pass<BLOCK, WORD>(k, cur, oth, hist, ac, S, S, tid);
-    __syncthreads();       // the pass's stores before the next pass's loads, its loads before the next pass's stores
-    unsigned char* t = cur;
-    cur = oth;
-    oth = t;
-  }
-  output_pass<BLOCK, WORD>(a.mean, a.std, S, S, a.vec_out, k, cur, hist, ac, o, et, el, eh, ew, tid);
-}
 
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void resized_crop_policy_kernel(const RcpArgs a) {
@@ -426,33 +392,20 @@ __global__ __launch_bounds__(BLOCK) void resized_crop_policy_kernel(const RcpArg
   float* o = a.out + (size_t)b * n;
 
   // ---- the sample's chain and rectangle (block-uniform; every lane computes them)
-  int et = 0, el = 0, eh = 0, ew = 0;
-  unsigned long long chain = 0;
-  if (valid) {
-    if (a.chain_in)
-      chain = clamp_chain(a.chain_in + (size_t)b * (NBDT_CHAIN_MAX_OPS * 3), a.nbins);
-    else
-      chain = draw_chain(a.key, gidx, a.mode, a.nbins, a.num_ops, a.magnitude, a.subpolicies, a.P);
-    if (a.erase_in)
-      clamp_erase(a.erase_in + (size_t)b * 4, S, S, et, el, eh, ew);
-    else
-      draw_erase(a.erase, S, S, erase_word(a.key, gidx), et, el, eh, ew);
-  }
-  if (tid == 0) {          // (the label and the box are the first launch's)
-    if (a.chain_out) store_chain(a.chain_out + (size_t)b * (NBDT_CHAIN_MAX_OPS * 3), chain);
-    if (a.erase_out) {
-      int* q = a.erase_out + (size_t)b * 4;
-      q[0] = et; q[1] = el; q[2] = eh; q[3] = ew;
-    }
-  }
+  int et, el, eh, ew;
+  unsigned long long chain;
+  chain_params(a.c, a.key, gidx, b, S, S, valid, chain, et, el, eh, ew);
+  if (tid == 0) store_chain_params(a.c, b, chain, et, el, eh, ew);   // (the label and the box are the first launch's)
   if (!valid) {      // (block-uniform) an index the host could not check: a zero image, no tile read
     for (int i = tid; i < n; i += BLOCK) o[i] = 0.f;
     return;
   }
   unsigned char* cur = a.A + (size_t)b * n;
   unsigned char* oth = a.Bt + (size_t)b * n;
-  if ((S & 3) == 0) chain_on_tiles<BLOCK, true>(a, chain, cur, oth, hist, ac, o, et, el, eh, ew, tid);
-  else chain_on_tiles<BLOCK, false>(a, chain, cur, oth, hist, ac, o, et, el, eh, ew, tid);
+  if ((S & 3) == 0)
+    run_chain<BLOCK, true>(a.c, chain, cur, oth, hist, ac, S, S, a.mean, a.std, a.vec_out, o, et, el, eh, ew, tid);
+  else
+    run_chain<BLOCK, false>(a.c, chain, cur, oth, hist, ac, S, S, a.mean, a.std, a.vec_out, o, et, el, eh, ew, tid);
 }
 
 // taps of one axis for the widest box (the whole side): PIL's ksize
@@ -593,38 +546,9 @@ extern "C" int nbdt_resized_crop_policy_batch_sharded(
     return rc;
   NBDT_REQUIRE(stage_a && stage_b && stage_a != stage_b, "null argument: the chain needs two distinct staging buffers");
   NBDT_REQUIRE((uintptr_t)stage_a % 16 == 0 && (uintptr_t)stage_b % 16 == 0, "the staging buffers must be 16-byte aligned");
-  NBDT_REQUIRE(mode == NBDT_CHAIN_RAND || mode == NBDT_CHAIN_SUBPOLICY || mode == NBDT_CHAIN_TA_WIDE,
-               "mode is NBDT_CHAIN_RAND, NBDT_CHAIN_SUBPOLICY or NBDT_CHAIN_TA_WIDE");
-  NBDT_REQUIRE(nbins >= 1 && nbins <= NBDT_CHAIN_MAX_BINS, "nbins must be 1..NBDT_CHAIN_MAX_BINS");
   RcpArgs p = {};
-  if (mode == NBDT_CHAIN_RAND) {
-    NBDT_REQUIRE(num_ops >= 0 && num_ops <= NBDT_CHAIN_MAX_OPS, "num_ops must be 0..NBDT_CHAIN_MAX_OPS");
-    NBDT_REQUIRE(magnitude >= 0 && magnitude < nbins, "magnitude must be a bin: 0 <= magnitude < nbins");
-    p.num_ops = num_ops;
-    p.magnitude = magnitude;
-  } else if (mode == NBDT_CHAIN_SUBPOLICY) {
-    NBDT_REQUIRE(subpolicies, "null argument: NBDT_CHAIN_SUBPOLICY needs the sub-policies");
-    NBDT_REQUIRE(P >= 1 && P <= NBDT_CHAIN_MAX_SUBPOLICIES, "P (the number of sub-policies) must be 1..NBDT_CHAIN_MAX_SUBPOLICIES");
-    p.subpolicies = subpolicies;
-    p.P = P;
-  } else {
-    NBDT_REQUIRE(nbins == NBDT_POLICY_BINS, "NBDT_CHAIN_TA_WIDE draws among NBDT_POLICY_BINS bins: nbins must be 31");
-  }
-  NBDT_REQUIRE(table || (mode == NBDT_CHAIN_RAND && num_ops == 0 && !chain_in),
-               "null argument: the chain needs its magnitude table");
-  NBDT_REQUIRE(erase_prob >= 0.0 && erase_prob <= 1.0, "erase_prob must be in [0, 1]");       // (NaN fails both)
-  if (erase_prob > 0.0 && !erase_in) {
-    NBDT_REQUIRE(erase_scale && erase_ratio && erase_ratio_table,
-                 "the erase draw needs erase_scale[2], erase_ratio[2] and the ratio table");
-    NBDT_REQUIRE(erase_scale[0] > 0.0 && erase_scale[0] <= erase_scale[1] && erase_scale[1] <= 1.0,
-                 "erase_scale must satisfy 0 < lo <= hi <= 1");
-    NBDT_REQUIRE(erase_ratio[0] >= 1.0 / 64.0 && erase_ratio[0] <= erase_ratio[1] && erase_ratio[1] <= 64.0,
-                 "erase_ratio must satisfy 1/64 <= lo <= hi <= 64");
-    p.erase.p = erase_prob;
-    p.erase.s0 = erase_scale[0];
-    p.erase.s1 = erase_scale[1];
-    p.erase.ratio_table = erase_ratio_table;
-  }
+  if (int rc = check_chain(p.c, mode, nbins, table, num_ops, magnitude, subpolicies, P, chain_in, true, true)) return rc;
+  if (int rc = check_erase(p.c, erase_prob, erase_scale, erase_ratio, erase_ratio_table, !erase_in)) return rc;
   a.out_u8 = (unsigned char*)stage_a;
   p.index = a.index; p.index_base = index_base; p.N = N;
   p.S = S;
@@ -632,12 +556,10 @@ extern "C" int nbdt_resized_crop_policy_batch_sharded(
   p.key = a.key;
   p.A = (unsigned char*)stage_a;
   p.Bt = (unsigned char*)stage_b;
-  p.table = table;
-  p.mode = mode; p.nbins = nbins;
-  p.chain_in = chain_in; p.erase_in = erase_in;
+  p.c.erase_in = erase_in;
   p.vec_out = (S % 4 == 0 && (uintptr_t)out % 16 == 0) ? 1 : 0;
   p.out = out;
-  p.chain_out = chain_out; p.erase_out = erase_out;
+  p.c.chain_out = chain_out; p.c.erase_out = erase_out;
   hipStream_t s = (hipStream_t)stream;
   launch_resample<true>(a, B, s);
   NBDT_LAUNCH_CHECK();

@@ -96,10 +96,7 @@ def _check_host_index(index, span, sharded):
         raise IndexError(f"index outside [0, {hi}): min {imin}, max {imax}")
 
 
-def _mix64(x):
-    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
-    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
-    return x ^ (x >> np.uint64(31))
+_mix64 = ops._mix64
 
 
 def draw_params(seed, epoch, index, pad):
@@ -146,38 +143,145 @@ def _check_policy(policy, policy_ops, policy_magnitude):
     return subs, policy_ops, policy_magnitude
 
 
-def _device_rows(v, name, shape, ok, what, device, who):
-    """An integer parameter tensor of `shape` for a batch launch, int32 on the device: a host tensor is checked with
-    `ok` (ValueError naming `what`) and copied, a device tensor goes to the kernel, which clamps it."""
+def _device_rows(v, name, shape, rule, args, device, who, dtype=None):
+    """An integer parameter tensor of `shape` for a batch launch, on the device: a host tensor is checked with
+    ``rule(rows as int64, *args)`` -- (the rows that are in range, the range in words for the ValueError) -- and copied, a
+    device tensor goes to the kernel, which clamps it.  dtype None: any integer type, handed on as int32; a dtype: exactly
+    that one, handed on as it is."""
     if not isinstance(v, torch.Tensor):
         v = torch.as_tensor(np.asarray(v))
-    if tuple(v.shape) != shape or v.is_floating_point() or v.dtype == torch.bool:
-        raise ValueError(f"{name} must be integer {list(shape)}, got {v.dtype} {tuple(v.shape)}")
+    wrong = v.is_floating_point() or v.dtype == torch.bool if dtype is None else v.dtype != dtype
+    if tuple(v.shape) != shape or wrong:
+        kind = "integer" if dtype is None else str(dtype).replace("torch.", "")
+        raise ValueError(f"{name} must be {kind} {list(shape)}, got {v.dtype} {tuple(v.shape)}")
     if not v.is_cuda:
-        if not bool(ok(v.long()).all()):
+        ok, what = rule(v.long(), *args)
+        if not bool(ok.all()):
             raise ValueError(f"{name} outside {what}")
         v = v.to(device, non_blocking=True)
     _C.require_gpu(v, who)
-    return v.to(dtype=torch.int32).contiguous()
+    want = dtype or torch.int32
+    return v if v.dtype == want and v.is_contiguous() else v.to(dtype=want).contiguous()
+
+
+# the rules of _device_rows: module-level, so that a batch call builds no closure
+def _crop_rule(p, pad):
+    return ((p >= 0).all(dim=1) & (p[:, 0] <= 2 * pad) & (p[:, 1] <= 2 * pad) & (p[:, 2] <= 1),
+            f"dy, dx in [0, {2 * pad}], flip in {{0, 1}}")
+
+
+def _box_rule(p, H, W):
+    return ((p[:, 0] >= 0) & (p[:, 1] >= 0) & (p[:, 2] >= 1) & (p[:, 3] >= 1) & (p[:, 0] + p[:, 2] <= H)
+            & (p[:, 1] + p[:, 3] <= W) & (p[:, 4] >= 0) & (p[:, 4] <= 1),
+            f"the {H} x {W} image (top, left >= 0, h, w >= 1, top + h <= H, left + w <= W) or flip outside {{0, 1}}")
+
+
+def _policy_rule(p, H, W):
+    return ((p[:, 0] >= 0) & (p[:, 0] < len(POLICY_OPS)) & (p[:, 1] >= 0) & (p[:, 1] < POLICY_BINS) & (p[:, 2] >= 0)
+            & (p[:, 2] <= 1) & (p[:, 3:] >= 0).all(dim=1) & (p[:, 3] + p[:, 5] <= H) & (p[:, 4] + p[:, 6] <= W),
+            f"op in [0, {len(POLICY_OPS) - 1}], bin in [0, {POLICY_BINS - 1}], sign in {{0, 1}} or an erase rectangle outside "
+            f"the {H} x {W} image")
+
+
+def _chain_rule(p, nbins):
+    return ((p[..., 0] >= 0) & (p[..., 0] < len(CHAIN_OPS)) & (p[..., 1] >= 0) & (p[..., 1] < nbins) & (p[..., 2] >= 0)
+            & (p[..., 2] <= 1), f"op in [0, {len(CHAIN_OPS) - 1}], bin in [0, {nbins - 1}], sign in {{0, 1}}")
+
+
+def _erase_rule(p, H, W):
+    return (p >= 0).all(dim=1) & (p[:, 0] + p[:, 2] <= H) & (p[:, 1] + p[:, 3] <= W), f"the {H} x {W} image"
 
 
 def _chain_rows(chain_params, erase_params, B, nbins, H, W, device, who):
     """chain_params [B,4,3] and erase_params [B,4] (either may be None) through ``_device_rows``."""
     if chain_params is not None:
-        chain_params = _device_rows(
-            chain_params, "chain_params", (B, CHAIN_MAX_OPS, 3),
-            lambda p: (p[..., 0] >= 0) & (p[..., 0] < len(CHAIN_OPS)) & (p[..., 1] >= 0) & (p[..., 1] < nbins)
-            & (p[..., 2] >= 0) & (p[..., 2] <= 1),
-            f"op in [0, {len(CHAIN_OPS) - 1}], bin in [0, {nbins - 1}], sign in {{0, 1}}", device, who)
+        chain_params = _device_rows(chain_params, "chain_params", (B, CHAIN_MAX_OPS, 3), _chain_rule, (nbins,), device, who)
     if erase_params is not None:
-        erase_params = _device_rows(
-            erase_params, "erase_params", (B, 4),
-            lambda p: (p >= 0).all(dim=1) & (p[:, 0] + p[:, 2] <= H) & (p[:, 1] + p[:, 3] <= W),
-            f"the {H} x {W} image", device, who)
+        erase_params = _device_rows(erase_params, "erase_params", (B, 4), _erase_rule, (H, W), device, who)
     return chain_params, erase_params
 
 
-class DeviceDataset:
+class _DeviceBatches:
+    """What DeviceDataset and ResizedCropDataset share: the settings and their checks, the placement of (a shard of) the
+    samples, the index of a batch, the device copies of the policies' tables and the tuple a batch returns.  The geometry,
+    `batch` and the routing between launches are each class's own."""
+
+    def __init__(self, x, y, mean, std, flip, device, policy, erase_prob, erase_scale, erase_ratio, policy_ops,
+                 policy_magnitude, dtypes):
+        """The settings, checked; `_hold` (after the subclass's own checks) moves the samples."""
+        who = type(self).__name__
+        self._who = who + ".batch"
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _C.NBDTHipError(f"{who} lives on an MI355X, not on {self.device} (no CPU fallback)")
+        # int32 [P,4,3] on the host when the policy is a list of sub-policies (AutoAugment), else None
+        self._subpolicies, policy_ops, policy_magnitude = _check_policy(policy, policy_ops, policy_magnitude)
+        self.policy = policy
+        self.policy_ops, self.policy_magnitude = policy_ops, policy_magnitude
+        self.erase_prob = _check_erase(erase_prob, erase_scale, erase_ratio)
+        self.erase_scale = tuple(float(v) for v in erase_scale)
+        self.erase_ratio = tuple(float(v) for v in erase_ratio)
+        if x.dim() != 4 or x.shape[1] != 3 or x.dtype not in dtypes:
+            kinds = " or ".join({torch.uint8: "uint8", torch.float32: "fp32"}[d] for d in dtypes)
+            raise ValueError(f"x must be {kinds} [N,3,H,W], got {x.dtype} {tuple(x.shape)}")
+        if y.dim() != 1 or y.shape[0] != x.shape[0] or y.is_floating_point():
+            raise ValueError(f"y must be integer [N] with N = {x.shape[0]}, got {y.dtype} {tuple(y.shape)}")
+        if len(mean) != 3 or len(std) != 3:
+            raise ValueError("mean and std have one entry per channel (3)")
+        self.mean = tuple(float(m) for m in mean)
+        self.std = tuple(float(s) for s in std)
+        self.flip = bool(flip)
+        self._tables_on_device = {}       # the policies' tables, each built and copied by the first batch that needs it
+
+    def _hold(self, x, y, shard):
+        self.sharded = shard is not None
+        self.x, self.y, self.shard_range, self.global_size = _place(type(self).__name__, x, y, shard, self.device)
+        self.device = self.x.device       # (with its index)
+
+    def __len__(self):
+        return self.x.shape[0]
+
+    @property
+    def shape(self):
+        return self.x.shape
+
+    def _index(self, index):
+        """`index` as a contiguous int64 device vector; a host one is range-checked first."""
+        if not isinstance(index, torch.Tensor):
+            index = torch.as_tensor(np.asarray(index))
+        if index.dim() != 1 or index.is_floating_point() or index.shape[0] == 0:
+            raise ValueError(f"index must be a non-empty integer vector, got {index.dtype} {tuple(index.shape)}")
+        if not index.is_cuda:
+            _check_host_index(index, self.shard_range, self.sharded)
+            index = index.to(self.device, non_blocking=True)
+        _C.require_gpu(index, self._who)
+        return index if index.dtype == torch.int64 and index.is_contiguous() else index.to(dtype=torch.int64).contiguous()
+
+    def _table_on_device(self, name, build, *args):
+        """The host table ``build(*args)`` on the device; built once."""
+        t = self._tables_on_device.get(name)
+        if t is None:
+            t = self._tables_on_device[name] = torch.from_numpy(build(*args).copy()).to(self.device)
+        return t
+
+    def _chain_tables(self, name, H, W):
+        """(chain table of ``chain_table(name, H, W)`` or None without a name, sub-policies or None, erase ratio table)."""
+        return (None if name is None else self._table_on_device("chain", chain_table, name, H, W),
+                None if self._subpolicies is None else self._table_on_device("subpolicies", np.asarray, self._subpolicies),
+                self._table_on_device("erase ratios", ratio_table, self.erase_ratio))
+
+    def _used(self, *shape):
+        """An int32 tensor for a launch to report what it used in."""
+        return torch.empty(shape, dtype=torch.int32, device=self.device)
+
+    def _extras(self, *extras):
+        """The optional returns after (img, targets[, params]): each is (wanted, what a launch wrote or None, its shape), in
+        the documented order; a wanted one that no launch wrote is zeros -- nothing was applied: Identity, no erase."""
+        return tuple(torch.zeros(shape, dtype=torch.int32, device=self.device) if t is None else t
+                     for wanted, t, shape in extras if wanted)
+
+
+class DeviceDataset(_DeviceBatches):
     """A dataset held on the device, batched by `nbdt_augment_batch`.
 
     x: uint8 or fp32 ``[N,3,H,W]``; y: integer ``[N]``; both are moved to `device` once.  A uint8 `x` is scaled by 1/255
@@ -203,78 +307,18 @@ class DeviceDataset:
 
     def __init__(self, x, y, mean, std, pad, flip=True, fill=None, device="cuda", shard=None, policy=None, erase_prob=0.0,
                  erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3), policy_ops=2, policy_magnitude=9):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _C.NBDTHipError(f"DeviceDataset lives on an MI355X, not on {device} (no CPU fallback)")
-        # int32 [P,4,3] on the host when the policy is a list of sub-policies (AutoAugment), else None
-        self._subpolicies, policy_ops, policy_magnitude = _check_policy(policy, policy_ops, policy_magnitude)
-        self.policy = policy
+        super().__init__(x, y, mean, std, flip, device, policy, erase_prob, erase_scale, erase_ratio, policy_ops,
+                         policy_magnitude, (torch.uint8, torch.float32))
         self.chain = policy is not None and policy != "ta_wide"       # RandAugment / AutoAugment: nbdt_policy_chain_batch
-        self.policy_ops, self.policy_magnitude = policy_ops, policy_magnitude
-        self.erase_prob = _check_erase(erase_prob, erase_scale, erase_ratio)
-        self.erase_scale = tuple(float(v) for v in erase_scale)
-        self.erase_ratio = tuple(float(v) for v in erase_ratio)
-        if x.dim() != 4 or x.shape[1] != 3 or x.dtype not in (torch.uint8, torch.float32):
-            raise ValueError(f"x must be uint8 or fp32 [N,3,H,W], got {x.dtype} {tuple(x.shape)}")
-        if y.dim() != 1 or y.shape[0] != x.shape[0] or y.is_floating_point():
-            raise ValueError(f"y must be integer [N] with N = {x.shape[0]}, got {y.dtype} {tuple(y.shape)}")
         if not 0 <= int(pad) <= MAX_PAD:
             raise ValueError(f"pad must be 0..{MAX_PAD}, got {pad}")
-        if len(mean) != 3 or len(std) != 3:
-            raise ValueError("mean and std have one entry per channel (3)")
-        self.mean = tuple(float(m) for m in mean)
-        self.std = tuple(float(s) for s in std)
         if fill is None:       # (0 - mean) / std in fp32, the kernel's value of a padded uint8 pixel
             fill = ((torch.zeros(3) - torch.tensor(self.mean)) / torch.tensor(self.std)).tolist()
         self.fill = tuple(float(f) for f in fill)
-        self.pad, self.flip = int(pad), bool(flip)
-        self.sharded = shard is not None
+        self.pad = int(pad)
         if policy is not None or self.erase_prob > 0.0:
             _check_policy_source(x)
-        self.x, self.y, self.shard_range, self.global_size = _place("DeviceDataset", x, y, shard, device)
-        self.device = self.x.device
-        self._policy_tables = None        # (policy table, ratio table) on the device, built by the first policy batch
-        self._chain_tables = None         # (chain table, sub-policies or None) on the device, likewise
-
-    def __len__(self):
-        return self.x.shape[0]
-
-    @property
-    def shape(self):
-        return self.x.shape
-
-    def _tables(self):
-        if self._policy_tables is None:
-            _check_policy_source(self.x)
-            H, W = self.x.shape[2], self.x.shape[3]
-            self._policy_tables = (torch.from_numpy(policy_table(H, W).copy()).to(self.device),
-                                   torch.from_numpy(ratio_table(self.erase_ratio).copy()).to(self.device))
-        return self._policy_tables
-
-    def _chain(self):
-        if self._chain_tables is None:
-            H, W = self.x.shape[2], self.x.shape[3]
-            table = chain_table("ra" if self.policy == "ra" else "cifar10", H, W)
-            subs = None if self._subpolicies is None else torch.from_numpy(self._subpolicies).to(self.device)
-            self._chain_tables = (torch.from_numpy(table.copy()).to(self.device), subs)
-        return self._chain_tables
-
-    def _batch_chain(self, index, img, targets, pad, flip, seed, epoch, params, used, base, chain_params, erase_params,
-                     return_chain_params, return_erase_params):
-        B, H, W = index.shape[0], self.x.shape[2], self.x.shape[3]
-        table, subs = self._chain()
-        nbins = table.shape[1]
-        chain_params, erase_params = _chain_rows(chain_params, erase_params, B, nbins, H, W, self.device,
-                                                 "DeviceDataset.batch")
-        ratios = self._tables()[1]
-        cused = torch.empty((B, CHAIN_MAX_OPS, 3), dtype=torch.int32, device=self.device) if return_chain_params else None
-        eused = torch.empty((B, 4), dtype=torch.int32, device=self.device) if return_erase_params else None
-        ops.policy_chain_batch(self.x, self.y, index, img, targets, pad, flip, self.mean, self.std, table, nbins,
-                               num_ops=self.policy_ops, magnitude=self.policy_magnitude, subpolicies=subs,
-                               erase_prob=self.erase_prob, erase_scale=self.erase_scale, erase_ratio=self.erase_ratio,
-                               ratio_table=ratios, seed=seed, epoch=epoch, params_in=params, chain_in=chain_params,
-                               erase_in=erase_params, params_out=used, chain_out=cused, erase_out=eused, index_base=base)
-        return cused, eused
+        self._hold(x, y, shard)
 
     def batch(self, index, epoch=0, seed=0, train=True, params=None, return_params=False, policy_params=None,
               return_policy_params=False, chain_params=None, return_chain_params=False, erase_params=None,
@@ -307,51 +351,19 @@ class DeviceDataset:
 
         Every call returns freshly allocated tensors (torch's caching allocator): train_step is asynchronous and the engine
         keeps `img` until the stem's weight gradient, so nothing handed out is ever overwritten by a later call."""
-        if not isinstance(index, torch.Tensor):
-            index = torch.as_tensor(np.asarray(index))
-        if index.dim() != 1 or index.is_floating_point() or index.shape[0] == 0:
-            raise ValueError(f"index must be a non-empty integer vector, got {index.dtype} {tuple(index.shape)}")
-        if not index.is_cuda:
-            _check_host_index(index, self.shard_range, self.sharded)
-            index = index.to(self.device, non_blocking=True)
-        _C.require_gpu(index, "DeviceDataset.batch")
-        index = index.to(dtype=torch.int64).contiguous()
+        who = self._who
+        index = self._index(index)
         pad, flip = (self.pad, self.flip) if train else (0, False)
-        B = index.shape[0]
+        B, H, W = index.shape[0], self.x.shape[2], self.x.shape[3]
         if params is not None:
             if not train:
                 raise ValueError("params replace the training draw; train=False has none")
-            if tuple(params.shape) != (B, 3) or params.dtype != torch.int8:
-                raise ValueError(f"params must be int8 [{B},3], got {params.dtype} {tuple(params.shape)}")
-            if not params.is_cuda:
-                lo, hi = params.min(dim=0).values, params.max(dim=0).values
-                if int(lo.min()) < 0 or int(hi[0]) > 2 * pad or int(hi[1]) > 2 * pad or int(hi[2]) > 1:
-                    raise ValueError(f"params outside dy, dx in [0, {2 * pad}], flip in {{0, 1}}")
-                params = params.to(self.device, non_blocking=True)
-            _C.require_gpu(params, "DeviceDataset.batch")
-            params = params.contiguous()
+            params = _device_rows(params, "params", (B, 3), _crop_rule, (pad,), self.device, who, dtype=torch.int8)
         if policy_params is not None:
             if not train:
                 raise ValueError("policy_params replace the training draw; train=False has none")
-            H, W = self.x.shape[2], self.x.shape[3]
-            if not isinstance(policy_params, torch.Tensor):
-                policy_params = torch.as_tensor(np.asarray(policy_params))
-            if tuple(policy_params.shape) != (B, 7) or policy_params.is_floating_point() \
-                    or policy_params.dtype == torch.bool:
-                raise ValueError(f"policy_params must be integer [{B},7], got {policy_params.dtype} "
-                                 f"{tuple(policy_params.shape)}")
             _check_policy_source(self.x)
-            if not policy_params.is_cuda:
-                p = policy_params.long()
-                ok = (p[:, 0] >= 0) & (p[:, 0] < len(POLICY_OPS)) & (p[:, 1] >= 0) & (p[:, 1] < POLICY_BINS) \
-                    & (p[:, 2] >= 0) & (p[:, 2] <= 1) & (p[:, 3] >= 0) & (p[:, 4] >= 0) & (p[:, 5] >= 0) & (p[:, 6] >= 0) \
-                    & (p[:, 3] + p[:, 5] <= H) & (p[:, 4] + p[:, 6] <= W)
-                if not bool(ok.all()):
-                    raise ValueError(f"policy_params outside op in [0, {len(POLICY_OPS) - 1}], bin in [0, {POLICY_BINS - 1}], "
-                                     f"sign in {{0, 1}} or an erase rectangle outside the {H} x {W} image")
-                policy_params = policy_params.to(self.device, non_blocking=True)
-            _C.require_gpu(policy_params, "DeviceDataset.batch")
-            policy_params = policy_params.to(dtype=torch.int32).contiguous()
+            policy_params = _device_rows(policy_params, "policy_params", (B, 7), _policy_rule, (H, W), self.device, who)
         chain_args = chain_params is not None or erase_params is not None or return_chain_params or return_erase_params
         if chain_args and not self.chain:
             raise ValueError("chain_params / erase_params and their returns belong to policy='ra', 'cifar10' or a list of "
@@ -365,33 +377,35 @@ class DeviceDataset:
         targets = torch.empty((B,), dtype=torch.int64, device=self.device)
         used = torch.empty((B, 3), dtype=torch.int8, device=self.device) if return_params else None
         base = self.shard_range[0] if self.sharded else None
+        pused = cused = eused = None
         if self.chain and train:
-            cused, eused = self._batch_chain(index, img, targets, pad, flip, seed, epoch, params, used, base, chain_params,
-                                             erase_params, return_chain_params, return_erase_params)
-            out = (img, targets, used) if return_params else (img, targets)
-            out += (cused,) if return_chain_params else ()
-            return out + ((eused,) if return_erase_params else ())
-        with_policy = train and (self.policy is not None or self.erase_prob > 0.0 or policy_params is not None)
-        if not with_policy:
+            table, subs, ratios = self._chain_tables("ra" if self.policy == "ra" else "cifar10", H, W)
+            nbins = table.shape[1]
+            chain_params, erase_params = _chain_rows(chain_params, erase_params, B, nbins, H, W, self.device, who)
+            cused = self._used(B, CHAIN_MAX_OPS, 3) if return_chain_params else None
+            eused = self._used(B, 4) if return_erase_params else None
+            ops.policy_chain_batch(self.x, self.y, index, img, targets, pad, flip, self.mean, self.std, table, nbins,
+                                   num_ops=self.policy_ops, magnitude=self.policy_magnitude, subpolicies=subs,
+                                   ratio_table=ratios, seed=seed, epoch=epoch, params_in=params, chain_in=chain_params,
+                                   erase_in=erase_params, params_out=used, chain_out=cused, erase_out=eused, index_base=base,
+                                   erase_prob=self.erase_prob, erase_scale=self.erase_scale, erase_ratio=self.erase_ratio)
+        elif train and (self.policy is not None or self.erase_prob > 0.0 or policy_params is not None):
+            table = self._table_on_device("policy", policy_table, H, W)
+            pused = self._used(B, 7) if return_policy_params else None
+            ops.policy_batch(self.x, self.y, index, img, targets, pad, flip, self.mean, self.std,
+                             policy=self.policy is not None, policy_table=table,
+                             ratio_table=self._table_on_device("erase ratios", ratio_table, self.erase_ratio), seed=seed,
+                             epoch=epoch, params_in=params, policy_in=policy_params, params_out=used, policy_out=pused,
+                             index_base=base, erase_prob=self.erase_prob, erase_scale=self.erase_scale,
+                             erase_ratio=self.erase_ratio)
+        else:
             ops.augment_batch(self.x, self.y, index, img, targets, pad, flip, mean=self.mean, std=self.std, fill=self.fill,
                               seed=seed, epoch=epoch, params_in=params, params_out=used, index_base=base)
-            out = (img, targets, used) if return_params else (img, targets)
-            if return_policy_params:         # nothing was applied: Identity, no erase
-                out += (torch.zeros((B, 7), dtype=torch.int32, device=self.device),)
-            if return_chain_params:
-                out += (torch.zeros((B, CHAIN_MAX_OPS, 3), dtype=torch.int32, device=self.device),)
-            if return_erase_params:
-                out += (torch.zeros((B, 4), dtype=torch.int32, device=self.device),)
-            return out
-        table, ratios = self._tables()
-        pused = torch.empty((B, 7), dtype=torch.int32, device=self.device) if return_policy_params else None
-        ops.policy_batch(self.x, self.y, index, img, targets, pad, flip, self.mean, self.std,
-                         policy=self.policy is not None, policy_table=table, erase_prob=self.erase_prob,
-                         erase_scale=self.erase_scale, erase_ratio=self.erase_ratio, ratio_table=ratios, seed=seed,
-                         epoch=epoch, params_in=params, policy_in=policy_params, params_out=used, policy_out=pused,
-                         index_base=base)
         out = (img, targets, used) if return_params else (img, targets)
-        return out + (pused,) if return_policy_params else out
+        if return_policy_params or return_chain_params or return_erase_params:
+            out += self._extras((return_policy_params, pused, (B, 7)), (return_chain_params, cused, (B, CHAIN_MAX_OPS, 3)),
+                                (return_erase_params, eused, (B, 4)))
+        return out
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -547,7 +561,7 @@ def resize_center_crop_geometry(H, W, size, resize):
     return (rs_h, rs_w), (int(round((rs_h - size) / 2.0)), int(round((rs_w - size) / 2.0)))
 
 
-class ResizedCropDataset:
+class ResizedCropDataset(_DeviceBatches):
     """A uint8 dataset held on the device, batched by `nbdt_resized_crop_batch`: the reference's ImageNet transforms.
 
     x: uint8 ``[N,3,H,W]`` (any fixed H x W up to 4096: ImageNet stored at 256 x 256, a downsampled ImageNet); y: integer
@@ -570,27 +584,12 @@ class ResizedCropDataset:
     def __init__(self, x, y, mean, std, size=224, resize=None, scale=(0.08, 1.0), ratio=(3.0 / 4.0, 4.0 / 3.0), flip=True,
                  device="cuda", shard=None, policy=None, erase_prob=0.0, erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3),
                  policy_ops=2, policy_magnitude=9):
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise _C.NBDTHipError(f"ResizedCropDataset lives on an MI355X, not on {device} (no CPU fallback)")
-        self._subpolicies, policy_ops, policy_magnitude = _check_policy(policy, policy_ops, policy_magnitude)
-        self.policy = policy
+        super().__init__(x, y, mean, std, flip, device, policy, erase_prob, erase_scale, erase_ratio, policy_ops,
+                         policy_magnitude, (torch.uint8,))
         self.chain = policy is not None          # every policy is a chain here: nbdt_resized_crop_policy_batch
-        self.policy_ops, self.policy_magnitude = policy_ops, policy_magnitude
-        self.erase_prob = _check_erase(erase_prob, erase_scale, erase_ratio)
-        self.erase_scale = tuple(float(v) for v in erase_scale)
-        self.erase_ratio = tuple(float(v) for v in erase_ratio)
-        if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.uint8:
-            raise ValueError(f"x must be uint8 [N,3,H,W], got {x.dtype} {tuple(x.shape)}")
-        if y.dim() != 1 or y.shape[0] != x.shape[0] or y.is_floating_point():
-            raise ValueError(f"y must be integer [N] with N = {x.shape[0]}, got {y.dtype} {tuple(y.shape)}")
         if not (1 <= x.shape[2] <= MAX_SIDE and 1 <= x.shape[3] <= MAX_SIDE):
             raise ValueError(f"image sides must be 1..{MAX_SIDE}, got {tuple(x.shape[2:])}")
-        if len(mean) != 3 or len(std) != 3:
-            raise ValueError("mean and std have one entry per channel (3)")
         _check_ranges(scale, ratio)
-        self.mean = tuple(float(m) for m in mean)
-        self.std = tuple(float(s) for s in std)
         self.size = int(size)
         self.resize = self.size + 32 if resize is None else int(resize)
         if not 1 <= self.size <= self.resize <= MAX_SIDE:
@@ -600,42 +599,18 @@ class ResizedCropDataset:
                              f"{RESIZED_CROP_POLICY_MAX_SIDE} x {RESIZED_CROP_POLICY_MAX_SIDE}, got size {self.size}")
         self.scale = tuple(float(v) for v in scale)
         self.ratio = tuple(float(v) for v in ratio)
-        self.flip = bool(flip)
         self.eval_resize, self.eval_window = resize_center_crop_geometry(x.shape[2], x.shape[3], self.size, self.resize)
         if max(self.eval_resize) > MAX_SIDE:
             raise ValueError(f"the evaluation resize {self.eval_resize} exceeds {MAX_SIDE}")
-        self.sharded = shard is not None
-        self.x, self.y, self.shard_range, self.global_size = _place("ResizedCropDataset", x, y, shard, device)
-        self.device = self.x.device
+        self._hold(x, y, shard)
         self._table = torch.from_numpy(ratio_table(self.ratio).copy()).to(self.device)
         self._whole = torch.empty((0, 5), dtype=torch.int32, device=self.device)     # evaluation boxes, grown on demand
-        self._chain_tables = None         # (chain table, sub-policies or None, erase ratios) on the device, built on demand
-
-    def __len__(self):
-        return self.x.shape[0]
-
-    @property
-    def shape(self):
-        return self.x.shape
 
     def _whole_image(self, B):
         if self._whole.shape[0] < B:
             row = torch.tensor([0, 0, self.x.shape[2], self.x.shape[3], 0], dtype=torch.int32)
             self._whole = row.repeat(B, 1).to(self.device)
         return self._whole[:B]
-
-    def _chain(self):
-        if self._chain_tables is None:
-            S = self.size
-            if self.policy is None:               # the erase alone: no operation reads a table
-                table = None
-            else:
-                name = self.policy if self.policy in ("ra", "ta_wide") else "cifar10"      # (AutoAugment's 10 bins)
-                table = torch.from_numpy(chain_table(name, S, S).copy()).to(self.device)
-            subs = None if self._subpolicies is None else torch.from_numpy(self._subpolicies).to(self.device)
-            ratios = torch.from_numpy(ratio_table(self.erase_ratio).copy()).to(self.device)
-            self._chain_tables = (table, subs, ratios)
-        return self._chain_tables
 
     def batch(self, index, epoch=0, seed=0, train=True, params=None, return_params=False, chain_params=None,
               return_chain_params=False, erase_params=None, return_erase_params=False):
@@ -661,80 +636,59 @@ class ResizedCropDataset:
         never applies a policy or an erase.
 
         Every call returns freshly allocated tensors, as DeviceDataset.batch does."""
-        H, W = self.x.shape[2], self.x.shape[3]
-        if not isinstance(index, torch.Tensor):
-            index = torch.as_tensor(np.asarray(index))
-        if index.dim() != 1 or index.is_floating_point() or index.shape[0] == 0:
-            raise ValueError(f"index must be a non-empty integer vector, got {index.dtype} {tuple(index.shape)}")
-        if not index.is_cuda:
-            _check_host_index(index, self.shard_range, self.sharded)
-            index = index.to(self.device, non_blocking=True)
-        _C.require_gpu(index, "ResizedCropDataset.batch")
-        index = index.to(dtype=torch.int64).contiguous()
-        B = index.shape[0]
+        who = self._who
+        index = self._index(index)
+        B, H, W, S = index.shape[0], self.x.shape[2], self.x.shape[3], self.size
         if params is not None:
             if not train:
                 raise ValueError("params replace the training draw; train=False has none")
-            if tuple(params.shape) != (B, 5) or params.dtype != torch.int32:
-                raise ValueError(f"params must be int32 [{B},5], got {params.dtype} {tuple(params.shape)}")
-            if not params.is_cuda:
-                p = params.long()
-                ok = (p[:, 0] >= 0) & (p[:, 1] >= 0) & (p[:, 2] >= 1) & (p[:, 3] >= 1) & (p[:, 0] + p[:, 2] <= H) \
-                    & (p[:, 1] + p[:, 3] <= W) & (p[:, 4] >= 0) & (p[:, 4] <= 1)
-                if not bool(ok.all()):
-                    raise ValueError(f"params outside the {H} x {W} image (top, left >= 0, h, w >= 1, top + h <= H, "
-                                     "left + w <= W) or flip outside {0, 1}")
-                params = params.to(self.device, non_blocking=True)
-            _C.require_gpu(params, "ResizedCropDataset.batch")
-            params = params.contiguous()
+            params = _device_rows(params, "params", (B, 5), _box_rule, (H, W), self.device, who, dtype=torch.int32)
         if chain_params is not None and not self.chain:
             raise ValueError("chain_params belong to policy='ta_wide', 'ra', 'cifar10', 'imagenet' or a list of "
                              f"sub-policies; this dataset has policy={self.policy!r}")
         if not train and (chain_params is not None or erase_params is not None):
             raise ValueError("chain_params / erase_params replace the training draw; train=False has none")
-        S = self.size
         with_policy = train and (self.chain or self.erase_prob > 0.0 or erase_params is not None)
         if with_policy and S > RESIZED_CROP_POLICY_MAX_SIDE:
             raise ValueError(f"the augmentation policy and random erasing take crops of at most "
                              f"{RESIZED_CROP_POLICY_MAX_SIDE} x {RESIZED_CROP_POLICY_MAX_SIDE}, got size {S}")
-        if train:
-            resize, window = (S, S), (0, 0)
-        else:
-            resize, window, params = self.eval_resize, self.eval_window, self._whole_image(B)
         img = torch.empty((B, 3, S, S), dtype=torch.float32, device=self.device)
         targets = torch.empty((B,), dtype=torch.int64, device=self.device)
-        used = torch.empty((B, 5), dtype=torch.int32, device=self.device) if return_params else None
+        used = self._used(B, 5) if return_params else None
         base = self.shard_range[0] if self.sharded else None
-        out = (img, targets, used) if return_params else (img, targets)
+        cused = eused = None
         if not with_policy:
-            ops.resized_crop_batch(self.x, self.y, index, img, targets, resize, window, self.flip and train, self.mean, self.std,
-                                   scale=self.scale, ratio=self.ratio, ratio_table=self._table, seed=seed, epoch=epoch,
-                                   params_in=params, params_out=used, index_base=base)
-            if return_chain_params:          # nothing was applied: Identity, no erase
-                out += (torch.zeros((B, CHAIN_MAX_OPS, 3), dtype=torch.int32, device=self.device),)
-            if return_erase_params:
-                out += (torch.zeros((B, 4), dtype=torch.int32, device=self.device),)
-            return out
-        table, subs, ratios = self._chain()
-        nbins = 1 if table is None else table.shape[1]
-        chain_params, erase_params = _chain_rows(chain_params, erase_params, B, nbins, S, S, self.device,
-                                                 "ResizedCropDataset.batch")
-        cused = torch.empty((B, CHAIN_MAX_OPS, 3), dtype=torch.int32, device=self.device) if return_chain_params else None
-        eused = torch.empty((B, 4), dtype=torch.int32, device=self.device) if return_erase_params else None
-        # the chain's two tiles per image: scratch of this call (the caching allocator reuses it in stream order)
-        stage_a = torch.empty((B, 3, S, S), dtype=torch.uint8, device=self.device)
-        stage_b = torch.empty((B, 3, S, S), dtype=torch.uint8, device=self.device)
-        ra = self.policy == "ra"
-        ops.resized_crop_policy_batch(self.x, self.y, index, img, targets, self.flip, self.mean, self.std, stage_a, stage_b,
-                                      scale=self.scale, ratio=self.ratio, ratio_table=self._table, table=table, nbins=nbins,
-                                      num_ops=self.policy_ops if ra else 0, magnitude=self.policy_magnitude if ra else 0,
-                                      subpolicies=subs, ta_wide=self.policy == "ta_wide", erase_prob=self.erase_prob,
-                                      erase_scale=self.erase_scale, erase_ratio=self.erase_ratio, erase_ratio_table=ratios,
-                                      seed=seed, epoch=epoch, params_in=params, chain_in=chain_params,
-                                      erase_in=erase_params, params_out=used, chain_out=cused, erase_out=eused,
-                                      index_base=base)
-        out += (cused,) if return_chain_params else ()
-        return out + ((eused,) if return_erase_params else ())
+            if train:
+                resize, window = (S, S), (0, 0)
+            else:
+                resize, window, params = self.eval_resize, self.eval_window, self._whole_image(B)
+            ops.resized_crop_batch(self.x, self.y, index, img, targets, resize, window, self.flip and train, self.mean,
+                                   self.std, scale=self.scale, ratio=self.ratio, ratio_table=self._table, seed=seed,
+                                   epoch=epoch, params_in=params, params_out=used, index_base=base)
+        else:
+            # the erase alone: no operation reads a table; AutoAugment's sub-policies share "cifar10"'s ten bins
+            name = self.policy if self.policy in (None, "ra", "ta_wide") else "cifar10"
+            table, subs, ratios = self._chain_tables(name, S, S)
+            nbins = 1 if table is None else table.shape[1]
+            chain_params, erase_params = _chain_rows(chain_params, erase_params, B, nbins, S, S, self.device, who)
+            cused = self._used(B, CHAIN_MAX_OPS, 3) if return_chain_params else None
+            eused = self._used(B, 4) if return_erase_params else None
+            # the chain's two tiles per image: scratch of this call (the caching allocator reuses it in stream order)
+            stage_a = torch.empty((B, 3, S, S), dtype=torch.uint8, device=self.device)
+            stage_b = torch.empty((B, 3, S, S), dtype=torch.uint8, device=self.device)
+            ra = self.policy == "ra"
+            ops.resized_crop_policy_batch(self.x, self.y, index, img, targets, self.flip, self.mean, self.std, stage_a, stage_b,
+                                          scale=self.scale, ratio=self.ratio, ratio_table=self._table, table=table, nbins=nbins,
+                                          num_ops=self.policy_ops if ra else 0, magnitude=self.policy_magnitude if ra else 0,
+                                          subpolicies=subs, ta_wide=self.policy == "ta_wide", erase_prob=self.erase_prob,
+                                          erase_scale=self.erase_scale, erase_ratio=self.erase_ratio,
+                                          erase_ratio_table=ratios, seed=seed, epoch=epoch, params_in=params,
+                                          chain_in=chain_params, erase_in=erase_params, params_out=used, chain_out=cused,
+                                          erase_out=eused, index_base=base)
+        out = (img, targets, used) if return_params else (img, targets)
+        if return_chain_params or return_erase_params:
+            out += self._extras((return_chain_params, cused, (B, CHAIN_MAX_OPS, 3)), (return_erase_params, eused, (B, 4)))
+        return out
 
 
 def resized_crop_policy_reference(img_u8, box, flip, size, chain, table, erase, mean, std):

@@ -694,6 +694,27 @@ def maxpool_bwd(gy, idx, gx):
     check(lib().nbdt_maxpool3x3s2_bwd(ptr(gy), ptr(idx), _storage(gy), B, H, W, C, ptr(gx), stream_ptr(gx.device)))
 
 
+# the batch launches of the data path (augment.hip, policy.hip, resample.hip): their small converters and their one call
+_M64 = (1 << 64) - 1
+
+
+def _f3(v):
+    return None if v is None else (ctypes.c_float * 3)(*[float(a) for a in v])
+
+
+def _d2(v):
+    return None if v is None else (ctypes.c_double * 2)(*[float(a) for a in v])
+
+
+def _batch_call(plain, sharded, src, labels_src, index, index_base, tail):
+    """The plain entry, or with index_base its _sharded twin (index_base goes in after `index`)."""
+    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
+    if index_base is None:
+        check(plain(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
+    else:
+        check(sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
+
+
 def augment_batch(src, labels_src, index, out, labels_out, pad, flip, mean=None, std=None, fill=None, seed=0, epoch=0,
                   params_in=None, params_out=None, index_base=None):
     """nbdt_augment_batch: out[B,3,H,W] fp32, labels_out[B] <- gather + zero-padded random crop + flip (+ /255 and normalise
@@ -701,15 +722,9 @@ def augment_batch(src, labels_src, index, out, labels_out, pad, flip, mean=None,
     index_base (nbdt_augment_batch_sharded): `src` holds the samples [index_base, index_base + N) of the dataset `index`
     names; the draw uses `index`, the gather `index - index_base`."""
     N, _, H, W = src.shape
-    f3 = lambda v: None if v is None else (ctypes.c_float * 3)(*[float(a) for a in v])
-    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
-    mask = (1 << 64) - 1
-    tail = (index.shape[0], N, H, W, int(pad), 1 if flip else 0, f3(mean), f3(std), f3(fill), int(seed) & mask,
-            int(epoch) & mask, ptr(params_in), ptr(out), ptr(labels_out), ptr(params_out), stream_ptr(src.device))
-    if index_base is None:
-        check(lib().nbdt_augment_batch(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
-    else:
-        check(lib().nbdt_augment_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
+    tail = (index.shape[0], N, H, W, int(pad), 1 if flip else 0, _f3(mean), _f3(std), _f3(fill), int(seed) & _M64,
+            int(epoch) & _M64, ptr(params_in), ptr(out), ptr(labels_out), ptr(params_out), stream_ptr(src.device))
+    _batch_call(lib().nbdt_augment_batch, lib().nbdt_augment_batch_sharded, src, labels_src, index, index_base, tail)
 
 
 def policy_batch(src, labels_src, index, out, labels_out, pad, flip, mean, std, policy=False, policy_table=None,
@@ -721,18 +736,11 @@ def policy_batch(src, labels_src, index, out, labels_out, pad, flip, mean, std, 
     device).  policy_in / policy_out: int32 [B,7] (op, bin, sign, top, left, h, w), device; policy_in replaces the policy
     and erase draw.  index_base: nbdt_policy_batch_sharded, as for augment_batch."""
     N, _, H, W = src.shape
-    f3 = lambda v: None if v is None else (ctypes.c_float * 3)(*[float(a) for a in v])
-    d2 = lambda v: None if v is None else (ctypes.c_double * 2)(*[float(a) for a in v])
-    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
-    mask = (1 << 64) - 1
-    tail = (index.shape[0], N, H, W, int(pad), 1 if flip else 0, f3(mean), f3(std),
-            _C.NBDT_POLICY_TA_WIDE if policy else _C.NBDT_POLICY_NONE, ptr(policy_table), float(erase_prob), d2(erase_scale),
-            d2(erase_ratio), ptr(ratio_table), int(seed) & mask, int(epoch) & mask, ptr(params_in), ptr(policy_in), ptr(out),
-            ptr(labels_out), ptr(params_out), ptr(policy_out), stream_ptr(src.device))
-    if index_base is None:
-        check(lib().nbdt_policy_batch(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
-    else:
-        check(lib().nbdt_policy_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
+    tail = (index.shape[0], N, H, W, int(pad), 1 if flip else 0, _f3(mean), _f3(std),
+            _C.NBDT_POLICY_TA_WIDE if policy else _C.NBDT_POLICY_NONE, ptr(policy_table), float(erase_prob), _d2(erase_scale),
+            _d2(erase_ratio), ptr(ratio_table), int(seed) & _M64, int(epoch) & _M64, ptr(params_in), ptr(policy_in),
+            ptr(out), ptr(labels_out), ptr(params_out), ptr(policy_out), stream_ptr(src.device))
+    _batch_call(lib().nbdt_policy_batch, lib().nbdt_policy_batch_sharded, src, labels_src, index, index_base, tail)
 
 
 def policy_chain_batch(src, labels_src, index, out, labels_out, pad, flip, mean, std, table, nbins, num_ops=0, magnitude=0,
@@ -745,20 +753,13 @@ def policy_chain_batch(src, labels_src, index, out, labels_out, pad, flip, mean,
     (op, bin, sign), erase_in / erase_out: int32 [B,4] (top, left, h, w), device; the *_in replace the draws.
     index_base: nbdt_policy_chain_batch_sharded, as for augment_batch."""
     N, _, H, W = src.shape
-    f3 = lambda v: None if v is None else (ctypes.c_float * 3)(*[float(a) for a in v])
-    d2 = lambda v: None if v is None else (ctypes.c_double * 2)(*[float(a) for a in v])
-    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
-    mask = (1 << 64) - 1
     mode = _C.NBDT_CHAIN_RAND if subpolicies is None else _C.NBDT_CHAIN_SUBPOLICY
-    tail = (index.shape[0], N, H, W, int(pad), 1 if flip else 0, f3(mean), f3(std), mode, int(nbins), ptr(table),
+    tail = (index.shape[0], N, H, W, int(pad), 1 if flip else 0, _f3(mean), _f3(std), mode, int(nbins), ptr(table),
             int(num_ops), int(magnitude), ptr(subpolicies), 0 if subpolicies is None else subpolicies.shape[0],
-            float(erase_prob), d2(erase_scale), d2(erase_ratio), ptr(ratio_table), int(seed) & mask, int(epoch) & mask,
-            ptr(params_in), ptr(chain_in), ptr(erase_in), ptr(out), ptr(labels_out), ptr(params_out), ptr(chain_out),
-            ptr(erase_out), stream_ptr(src.device))
-    if index_base is None:
-        check(lib().nbdt_policy_chain_batch(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
-    else:
-        check(lib().nbdt_policy_chain_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
+            float(erase_prob), _d2(erase_scale), _d2(erase_ratio), ptr(ratio_table), int(seed) & _M64,
+            int(epoch) & _M64, ptr(params_in), ptr(chain_in), ptr(erase_in), ptr(out), ptr(labels_out), ptr(params_out),
+            ptr(chain_out), ptr(erase_out), stream_ptr(src.device))
+    _batch_call(lib().nbdt_policy_chain_batch, lib().nbdt_policy_chain_batch_sharded, src, labels_src, index, index_base, tail)
 
 
 def mix_batch(x, y, out, tgt, lam=1.0, box=(0, 0, 0, 0), lam_t=1.0):
@@ -786,17 +787,11 @@ def resized_crop_batch(src, labels_src, index, out, labels_out, resize, window, 
     index_base (nbdt_resized_crop_batch_sharded): `src` holds the samples [index_base, index_base + N) of the dataset
     `index` names; the draw uses `index`, the gather `index - index_base`."""
     N, _, H, W = src.shape
-    f3 = lambda v: (ctypes.c_float * 3)(*[float(a) for a in v])
-    d2 = lambda v: None if v is None else (ctypes.c_double * 2)(*[float(a) for a in v])
-    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
-    mask = (1 << 64) - 1
     tail = (index.shape[0], N, H, W, int(resize[0]), int(resize[1]), int(window[0]), int(window[1]), out.shape[2],
-            out.shape[3], 1 if flip else 0, f3(mean), f3(std), d2(scale), d2(ratio), ptr(ratio_table), int(seed) & mask,
-            int(epoch) & mask, ptr(params_in), ptr(out), ptr(labels_out), ptr(params_out), stream_ptr(src.device))
-    if index_base is None:
-        check(lib().nbdt_resized_crop_batch(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
-    else:
-        check(lib().nbdt_resized_crop_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base), *tail))
+            out.shape[3], 1 if flip else 0, _f3(mean), _f3(std), _d2(scale), _d2(ratio), ptr(ratio_table),
+            int(seed) & _M64, int(epoch) & _M64, ptr(params_in), ptr(out), ptr(labels_out), ptr(params_out),
+            stream_ptr(src.device))
+    _batch_call(lib().nbdt_resized_crop_batch, lib().nbdt_resized_crop_batch_sharded, src, labels_src, index, index_base, tail)
 
 
 def resized_crop_policy_batch(src, labels_src, index, out, labels_out, flip, mean, std, stage_a, stage_b, scale=None,
@@ -817,25 +812,18 @@ def resized_crop_policy_batch(src, labels_src, index, out, labels_out, flip, mea
         raise _C.NBDTHipError(f"resized_crop_policy_batch: out must be [B,3,S,S] and both staging buffers uint8 of that "
                               f"shape, got out {tuple(out.shape)}, stage_a {stage_a.dtype} {tuple(stage_a.shape)}, stage_b "
                               f"{stage_b.dtype} {tuple(stage_b.shape)}")
-    f3 = lambda v: (ctypes.c_float * 3)(*[float(a) for a in v])
-    d2 = lambda v: None if v is None else (ctypes.c_double * 2)(*[float(a) for a in v])
-    dtype = _C.NBDT_U8 if src.dtype == torch.uint8 else _C.NBDT_F32
-    mask = (1 << 64) - 1
     if subpolicies is not None:
         mode = _C.NBDT_CHAIN_SUBPOLICY
     else:
         mode = _C.NBDT_CHAIN_TA_WIDE if ta_wide else _C.NBDT_CHAIN_RAND
-    tail = (index.shape[0], N, H, W, out.shape[2], 1 if flip else 0, f3(mean), f3(std), d2(scale), d2(ratio),
+    tail = (index.shape[0], N, H, W, out.shape[2], 1 if flip else 0, _f3(mean), _f3(std), _d2(scale), _d2(ratio),
             ptr(ratio_table), mode, int(nbins), ptr(table), int(num_ops), int(magnitude), ptr(subpolicies),
-            0 if subpolicies is None else subpolicies.shape[0], float(erase_prob), d2(erase_scale), d2(erase_ratio),
-            ptr(erase_ratio_table), int(seed) & mask, int(epoch) & mask, ptr(params_in), ptr(chain_in), ptr(erase_in),
+            0 if subpolicies is None else subpolicies.shape[0], float(erase_prob), _d2(erase_scale), _d2(erase_ratio),
+            ptr(erase_ratio_table), int(seed) & _M64, int(epoch) & _M64, ptr(params_in), ptr(chain_in), ptr(erase_in),
             ptr(stage_a), ptr(stage_b), ptr(out), ptr(labels_out), ptr(params_out), ptr(chain_out), ptr(erase_out),
             stream_ptr(src.device))
-    if index_base is None:
-        check(lib().nbdt_resized_crop_policy_batch(ptr(src), dtype, ptr(labels_src), ptr(index), *tail))
-    else:
-        check(lib().nbdt_resized_crop_policy_batch_sharded(ptr(src), dtype, ptr(labels_src), ptr(index), int(index_base),
-                                                           *tail))
+    _batch_call(lib().nbdt_resized_crop_policy_batch, lib().nbdt_resized_crop_policy_batch_sharded, src, labels_src, index,
+                index_base, tail)
 
 
 def resized_crop_band_rows(H, W, resize, window, out_size):
@@ -1222,10 +1210,7 @@ def stochastic_depth_draw(table, prob, scale, seed, stream, counter):
                                            U, B, ptr(table), stream_ptr(table.device)))
 
 
-_M64 = (1 << 64) - 1
-
-
-def _mix64(x):      # splitmix64's finaliser: nbdt/data.py _mix64, csrc/effnet.hip mix64
+def _mix64(x):      # splitmix64's finaliser (csrc/effnet.hip, csrc/policy_ops.h mix64); nbdt/data.py's draws use this one
     x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
     x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
     return x ^ (x >> np.uint64(31))

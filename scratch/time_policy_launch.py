@@ -4,7 +4,7 @@ the median (and minimum) of 20 event-bracketed calls after 3 warm-up calls and t
 back, three interleaved rounds; then one round per
 operation (every image of the batch given that operation at bin 15), which shows what the slowest block of a mixed batch
 costs.  Step: DeviceDataset.batch + train_step at 512 x 32 x 32, the median of 20 event-bracketed steps after 3, alternating
-policy off / on.  profiles/policy_launch.txt."""
+policy off / on (--no-step: the launches only).  profiles/policy_launch.txt."""
 import os
 import statistics
 import sys
@@ -20,6 +20,7 @@ from nbdt.engine import WRNEngine, train_step  # noqa: E402
 from nbdt.loss import SoftTreeSupLoss  # noqa: E402
 
 tag = sys.argv[1] if len(sys.argv) > 1 else "run"
+with_step = "--no-step" not in sys.argv
 B = 512
 
 
@@ -83,6 +84,9 @@ for name, (plain, policy, index) in sets.items():
         pp = torch.tensor([[op, 15, 0, 0, 0, 0, 0]] * B, dtype=torch.int32, device="cuda:0")
         per_op.append(f"{op_name} {streamed(lambda: plain.batch(index, policy_params=pp)):.1f}")
     print(f"{tag} {name} every image the same op, back to back, us per call: " + ", ".join(per_op))
+
+if not with_step:
+    sys.exit(0)
 
 eng = WRNEngine(num_classes=10, blocks=28, width_factor=10, device="cuda:0", seed=0)
 crit = SoftTreeSupLoss(dataset="CIFAR10", criterion=nn.CrossEntropyLoss(), hierarchy="induced-wrn28_10_cifar10")

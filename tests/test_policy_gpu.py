@@ -291,6 +291,12 @@ def test_refusals_come_before_any_launch(monkeypatch):
     with pytest.raises(_C.NBDTHipError, match="49152"):
         ops.policy_batch(xbig.cuda(), y.cuda(), index.cuda(), torch.empty(4, 3, 129, 128, device="cuda"), lab, 4, True,
                          CIFAR["mean"], CIFAR["std"])
+    # ... and policy_in without the table its operations would index
+    x8 = torch.zeros(4, 3, 32, 32, dtype=torch.uint8, device="cuda")
+    rows = torch.tensor([NOP, (5, 15, 0, 0, 0, 0, 0), NOP, NOP], dtype=torch.int32, device="cuda")
+    with pytest.raises(_C.NBDTHipError, match="policy table"):
+        ops.policy_batch(x8, y.cuda(), index.cuda(), out, lab, 4, True, CIFAR["mean"], CIFAR["std"], policy=False,
+                         policy_table=None, policy_in=rows)
 
 
 def test_device_policy_params_are_clamped_not_trusted():
