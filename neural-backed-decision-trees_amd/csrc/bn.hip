@@ -11,11 +11,10 @@
 //
 // Roofline: HBM.  Algorithmic bytes per element: stats 2 (read x); apply 4 (+2 residual);
 // bwd_reduce 6; bwd_apply 8 (+2 gx_add, +2 g_resid).
-#include "common.h"
+#include "bn_sums.h"
 
 using namespace nbdt;
 
-constexpr int kSlots = NBDT_BN_SLOTS;
 constexpr int kMaxThreads = 256;
 
 struct Layout {  // thread layout for a C-channel tensor: C8 channel chunks x PY pixel rows
@@ -36,33 +35,6 @@ static int grid_for(const PadGeom& g, const Layout& l, int pixels_per_thread) {
   return (int)want;
 }
 
-// fold per-thread 8-channel partial sums across the PY pixel rows of the block, then add them
-// to slot (blockIdx & slot_mask) of scratch[slot][which][C].  slot_mask = kSlots - 1: the 32 replicated accumulators
-// (several blocks add to one slot, in whatever order they finish); slot_mask = ~0 (deterministic mode): `scratch` is
-// a zeroed row per BLOCK, every address receives exactly one add, and det_fold() sums the rows in block order.
-template <int NQ>
-__device__ __forceinline__ void block_fold_to_slots(float (&acc)[NQ][8], int cx, int py, int c8, int PY, int C,
-                                                    float* scratch, float* lds, unsigned slot_mask) {
-  // lds: [PY][c8][NQ*8]
-  float* mine = lds + ((size_t)py * c8 + cx) * (NQ * 8);
-#pragma unroll
-  for (int q = 0; q < NQ; ++q)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) mine[q * 8 + i] = acc[q][i];
-  __syncthreads();
-  // output o = q * (c8*8) + channel goes to thread o % (c8*PY): consecutive threads add to consecutive addresses (one
-  // 256-byte run per wave; thread (cx, py) folding element e = py, py+PY, ... of ITS chunk put a wave's lanes 32 bytes
-  // apart -- 64 sectors per atomic instruction once c8 >= 64).  Each sum is its PY partials in ascending row order.
-  const int nch = c8 * 8, nthr = c8 * PY;
-  for (int o = py * c8 + cx; o < NQ * nch; o += nthr) {
-    const int q = o / nch, c = o - q * nch;
-    const float* src = lds + (size_t)(c >> 3) * (NQ * 8) + q * 8 + (c & 7);
-    float s = 0.f;
-    for (int r = 0; r < PY; ++r) s += src[(size_t)r * c8 * (NQ * 8)];
-    atomicAdd(scratch + ((size_t)(blockIdx.x & slot_mask) * NQ + q) * C + c, s);
-  }
-}
-
 __global__ __launch_bounds__(kMaxThreads) void bn_stats_kernel(const bf16_t* __restrict__ x, PadGeom g, int c8,
                                                                int PY, float* __restrict__ scratch,
                                                                unsigned slot_mask) {
@@ -81,7 +53,9 @@ __global__ __launch_bounds__(kMaxThreads) void bn_stats_kernel(const bf16_t* __r
       acc[1][i] += f[i] * f[i];
     }
   }
-  block_fold_to_slots<2>(acc, cx, py, c8, PY, g.C, scratch, lds, slot_mask);
+  block_fold<2>(acc, cx, py, c8, PY, lds, [&](int q, int c, float s) {
+    slot_add<2>(scratch, blockIdx.x & slot_mask, g.C, q, c, s);
+  });
 }
 
 // 1 block: fold slots; mode 0 = forward statistics, mode 1 = backward sums
@@ -113,29 +87,6 @@ __global__ __launch_bounds__(256) void bn_finalize_kernel(float* __restrict__ sc
       const float unbiased = n > 1.f ? var * n / (n - 1.f) : var;
       running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
     }
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_finalize_kernel(float* __restrict__ scratch, int C,
-                                                              float* __restrict__ dsum,
-                                                              float* __restrict__ dgamma,
-                                                              float* __restrict__ dbeta) {
-  for (int c = blockIdx.x * 256 + threadIdx.x; c < C; c += gridDim.x * 256) {
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < kSlots; ++k) {
-      s0 += scratch[((size_t)k * 2 + 0) * C + c];
-      s1 += scratch[((size_t)k * 2 + 1) * C + c];
-    }
-#pragma unroll 8
-    for (int k = 0; k < kSlots; ++k) {
-      scratch[((size_t)k * 2 + 0) * C + c] = 0.f;
-      scratch[((size_t)k * 2 + 1) * C + c] = 0.f;
-    }
-    dsum[c] = s0;
-    dsum[C + c] = s1;
-    if (dbeta) dbeta[c] += s0;
-    if (dgamma) dgamma[c] += s1;
   }
 }
 
@@ -248,7 +199,9 @@ __global__ __launch_bounds__(kMaxThreads) void bn_bwd_reduce_kernel(const bf16_t
     }
     one(p, x0, g0, y0);
   }
-  block_fold_to_slots<2>(acc, cx, py, c8, PY, g.C, scratch, lds, slot_mask);
+  block_fold<2>(acc, cx, py, c8, PY, lds, [&](int q, int c, float s) {
+    slot_add<2>(scratch, blockIdx.x & slot_mask, g.C, q, c, s);
+  });
 }
 
 template <bool RELU, bool POOL, bool HAS_ADD, bool HAS_GRES>
@@ -499,7 +452,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_reduce_cus_kernel(const bf16_t* _
     const int which = e / (c8 * 8), c = e - which * (c8 * 8);
     float s = 0.f;
     for (int r = 0; r < PY; ++r) s += lds[((size_t)r * c8 + (c >> 3)) * 16 + which * 8 + (c & 7)];
-    atomicAdd(scratch + ((size_t)(blockIdx.x & slot_mask) * 2 + which) * g.C + c, s);
+    slot_add<2>(scratch, blockIdx.x & slot_mask, g.C, which, c, s);
   }
 }
 
@@ -538,36 +491,6 @@ __global__ __launch_bounds__(256) void bn_relu_pool_kernel(const bf16_t* __restr
 }
 
 // ------------------------------------------------------------------------------------------ host
-
-static int check_shape(int B, int H, int W, int C) {
-  NBDT_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "empty tensor");
-  NBDT_REQUIRE(C % 8 == 0 && C / 8 <= kMaxThreads, "C must be a multiple of 8 and <= 2048");
-  NBDT_REQUIRE((long long)B * (H + 2) * (W + 2) * C < (1ll << 31), "tensor too large for 32-bit offsets");
-  return NBDT_OK;
-}
-
-
-// Where a reduction kernel of `grid` blocks adds its per-block sums of n = 2*C floats.  Normally the caller's 32-slot
-// scratch; in deterministic mode (nbdt_set_deterministic) a zeroed library-owned row per block -- each address then
-// receives exactly one atomic add -- that slot_finish() sums in block order into slot 0 of the caller's scratch, so
-// the finalize kernels (which fold the 32 slots in a fixed order anyway) need no second form.
-struct SlotTarget {
-  float* ptr;
-  unsigned mask;
-  bool det;
-};
-static int slot_target(hipStream_t st, float* scratch, int grid, size_t n, SlotTarget* t) {
-  t->ptr = scratch; t->mask = kSlots - 1; t->det = false;
-  if (!deterministic()) return NBDT_OK;
-  float* rows = det_rows(st, (size_t)grid * n);
-  if (!rows) return nbdt::fail(NBDT_ENOMEM, "deterministic mode: %s (%s)", "no workspace for the per-block rows", nbdt::det_rows_why());
-  NBDT_HIP_CHECK(hipMemsetAsync(rows, 0, (size_t)grid * n * sizeof(float), st));
-  t->ptr = rows; t->mask = ~0u; t->det = true;
-  return NBDT_OK;
-}
-static int slot_finish(hipStream_t st, const SlotTarget& t, int grid, size_t n, float* scratch) {
-  return t.det ? det_fold(st, t.ptr, grid, n, scratch) : NBDT_OK;
-}
 
 extern "C" int nbdt_bn_stats(const void* x, int32_t B, int32_t H, int32_t W, int32_t C, float eps, float momentum,
                              float* running_mean, float* running_var, float* scratch, float* save_mean,

@@ -10,14 +10,13 @@
 //   writes a*gate directly, and every backward pass recomputes a / swish'(bn(x)) from x.
 // Algorithmic bytes per element: pool 2, apply/scale 4 (+2 residual), se_bwd_reduce 4,
 // bwd_reduce 4, bwd_apply 6 (+2 gx_add); depthwise fwd 4, bwd_data 4, bwd_weight 4.
-#include "common.h"
+#include "bn_sums.h"
 #include <stdlib.h>
 
 using namespace nbdt;
 
 namespace {
 
-constexpr int kSlots = NBDT_BN_SLOTS;
 constexpr int kThreads = 256;
 
 struct MbGeom {
@@ -42,13 +41,6 @@ MbGeom mb_geom(int B, int H, int W, int C, int ppt) {
   g.slices = (g.hw + g.PY * ppt - 1) / (g.PY * ppt);
   if (g.slices < 1) g.slices = 1;
   return g;
-}
-
-int check_mb(int B, int H, int W, int C) {
-  NBDT_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "empty tensor");
-  NBDT_REQUIRE(C % 8 == 0 && C / 8 <= kThreads, "C must be a multiple of 8 and <= 2048");
-  NBDT_REQUIRE((long long)B * (H + 2) * (W + 2) * C < (1ll << 31), "tensor too large for 32-bit offsets");
-  return NBDT_OK;
 }
 
 __device__ __forceinline__ int pix_off(const MbGeom& g, int b, int p, int cx) {
@@ -96,31 +88,6 @@ __device__ __forceinline__ void load_bn(BnRegs& r, const float* mean, const floa
     const int c = cx * 8 + i;
     r.sc[i] = gamma[c] * rstd[c];
     r.sh[i] = beta[c] - mean[c] * r.sc[i];
-  }
-}
-
-// fold NQ*8 per-thread partials over the PY pixel rows of the block and hand every sum to `sink(q, channel, value)`.
-// Output o = q * (c8*8) + channel goes to thread o % (c8*PY): CONSECUTIVE THREADS HOLD CONSECUTIVE CHANNELS, so the
-// sinks' global atomics are one contiguous 256-byte run per wave.  (Round 1 gave chunk cx's element e to thread
-// (cx, e % PY): lanes 32 bytes apart, 64 sectors per atomic instruction -- that, not the arithmetic, was most of the
-// time of every statistics / weight-gradient kernel of this file on the narrow late layers: profiles/r04_dw_wgrad.txt.)
-// A sum is still its PY partials in ascending row order: the same bits as before.
-template <int NQ, typename Sink>
-__device__ __forceinline__ void block_fold(float (&acc)[NQ][8], int cx, int py, int c8, int PY, float* lds,
-                                           Sink sink) {
-  float* mine = lds + ((size_t)py * c8 + cx) * (NQ * 8);
-#pragma unroll
-  for (int q = 0; q < NQ; ++q)
-#pragma unroll
-    for (int i = 0; i < 8; ++i) mine[q * 8 + i] = acc[q][i];
-  __syncthreads();
-  const int nch = c8 * 8, nthr = c8 * PY;
-  for (int o = py * c8 + cx; o < NQ * nch; o += nthr) {
-    const int q = o / nch, c = o - q * nch;
-    const float* src = lds + (size_t)(c >> 3) * (NQ * 8) + q * 8 + (c & 7);
-    float s = 0.f;
-    for (int r = 0; r < PY; ++r) s += src[(size_t)r * c8 * (NQ * 8)];
-    sink(q, c, s);
   }
 }
 
@@ -246,9 +213,7 @@ __global__ __launch_bounds__(kThreads) void mb_bwd_reduce_kernel(
     }
   }
   const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & slot_mask;   // (deterministic mode: a row per block)
-  block_fold<2>(acc, cx, py, g.c8, g.PY, lds, [&](int q, int c, float s) {
-    atomicAdd(scratch + ((size_t)slot * 2 + q) * g.C + c, s);
-  });
+  block_fold<2>(acc, cx, py, g.c8, g.PY, lds, [&](int q, int c, float s) { slot_add<2>(scratch, slot, g.C, q, c, s); });
 }
 
 // backward pass 2: gx = gamma*rstd * (g_y - mean(g_y) - xhat * mean(g_y*xhat)) [+ gx_add]
@@ -297,29 +262,6 @@ __global__ __launch_bounds__(kThreads) void mb_bwd_apply_kernel(
       out[i] = v;
     }
     *(u32x4_t*)(gx + o) = pack8(out);
-  }
-}
-
-__global__ __launch_bounds__(256) void mb_bwd_finalize_kernel(float* __restrict__ scratch, int C,
-                                                              float* __restrict__ dsum,
-                                                              float* __restrict__ dgamma,
-                                                              float* __restrict__ dbeta) {
-  for (int c = blockIdx.x * 256 + threadIdx.x; c < C; c += gridDim.x * 256) {
-    float s0 = 0.f, s1 = 0.f;
-#pragma unroll 8
-    for (int k = 0; k < kSlots; ++k) {
-      s0 += scratch[((size_t)k * 2 + 0) * C + c];
-      s1 += scratch[((size_t)k * 2 + 1) * C + c];
-    }
-#pragma unroll 8
-    for (int k = 0; k < kSlots; ++k) {
-      scratch[((size_t)k * 2 + 0) * C + c] = 0.f;   // zero-on-entry contract for the next user
-      scratch[((size_t)k * 2 + 1) * C + c] = 0.f;
-    }
-    dsum[c] = s0;
-    dsum[C + c] = s1;
-    if (dbeta) dbeta[c] += s0;
-    if (dgamma) dgamma[c] += s1;
   }
 }
 
@@ -526,31 +468,8 @@ __global__ __launch_bounds__(kThreads) void dw_row_kernel(const bf16_t* __restri
     }
   if (STATS) {
     const unsigned slot = (blockIdx.x + blockIdx.y * gridDim.x) & slot_mask;   // (deterministic mode: a row per block)
-    block_fold<2>(st, cx, py, g.c8, PY, lds, [&](int q, int c, float v) {
-      atomicAdd(stats + ((size_t)slot * 2 + q) * g.C + c, v);
-    });
+    block_fold<2>(st, cx, py, g.c8, PY, lds, [&](int q, int c, float v) { slot_add<2>(stats, slot, g.C, q, c, v); });
   }
-}
-
-// Deterministic mode (nbdt_set_deterministic): where a reduction kernel of `blocks` blocks adds its per-block sums of n
-// floats -- the caller's 32-slot scratch, or a zeroed library-owned row per block that slot_finish() sums in block
-// order into slot 0 of the caller's scratch (same scheme as csrc/bn.hip).
-struct SlotTarget {
-  float* ptr;
-  unsigned mask;
-  bool det;
-};
-static int slot_target(hipStream_t st, float* scratch, int blocks, size_t n, SlotTarget* t) {
-  t->ptr = scratch; t->mask = kSlots - 1; t->det = false;
-  if (!deterministic()) return NBDT_OK;
-  float* rows = det_rows(st, (size_t)blocks * n);
-  if (!rows) return nbdt::fail(NBDT_ENOMEM, "deterministic mode: %s (%s)", "no workspace for the per-block rows", nbdt::det_rows_why());
-  NBDT_HIP_CHECK(hipMemsetAsync(rows, 0, (size_t)blocks * n * sizeof(float), st));
-  t->ptr = rows; t->mask = ~0u; t->det = true;
-  return NBDT_OK;
-}
-static int slot_finish(hipStream_t st, const SlotTarget& t, int blocks, size_t n, float* scratch) {
-  return t.det ? det_fold(st, t.ptr, blocks, n, scratch) : NBDT_OK;
 }
 
 template <int K, int S, bool FLIP>
@@ -990,7 +909,7 @@ static int bn_act_apply_impl(const void* x, const float* save_mean, const float*
   NBDT_REQUIRE(x && save_mean && save_rstd && gamma && beta && y, "null argument");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
   NBDT_REQUIRE(!row_scale || (residual && !gate), "row_scale scales the branch of a residual add: it needs a residual and takes no gate");
-  int rc = check_mb(B, H, W, C);
+  int rc = check_shape(B, H, W, C);
   if (rc) return rc;
   const MbGeom g = mb_geom(B, H, W, C, kPpt);
   const dim3 grid(g.slices, B), blk(g.threads);
@@ -1030,7 +949,7 @@ extern "C" int nbdt_bn_act_pool(const void* x, const float* save_mean, const flo
                                 int32_t W, int32_t C, float* out, void* stream) {
   NBDT_REQUIRE(x && save_mean && save_rstd && gamma && beta && out, "null argument");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
-  int rc = check_mb(B, H, W, C);
+  int rc = check_shape(B, H, W, C);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   NBDT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)B * C * sizeof(float), st));
@@ -1069,7 +988,7 @@ static int bn_act_bwd_impl(const void* gu, const float* gate, const float* gpool
   NBDT_REQUIRE(gu || (gpool && !gate), "need an upstream gradient tensor or a pooled gradient");
   NBDT_REQUIRE(!gate || (gu && gpool), "the SE form needs gu, gate and gpool");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
-  int rc = check_mb(B, H, W, C);
+  int rc = check_shape(B, H, W, C);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const bool se = gate != nullptr, pool = gu == nullptr;
@@ -1098,7 +1017,7 @@ static int bn_act_bwd_impl(const void* gu, const float* gate, const float* gpool
     if (rc) return rc;
   }
   if (!dsum_ready) {      // (dsum_ready: nbdt_bn_act_se_bwd_apply's own finalize kernel already wrote dsum / dgamma / dbeta)
-    hipLaunchKernelGGL(mb_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, scratch, C, dsum, dgamma, dbeta);
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, st, scratch, C, dsum, dgamma, dbeta);
     NBDT_LAUNCH_CHECK();
   }
   {
@@ -1153,7 +1072,7 @@ extern "C" int nbdt_bn_act_se_sums(const void* gu, const void* x, const float* s
   NBDT_REQUIRE(gu && x && save_mean && save_rstd && gamma && beta && sums, "null argument");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
   NBDT_REQUIRE(!deterministic(), "nbdt_bn_act_se_sums adds its pixel slices with atomics: use nbdt_bn_act_pool + nbdt_bn_act_bwd in deterministic mode");
-  int rc = check_mb(B, H, W, C);
+  int rc = check_shape(B, H, W, C);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const MbGeom g = mb_geom(B, H, W, C, 2 * kPpt);
@@ -1176,7 +1095,7 @@ extern "C" int nbdt_bn_act_se_bwd_apply(const void* gu, const float* gate, const
   // dgamma / dbeta, so a call refused after it would leave them changed (and a retry would count them twice)
   NBDT_REQUIRE(gu && gate && gpool && sums && dsum && x && save_mean && save_rstd && gamma && beta && gx, "null argument");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
-  int rc = check_mb(B, H, W, C);
+  int rc = check_shape(B, H, W, C);
   if (rc) return rc;
   hipLaunchKernelGGL(mb_se_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, sums, gate, gpool,
                      B, C, 1.f / (float)(H * W), dsum, dgamma, dbeta);
@@ -1186,7 +1105,7 @@ extern "C" int nbdt_bn_act_se_bwd_apply(const void* gu, const float* gate, const
 }
 
 static int check_dw(int B, int H, int W, int C, int k, int stride) {
-  int rc = check_mb(B, H, W, C);
+  int rc = check_shape(B, H, W, C);
   if (rc) return rc;
   NBDT_REQUIRE(k == 3 || k == 5, "depthwise kernel size must be 3 or 5");
   NBDT_REQUIRE(stride == 1 || stride == 2, "stride must be 1 or 2");

@@ -444,13 +444,17 @@ class BatchNorm:
     def beta(self):
         return self.store.p(self.name + ".bias")
 
-    def stats(self, x, training, fused=False):
-        """fused=True: the producing conv's epilogue already wrote per-tile partial sums (fold only)."""
+    def stats(self, x, training, fused=False, slots_filled=False):
+        """fused=True: the producing conv's epilogue already wrote per-tile partial sums (fold only).
+        slots_filled=True: the producing kernel (a depthwise conv given the owner's scratch) left the sums in the slots."""
         if training:
             self._affine = None        # running statistics are about to change
             if fused:
                 ops.bn_finalize(x, self.owner.partials(x), self.mean, self.rstd, self.running_mean,
                                 self.running_var)
+            elif slots_filled:
+                ops.bn_stats(x, self.owner.scratch(self.C), self.mean, self.rstd, self.running_mean,
+                             self.running_var, slots_filled=True)
             else:
                 ops.bn_stats(x, self.owner.scratch(self.C), self.mean, self.rstd, self.running_mean,
                              self.running_var)
@@ -461,6 +465,10 @@ class BatchNorm:
 
     def apply(self, x, y, relu=True, residual=None):
         ops.bn_apply(x, self.mean, self.rstd, self.gamma, self.beta, y, relu=relu, residual=residual)
+
+    def apply_s2d(self, x, y, relu=True):
+        """apply() written as the space-to-depth copy the stride-2 convs of a shape-changing unit read."""
+        ops.bn_apply_s2d(x, self.mean, self.rstd, self.gamma, self.beta, y, relu=relu)
 
     def backward_fused(self, gy, x, gx, partials, gx_add=None, cus=0):
         """Backward of relu(bn(x)) when the dgrad that produced gy already wrote the reduction partials.
@@ -480,6 +488,52 @@ class BatchNorm:
         ops.bn_bwd(gy, y, x, self.mean, self.rstd, self.gamma, self.owner.scratch(self.C), self.dsum,
                    self.store.g(self.name + ".weight"), self.store.g(self.name + ".bias"), gx, relu=relu,
                    gx_add=gx_add, g_resid=g_resid, beta=self.beta)
+
+    def pool_backward(self, gpooled, x, gx):
+        """Backward of mean_hw relu(bn(x)) from dL/dpooled [B, C]."""
+        ops.pool_bn_bwd(gpooled, x, self.mean, self.rstd, self.gamma, self.beta, self.owner.scratch(self.C), self.dsum,
+                        self.store.g(self.name + ".weight"), self.store.g(self.name + ".bias"), gx)
+
+    # ---- the activation family (csrc/effnet.hip): act(bn(x)) with a squeeze-and-excitation gate, a residual, a per-image
+    # row scale.  Each method is its nbdt.ops entry with this BatchNorm's vectors, the owner's scratch and the two
+    # gradient views filled in; row_scale is handed on only when there is one (the call without it is the plain entry's).
+    def act_apply(self, x, y, act=ops.ACT_SWISH, gate=None, residual=None, row_scale=None):
+        if row_scale is not None:
+            ops.bn_act_apply(x, self.mean, self.rstd, self.gamma, self.beta, y, act=act, gate=gate, residual=residual,
+                             row_scale=row_scale)
+        else:
+            ops.bn_act_apply(x, self.mean, self.rstd, self.gamma, self.beta, y, act=act, gate=gate, residual=residual)
+
+    def act_pool(self, x, out, act=ops.ACT_SWISH, mul=None, scale=None):
+        ops.bn_act_pool(x, self.mean, self.rstd, self.gamma, self.beta, out, act=act, mul=mul, scale=scale)
+
+    def act_backward(self, gu, x, gx, act=ops.ACT_SWISH, gate=None, gpool=None, gx_add=None, row_scale=None):
+        if row_scale is not None:
+            ops.bn_act_bwd(gu, x, self.mean, self.rstd, self.gamma, self.beta, self.owner.scratch(self.C), self.dsum,
+                           self.store.g(self.name + ".weight"), self.store.g(self.name + ".bias"), gx, act=act,
+                           gate=gate, gpool=gpool, gx_add=gx_add, row_scale=row_scale)
+        else:
+            ops.bn_act_bwd(gu, x, self.mean, self.rstd, self.gamma, self.beta, self.owner.scratch(self.C), self.dsum,
+                           self.store.g(self.name + ".weight"), self.store.g(self.name + ".bias"), gx, act=act,
+                           gate=gate, gpool=gpool, gx_add=gx_add)
+
+    def act_backward_apply(self, gu, x, gx, act=ops.ACT_SWISH, gx_add=None):
+        """act_backward without its reduction pass: the producing kernel filled the owner's slots."""
+        ops.bn_act_bwd_apply(gu, x, self.mean, self.rstd, self.gamma, self.beta, self.owner.scratch(self.C), self.dsum,
+                             self.store.g(self.name + ".weight"), self.store.g(self.name + ".bias"), gx, act=act,
+                             gx_add=gx_add)
+
+    def dwconv_backward_data(self, gy, w, gx, k, x):
+        """ops.dwconv_bwd_data_bn: the stride-1 depthwise data gradient gx = dL/d(swish(bn(x))), which also leaves this
+        BatchNorm's backward sums in the owner's slots (DepthwiseConv.backward_data(bn=...); act_backward_apply follows)."""
+        ops.dwconv_bwd_data_bn(gy, w, gx, k, x, self.mean, self.rstd, self.gamma, self.beta, self.owner.scratch(self.C))
+
+    def act_se_sums(self, gu, x, sums, act=ops.ACT_SWISH):
+        ops.bn_act_se_sums(gu, x, self.mean, self.rstd, self.gamma, self.beta, sums, act=act)
+
+    def act_se_backward_apply(self, gu, gate, gpool, sums, x, gx, act=ops.ACT_SWISH):
+        ops.bn_act_se_bwd_apply(gu, gate, gpool, sums, x, self.mean, self.rstd, self.gamma, self.beta, self.dsum,
+                                self.store.g(self.name + ".weight"), self.store.g(self.name + ".bias"), gx, act=act)
 
 
 class _Engine:
@@ -713,20 +767,38 @@ class _Engine:
         B, Hp, Wp, _ = out.shape
         return self.share_stage_us.get((Hp - 2) * (Wp - 2), self._share_split[1]) * (B / 512.0)
 
-    def _share_plan(self, conv, x, elements, tensors, us=None):
-        """(weight-gradient descriptor, its CU budget, CUs for the elementwise pass of `tensors` tensors of `elements`
-        bf16 that runs beside it)."""
-        gbps, us0, lo, hi = self._cu_share
-        B, Hp, Wp, _ = x.shape
-        desc = conv.plan(B, Hp - 2, Wp - 2)[3]
-        budget, n = ops.plan_cu_share(desc, elements, tensors, gbps, us0 if us is None else us, lo, hi)
-        return desc, budget, n
-
-    def _share_pair(self, conv, x, gout, elements, tensors, us=None):
-        """Issue conv's weight gradient on the second stream next to the pass that follows; returns the pass's CUs."""
-        _, budget, n = self._share_plan(conv, x, elements, tensors, us)
-        conv.backward_weight(x, gout, cu_budget=budget)
-        return n
+    def _pair_backward(self, conv, bn, form, g, a, t, ga, gt, share=None, tensors=0, gx_add=None):
+        """Backward of a (conv, preceding BatchNorm) pair: g = dL/d(conv output) -> gt = dL/dt [+ gx_add], where the conv
+        read a = relu(bn(t)) and ga = dL/da is the buffer between the two.  The order of these launches is the
+        cross-stream protocol (weight gradients go to the second stream, see Conv._wgrad); every engine's pairs run here.
+          "split"  data gradient with its plain epilogue; the weight gradient AFTER it, sized for 256 - n CUs; the whole
+                   BatchNorm backward (sums, fold, elementwise pass) on n CUs beside it (needs `share`);
+          "fused"  the data gradient's epilogue also emits bn's backward sums.  Without `share` the weight gradient is
+                   issued first and the elementwise pass runs on all CUs; with it the weight gradient follows the data
+                   gradient with a CU budget and the pass is confined to n CUs;
+          "plain"  weight gradient, data gradient with its plain epilogue, the sums in a pass of their own on all CUs.
+        share: None, or (gbps_per_cu, target_us, min_cus, max_cus) for ops.plan_cu_share, with `tensors` the tensor
+        passes of the confined work over ga's elements."""
+        if form == "plain":
+            conv.backward_weight(a, g)
+            conv.backward_data(g, ga)
+            bn.backward(ga, None, t, gt, relu=True, gx_add=gx_add)   # mask recomputed from t: a not re-read
+            return
+        fused = form == "fused"
+        assert fused or share is not None, "the split form is a CU-sharing form"
+        partials = self.partials(t) if fused else None
+        if fused and share is None:
+            conv.backward_weight(a, g)
+        conv.backward_data(g, ga, bn=bn if fused else None, bn_x=t if fused else None, partials=partials)
+        n = 0
+        if share is not None:
+            B, Hp, Wp, C = ga.shape
+            budget, n = ops.plan_cu_share(conv.plan(B, Hp - 2, Wp - 2)[3], B * (Hp - 2) * (Wp - 2) * C, tensors, *share)
+            conv.backward_weight(a, g, cu_budget=budget)
+        if fused:
+            bn.backward_fused(ga, t, gt, partials, gx_add=gx_add, cus=n)
+        else:
+            bn.backward_cus(ga, t, gt, n, gx_add=gx_add)
 
     def _calibration_unit(self):
         """The unit whose conv2 pair the calibration times (subclasses with CU sharing override)."""
@@ -773,7 +845,9 @@ class _Engine:
         ops.interior(g).normal_(0.0, 1e-3, generator=torch.Generator(device=self.device).manual_seed(0x5eed))
         split, split_us = self._share_split[0], self._split_us(t)
         elements = B * h * w * cout
-        desc, budget, n = self._share_plan(conv, a2, elements, 5 if split else 3, split_us if split else None)
+        gbps, us, lo, hi_cus = self._cu_share
+        desc = conv.plan(B, h, w)[3]
+        budget, n = ops.plan_cu_share(desc, elements, 5 if split else 3, gbps, split_us if split else us, lo, hi_cus)
         main = torch.cuda.current_stream(self.device)
         dw = torch.zeros_like(self.store.g(conv.name))
         dsum = torch.empty(2 * bn.C, device=self.device)
@@ -1462,7 +1536,7 @@ class WRNEngine(_Engine):
             u["seg"] = seg
             if seg and s == 2:
                 a1 = self.s2d_buf(k + ".a1", B, h, w, cin)
-                ops.bn_apply_s2d(x, u["bn1"].mean, u["bn1"].rstd, u["bn1"].gamma, u["bn1"].beta, a1, relu=True)
+                u["bn1"].apply_s2d(x, a1, relu=True)
             else:
                 a1 = self.buf(k + ".a1", B, h, w, cin)
                 u["bn1"].apply(x, a1, relu=True)
@@ -1518,9 +1592,7 @@ class WRNEngine(_Engine):
         h, w = self._hw
         C = _pad32(self.feat_c)
         g = self.buf(f"g_out{C}", B, h, w, C)
-        pb = self.post_bn
-        ops.pool_bn_bwd(gpool, self._x_last, pb.mean, pb.rstd, pb.gamma, pb.beta, self.scratch(C), pb.dsum,
-                        st.g(pb.name + ".weight"), st.g(pb.name + ".bias"), g)
+        self.post_bn.pool_backward(gpool, self._x_last, g)
         form, share = self._backward_form()
         for i, u in self._units_backward(self.units, comm):
             # The buffers a weight gradient of unit i - 1 can still be reading (see _units_backward) are not the ones unit
@@ -1541,11 +1613,12 @@ class WRNEngine(_Engine):
             # the unit's input gradient must not alias its output gradient `g` (nor, see above, the one before that)
             g_in = self.buf(f"g_in{cin}_{hi}_{(i + 1) % 3}{tag}", B, hi, wi, cin)
             u["dbg"] = {"g_out": g, "ga2": ga2, "gt": gt, "ga1": ga1, "g_in": g_in}
-            self._conv2_backward(u, form, share, g, a2, t, ga2, gt)
+            numbers = self._pair_share(form, gt) if share else None
+            self._conv2_backward(u, form, numbers, g, a2, t, ga2, gt)
             if u["seg"]:
                 self._seg_conv1_backward(u, form, g, a1, gt, ga1, g_in)
             else:
-                self._conv1_backward(u, form, share, g, a1, gt, ga1, g_in)
+                self._conv1_backward(u, form, numbers, g, a1, gt, ga1, g_in)
             g, h, w = g_in, hi, wi
         ops.stem_wgrad(self._img, g, st.g("features.init_block.weight"), self.stem_c)
         self._end_backward(comm)
@@ -1568,26 +1641,18 @@ class WRNEngine(_Engine):
             return "fused", share
         return "plain", False
 
+    def _pair_share(self, form, gt):
+        """ops.plan_cu_share's numbers for the pairs of one unit: the split form's time budget is its stage's."""
+        if form != "split":
+            return self._cu_share
+        gbps, _, lo, hi = self._cu_share
+        return gbps, self._split_us(gt), lo, hi
+
     def _conv2_backward(self, u, form, share, g, a2, t, ga2, gt):
         """conv2 and bn2 of one unit: dL/d(out) `g` -> dL/dt `gt`."""
-        conv, bn = u["conv2"], u["bn2"]
-        B, Hp, Wp, C = gt.shape
-        elements = B * (Hp - 2) * (Wp - 2) * C
-        if form == "split":
-            conv.backward_data(g, ga2)
-            n2 = self._share_pair(conv, a2, g, elements, self.share_bn2_tensors, self._split_us(gt))
-            bn.backward_cus(ga2, t, gt, n2)
-        elif form == "fused":   # the dgrad epilogue also produces bn2's backward sums (ga2 is not re-read for them)
-            if not share:
-                conv.backward_weight(a2, g)
-            conv.backward_data(g, ga2, bn=bn, bn_x=t, partials=self.partials(t))
-            n2 = self._share_pair(conv, a2, g, elements, 3) if share else 0
-            bn.backward_fused(ga2, t, gt, self.partials(t), cus=n2)
-        else:
-            conv.backward_weight(a2, g)
-            conv.backward_data(g, ga2)
-            bn.backward(ga2, None, t, gt, relu=True)   # mask recomputed from t: a2 not re-read
-        if share and self._share_join:
+        self._pair_backward(u["conv2"], u["bn2"], form, g, a2, t, ga2, gt, share=share,
+                            tensors=self.share_bn2_tensors if form == "split" else 3)
+        if share is not None and self._share_join:
             # The next data gradient is one persistent block per CU with a fixed share of the tiles: blocks that found
             # their CU still held by the weight gradient would start late and finish late, and the delay would push the
             # next weight gradient under the next data gradient, and so on (measured: 19.1 -> 26 ms per step with the
@@ -1599,26 +1664,15 @@ class WRNEngine(_Engine):
         """conv1, the shortcut conv (if any) and bn1 of a unit on the dense kernels: dL/dt `gt` and dL/d(out) `g` ->
         dL/d(x_in) `g_in`.  The shared and fused forms are for units without a shortcut conv."""
         conv, bn, x_in = u["conv1"], u["bn1"], u["x_in"]
-        B, Hp, Wp, C = ga1.shape
-        if u["idconv"] is None and form == "split":
-            conv.backward_data(gt, ga1)
-            n1 = self._share_pair(conv, a1, gt, B * (Hp - 2) * (Wp - 2) * C, self.share_bn1_tensors, self._split_us(gt))
-            bn.backward_cus(ga1, x_in, g_in, n1, gx_add=g)
-        elif u["idconv"] is None and form == "fused":
-            if not share:
-                conv.backward_weight(a1, gt)
-            conv.backward_data(gt, ga1, bn=bn, bn_x=x_in, partials=self.partials(x_in))
-            n1 = self._share_pair(conv, a1, gt, B * (Hp - 2) * (Wp - 2) * C, 4) if share else 0
-            bn.backward_fused(ga1, x_in, g_in, self.partials(x_in), gx_add=g, cus=n1)
-        else:
-            conv.backward_weight(a1, gt)
-            conv.backward_data(gt, ga1)
-            if u["idconv"] is not None:
-                u["idconv"].backward_weight(a1, g)
-                u["idconv"].backward_data(g, ga1, accumulate=True)
-                bn.backward(ga1, None, x_in, g_in, relu=True)
-            else:
-                bn.backward(ga1, None, x_in, g_in, relu=True, gx_add=g)
+        if u["idconv"] is None:
+            self._pair_backward(conv, bn, form, gt, a1, x_in, ga1, g_in, share=share,
+                                tensors=self.share_bn1_tensors if form == "split" else 4, gx_add=g)
+            return
+        conv.backward_weight(a1, gt)
+        conv.backward_data(gt, ga1)
+        u["idconv"].backward_weight(a1, g)
+        u["idconv"].backward_data(g, ga1, accumulate=True)
+        bn.backward(ga1, None, x_in, g_in, relu=True)
 
     def _seg_conv1_backward(self, u, form, g, a1, gt, ga1, g_in):
         """conv1, shortcut and bn1 of a slice-list unit: the two data gradients in one launch (strided: the four parity
@@ -1864,8 +1918,11 @@ class ResNetEngine(_Engine):
         fused = self.fuse_bn1_bwd and self.act_dtype == torch.bfloat16
         share = (fused and self.res_share is not None and (two_streams or self.debug_share_serial)
                  and ops.cu_topology_is_mi355x(self.device))
+        form = "fused" if fused else "plain"
+        numbers = None
         if share:
             gbps, us, lo, hi_cus = self.res_share
+            numbers = (gbps, us * B / 128.0, lo, hi_cus)
         for i, blk in self._units_backward(self.blocks, comm):
             # the buffers a weight gradient reads (every gt / gts) alternate between consecutive blocks, and so does
             # the block's input gradient: the block in flight never overwrites what the previous one's may be reading
@@ -1889,20 +1946,8 @@ class ResNetEngine(_Engine):
                 t, a = self.buf(tk, B, hh, ww, c), self.buf(ak, B, hh, ww, c)
                 ga = self.buf(gak + tag, B, hh, ww, c)
                 gt_prev = self.buf(f"{gtk}{par}{tag}", B, hh, ww, c)
-                if share and fusable:
-                    conv.backward_data(gt, ga, bn=bn, bn_x=t, partials=self.partials(t))
-                    budget, n1 = ops.plan_cu_share(conv.plan(B, hh, ww)[3], B * hh * ww * c, 3, gbps, us * B / 128.0, lo,
-                                                   hi_cus)
-                    conv.backward_weight(a, gt, cu_budget=budget)
-                    bn.backward_fused(ga, t, gt_prev, self.partials(t), cus=n1)
-                elif fused and fusable:
-                    conv.backward_weight(a, gt)
-                    conv.backward_data(gt, ga, bn=bn, bn_x=t, partials=self.partials(t))
-                    bn.backward_fused(ga, t, gt_prev, self.partials(t))
-                else:
-                    conv.backward_weight(a, gt)
-                    conv.backward_data(gt, ga)
-                    bn.backward(ga, None, t, gt_prev, relu=True)
+                self._pair_backward(conv, bn, form if fusable else "plain", gt, a, t, ga, gt_prev, share=numbers,
+                                    tensors=3)
                 gt = gt_prev
             conv1 = blk["conv1"]
             conv1.backward_weight(x_in, gt)

@@ -52,7 +52,13 @@ class DepthwiseConv:
     def forward(self, x, y, bn_scratch=None):
         ops.dwconv_fwd(x, self.store.p(self.name), y, self.k, self.stride, bn_scratch)
 
-    def backward_data(self, gy, gx):
+    def backward_data(self, gy, gx, bn=None, bn_x=None):
+        """bn/bn_x: `gx` is dL/d(swish(bn(bn_x))) -- also leave that BatchNorm's backward sums in its owner's slots
+        (stride 1 only; follow with bn.act_backward_apply)."""
+        if bn is not None:
+            assert self.stride == 1
+            bn.dwconv_backward_data(gy, self.store.p(self.name), gx, self.k, bn_x)
+            return
         ops.dwconv_bwd_data(gy, self.store.p(self.name), gx, self.k, self.stride)
 
     def backward_weight(self, x, gy, also):
@@ -251,8 +257,7 @@ class EfficientNetEngine(_Engine):
         x = self.buf("a0", B, h, w, c0)
         ops.stem_conv(img, self.store.p("features.init_block.conv.conv.weight"), t0, self.stem_c, stride=2)
         self.bn0.stats(t0, training)
-        bn = self.bn0
-        ops.bn_act_apply(t0, bn.mean, bn.rstd, bn.gamma, bn.beta, x, act=ACT)
+        self.bn0.act_apply(t0, x, act=ACT)
         self._sd_rows = None
         if training and self.stochastic_depth_prob > 0.0:
             # ONE launch draws every unit's per-image factors; a unit's row rides in the residual add it already makes
@@ -272,9 +277,8 @@ class EfficientNetEngine(_Engine):
                     u["conv1"].forward_affine(x, e_act, u["bn1"], act=2)
                 else:
                     u["conv1"].forward(x, e_raw, bn_scratch=self.partials(e_raw) if fuse else None)
-                    bn = u["bn1"]
-                    bn.stats(e_raw, training, fused=fuse)
-                    ops.bn_act_apply(e_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, e_act, act=ACT)
+                    u["bn1"].stats(e_raw, training, fused=fuse)
+                    u["bn1"].act_apply(e_raw, e_act, act=ACT)
             else:
                 e_act = x
             d_raw = self.buf(k + ".d_raw", B, ho, wo, mid)
@@ -282,17 +286,15 @@ class EfficientNetEngine(_Engine):
             bn = u["bn2"]
             if fuse:   # the depthwise kernel leaves sum / sum-of-squares in the BN slots: fold only
                 u["dw"].forward(e_act, d_raw, bn_scratch=self.scratch(bn.C))
-                ops.bn_stats(d_raw, self.scratch(bn.C), bn.mean, bn.rstd, bn.running_mean, bn.running_var,
-                             slots_filled=True)
-                bn.num_batches_tracked += 1
+                bn.stats(d_raw, training, slots_filled=True)
             else:
                 u["dw"].forward(e_act, d_raw)
                 bn.stats(d_raw, training)
             pooled, gate = self._vec(k + ".pooled", B, mid), self._vec(k + ".gate", B, mid)
             pre1 = self._vec(k + ".pre1", B, u["se"].mid)
-            ops.bn_act_pool(d_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, pooled, act=ACT)
+            bn.act_pool(d_raw, pooled, act=ACT)
             u["se"].forward(pooled, pre1, gate)
-            ops.bn_act_apply(d_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, d_se, act=ACT, gate=gate)
+            bn.act_apply(d_raw, d_se, act=ACT, gate=gate)
             p_raw = self.buf(k + ".p_raw", B, ho, wo, cout)
             out = self.buf(k + ".out", B, ho, wo, cout)
             if not training and self.fuse_eval:       # project conv + BN (+ skip) in one launch
@@ -302,20 +304,17 @@ class EfficientNetEngine(_Engine):
                 bn = u["bn3"]
                 bn.stats(p_raw, training, fused=fuse)
                 if u["residual"] and self._sd_rows is not None:
-                    ops.bn_act_apply(p_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, out, act=ops.ACT_NONE, residual=x,
-                                     row_scale=self._sd_rows[u["index"]])
+                    bn.act_apply(p_raw, out, act=ops.ACT_NONE, residual=x, row_scale=self._sd_rows[u["index"]])
                 else:
-                    ops.bn_act_apply(p_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, out, act=ops.ACT_NONE,
-                                     residual=x if u["residual"] else None)
+                    bn.act_apply(p_raw, out, act=ops.ACT_NONE, residual=x if u["residual"] else None)
             u["x_in"], u["hw_in"] = x, (h, w)
             x, h, w = out, ho, wo
         self._x_last, self._hw = x, (h, w)
         f_raw = self.buf("f_raw", B, h, w, self.feat_c)
         self.final_conv.forward(x, f_raw, bn_scratch=self.partials(f_raw) if fuse else None)
-        bn = self.final_bn
-        bn.stats(f_raw, training, fused=fuse)
+        self.final_bn.stats(f_raw, training, fused=fuse)
         self._pooled = self._vec("pooled", B, self.feat_c)
-        ops.bn_act_pool(f_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self._pooled, act=ACT)
+        self.final_bn.act_pool(f_raw, self._pooled, act=ACT)
         feat = self._pooled
         self._dropped = training and self.dropout_rate > 0.0
         if self._dropped:
@@ -347,9 +346,7 @@ class EfficientNetEngine(_Engine):
         h, w = self._hw
         f_raw = self.buf("f_raw", B, h, w, self.feat_c)
         gf = self.buf("g_f", B, h, w, self.feat_c)
-        bn = self.final_bn
-        ops.bn_act_bwd(None, f_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
-                       st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), gf, act=ACT, gpool=gpooled)
+        self.final_bn.act_backward(None, f_raw, gf, act=ACT, gpool=gpooled)
         self.final_conv.backward_weight(self._x_last, gf)
         g = self.buf(f"g_{self._x_last.shape[3]}_{h}", B, h, w, self._x_last.shape[3])
         self.final_conv.backward_data(gf, g)
@@ -371,12 +368,9 @@ class EfficientNetEngine(_Engine):
             bn = u["bn3"]
             if u["residual"] and self._sd_rows is not None:
                 # out = x_in + r[b] * bn3(p_raw): the branch gradient is g * r[b]; g itself stays the skip gradient
-                ops.bn_act_bwd(g, p_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
-                               st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), gp, act=ops.ACT_NONE,
-                               row_scale=self._sd_rows[u["index"]])
+                bn.act_backward(g, p_raw, gp, act=ops.ACT_NONE, row_scale=self._sd_rows[u["index"]])
             else:
-                ops.bn_act_bwd(g, p_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
-                               st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), gp, act=ops.ACT_NONE)
+                bn.act_backward(g, p_raw, gp, act=ops.ACT_NONE)
             u["conv3"].backward_weight(d_se, gp)
             u["conv3"].backward_data(gp, gd)
             # squeeze-and-excitation + BatchNorm/swish of the depthwise output (gd rewritten in place)
@@ -391,23 +385,21 @@ class EfficientNetEngine(_Engine):
                 if id(sums) in self._se_sums_dirty:   # a backward that stopped between the two calls (an exception, an
                     sums.zero_()                      # interrupt) left its sums behind: never accumulate on top of them
                 self._se_sums_dirty.add(id(sums))
-                ops.bn_act_se_sums(gd, d_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, sums, act=ACT)
+                bn.act_se_sums(gd, d_raw, sums, act=ACT)
                 dgate = sums[0]
             else:
                 dgate = self._vec(f"dgate{tag}", B, mid)
-                ops.bn_act_pool(d_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, dgate, act=ACT, mul=gd, scale=1.0)
+                bn.act_pool(d_raw, dgate, act=ACT, mul=gd, scale=1.0)
             # the SE block's parameter gradients go behind the depthwise weight gradient on the second stream (their
             # workspaces alternate between consecutive units like the gradient buffers)
             se_params = u["se"].backward(dgate, gate, self._vec(k + ".pre1", B, u["se"].mid),
                                          self._vec(k + ".pooled", B, mid), self._vec(f"dpre2_{par}{tag}", B, mid),
                                          self._vec(f"dpre1_{par}{tag}", B, u["se"].mid), gpool)
             if one_pass:
-                ops.bn_act_se_bwd_apply(gd, gate, gpool, sums, d_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, bn.dsum,
-                                        st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), gd, act=ACT)
+                bn.act_se_backward_apply(gd, gate, gpool, sums, d_raw, gd, act=ACT)
                 self._se_sums_dirty.discard(id(sums))
             else:
-                ops.bn_act_bwd(gd, d_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
-                               st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), gd, act=ACT, gate=gate, gpool=gpool)
+                bn.act_backward(gd, d_raw, gd, act=ACT, gate=gate, gpool=gpool)
             x_in = u["x_in"]
             if u["conv1"] is not None:
                 e_raw = self.buf(k + ".e_raw", B, hi, wi, mid)
@@ -418,14 +410,11 @@ class EfficientNetEngine(_Engine):
                 if u["dw"].stride == 1:
                     # the depthwise data gradient's epilogue leaves bn1's backward sums in the slots: no reduction
                     # pass over ge and e_raw (5.5 % of a step), e_raw is read once there
-                    ops.dwconv_bwd_data_bn(gd, st.p(u["dw"].name), ge, u["dw"].k, e_raw, bn.mean, bn.rstd, bn.gamma,
-                                           bn.beta, self.scratch(bn.C))
-                    ops.bn_act_bwd_apply(ge, e_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
-                                         st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), ge, act=ACT)
+                    u["dw"].backward_data(gd, ge, bn=bn, bn_x=e_raw)
+                    bn.act_backward_apply(ge, e_raw, ge, act=ACT)
                 else:
                     u["dw"].backward_data(gd, ge)
-                    ops.bn_act_bwd(ge, e_raw, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
-                                   st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), ge, act=ACT)
+                    bn.act_backward(ge, e_raw, ge, act=ACT)
                 u["conv1"].backward_weight(x_in, ge)
                 if u["residual"]:
                     # out = bn3(...) + x_in: the unit-output gradient g is also the skip gradient ->
@@ -441,9 +430,7 @@ class EfficientNetEngine(_Engine):
                 u["dw"].backward_data(gd, g_in)
             u["dbg"] = {"g_out": g, "g_in": g_in, "gp": gp, "gd": gd}
             g, h, w = g_in, hi, wi
-        bn = self.bn0
         t0 = self.buf("t0", B, h, w, _pad32(self.stem_c))
-        ops.bn_act_bwd(g, t0, bn.mean, bn.rstd, bn.gamma, bn.beta, self.scratch(bn.C), bn.dsum,
-                       st.g(bn.name + ".weight"), st.g(bn.name + ".bias"), g, act=ACT)
+        self.bn0.act_backward(g, t0, g, act=ACT)
         ops.stem_wgrad(self._img, g, st.g("features.init_block.conv.conv.weight"), self.stem_c, stride=2)
         self._end_backward(comm)
