@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 import nbdt_oracle as O
+from _tree_shapes import caterpillar as _caterpillar
 from conftest import GOLDEN_CASES
 
 pytestmark = pytest.mark.gpu
@@ -122,24 +123,6 @@ def test_full_size_vs_oracle(B, ds, h, pkg_dir):
     assert abs(hl.item() - hlo) <= 1e-5 * abs(hlo)
     np.testing.assert_allclose(hgz.cpu().numpy(), hdzo, atol=1e-6, rtol=1e-5)
     assert np.abs(hgz.cpu().numpy().sum(1)).max() < 1e-6
-
-
-def _caterpillar(tmp_path, C):
-    """Every inner node keeps one leaf and hands the rest down: depth C-1, sum of leaf depths ~ C*C/2."""
-    import json
-    leaves = [f"f{i:08d}" for i in range(C)]
-    inner = [f"n{i:08d}" for i in range(C - 1)]
-    links = []
-    for i in range(C - 1):
-        links.append({"source": inner[i], "target": leaves[i]})
-        links.append({"source": inner[i], "target": inner[i + 1] if i + 1 < C - 1 else leaves[C - 1]})
-    pg, pw = str(tmp_path / f"cat{C}.json"), str(tmp_path / f"cat{C}.txt")
-    with open(pg, "w") as f:
-        json.dump({"directed": True, "multigraph": False, "graph": {},
-                   "nodes": [{"id": w} for w in inner + leaves], "links": links}, f)
-    with open(pw, "w") as f:
-        f.write("\n".join(leaves) + "\n")
-    return pg, pw, leaves
 
 
 @pytest.mark.parametrize("C", [640, 900])
