@@ -1330,6 +1330,39 @@ int nbdt_resized_crop_policy_batch_sharded(const void* src, int32_t src_dtype, c
                                            void* stage_a, void* stage_b, float* out, int64_t* labels_out, int32_t* params_out,
                                            int32_t* chain_out, int32_t* erase_out, void* stream);
 
+/* ------------------------------------------------------------------ padded strided convolutions (nbdt_version() >= 126)
+ * The depthwise and stem convolutions for ANY extent and a low-side padding, per axis:
+ *   Ho = ceil(H / stride);  output o reads inputs o * stride + r - pad_lo for r in [0, k);  reads outside [0, H) are zero.
+ * pad_lo = k / 2 is PyTorch's symmetric padding=k/2 (for which the functions above are the special case "the stride
+ * divides the extent"); TensorFlow's "SAME" padding is pad_lo = max((Ho - 1) * stride + k - H, 0) / 2, which differs from
+ * it only at stride 2 on an even extent: 0 at k = 3, 1 at k = 5.  pad_top / pad_left are the two axes' pad_lo.
+ * Tensors, weights, bn_scratch and deterministic mode as in nbdt_dwconv_fwd / _bwd_data / _bwd_weight and nbdt_stem_conv /
+ * _wgrad, with y / gy of size [B][Ho + 2][Wo + 2][C]; with pad_lo = k / 2 on even extents the results are theirs bit for
+ * bit.  NBDT_EINVAL before any device work: pad_top or pad_left outside [0, k / 2], k not 3 or 5 (the stem is k = 3),
+ * stride not 1 or 2, stride 1 with a padding other than k / 2, non-positive extents. */
+int nbdt_dwconv_fwd_pad(const void* x, const float* w, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
+                        int32_t stride, int32_t pad_top, int32_t pad_left, void* y, float* bn_scratch, void* stream);
+/* H, W: the INPUT-sized gradient being written */
+int nbdt_dwconv_bwd_data_pad(const void* gy, const float* w, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
+                             int32_t stride, int32_t pad_top, int32_t pad_left, void* gx, void* stream);
+int nbdt_dwconv_bwd_weight_pad(const void* x, const void* gy, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
+                               int32_t stride, int32_t pad_top, int32_t pad_left, float* dw, void* stream);
+int nbdt_stem_conv_pad(const float* img, const float* w, int32_t B, int32_t H, int32_t W, int32_t cout_real, int32_t cpad,
+                       int32_t stride, int32_t pad_top, int32_t pad_left, void* out, void* stream);
+int nbdt_stem_wgrad_pad(const float* img, const void* gy, int32_t B, int32_t H, int32_t W, int32_t cout_real, int32_t cpad,
+                        int32_t stride, int32_t pad_top, int32_t pad_left, float* dw, void* stream);
+/* their fp32 twins (reference mode, see nbdt_ref_dwconv_fwd) */
+int nbdt_ref_dwconv_fwd_pad(const float* x, const float* w, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
+                            int32_t stride, int32_t pad_top, int32_t pad_left, float* y, void* stream);
+int nbdt_ref_dwconv_bwd_data_pad(const float* gy, const float* w, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
+                                 int32_t stride, int32_t pad_top, int32_t pad_left, float* gx, void* stream);
+int nbdt_ref_dwconv_bwd_weight_pad(const float* x, const float* gy, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
+                                   int32_t stride, int32_t pad_top, int32_t pad_left, float* dw, void* stream);
+int nbdt_ref_stem_conv_pad(const float* img, const float* w, int32_t B, int32_t H, int32_t W, int32_t cout_real,
+                           int32_t cpad, int32_t stride, int32_t pad_top, int32_t pad_left, float* out, void* stream);
+int nbdt_ref_stem_wgrad_pad(const float* img, const float* gy, int32_t B, int32_t H, int32_t W, int32_t cout_real,
+                            int32_t cpad, int32_t stride, int32_t pad_top, int32_t pad_left, float* dw, void* stream);
+
 /* ------------------------------------------------------------------ measurement probe (not on the product path) */
 /* A register-only stream of independent v_mfma_f32_32x32x16_bf16 on `blocks` CUs (one 512-thread block each, two waves
  * per SIMD): every wave issues iters x 16 of them (x 32768 flop).  bench.py times the launch for `roofline.mfma_stream`

@@ -497,7 +497,7 @@ extern "C" int nbdt_bn_stats(const void* x, int32_t B, int32_t H, int32_t W, int
                              float* save_rstd, void* stream) {
   NBDT_REQUIRE(scratch && save_mean && save_rstd, "null argument");
   NBDT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "running stats must be both set or both NULL");
-  int rc = check_shape(B, H, W, C);
+  int rc = x ? check_shape(B, H, W, C) : check_shape_wide(B, H, W, C);     // (the fold alone takes any channel count)
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const PadGeom g = make_geom(B, H, W, C);
@@ -631,7 +631,7 @@ extern "C" int nbdt_bn_finalize(int32_t B, int32_t H, int32_t W, int32_t C, floa
                                 float* save_rstd, void* stream) {
   NBDT_REQUIRE(partials && save_mean && save_rstd, "null argument");
   NBDT_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "running stats must be both set or both NULL");
-  int rc = check_shape(B, H, W, C);
+  int rc = check_shape_wide(B, H, W, C);
   if (rc) return rc;
   const long long npix = (long long)B * H * W;
   const int rows = (int)((npix + 255) / 256);   // = the pixel tiles of nbdt_conv_igemm_stats

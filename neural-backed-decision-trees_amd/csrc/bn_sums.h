@@ -19,6 +19,15 @@ int check_shape(int B, int H, int W, int C) {
   return NBDT_OK;
 }
 
+// the same without the 256-chunk limit: for entry points whose kernels index channels by a grid dimension, or that launch
+// the streaming kernels once per channel range (effnet.hip: chan_slices)
+int check_shape_wide(int B, int H, int W, int C) {
+  NBDT_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "empty tensor");
+  NBDT_REQUIRE(C % 8 == 0, "C must be a multiple of 8");
+  NBDT_REQUIRE((long long)B * (H + 2) * (W + 2) * C < (1ll << 31), "tensor too large for 32-bit offsets");
+  return NBDT_OK;
+}
+
 // fold NQ*8 per-thread partials over the PY pixel rows of the block and hand every sum to `sink(q, channel, value)`.
 // lds: [PY][c8][NQ*8] floats.  Output o = q * (c8*8) + channel goes to thread o % (c8*PY): CONSECUTIVE THREADS HOLD
 // CONSECUTIVE CHANNELS, so the sinks' global atomics are one contiguous 256-byte run per wave (thread (cx, py) folding

@@ -1,4 +1,4 @@
-// MBConv building blocks of EfficientNet-B0 on gfx950 (pytorchcv `efficientnet_b0`
+// MBConv building blocks of EfficientNet-B0 .. B7 on gfx950 (pytorchcv `efficientnet_b0` .. `efficientnet_b7b`
 // behind reference nbdt/models/__init__.py:3): depthwise 3x3/5x5 convolution, BatchNorm + swish,
 // squeeze-and-excitation, dropout.  The 1x1 expand/project convolutions are the implicit-GEMM kernels
 // of conv_dma.hip; everything here is an HBM-bound streaming pass over padded NHWC bf16 tensors
@@ -26,14 +26,15 @@ struct MbGeom {
   int c8, PY, threads, slices;
 };
 
-MbGeom mb_geom(int B, int H, int W, int C, int ppt) {
+// cs: the channels of THIS launch (a range of the tensor's C, see chan_slices); 0 = all of them
+MbGeom mb_geom(int B, int H, int W, int C, int ppt, int cs = 0) {
   MbGeom g;
   g.B = B; g.H = H; g.W = W; g.C = C;
   g.hw = H * W;
   g.row = (W + 2) * C;
   g.img = (H + 2) * g.row;
   g.div_w = make_fastdiv((unsigned)W);
-  g.c8 = C / 8;
+  g.c8 = (cs ? cs : C) / 8;
   g.PY = kThreads / g.c8;
   if (g.PY < 1) g.PY = 1;
   if (g.PY > g.hw) g.PY = g.hw;
@@ -42,6 +43,27 @@ MbGeom mb_geom(int B, int H, int W, int C, int ppt) {
   if (g.slices < 1) g.slices = 1;
   return g;
 }
+
+// Channel ranges.  A block of the streaming kernels below holds ALL 8-channel chunks of its launch along its threads, so a
+// launch takes at most 256 chunks: 2048 channels (B0's widest tensor has 1152, B1's 1920).  A wider tensor -- B2..B7
+// expand to 2112..3840 channels -- goes as ceil(chunks / 256) launches over near-equal channel ranges: the kernel gets the
+// tensor's strides (g.C), its range's chunk count (g.c8), and every channel-indexed pointer advanced to the range
+// (tensors, [B][C] vectors, [slot][q][C] sums and [tap][C] weights all have the channel fastest).  Up to 2048 channels
+// this is the one launch it always was.
+struct ChanSlices {
+  int n, per;      // launches, channels of each (the last may be shorter)
+};
+inline ChanSlices chan_slices(int C) {
+  const int c8 = C / 8, n = (c8 + 255) / 256;
+  return ChanSlices{n, (c8 + n - 1) / n * 8};
+}
+template <typename T>
+inline T* at(T* p, int c0) { return p ? p + c0 : p; }
+inline const bf16_t* at16(const void* p, int c0) { return p ? (const bf16_t*)p + c0 : nullptr; }
+inline bf16_t* at16(void* p, int c0) { return p ? (bf16_t*)p + c0 : nullptr; }
+#define NBDT_FOR_SLICES(C)                                                                 \
+  for (int c0 = 0, cs_per = chan_slices(C).per, cs = cs_per < (C) ? cs_per : (C); c0 < (C); \
+       c0 += cs_per, cs = (C) - c0 < cs_per ? (C) - c0 : cs_per)
 
 __device__ __forceinline__ int pix_off(const MbGeom& g, int b, int p, int cx) {
   const int h = (int)fdiv((unsigned)p, g.div_w);
@@ -360,6 +382,7 @@ struct DwGeom {
   MbGeom out;            // geometry of the OUTPUT tensor (Ho, Wo)
   int Hi, Wi, rowi, imgi;
   int k, stride, pad;
+  int pad_t, pad_l;       // low-side padding per axis (k / 2, or TF "SAME": see dw_pad_ok)
 };
 
 
@@ -376,7 +399,9 @@ struct DwBn {
   const bf16_t* x;     // the BatchNorm's input (same geometry as this launch's output)
   const float *mean, *rstd, *gamma, *beta;
 };
-template <int K, int S, int TW, bool FLIP, int STATS>
+// RT: the low-side padding is a run-time value (d.pad_t, d.pad_l in [0, K/2]) -- it only moves the window's origin, the
+// tap index stays static; RT = false is the symmetric K/2 of every stride-1 launch, generated as before.
+template <int K, int S, int TW, bool FLIP, int STATS, bool RT = false>
 __global__ __launch_bounds__(kThreads) void dw_row_kernel(const bf16_t* __restrict__ x,
                                                           const float* __restrict__ w, DwGeom d, int nseg,
                                                           int PY, bf16_t* __restrict__ y,
@@ -384,6 +409,7 @@ __global__ __launch_bounds__(kThreads) void dw_row_kernel(const bf16_t* __restri
   extern __shared__ float lds[];
   const MbGeom& g = d.out;
   constexpr int PAD = K / 2, SPAN = TW * S + K - S;
+  const int pad_t = RT ? d.pad_t : PAD, pad_l = RT ? d.pad_l : PAD;
   const unsigned lb = xcd_contiguous(blockIdx.x + blockIdx.y * gridDim.x, gridDim.x * gridDim.y);   // (image, row block)
   const int cx = threadIdx.x % g.c8, py = threadIdx.x / g.c8, b = (int)(lb / gridDim.x);
   int item = (int)(lb % gridDim.x) * PY + py;
@@ -399,7 +425,7 @@ __global__ __launch_bounds__(kThreads) void dw_row_kernel(const bf16_t* __restri
     for (int i = 0; i < 8; ++i) acc[t][i] = 0.f;
 #pragma unroll
   for (int r = 0; r < K; ++r) {
-    const int hi = ho * S + r - PAD;
+    const int hi = ho * S + r - pad_t;
     if (hi < -1 || hi > d.Hi) continue;                  // outside even the zero border
     float wr[K][8];
 #pragma unroll
@@ -413,7 +439,7 @@ __global__ __launch_bounds__(kThreads) void dw_row_kernel(const bf16_t* __restri
     const bf16_t* xrow = x + (size_t)b * d.imgi + (hi + 1) * d.rowi + g.C + cx * 8;   // + wi * C
 #pragma unroll
     for (int j = 0; j < SPAN; ++j) {
-      const int wi = wo0 * S - PAD + j;
+      const int wi = wo0 * S - pad_l + j;
       if (wi < -1 || wi > d.Wi) continue;
       float f[8];
       unpack8(*(const u32x4_t*)(xrow + wi * g.C), f);
@@ -472,43 +498,54 @@ __global__ __launch_bounds__(kThreads) void dw_row_kernel(const bf16_t* __restri
   }
 }
 
-template <int K, int S, bool FLIP>
+template <int K, int S, bool FLIP, bool RT = false>
 static int launch_dw_row(const void* x, const float* w, const DwGeom& d, int B, void* y, float* stats_out,
                          hipStream_t st, const DwBn* bn = nullptr) {
-  const int Wo = d.out.W, Ho = d.out.H;
+  const int Wo = d.out.W, Ho = d.out.H, C = d.out.C;
   const int tw = (Wo % 7 == 0) ? 7 : (Wo >= 8 ? 8 : 4);
   const int nseg = (Wo + tw - 1) / tw;
-  int PY = kThreads / d.out.c8;
-  if (PY < 1) PY = 1;
-  if (PY > Ho * nseg) PY = Ho * nseg;
-  const dim3 grid((Ho * nseg + PY - 1) / PY, B), blk(d.out.c8 * PY);
+  auto rows_per_block = [&](int c8) {
+    int PY = kThreads / c8;
+    if (PY < 1) PY = 1;
+    if (PY > Ho * nseg) PY = Ho * nseg;
+    return PY;
+  };
   SlotTarget tgt{stats_out, kSlots - 1, false};
-  const int nblk = (int)(grid.x * grid.y);
+  const int PY0 = rows_per_block(chan_slices(C).per / 8);      // the first channel range: no later one has more blocks
+  const int nblk = (Ho * nseg + PY0 - 1) / PY0 * B;
   if (stats_out) {
-    const int rc = slot_target(st, stats_out, nblk, 2 * (size_t)d.out.C, &tgt);
+    const int rc = slot_target(st, stats_out, nblk, 2 * (size_t)C, &tgt);
     if (rc) return rc;
   }
-  float* const stats = tgt.ptr;
   const unsigned slot_mask = tgt.mask;
-  const size_t shmem = stats ? (size_t)d.out.c8 * PY * 16 * sizeof(float) : 0;
 #define NBDT_GO(TW)                                                                                              \
   do {                                                                                                           \
-    if (stats && bn) hipLaunchKernelGGL((dw_row_kernel<K, S, TW, FLIP, 2>), grid, blk, shmem, st, (const bf16_t*)x, w, d, nseg, PY, (bf16_t*)y, stats, slot_mask, *bn); \
-    else if (stats) hipLaunchKernelGGL((dw_row_kernel<K, S, TW, FLIP, 1>), grid, blk, shmem, st, (const bf16_t*)x, w, d, nseg, PY, (bf16_t*)y, stats, slot_mask, DwBn{}); \
-    else hipLaunchKernelGGL((dw_row_kernel<K, S, TW, FLIP, 0>), grid, blk, 0, st, (const bf16_t*)x, w, d, nseg, PY, (bf16_t*)y, stats, slot_mask, DwBn{}); \
+    if (stats && bn) hipLaunchKernelGGL((dw_row_kernel<K, S, TW, FLIP, 2, RT>), grid, blk, shmem, st, at16(x, c0), w + c0, ds, nseg, PY, at16(y, c0), stats, slot_mask, bns); \
+    else if (stats) hipLaunchKernelGGL((dw_row_kernel<K, S, TW, FLIP, 1, RT>), grid, blk, shmem, st, at16(x, c0), w + c0, ds, nseg, PY, at16(y, c0), stats, slot_mask, DwBn{}); \
+    else hipLaunchKernelGGL((dw_row_kernel<K, S, TW, FLIP, 0, RT>), grid, blk, 0, st, at16(x, c0), w + c0, ds, nseg, PY, at16(y, c0), stats, slot_mask, DwBn{}); \
   } while (0)
-  if (tw == 7) NBDT_GO(7); else if (tw == 8) NBDT_GO(8); else NBDT_GO(4);
+  NBDT_FOR_SLICES(C) {
+    DwGeom ds = d;
+    ds.out = mb_geom(B, Ho, Wo, C, 4, cs);
+    const int PY = rows_per_block(ds.out.c8);
+    const dim3 grid((Ho * nseg + PY - 1) / PY, B), blk(ds.out.c8 * PY);
+    float* const stats = at(tgt.ptr, c0);
+    const size_t shmem = stats ? (size_t)ds.out.c8 * PY * 16 * sizeof(float) : 0;
+    DwBn bns{};
+    if (bn) bns = DwBn{bn->x + c0, bn->mean + c0, bn->rstd + c0, bn->gamma + c0, bn->beta + c0};
+    if (tw == 7) NBDT_GO(7); else if (tw == 8) NBDT_GO(8); else NBDT_GO(4);
+    NBDT_LAUNCH_CHECK();
+  }
 #undef NBDT_GO
-  NBDT_LAUNCH_CHECK();
-  return stats_out ? slot_finish(st, tgt, nblk, 2 * (size_t)d.out.C, stats_out) : NBDT_OK;
+  return stats_out ? slot_finish(st, tgt, nblk, 2 * (size_t)C, stats_out) : NBDT_OK;
 }
 
 // gx[hi][wi] = sum_{r,s : (hi+pad-r) % stride == 0, ...} gy[(hi+pad-r)/stride][(wi+pad-s)/stride] * w[r][s]
 // `in` = geometry of the INPUT-sized gradient being written
 __global__ __launch_bounds__(kThreads) void dw_bwd_data_kernel(const bf16_t* __restrict__ gy,
                                                                const float* __restrict__ w, MbGeom in, int Ho,
-                                                               int Wo, int k, int stride, int pad, int ppt,
-                                                               bf16_t* __restrict__ gx) {
+                                                               int Wo, int k, int stride, int pad_t, int pad_l,
+                                                               int ppt, bf16_t* __restrict__ gx) {
   const unsigned lb = xcd_contiguous(blockIdx.x + blockIdx.y * gridDim.x, gridDim.x * gridDim.y);
   const int cx = threadIdx.x % in.c8, py = threadIdx.x / in.c8, b = (int)(lb / gridDim.x);
   const int rowo = (Wo + 2) * in.C, imgo = (Ho + 2) * rowo;
@@ -522,12 +559,12 @@ __global__ __launch_bounds__(kThreads) void dw_bwd_data_kernel(const bf16_t* __r
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[i] = 0.f;
     for (int r = 0; r < k; ++r) {
-      const int th = hi + pad - r;
+      const int th = hi + pad_t - r;
       if (th < 0 || (stride == 2 && (th & 1))) continue;
       const int ho = stride == 2 ? th >> 1 : th;
       if (ho >= Ho) continue;
       for (int s = 0; s < k; ++s) {
-        const int tw = wi + pad - s;
+        const int tw = wi + pad_l - s;
         if (tw < 0 || (stride == 2 && (tw & 1))) continue;
         const int wo = stride == 2 ? tw >> 1 : tw;
         if (wo >= Wo) continue;
@@ -550,12 +587,19 @@ __global__ __launch_bounds__(kThreads) void dw_bwd_data_kernel(const bf16_t* __r
 // r of the right parity it loads the TW/2 + K/2 + 1 gradient pixels of output row (hi + pad - r)/2 that reach the segment
 // ONCE and feeds each to the outputs it reaches (tap s = t + pad - 2 (wo - wi0/2), static after unrolling).  The gradient
 // tensor's zero border stands in for wo = -1 and wo = Wo.  Same sums in a different order than the gather kernel.
-template <int K, int TW>
+// PL: the low-side padding of the columns, which fixes the taps and so stays a compile-time value (K/2, or one less for
+// "SAME" padding on an even width); RT: the rows' low-side padding comes from pad_top instead of K/2 -- it only selects
+// which kernel rows have the right parity.  Ho, Wo = ceil(H / 2), ceil(W / 2): any input extent.
+template <int K, int TW, int PL = K / 2, bool RT = false>
 __global__ __launch_bounds__(kThreads) void dw_bwd_data_s2_row_kernel(const bf16_t* __restrict__ gy,
                                                                       const float* __restrict__ w, MbGeom in, int Ho,
-                                                                      int Wo, int nseg, int PY, bf16_t* __restrict__ gx) {
-  // gradient columns wo = wi0/2 - 1 + j that reach the segment: tap s = t + PAD + 2 - 2 j in [0, K) for some t in [0, TW)
-  constexpr int PAD = K / 2, J0 = PAD == 1 ? 1 : 0, J1 = (TW + PAD + 1) / 2, SPAN = J1 - J0 + 1;
+                                                                      int Wo, int nseg, int PY, int pad_top,
+                                                                      bf16_t* __restrict__ gx) {
+  // gradient columns wo = wi0/2 - 1 + j that reach the segment: tap s = t + PL + 2 - 2 j in [0, K) for some t in [0, TW)
+  // (PL = K/2: J0 = 1 at K = 3, 0 at K = 5, J1 = (TW + K/2 + 1) / 2)
+  static_assert(PL >= 0 && PL <= K / 2, "low-side padding in [0, K/2]");
+  constexpr int PAD = PL, J0 = 1 - (K - 1 - PL) / 2, J1 = (TW - 1 + PL) / 2 + 1, SPAN = J1 - J0 + 1;
+  const int pad_t = RT ? pad_top : K / 2;
   const unsigned lb = xcd_contiguous(blockIdx.x + blockIdx.y * gridDim.x, gridDim.x * gridDim.y);
   const int cx = threadIdx.x % in.c8, py = threadIdx.x / in.c8, b = (int)(lb / gridDim.x);
   const int item = (int)(lb % gridDim.x) * PY + py;
@@ -570,7 +614,7 @@ __global__ __launch_bounds__(kThreads) void dw_bwd_data_s2_row_kernel(const bf16
     for (int i = 0; i < 8; ++i) acc[t][i] = 0.f;
 #pragma unroll
   for (int r = 0; r < K; ++r) {
-    const int th = hi + PAD - r;
+    const int th = hi + pad_t - r;
     if (th < 0 || (th & 1) || (th >> 1) >= Ho) continue;
     const int ho = th >> 1;
     float wr[K][8];
@@ -617,7 +661,8 @@ __global__ __launch_bounds__(kThreads) void dw_bwd_data_s2_row_kernel(const bf16
 // channel block).  Wide layers used to put ALL their channel chunks into a block -- 1152 channels: 144 threads, ONE
 // row -- so a block folded one row of 18 images before its K*8 atomics per thread, and the chip held 630 waves, each a
 // serial walk over 126 pixels.  With the channels split, 7 rows fold in the block and the batch chunk shrinks instead.
-template <int K, int S, int U>
+// RT: low-side padding from d.pad_t / d.pad_l (see dw_row_kernel) -- the window's origin moves, the walk does not change.
+template <int K, int S, int U, bool RT = false>
 __global__ __launch_bounds__(kThreads) void dw_bwd_weight_kernel(const bf16_t* __restrict__ x,
                                                                  const bf16_t* __restrict__ gy, DwGeom d, int PY,
                                                                  int CB, int cblocks, int bchunk,
@@ -633,14 +678,14 @@ __global__ __launch_bounds__(kThreads) void dw_bwd_weight_kernel(const bf16_t* _
   const int cxl = threadIdx.x % CB, py = threadIdx.x / CB;
   const int cx = cb * CB + cxl;
   const bool live = cx < g.c8;
-  constexpr int PAD = K / 2;
+  const int PAD = RT ? d.pad_l : K / 2;
   float acc[K][8];
 #pragma unroll
   for (int s = 0; s < K; ++s)
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[s][i] = 0.f;
   const int ho = rb * PY + py;
-  const int hi = ho * S + r - PAD;
+  const int hi = ho * S + r - (RT ? d.pad_t : K / 2);
   const int b0 = by * bchunk;
   const int b1 = b0 + bchunk < g.B ? b0 + bchunk : g.B;
   if (live && ho < g.H && hi >= 0 && hi < d.Hi) {
@@ -909,12 +954,10 @@ static int bn_act_apply_impl(const void* x, const float* save_mean, const float*
   NBDT_REQUIRE(x && save_mean && save_rstd && gamma && beta && y, "null argument");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
   NBDT_REQUIRE(!row_scale || (residual && !gate), "row_scale scales the branch of a residual add: it needs a residual and takes no gate");
-  int rc = check_shape(B, H, W, C);
+  int rc = check_shape_wide(B, H, W, C);
   if (rc) return rc;
-  const MbGeom g = mb_geom(B, H, W, C, kPpt);
-  const dim3 grid(g.slices, B), blk(g.threads);
   hipStream_t st = (hipStream_t)stream;
-#define NBDT_APPLY(A, GATE, RES, ROWS) hipLaunchKernelGGL((mb_apply_kernel<A, GATE, RES, ROWS>), grid, blk, 0, st, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, gate, (const bf16_t*)residual, row_scale, g, kPpt, (bf16_t*)y)
+#define NBDT_APPLY(A, GATE, RES, ROWS) hipLaunchKernelGGL((mb_apply_kernel<A, GATE, RES, ROWS>), grid, blk, 0, st, at16(x, c0), at(save_mean, c0), at(save_rstd, c0), at(gamma, c0), at(beta, c0), at(gate, c0), at16(residual, c0), row_scale, g, kPpt, at16(y, c0))
 #define NBDT_GO(A)                                  \
   do {                                              \
     if (row_scale) NBDT_APPLY(A, false, true, true);      \
@@ -923,10 +966,14 @@ static int bn_act_apply_impl(const void* x, const float* save_mean, const float*
     else if (residual) NBDT_APPLY(A, false, true, false); \
     else NBDT_APPLY(A, false, false, false);              \
   } while (0)
-  NBDT_ACT_SWITCH(act, NBDT_GO);
+  NBDT_FOR_SLICES(C) {
+    const MbGeom g = mb_geom(B, H, W, C, kPpt, cs);
+    const dim3 grid(g.slices, B), blk(g.threads);
+    NBDT_ACT_SWITCH(act, NBDT_GO);
+    NBDT_LAUNCH_CHECK();
+  }
 #undef NBDT_GO
 #undef NBDT_APPLY
-  NBDT_LAUNCH_CHECK();
   return NBDT_OK;
 }
 
@@ -949,13 +996,11 @@ extern "C" int nbdt_bn_act_pool(const void* x, const float* save_mean, const flo
                                 int32_t W, int32_t C, float* out, void* stream) {
   NBDT_REQUIRE(x && save_mean && save_rstd && gamma && beta && out, "null argument");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
-  int rc = check_shape(B, H, W, C);
+  int rc = check_shape_wide(B, H, W, C);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   NBDT_HIP_CHECK(hipMemsetAsync(out, 0, (size_t)B * C * sizeof(float), st));
-  const MbGeom g = mb_geom(B, H, W, C, 2 * kPpt);
-  const dim3 grid(g.slices, B), blk(g.threads);
-  const size_t shmem = (size_t)g.threads * 8 * sizeof(float);
+  const MbGeom g = mb_geom(B, H, W, C, 2 * kPpt, chan_slices(C).per);   // the first range: no later one has more pixel slices
   float* target = out;           // deterministic mode: a zeroed copy of `out` per pixel slice, folded in slice order
   long long row_stride = 0;
   const size_t n_out = (size_t)B * C;
@@ -967,12 +1012,17 @@ extern "C" int nbdt_bn_act_pool(const void* x, const float* save_mean, const flo
   }
 #define NBDT_GO(A)                                                                                              \
   do {                                                                                                          \
-    if (mul) hipLaunchKernelGGL((mb_pool_kernel<A, true>), grid, blk, shmem, st, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, (const bf16_t*)mul, g, 2 * kPpt, scale, target, row_stride); \
-    else hipLaunchKernelGGL((mb_pool_kernel<A, false>), grid, blk, shmem, st, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, (const bf16_t*)mul, g, 2 * kPpt, scale, target, row_stride); \
+    if (mul) hipLaunchKernelGGL((mb_pool_kernel<A, true>), grid, blk, shmem, st, at16(x, c0), at(save_mean, c0), at(save_rstd, c0), at(gamma, c0), at(beta, c0), at16(mul, c0), gs, 2 * kPpt, scale, target + c0, row_stride); \
+    else hipLaunchKernelGGL((mb_pool_kernel<A, false>), grid, blk, shmem, st, at16(x, c0), at(save_mean, c0), at(save_rstd, c0), at(gamma, c0), at(beta, c0), at16(mul, c0), gs, 2 * kPpt, scale, target + c0, row_stride); \
   } while (0)
-  NBDT_ACT_SWITCH(act, NBDT_GO);
+  NBDT_FOR_SLICES(C) {
+    const MbGeom gs = mb_geom(B, H, W, C, 2 * kPpt, cs);
+    const dim3 grid(gs.slices, B), blk(gs.threads);
+    const size_t shmem = (size_t)gs.threads * 8 * sizeof(float);
+    NBDT_ACT_SWITCH(act, NBDT_GO);
+    NBDT_LAUNCH_CHECK();
+  }
 #undef NBDT_GO
-  NBDT_LAUNCH_CHECK();
   if (target != out) return det_fold(st, target, g.slices, n_out, out);
   return NBDT_OK;
 }
@@ -988,20 +1038,17 @@ static int bn_act_bwd_impl(const void* gu, const float* gate, const float* gpool
   NBDT_REQUIRE(gu || (gpool && !gate), "need an upstream gradient tensor or a pooled gradient");
   NBDT_REQUIRE(!gate || (gu && gpool), "the SE form needs gu, gate and gpool");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
-  int rc = check_shape(B, H, W, C);
+  int rc = check_shape_wide(B, H, W, C);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   const bool se = gate != nullptr, pool = gu == nullptr;
   NBDT_REQUIRE(!(pool && gx_add), "pooled form has no gx_add");
   if (!sums_ready && !dsum_ready) {      // (sums_ready: the producing kernel -- nbdt_dwconv_bwd_data_bn -- already filled the slots)
-    const MbGeom g = mb_geom(B, H, W, C, 2 * kPpt);
-    const dim3 grid(g.slices, B), blk(g.threads);
-    const size_t shmem = (size_t)g.threads * 16 * sizeof(float);
     SlotTarget tgt;
-    const int nblk = g.slices * B;
+    const int nblk = mb_geom(B, H, W, C, 2 * kPpt, chan_slices(C).per).slices * B;     // (the first range has the most blocks)
     rc = slot_target(st, scratch, nblk, 2 * (size_t)C, &tgt);
     if (rc) return rc;
-#define NBDT_REDUCE(A, SE, POOL, ROWS) hipLaunchKernelGGL((mb_bwd_reduce_kernel<A, SE, POOL, ROWS>), grid, blk, shmem, st, (const bf16_t*)gu, gate, gpool, row_scale, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, g, 2 * kPpt, tgt.ptr, tgt.mask)
+#define NBDT_REDUCE(A, SE, POOL, ROWS) hipLaunchKernelGGL((mb_bwd_reduce_kernel<A, SE, POOL, ROWS>), grid, blk, shmem, st, at16(gu, c0), at(gate, c0), at(gpool, c0), row_scale, at16(x, c0), at(save_mean, c0), at(save_rstd, c0), at(gamma, c0), at(beta, c0), g, 2 * kPpt, tgt.ptr + c0, tgt.mask)
 #define NBDT_GO(A)                                        \
   do {                                                    \
     if (row_scale) NBDT_REDUCE(A, false, false, true);    \
@@ -1009,10 +1056,15 @@ static int bn_act_bwd_impl(const void* gu, const float* gate, const float* gpool
     else if (pool) NBDT_REDUCE(A, false, true, false);    \
     else NBDT_REDUCE(A, false, false, false);             \
   } while (0)
-    NBDT_ACT_SWITCH(act, NBDT_GO);
+    NBDT_FOR_SLICES(C) {
+      const MbGeom g = mb_geom(B, H, W, C, 2 * kPpt, cs);
+      const dim3 grid(g.slices, B), blk(g.threads);
+      const size_t shmem = (size_t)g.threads * 16 * sizeof(float);
+      NBDT_ACT_SWITCH(act, NBDT_GO);
+      NBDT_LAUNCH_CHECK();
+    }
 #undef NBDT_GO
 #undef NBDT_REDUCE
-    NBDT_LAUNCH_CHECK();
     rc = slot_finish(st, tgt, nblk, 2 * (size_t)C, scratch);
     if (rc) return rc;
   }
@@ -1021,9 +1073,7 @@ static int bn_act_bwd_impl(const void* gu, const float* gate, const float* gpool
     NBDT_LAUNCH_CHECK();
   }
   {
-    const MbGeom g = mb_geom(B, H, W, C, kPpt);
-    const dim3 grid(g.slices, B), blk(g.threads);
-#define NBDT_BWD(A, SE, POOL, ADD, ROWS) hipLaunchKernelGGL((mb_bwd_apply_kernel<A, SE, POOL, ADD, ROWS>), grid, blk, 0, st, (const bf16_t*)gu, gate, gpool, row_scale, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, dsum, (const bf16_t*)gx_add, g, kPpt, (bf16_t*)gx)
+#define NBDT_BWD(A, SE, POOL, ADD, ROWS) hipLaunchKernelGGL((mb_bwd_apply_kernel<A, SE, POOL, ADD, ROWS>), grid, blk, 0, st, at16(gu, c0), at(gate, c0), at(gpool, c0), row_scale, at16(x, c0), at(save_mean, c0), at(save_rstd, c0), at(gamma, c0), at(beta, c0), at((const float*)dsum, c0), at16(gx_add, c0), g, kPpt, at16(gx, c0))
 #define NBDT_GO(A)                                                                            \
   do {                                                                                        \
     if (row_scale) { if (gx_add) NBDT_BWD(A, false, false, true, true); else NBDT_BWD(A, false, false, false, true); } \
@@ -1031,10 +1081,14 @@ static int bn_act_bwd_impl(const void* gu, const float* gate, const float* gpool
     else if (pool) NBDT_BWD(A, false, true, false, false);                                    \
     else { if (gx_add) NBDT_BWD(A, false, false, true, false); else NBDT_BWD(A, false, false, false, false); }         \
   } while (0)
-    NBDT_ACT_SWITCH(act, NBDT_GO);
+    NBDT_FOR_SLICES(C) {
+      const MbGeom g = mb_geom(B, H, W, C, kPpt, cs);
+      const dim3 grid(g.slices, B), blk(g.threads);
+      NBDT_ACT_SWITCH(act, NBDT_GO);
+      NBDT_LAUNCH_CHECK();
+    }
 #undef NBDT_GO
 #undef NBDT_BWD
-    NBDT_LAUNCH_CHECK();
   }
   return NBDT_OK;
 }
@@ -1072,17 +1126,19 @@ extern "C" int nbdt_bn_act_se_sums(const void* gu, const void* x, const float* s
   NBDT_REQUIRE(gu && x && save_mean && save_rstd && gamma && beta && sums, "null argument");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
   NBDT_REQUIRE(!deterministic(), "nbdt_bn_act_se_sums adds its pixel slices with atomics: use nbdt_bn_act_pool + nbdt_bn_act_bwd in deterministic mode");
-  int rc = check_shape(B, H, W, C);
+  int rc = check_shape_wide(B, H, W, C);
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  const MbGeom g = mb_geom(B, H, W, C, 2 * kPpt);
-  const dim3 grid(g.slices, B), blk(g.threads);
-  const size_t shmem = (size_t)g.threads * 40 * sizeof(float);
 #define NBDT_GO(A)                                                                                              \
-  hipLaunchKernelGGL((mb_se_sums_kernel<A>), grid, blk, shmem, st, (const bf16_t*)gu, (const bf16_t*)x, save_mean, save_rstd, gamma, beta, g, 2 * kPpt, sums)
-  NBDT_ACT_SWITCH(act, NBDT_GO);
+  hipLaunchKernelGGL((mb_se_sums_kernel<A>), grid, blk, shmem, st, at16(gu, c0), at16(x, c0), at(save_mean, c0), at(save_rstd, c0), at(gamma, c0), at(beta, c0), g, 2 * kPpt, sums + c0)
+  NBDT_FOR_SLICES(C) {
+    const MbGeom g = mb_geom(B, H, W, C, 2 * kPpt, cs);
+    const dim3 grid(g.slices, B), blk(g.threads);
+    const size_t shmem = (size_t)g.threads * 40 * sizeof(float);
+    NBDT_ACT_SWITCH(act, NBDT_GO);
+    NBDT_LAUNCH_CHECK();
+  }
 #undef NBDT_GO
-  NBDT_LAUNCH_CHECK();
   return NBDT_OK;
 }
 
@@ -1095,7 +1151,7 @@ extern "C" int nbdt_bn_act_se_bwd_apply(const void* gu, const float* gate, const
   // dgamma / dbeta, so a call refused after it would leave them changed (and a retry would count them twice)
   NBDT_REQUIRE(gu && gate && gpool && sums && dsum && x && save_mean && save_rstd && gamma && beta && gx, "null argument");
   NBDT_REQUIRE(act >= 0 && act <= 2, "unknown activation");
-  int rc = check_shape(B, H, W, C);
+  int rc = check_shape_wide(B, H, W, C);
   if (rc) return rc;
   hipLaunchKernelGGL(mb_se_finalize_kernel, dim3((C + 63) / 64), dim3(256), 0, (hipStream_t)stream, sums, gate, gpool,
                      B, C, 1.f / (float)(H * W), dsum, dgamma, dbeta);
@@ -1104,8 +1160,21 @@ extern "C" int nbdt_bn_act_se_bwd_apply(const void* gu, const float* gate, const
                          dgamma, dbeta, gx, stream, false, true);
 }
 
+// Geometry of every depthwise launch, per axis: Ho = ceil(H / stride); output o reads inputs o * stride + r - pad_lo for r
+// in [0, k); reads outside [0, H) are zero (the tensor's one-pixel zero border, or skipped).  pad_lo = k / 2 is PyTorch's
+// symmetric padding; TF "SAME" padding is pad_lo = max((Ho - 1) * stride + k - H, 0) / 2, which differs only for stride 2
+// on an even extent (0 at k = 3, 1 at k = 5).  The entry points without a padding argument are pad_lo = k / 2 on extents
+// the stride divides, as they always were.
+static int check_dw(int B, int H, int W, int C, int k, int stride, int pad_t, int pad_l) {
+  NBDT_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "empty tensor");
+  NBDT_REQUIRE(k == 3 || k == 5, "depthwise kernel size must be 3 or 5");
+  NBDT_REQUIRE(stride == 1 || stride == 2, "stride must be 1 or 2");
+  NBDT_REQUIRE(pad_t >= 0 && pad_t <= k / 2 && pad_l >= 0 && pad_l <= k / 2, "low-side padding must be in [0, k / 2]");
+  NBDT_REQUIRE(stride == 2 || (pad_t == k / 2 && pad_l == k / 2), "stride 1 pads k / 2 on both sides");
+  return check_shape_wide(B, H, W, C);
+}
 static int check_dw(int B, int H, int W, int C, int k, int stride) {
-  int rc = check_shape(B, H, W, C);
+  int rc = check_shape_wide(B, H, W, C);
   if (rc) return rc;
   NBDT_REQUIRE(k == 3 || k == 5, "depthwise kernel size must be 3 or 5");
   NBDT_REQUIRE(stride == 1 || stride == 2, "stride must be 1 or 2");
@@ -1113,14 +1182,27 @@ static int check_dw(int B, int H, int W, int C, int k, int stride) {
   return NBDT_OK;
 }
 
-static DwGeom dw_geom(int B, int H, int W, int C, int k, int stride, int ppt) {
+static DwGeom dw_geom(int B, int H, int W, int C, int k, int stride, int ppt, int pad_t, int pad_l) {
   DwGeom d;
-  d.out = mb_geom(B, H / stride, W / stride, C, ppt);
+  d.out = mb_geom(B, (H + stride - 1) / stride, (W + stride - 1) / stride, C, ppt);
   d.Hi = H; d.Wi = W;
   d.rowi = (W + 2) * C;
   d.imgi = (H + 2) * d.rowi;
   d.k = k; d.stride = stride; d.pad = k / 2;
+  d.pad_t = pad_t; d.pad_l = pad_l;
   return d;
+}
+
+// (checked arguments)  Symmetric padding takes the instantiations with the compile-time K/2, whatever the extents.
+static int dwconv_fwd_impl(const void* x, const float* w, int B, int H, int W, int C, int k, int stride, int pad_t,
+                           int pad_l, void* y, float* bn_scratch, hipStream_t st) {
+  const DwGeom d = dw_geom(B, H, W, C, k, stride, 4, pad_t, pad_l);
+  if (stride == 1) return k == 3 ? launch_dw_row<3, 1, false>(x, w, d, B, y, bn_scratch, st)
+                                 : launch_dw_row<5, 1, false>(x, w, d, B, y, bn_scratch, st);
+  if (pad_t == k / 2 && pad_l == k / 2) return k == 3 ? launch_dw_row<3, 2, false>(x, w, d, B, y, bn_scratch, st)
+                                                      : launch_dw_row<5, 2, false>(x, w, d, B, y, bn_scratch, st);
+  return k == 3 ? launch_dw_row<3, 2, false, true>(x, w, d, B, y, bn_scratch, st)
+                : launch_dw_row<5, 2, false, true>(x, w, d, B, y, bn_scratch, st);
 }
 
 extern "C" int nbdt_dwconv_fwd(const void* x, const float* w, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
@@ -1128,12 +1210,54 @@ extern "C" int nbdt_dwconv_fwd(const void* x, const float* w, int32_t B, int32_t
   NBDT_REQUIRE(x && w && y, "null argument");
   int rc = check_dw(B, H, W, C, k, stride);
   if (rc) return rc;
-  const DwGeom d = dw_geom(B, H, W, C, k, stride, 4);
-  hipStream_t st = (hipStream_t)stream;
-  if (k == 3) return stride == 1 ? launch_dw_row<3, 1, false>(x, w, d, B, y, bn_scratch, st)
-                                 : launch_dw_row<3, 2, false>(x, w, d, B, y, bn_scratch, st);
-  return stride == 1 ? launch_dw_row<5, 1, false>(x, w, d, B, y, bn_scratch, st)
-                     : launch_dw_row<5, 2, false>(x, w, d, B, y, bn_scratch, st);
+  return dwconv_fwd_impl(x, w, B, H, W, C, k, stride, k / 2, k / 2, y, bn_scratch, (hipStream_t)stream);
+}
+
+extern "C" int nbdt_dwconv_fwd_pad(const void* x, const float* w, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
+                                   int32_t stride, int32_t pad_top, int32_t pad_left, void* y, float* bn_scratch,
+                                   void* stream) {
+  int rc = check_dw(B, H, W, C, k, stride, pad_top, pad_left);
+  if (rc) return rc;
+  NBDT_REQUIRE(x && w && y, "null argument");
+  return dwconv_fwd_impl(x, w, B, H, W, C, k, stride, pad_top, pad_left, y, bn_scratch, (hipStream_t)stream);
+}
+
+static int dwconv_bwd_data_impl(const void* gy, const float* w, int B, int H, int W, int C, int k, int stride, int pad_t,
+                                int pad_l, void* gx, hipStream_t st) {
+  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
+  if (stride == 1) {   // same correlation with the kernel rotated by 180 degrees
+    const DwGeom d = dw_geom(B, H, W, C, k, 1, 4, k / 2, k / 2);
+    return k == 3 ? launch_dw_row<3, 1, true>(gy, w, d, B, gx, nullptr, st)
+                  : launch_dw_row<5, 1, true>(gy, w, d, B, gx, nullptr, st);
+  }
+  NBDT_FOR_SLICES(C) {
+  const MbGeom in = mb_geom(B, H, W, C, 4, cs);
+  if (W % 4 == 0) {     // row-segment form: segments of 8 (or 4) input pixels
+    const int tw = W % 8 == 0 ? 8 : 4;
+    const int nseg = W / tw;
+    int PY = kThreads / in.c8;
+    if (PY < 1) PY = 1;
+    if (PY > H * nseg) PY = H * nseg;
+    const dim3 grid((H * nseg + PY - 1) / PY, B), blk(in.c8 * PY);
+#define NBDT_ROW(K, TW, PL, RT) hipLaunchKernelGGL((dw_bwd_data_s2_row_kernel<K, TW, PL, RT>), grid, blk, 0, st, at16(gy, c0), w + c0, in, Ho, Wo, nseg, PY, pad_t, at16(gx, c0))
+#define NBDT_GO(K, TW)                                                     \
+  do {                                                                     \
+    if (pad_l == K / 2 && pad_t == K / 2) NBDT_ROW(K, TW, K / 2, false);   \
+    else if (pad_l == K / 2) NBDT_ROW(K, TW, K / 2, true);                 \
+    else if (pad_l == K / 2 - 1) NBDT_ROW(K, TW, K / 2 - 1, true);         \
+    else NBDT_ROW(K, TW, 0, true);                                         \
+  } while (0)
+    if (k == 3) { if (tw == 8) NBDT_GO(3, 8); else NBDT_GO(3, 4); }
+    else        { if (tw == 8) NBDT_GO(5, 8); else NBDT_GO(5, 4); }
+#undef NBDT_GO
+#undef NBDT_ROW
+  } else {
+    hipLaunchKernelGGL(dw_bwd_data_kernel, dim3(in.slices, B), dim3(in.threads), 0, st, at16(gy, c0), w + c0, in,
+                       Ho, Wo, k, stride, pad_t, pad_l, 4, at16(gx, c0));
+  }
+  NBDT_LAUNCH_CHECK();
+  }
+  return NBDT_OK;
 }
 
 extern "C" int nbdt_dwconv_bwd_data(const void* gy, const float* w, int32_t B, int32_t H, int32_t W, int32_t C,
@@ -1141,29 +1265,16 @@ extern "C" int nbdt_dwconv_bwd_data(const void* gy, const float* w, int32_t B, i
   NBDT_REQUIRE(gy && w && gx, "null argument");
   int rc = check_dw(B, H, W, C, k, stride);
   if (rc) return rc;
-  const MbGeom in = mb_geom(B, H, W, C, 4);
-  hipStream_t st = (hipStream_t)stream;
-  if (stride == 1) {   // same correlation with the kernel rotated by 180 degrees
-    const DwGeom d = dw_geom(B, H, W, C, k, 1, 4);
-    return k == 3 ? launch_dw_row<3, 1, true>(gy, w, d, B, gx, nullptr, st)
-                  : launch_dw_row<5, 1, true>(gy, w, d, B, gx, nullptr, st);
-  } else if (W % 4 == 0) {     // row-segment form: segments of 8 (or 4) input pixels
-    const int tw = W % 8 == 0 ? 8 : 4;
-    const int nseg = W / tw;
-    int PY = kThreads / in.c8;
-    if (PY < 1) PY = 1;
-    if (PY > H * nseg) PY = H * nseg;
-    const dim3 grid((H * nseg + PY - 1) / PY, B), blk(in.c8 * PY);
-#define NBDT_GO(K, TW) hipLaunchKernelGGL((dw_bwd_data_s2_row_kernel<K, TW>), grid, blk, 0, st, (const bf16_t*)gy, w, in, H / 2, W / 2, nseg, PY, (bf16_t*)gx)
-    if (k == 3) { if (tw == 8) NBDT_GO(3, 8); else NBDT_GO(3, 4); }
-    else        { if (tw == 8) NBDT_GO(5, 8); else NBDT_GO(5, 4); }
-#undef NBDT_GO
-  } else {
-    hipLaunchKernelGGL(dw_bwd_data_kernel, dim3(in.slices, B), dim3(in.threads), 0, st, (const bf16_t*)gy, w, in,
-                       H / stride, W / stride, k, stride, k / 2, 4, (bf16_t*)gx);
-  }
-  NBDT_LAUNCH_CHECK();
-  return NBDT_OK;
+  return dwconv_bwd_data_impl(gy, w, B, H, W, C, k, stride, k / 2, k / 2, gx, (hipStream_t)stream);
+}
+
+extern "C" int nbdt_dwconv_bwd_data_pad(const void* gy, const float* w, int32_t B, int32_t H, int32_t W, int32_t C,
+                                        int32_t k, int32_t stride, int32_t pad_top, int32_t pad_left, void* gx,
+                                        void* stream) {
+  int rc = check_dw(B, H, W, C, k, stride, pad_top, pad_left);
+  if (rc) return rc;
+  NBDT_REQUIRE(gy && w && gx, "null argument");
+  return dwconv_bwd_data_impl(gy, w, B, H, W, C, k, stride, pad_top, pad_left, gx, (hipStream_t)stream);
 }
 
 extern "C" int nbdt_dwconv_bwd_data_bn(const void* gy, const float* w, int32_t B, int32_t H, int32_t W, int32_t C,
@@ -1173,20 +1284,18 @@ extern "C" int nbdt_dwconv_bwd_data_bn(const void* gy, const float* w, int32_t B
   NBDT_REQUIRE(gy && w && gx && bn_x && save_mean && save_rstd && gamma && beta && scratch, "null argument");
   int rc = check_dw(B, H, W, C, k, 1);
   if (rc) return rc;
-  const DwGeom d = dw_geom(B, H, W, C, k, 1, 4);
+  const DwGeom d = dw_geom(B, H, W, C, k, 1, 4, k / 2, k / 2);
   const DwBn bn{(const bf16_t*)bn_x, save_mean, save_rstd, gamma, beta};
   hipStream_t st = (hipStream_t)stream;
   return k == 3 ? launch_dw_row<3, 1, true>(gy, w, d, B, gx, scratch, st, &bn)
                 : launch_dw_row<5, 1, true>(gy, w, d, B, gx, scratch, st, &bn);
 }
 
-extern "C" int nbdt_dwconv_bwd_weight(const void* x, const void* gy, int32_t B, int32_t H, int32_t W, int32_t C,
-                                      int32_t k, int32_t stride, float* dw, void* stream) {
-  NBDT_REQUIRE(x && gy && dw, "null argument");
-  int rc = check_dw(B, H, W, C, k, stride);
-  if (rc) return rc;
-  const DwGeom d = dw_geom(B, H, W, C, k, stride, 1);
-  const int Ho = H / stride;
+static int dwconv_bwd_weight_impl(const void* x, const void* gy, int B, int H, int W, int C, int k, int stride, int pad_t,
+                                  int pad_l, float* dw, void* stream) {
+  const DwGeom d = dw_geom(B, H, W, C, k, stride, 1, pad_t, pad_l);
+  const int Ho = d.out.H, Wo = d.out.W;
+  const bool rt = pad_t != k / 2 || pad_l != k / 2;       // (stride 2 only: check_dw)
   const int cblocks = (d.out.c8 + 31) / 32, CB = (d.out.c8 + cblocks - 1) / cblocks;
   int PY = kThreads / CB;
   if (PY > Ho) PY = Ho;
@@ -1194,8 +1303,8 @@ extern "C" int nbdt_dwconv_bwd_weight(const void* x, const void* gy, int32_t B, 
   // every block ends in CB*k*8 global atomics on addresses every other block of its channels adds to as well: let a
   // thread walk about target_px output pixels (several images when rows are short) before the block folds
   // (profiles/r04_dw_wgrad.txt: rows of 28+ outputs are fastest at ~128 pixels per thread, shorter ones at ~64)
-  const int target_px = W / stride >= 28 ? 128 : 64;
-  int bchunk = target_px / (W / stride);
+  const int target_px = Wo >= 28 ? 128 : 64;
+  int bchunk = target_px / Wo;
   if (bchunk < 1) bchunk = 1;
   if (bchunk > B) bchunk = B;
   const dim3 grid(((Ho + PY - 1) / PY) * cblocks, (B + bchunk - 1) / bchunk, k), blk(threads);
@@ -1211,12 +1320,12 @@ extern "C" int nbdt_dwconv_bwd_weight(const void* x, const void* gy, int32_t B, 
     NBDT_HIP_CHECK(hipMemsetAsync(target, 0, (size_t)nrows * n_dw * sizeof(float), st));
     row_stride = (long long)n_dw;
   }
-#define NBDT_GO(K, S, U) hipLaunchKernelGGL((dw_bwd_weight_kernel<K, S, U>), grid, blk, shmem, st, (const bf16_t*)x, (const bf16_t*)gy, d, PY, CB, cblocks, bchunk, target, row_stride)
+#define NBDT_GO(K, S, U, RT) hipLaunchKernelGGL((dw_bwd_weight_kernel<K, S, U, RT>), grid, blk, shmem, st, (const bf16_t*)x, (const bf16_t*)gy, d, PY, CB, cblocks, bchunk, target, row_stride)
   // pixels in flight per thread: the short-row layers (<= 28 wide: few waves per CU, a row is a chain of round trips)
   // want 8; the long-row stride-1 layers are bandwidth-bound and lose occupancy to the registers of more than 1
-  const bool long_rows = W / stride >= 56;
-#define NBDT_GO_S1(K) { if (long_rows) NBDT_GO(K, 1, 1); else NBDT_GO(K, 1, 8); }
-#define NBDT_GO_S2(K) { NBDT_GO(K, 2, 4); }
+  const bool long_rows = Wo >= 56;
+#define NBDT_GO_S1(K) { if (long_rows) NBDT_GO(K, 1, 1, false); else NBDT_GO(K, 1, 8, false); }
+#define NBDT_GO_S2(K) { if (rt) NBDT_GO(K, 2, 4, true); else NBDT_GO(K, 2, 4, false); }
   if (k == 3) { if (stride == 1) NBDT_GO_S1(3) else NBDT_GO_S2(3) }
   else { if (stride == 1) NBDT_GO_S1(5) else NBDT_GO_S2(5) }
 #undef NBDT_GO_S1
@@ -1225,6 +1334,23 @@ extern "C" int nbdt_dwconv_bwd_weight(const void* x, const void* gy, int32_t B, 
   NBDT_LAUNCH_CHECK();
   if (target != dw) return det_fold(st, target, nrows, n_dw, dw);
   return NBDT_OK;
+}
+
+extern "C" int nbdt_dwconv_bwd_weight(const void* x, const void* gy, int32_t B, int32_t H, int32_t W, int32_t C,
+                                      int32_t k, int32_t stride, float* dw, void* stream) {
+  NBDT_REQUIRE(x && gy && dw, "null argument");
+  int rc = check_dw(B, H, W, C, k, stride);
+  if (rc) return rc;
+  return dwconv_bwd_weight_impl(x, gy, B, H, W, C, k, stride, k / 2, k / 2, dw, stream);
+}
+
+extern "C" int nbdt_dwconv_bwd_weight_pad(const void* x, const void* gy, int32_t B, int32_t H, int32_t W, int32_t C,
+                                          int32_t k, int32_t stride, int32_t pad_top, int32_t pad_left, float* dw,
+                                          void* stream) {
+  int rc = check_dw(B, H, W, C, k, stride, pad_top, pad_left);
+  if (rc) return rc;
+  NBDT_REQUIRE(x && gy && dw, "null argument");
+  return dwconv_bwd_weight_impl(x, gy, B, H, W, C, k, stride, pad_top, pad_left, dw, stream);
 }
 
 extern "C" int nbdt_se_gate_fwd(const float* pooled, const float* w1, const float* b1, const float* w2,

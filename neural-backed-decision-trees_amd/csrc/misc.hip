@@ -169,14 +169,14 @@ extern "C" int nbdt_get_reserved_cus(void) { return nbdt::reserved_cus(); }
 // images and 115 us for ResNet18's 64-channel stem at 128 x 64x64.)
 __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                         int B, int H, int W, int cout, int cpad, int stride,
-                                                        bf16_t* __restrict__ out) {
+                                                        int pad_t, int pad_l, bf16_t* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float wl[];  // [27][cout]
   for (int i = threadIdx.x; i < cout * 27; i += 256) {
     const int co = i / 27, t = i - co * 27;
     wl[t * cout + co] = w[i];
   }
   __syncthreads();
-  const int Ho = H / stride, Wo = W / stride;   // H, W: image size; output is Ho x Wo
+  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;   // H, W: image size; output is Ho x Wo
   const long long total = (long long)B * Ho * Wo;
   const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
   if (p >= total) return;
@@ -184,10 +184,10 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
   float v[27];
 #pragma unroll
   for (int r = 0; r < 3; ++r) {
-    const int yy = y * stride + r - 1;
+    const int yy = y * stride + r - pad_t;
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
-      const int xx = x * stride + s - 1;
+      const int xx = x * stride + s - pad_l;
       const bool in = yy >= 0 && yy < H && xx >= 0 && xx < W;
 #pragma unroll
       for (int ci = 0; ci < 3; ++ci)
@@ -225,7 +225,8 @@ typedef __attribute__((ext_vector_type(16))) float stem_f32x16;
 template <int CO_T>
 __global__ __launch_bounds__(256) void stem_wgrad_mfma_kernel(const float* __restrict__ img, const bf16_t* __restrict__ gy,
                                                               int B, int H, int W, int cout, int cpad, int stride,
-                                                              int tiles_per_block, float* __restrict__ dw, int row_stride) {
+                                                              int pad_t, int pad_l, int tiles_per_block,
+                                                              float* __restrict__ dw, int row_stride) {
   extern __shared__ __attribute__((aligned(16))) float lds[];  // gy tile [64][gp], patch tile [64][33]; then [4][CO_T][1024]
   // row pitches: a thread owns a PIXEL when it fills the tiles, so lane l writes row l -- pitch 32 would put all 64 lanes of
   // a patch store on two banks (that version ran at the scalar kernel's speed), cout + 32 the float4 stores of gy likewise.
@@ -234,7 +235,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_mfma_kernel(const float* __res
   constexpr int PP = 33;
   float* gl = lds;
   float* pl = lds + 64 * gp;
-  const int Ho = H / stride, Wo = W / stride;
+  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
   const int npix = B * Ho * Wo;
   const int c8 = cout / 8;
   const int lp = threadIdx.x & 63, part = threadIdx.x >> 6;
@@ -270,7 +271,7 @@ __global__ __launch_bounds__(256) void stem_wgrad_mfma_kernel(const float* __res
         const int k = part + 4 * i;              // 0..31; columns 27..31 are zero
         const int kc = k < 27 ? k : 26;
         const int r = kc / 9, s2 = (kc / 3) % 3, ci = kc % 3;
-        const int yy = y * stride + r - 1, xx = x * stride + s2 - 1;
+        const int yy = y * stride + r - pad_t, xx = x * stride + s2 - pad_l;
         const bool in = k < 27 && live && yy >= 0 && yy < H && xx >= 0 && xx < W;
         const int yc = yy < 0 ? 0 : (yy >= H ? H - 1 : yy), xc = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
         const float v = img[(((size_t)b * 3 + ci) * H + yc) * W + xc];
@@ -324,26 +325,49 @@ __global__ __launch_bounds__(256) void stem_wgrad_mfma_kernel(const float* __res
   }
 }
 
+// Low-side padding (pad_t, pad_l) in [0, 1]: 1 is Conv2d(3, cout, 3, padding=1); TF "SAME" padding at stride 2 is 0 on an
+// even extent.  Ho = ceil(H / stride) (csrc/effnet.hip: check_dw).
+static int stem_conv_impl(const float* img, const float* w, int B, int H, int W, int cout_real, int cpad, int stride,
+                          int pad_t, int pad_l, void* out, void* stream) {
+  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
+  const long long total = (long long)B * Ho * Wo;      // one thread per output pixel
+  hipLaunchKernelGGL(stem_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), cout_real * 27 * sizeof(float),
+                     (hipStream_t)stream, img, w, B, H, W, cout_real, cpad, stride, pad_t, pad_l, (bf16_t*)out);
+  NBDT_LAUNCH_CHECK();
+  return NBDT_OK;
+}
+
 extern "C" int nbdt_stem_conv(const float* img, const float* w, int32_t B, int32_t H, int32_t W, int32_t cout_real,
                               int32_t cpad, int32_t stride, void* out, void* stream) {
   NBDT_REQUIRE(img && w && out, "null argument");
   NBDT_REQUIRE(B > 0 && H > 0 && W > 0, "empty image batch");
   NBDT_REQUIRE((stride == 1 || stride == 2) && H % stride == 0 && W % stride == 0, "bad stem stride");
   NBDT_REQUIRE(cout_real > 0 && cout_real % 8 == 0 && cout_real <= cpad && cpad % 8 == 0, "bad stem channels");
-  const long long total = (long long)B * (H / stride) * (W / stride);      // one thread per output pixel
-  hipLaunchKernelGGL(stem_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), cout_real * 27 * sizeof(float),
-                     (hipStream_t)stream, img, w, B, H, W, cout_real, cpad, stride, (bf16_t*)out);
-  NBDT_LAUNCH_CHECK();
+  return stem_conv_impl(img, w, B, H, W, cout_real, cpad, stride, 1, 1, out, stream);
+}
+
+static int check_stem_pad(int B, int H, int W, int stride, int pad_t, int pad_l) {
+  NBDT_REQUIRE(B > 0 && H > 0 && W > 0, "empty image batch");
+  NBDT_REQUIRE(stride == 1 || stride == 2, "stride must be 1 or 2");
+  NBDT_REQUIRE(pad_t >= 0 && pad_t <= 1 && pad_l >= 0 && pad_l <= 1, "low-side padding must be in [0, k / 2]");
+  NBDT_REQUIRE(stride == 2 || (pad_t == 1 && pad_l == 1), "stride 1 pads k / 2 on both sides");
+  NBDT_REQUIRE((long long)B * ((H + stride - 1) / stride) * ((W + stride - 1) / stride) < (1ll << 31) / 64, "image batch too large");
   return NBDT_OK;
 }
 
-extern "C" int nbdt_stem_wgrad(const float* img, const void* gy, int32_t B, int32_t H, int32_t W, int32_t cout_real,
-                               int32_t cpad, int32_t stride, float* dw, void* stream) {
-  NBDT_REQUIRE(img && gy && dw, "null argument");
-  NBDT_REQUIRE((stride == 1 || stride == 2) && H % stride == 0 && W % stride == 0, "bad stem stride");
-  NBDT_REQUIRE(cout_real > 0 && cout_real % 8 == 0 && cout_real <= 72 && cout_real <= cpad,
-               "stem wgrad supports cout = 8, 16, ..., 72");
-  const int npix = B * (H / stride) * (W / stride);
+extern "C" int nbdt_stem_conv_pad(const float* img, const float* w, int32_t B, int32_t H, int32_t W, int32_t cout_real,
+                                  int32_t cpad, int32_t stride, int32_t pad_top, int32_t pad_left, void* out,
+                                  void* stream) {
+  int rc = check_stem_pad(B, H, W, stride, pad_top, pad_left);
+  if (rc) return rc;
+  NBDT_REQUIRE(img && w && out, "null argument");
+  NBDT_REQUIRE(cout_real > 0 && cout_real % 8 == 0 && cout_real <= cpad && cpad % 8 == 0, "bad stem channels");
+  return stem_conv_impl(img, w, B, H, W, cout_real, cpad, stride, pad_top, pad_left, out, stream);
+}
+
+static int stem_wgrad_impl(const float* img, const void* gy, int B, int H, int W, int cout_real, int cpad, int stride,
+                           int pad_t, int pad_l, float* dw, void* stream) {
+  const int npix = B * ((H + stride - 1) / stride) * ((W + stride - 1) / stride);
   const int tiles = (npix + 63) / 64;
   int blocks = tiles < 1024 ? tiles : 1024;
   const int tpb = (tiles + blocks - 1) / blocks;
@@ -362,12 +386,32 @@ extern "C" int nbdt_stem_wgrad(const float* img, const void* gy, int32_t B, int3
   }
 #define NBDT_STEM(T)                                                                                                  \
   hipLaunchKernelGGL(stem_wgrad_mfma_kernel<T>, dim3(blocks), dim3(256), shmem, st, img, (const bf16_t*)gy, B, H, W,  \
-                     cout_real, cpad, stride, tpb, target, target == dw ? 0 : nout)
+                     cout_real, cpad, stride, pad_t, pad_l, tpb, target, target == dw ? 0 : nout)
   if (co_t == 1) NBDT_STEM(1); else if (co_t == 2) NBDT_STEM(2); else NBDT_STEM(3);
 #undef NBDT_STEM
   NBDT_LAUNCH_CHECK();
   if (target != dw) return det_fold(st, target, blocks, (size_t)nout, dw);
   return NBDT_OK;
+}
+
+extern "C" int nbdt_stem_wgrad(const float* img, const void* gy, int32_t B, int32_t H, int32_t W, int32_t cout_real,
+                               int32_t cpad, int32_t stride, float* dw, void* stream) {
+  NBDT_REQUIRE(img && gy && dw, "null argument");
+  NBDT_REQUIRE((stride == 1 || stride == 2) && H % stride == 0 && W % stride == 0, "bad stem stride");
+  NBDT_REQUIRE(cout_real > 0 && cout_real % 8 == 0 && cout_real <= 72 && cout_real <= cpad,
+               "stem wgrad supports cout = 8, 16, ..., 72");
+  return stem_wgrad_impl(img, gy, B, H, W, cout_real, cpad, stride, 1, 1, dw, stream);
+}
+
+extern "C" int nbdt_stem_wgrad_pad(const float* img, const void* gy, int32_t B, int32_t H, int32_t W, int32_t cout_real,
+                                   int32_t cpad, int32_t stride, int32_t pad_top, int32_t pad_left, float* dw,
+                                   void* stream) {
+  int rc = check_stem_pad(B, H, W, stride, pad_top, pad_left);
+  if (rc) return rc;
+  NBDT_REQUIRE(img && gy && dw, "null argument");
+  NBDT_REQUIRE(cout_real > 0 && cout_real % 8 == 0 && cout_real <= 72 && cout_real <= cpad,
+               "stem wgrad supports cout = 8, 16, ..., 72");
+  return stem_wgrad_impl(img, gy, B, H, W, cout_real, cpad, stride, pad_top, pad_left, dw, stream);
 }
 
 // ------------------------------------------------------------------------------------------ linear

@@ -195,8 +195,8 @@ __global__ __launch_bounds__(256) void ref_bn_relu_pool_kernel(const float* __re
 // stem Conv2d(3 -> cout_real, 3x3, pad 1): NCHW fp32 image -> padded NHWC fp32; w [cout][3][3][3] (co, r, s, ci)
 __global__ __launch_bounds__(256) void ref_stem_conv_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                             int B, int H, int W, int cout, int cpad, int stride,
-                                                            float* __restrict__ out) {
-  const int Ho = H / stride, Wo = W / stride;
+                                                            int pad_t, int pad_l, float* __restrict__ out) {
+  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long long)B * Ho * Wo * cout) return;
   const int co = (int)(idx % cout);
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void ref_stem_conv_kernel(const float* __restr
   float acc = 0.f;
   for (int r = 0; r < 3; ++r)
     for (int s = 0; s < 3; ++s) {
-      const int yy = yo * stride + r - 1, xx = xo * stride + s - 1;
+      const int yy = yo * stride + r - pad_t, xx = xo * stride + s - pad_l;
       if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
       for (int ci = 0; ci < 3; ++ci)
         acc += img[(((size_t)b * 3 + ci) * H + yy) * W + xx] * w[((co * 3 + r) * 3 + s) * 3 + ci];
@@ -215,16 +215,16 @@ __global__ __launch_bounds__(256) void ref_stem_conv_kernel(const float* __restr
 
 __global__ __launch_bounds__(256) void ref_stem_wgrad_kernel(const float* __restrict__ img, const float* __restrict__ gy,
                                                              int B, int H, int W, int cout, int cpad, int stride,
-                                                             float* __restrict__ dw) {
+                                                             int pad_t, int pad_l, float* __restrict__ dw) {
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= cout * 27) return;
   const int ci = idx % 3, s = (idx / 3) % 3, r = (idx / 9) % 3, co = idx / 27;
-  const int Ho = H / stride, Wo = W / stride;
+  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
   double acc = 0.0;
   for (int b = 0; b < B; ++b)
     for (int yo = 0; yo < Ho; ++yo)
       for (int xo = 0; xo < Wo; ++xo) {
-        const int yy = yo * stride + r - 1, xx = xo * stride + s - 1;
+        const int yy = yo * stride + r - pad_t, xx = xo * stride + s - pad_l;
         if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
         acc += (double)gy[(((size_t)b * (Ho + 2) + yo + 1) * (Wo + 2) + xo + 1) * cpad + co] *
                (double)img[(((size_t)b * 3 + ci) * H + yy) * W + xx];
@@ -355,21 +355,56 @@ extern "C" int nbdt_ref_bn_relu_pool(const float* x, const float* save_mean, con
   return NBDT_OK;
 }
 
+static int ref_check_pad(int B, int H, int W, int k, int stride, int pad_t, int pad_l) {
+  NBDT_REQUIRE(B > 0 && H > 0 && W > 0, "empty tensor");
+  NBDT_REQUIRE(k == 3 || k == 5, "kernel size must be 3 or 5");
+  NBDT_REQUIRE(stride == 1 || stride == 2, "stride must be 1 or 2");
+  NBDT_REQUIRE(pad_t >= 0 && pad_t <= k / 2 && pad_l >= 0 && pad_l <= k / 2, "low-side padding must be in [0, k / 2]");
+  NBDT_REQUIRE(stride == 2 || (pad_t == k / 2 && pad_l == k / 2), "stride 1 pads k / 2 on both sides");
+  return NBDT_OK;
+}
+
+static int ref_stem_conv_impl(const float* img, const float* w, int B, int H, int W, int cout_real, int cpad, int stride,
+                              int pad_t, int pad_l, float* out, void* stream) {
+  const long long total = (long long)B * ((H + stride - 1) / stride) * ((W + stride - 1) / stride) * cout_real;
+  hipLaunchKernelGGL(ref_stem_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, w,
+                     B, H, W, cout_real, cpad, stride, pad_t, pad_l, out);
+  NBDT_LAUNCH_CHECK();
+  return NBDT_OK;
+}
+
 extern "C" int nbdt_ref_stem_conv(const float* img, const float* w, int32_t B, int32_t H, int32_t W, int32_t cout_real,
                                   int32_t cpad, int32_t stride, float* out, void* stream) {
   NBDT_REQUIRE(img && w && out && (stride == 1 || stride == 2), "bad argument");
-  const long long total = (long long)B * (H / stride) * (W / stride) * cout_real;
-  hipLaunchKernelGGL(ref_stem_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, img, w,
-                     B, H, W, cout_real, cpad, stride, out);
-  NBDT_LAUNCH_CHECK();
-  return NBDT_OK;
+  NBDT_REQUIRE(H % stride == 0 && W % stride == 0, "bad stem stride");
+  return ref_stem_conv_impl(img, w, B, H, W, cout_real, cpad, stride, 1, 1, out, stream);
+}
+
+extern "C" int nbdt_ref_stem_conv_pad(const float* img, const float* w, int32_t B, int32_t H, int32_t W, int32_t cout_real,
+                                      int32_t cpad, int32_t stride, int32_t pad_top, int32_t pad_left, float* out,
+                                      void* stream) {
+  if (int rc = ref_check_pad(B, H, W, 3, stride, pad_top, pad_left)) return rc;
+  NBDT_REQUIRE(img && w && out && cout_real > 0 && cout_real <= cpad, "bad argument");
+  return ref_stem_conv_impl(img, w, B, H, W, cout_real, cpad, stride, pad_top, pad_left, out, stream);
 }
 
 extern "C" int nbdt_ref_stem_wgrad(const float* img, const float* gy, int32_t B, int32_t H, int32_t W, int32_t cout_real,
                                    int32_t cpad, int32_t stride, float* dw, void* stream) {
   NBDT_REQUIRE(img && gy && dw && (stride == 1 || stride == 2), "bad argument");
+  NBDT_REQUIRE(H % stride == 0 && W % stride == 0, "bad stem stride");
   hipLaunchKernelGGL(ref_stem_wgrad_kernel, dim3((cout_real * 27 + 255) / 256), dim3(256), 0, (hipStream_t)stream, img, gy,
-                     B, H, W, cout_real, cpad, stride, dw);
+                     B, H, W, cout_real, cpad, stride, 1, 1, dw);
+  NBDT_LAUNCH_CHECK();
+  return NBDT_OK;
+}
+
+extern "C" int nbdt_ref_stem_wgrad_pad(const float* img, const float* gy, int32_t B, int32_t H, int32_t W,
+                                       int32_t cout_real, int32_t cpad, int32_t stride, int32_t pad_top, int32_t pad_left,
+                                       float* dw, void* stream) {
+  if (int rc = ref_check_pad(B, H, W, 3, stride, pad_top, pad_left)) return rc;
+  NBDT_REQUIRE(img && gy && dw && cout_real > 0 && cout_real <= cpad, "bad argument");
+  hipLaunchKernelGGL(ref_stem_wgrad_kernel, dim3((cout_real * 27 + 255) / 256), dim3(256), 0, (hipStream_t)stream, img, gy,
+                     B, H, W, cout_real, cpad, stride, pad_top, pad_left, dw);
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;
 }
@@ -493,8 +528,9 @@ __global__ __launch_bounds__(256) void ref_bn_act_bwd_apply_kernel(const float* 
 
 // depthwise Conv2d(C, C, k, stride, padding k/2, groups = C); w [k*k][C]; x [B][H+2][W+2][C] -> y [B][H/s+2][W/s+2][C]
 __global__ __launch_bounds__(256) void ref_dw_fwd_kernel(const float* __restrict__ x, const float* __restrict__ w, int B,
-                                                         int H, int W, int C, int k, int stride, float* __restrict__ y) {
-  const int Ho = H / stride, Wo = W / stride, pad = k / 2;
+                                                         int H, int W, int C, int k, int stride, int pad_t, int pad_l,
+                                                         float* __restrict__ y) {
+  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long long)B * Ho * Wo * C) return;
   const int c = (int)(idx % C);
@@ -503,7 +539,7 @@ __global__ __launch_bounds__(256) void ref_dw_fwd_kernel(const float* __restrict
   float acc = 0.f;
   for (int r = 0; r < k; ++r)
     for (int s = 0; s < k; ++s) {
-      const int hi = ho * stride + r - pad, wi = wo * stride + s - pad;
+      const int hi = ho * stride + r - pad_t, wi = wo * stride + s - pad_l;
       if (hi < 0 || hi >= H || wi < 0 || wi >= W) continue;
       acc += x[(((size_t)b * (H + 2) + hi + 1) * (W + 2) + wi + 1) * C + c] * w[(size_t)(r * k + s) * C + c];
     }
@@ -513,8 +549,8 @@ __global__ __launch_bounds__(256) void ref_dw_fwd_kernel(const float* __restrict
 // gx[hi][wi] = sum over (r, s) with (hi + pad - r, wi + pad - s) = stride * (ho, wo) of gy[ho][wo] * w[r][s]
 __global__ __launch_bounds__(256) void ref_dw_bwd_data_kernel(const float* __restrict__ gy, const float* __restrict__ w,
                                                               int B, int H, int W, int C, int k, int stride,
-                                                              float* __restrict__ gx) {
-  const int Ho = H / stride, Wo = W / stride, pad = k / 2;
+                                                              int pad_t, int pad_l, float* __restrict__ gx) {
+  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
   const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long long)B * H * W * C) return;
   const int c = (int)(idx % C);
@@ -522,10 +558,10 @@ __global__ __launch_bounds__(256) void ref_dw_bwd_data_kernel(const float* __res
   const int wi = p % W, hi = (p / W) % H, b = p / (W * H);
   float acc = 0.f;
   for (int r = 0; r < k; ++r) {
-    const int th = hi + pad - r;
+    const int th = hi + pad_t - r;
     if (th < 0 || th % stride != 0 || th / stride >= Ho) continue;
     for (int s = 0; s < k; ++s) {
-      const int tw = wi + pad - s;
+      const int tw = wi + pad_l - s;
       if (tw < 0 || tw % stride != 0 || tw / stride >= Wo) continue;
       acc += gy[(((size_t)b * (Ho + 2) + th / stride + 1) * (Wo + 2) + tw / stride + 1) * C + c] *
              w[(size_t)(r * k + s) * C + c];
@@ -537,8 +573,8 @@ __global__ __launch_bounds__(256) void ref_dw_bwd_data_kernel(const float* __res
 // dw[r*k + s][c] += sum over images and output pixels of gy[ho][wo] * x[ho*stride + r - pad][wo*stride + s - pad]
 __global__ __launch_bounds__(256) void ref_dw_bwd_weight_kernel(const float* __restrict__ x, const float* __restrict__ gy,
                                                                 int B, int H, int W, int C, int k, int stride,
-                                                                float* __restrict__ dw) {
-  const int Ho = H / stride, Wo = W / stride, pad = k / 2;
+                                                                int pad_t, int pad_l, float* __restrict__ dw) {
+  const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= k * k * C) return;
   const int c = idx % C, t = idx / C;
@@ -546,10 +582,10 @@ __global__ __launch_bounds__(256) void ref_dw_bwd_weight_kernel(const float* __r
   double acc = 0.0;
   for (int b = 0; b < B; ++b)
     for (int ho = 0; ho < Ho; ++ho) {
-      const int hi = ho * stride + r - pad;
+      const int hi = ho * stride + r - pad_t;
       if (hi < 0 || hi >= H) continue;
       for (int wo = 0; wo < Wo; ++wo) {
-        const int wi = wo * stride + s - pad;
+        const int wi = wo * stride + s - pad_l;
         if (wi < 0 || wi >= W) continue;
         acc += (double)gy[(((size_t)b * (Ho + 2) + ho + 1) * (Wo + 2) + wo + 1) * C + c] *
                (double)x[(((size_t)b * (H + 2) + hi + 1) * (W + 2) + wi + 1) * C + c];
@@ -645,15 +681,35 @@ static int ref_check_dw(int B, int H, int W, int C, int k, int stride) {
   return NBDT_OK;
 }
 
+static int ref_dwconv_fwd_impl(const float* x, const float* w, int B, int H, int W, int C, int k, int stride, int pad_t,
+                               int pad_l, float* y, void* stream) {
+  const long long total = (long long)B * ((H + stride - 1) / stride) * ((W + stride - 1) / stride) * C;
+  hipLaunchKernelGGL(ref_dw_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, w, B,
+                     H, W, C, k, stride, pad_t, pad_l, y);
+  NBDT_LAUNCH_CHECK();
+  return NBDT_OK;
+}
+static int ref_dwconv_bwd_data_impl(const float* gy, const float* w, int B, int H, int W, int C, int k, int stride,
+                                    int pad_t, int pad_l, float* gx, void* stream) {
+  const long long total = (long long)B * H * W * C;
+  hipLaunchKernelGGL(ref_dw_bwd_data_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gy,
+                     w, B, H, W, C, k, stride, pad_t, pad_l, gx);
+  NBDT_LAUNCH_CHECK();
+  return NBDT_OK;
+}
+static int ref_dwconv_bwd_weight_impl(const float* x, const float* gy, int B, int H, int W, int C, int k, int stride,
+                                      int pad_t, int pad_l, float* dw, void* stream) {
+  hipLaunchKernelGGL(ref_dw_bwd_weight_kernel, dim3((k * k * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, gy, B,
+                     H, W, C, k, stride, pad_t, pad_l, dw);
+  NBDT_LAUNCH_CHECK();
+  return NBDT_OK;
+}
+
 extern "C" int nbdt_ref_dwconv_fwd(const float* x, const float* w, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
                                    int32_t stride, float* y, void* stream) {
   NBDT_REQUIRE(x && w && y, "null argument");
   if (int rc = ref_check_dw(B, H, W, C, k, stride)) return rc;
-  const long long total = (long long)B * (H / stride) * (W / stride) * C;
-  hipLaunchKernelGGL(ref_dw_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, w, B,
-                     H, W, C, k, stride, y);
-  NBDT_LAUNCH_CHECK();
-  return NBDT_OK;
+  return ref_dwconv_fwd_impl(x, w, B, H, W, C, k, stride, k / 2, k / 2, y, stream);
 }
 
 /* H, W: the INPUT-sized gradient being written (like nbdt_dwconv_bwd_data) */
@@ -661,19 +717,37 @@ extern "C" int nbdt_ref_dwconv_bwd_data(const float* gy, const float* w, int32_t
                                         int32_t k, int32_t stride, float* gx, void* stream) {
   NBDT_REQUIRE(gy && w && gx, "null argument");
   if (int rc = ref_check_dw(B, H, W, C, k, stride)) return rc;
-  const long long total = (long long)B * H * W * C;
-  hipLaunchKernelGGL(ref_dw_bwd_data_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gy,
-                     w, B, H, W, C, k, stride, gx);
-  NBDT_LAUNCH_CHECK();
-  return NBDT_OK;
+  return ref_dwconv_bwd_data_impl(gy, w, B, H, W, C, k, stride, k / 2, k / 2, gx, stream);
 }
 
 extern "C" int nbdt_ref_dwconv_bwd_weight(const float* x, const float* gy, int32_t B, int32_t H, int32_t W, int32_t C,
                                           int32_t k, int32_t stride, float* dw, void* stream) {
   NBDT_REQUIRE(x && gy && dw, "null argument");
   if (int rc = ref_check_dw(B, H, W, C, k, stride)) return rc;
-  hipLaunchKernelGGL(ref_dw_bwd_weight_kernel, dim3((k * k * C + 255) / 256), dim3(256), 0, (hipStream_t)stream, x, gy, B,
-                     H, W, C, k, stride, dw);
-  NBDT_LAUNCH_CHECK();
-  return NBDT_OK;
+  return ref_dwconv_bwd_weight_impl(x, gy, B, H, W, C, k, stride, k / 2, k / 2, dw, stream);
+}
+
+/* the same three with a low-side padding and any extents (nbdt_dwconv_fwd_pad / _bwd_data_pad / _bwd_weight_pad) */
+extern "C" int nbdt_ref_dwconv_fwd_pad(const float* x, const float* w, int32_t B, int32_t H, int32_t W, int32_t C,
+                                       int32_t k, int32_t stride, int32_t pad_top, int32_t pad_left, float* y,
+                                       void* stream) {
+  if (int rc = ref_check_pad(B, H, W, k, stride, pad_top, pad_left)) return rc;
+  NBDT_REQUIRE(x && w && y && C > 0, "null argument");
+  return ref_dwconv_fwd_impl(x, w, B, H, W, C, k, stride, pad_top, pad_left, y, stream);
+}
+
+extern "C" int nbdt_ref_dwconv_bwd_data_pad(const float* gy, const float* w, int32_t B, int32_t H, int32_t W, int32_t C,
+                                            int32_t k, int32_t stride, int32_t pad_top, int32_t pad_left, float* gx,
+                                            void* stream) {
+  if (int rc = ref_check_pad(B, H, W, k, stride, pad_top, pad_left)) return rc;
+  NBDT_REQUIRE(gy && w && gx && C > 0, "null argument");
+  return ref_dwconv_bwd_data_impl(gy, w, B, H, W, C, k, stride, pad_top, pad_left, gx, stream);
+}
+
+extern "C" int nbdt_ref_dwconv_bwd_weight_pad(const float* x, const float* gy, int32_t B, int32_t H, int32_t W, int32_t C,
+                                              int32_t k, int32_t stride, int32_t pad_top, int32_t pad_left, float* dw,
+                                              void* stream) {
+  if (int rc = ref_check_pad(B, H, W, k, stride, pad_top, pad_left)) return rc;
+  NBDT_REQUIRE(x && gy && dw && C > 0, "null argument");
+  return ref_dwconv_bwd_weight_impl(x, gy, B, H, W, C, k, stride, pad_top, pad_left, dw, stream);
 }

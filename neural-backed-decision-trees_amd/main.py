@@ -92,8 +92,9 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   checkpoint gains ``net_ema``, ``acc_ema`` and ``ema_updates`` and its name ``-ema``.  ``--resume`` restores the average
   when the checkpoint has one, else starts it from the loaded weights; ``--eval --resume --use-ema`` evaluates ``net_ema``.
   ``SoftTreeLoss`` keeps inducing hierarchies from the live classifier.  Every rank keeps its own, bit-identical, average.
-* ``--stochastic-depth P`` (``--arch efficientnet_b0``) is torchvision's ``StochasticDepth(p, mode="row")``: in training,
-  image ``b`` of MBConv unit ``i`` of 16 loses its branch with probability ``P * i / 16`` wherever the unit has a skip
+* ``--stochastic-depth P`` (``--arch efficientnet_b0`` .. ``efficientnet_b7b``) is torchvision's
+  ``StochasticDepth(p, mode="row")``: in training, image ``b`` of MBConv unit ``i`` of the architecture's ``U`` units (16 for
+  B0, 55 for B7) loses its branch with probability ``P * i / U`` wherever the unit has a skip
   connection, inside the residual add and the BatchNorm backward that run anyway, plus one launch per forward that
   draws the factors (``engine.set_stochastic_depth(P, stream=rank)``: every rank and every micro-batch of
   ``--accum-steps`` draws its own).  Evaluation and ``--eval`` ignore it.  The draw's counter is not saved: a resumed run
@@ -257,7 +258,7 @@ def build_parser():
                         "(engine.clip_grad_norm; torchvision's --clip-grad-norm).  Default: off")
     p.add_argument("--stochastic-depth", type=float, default=0.0, metavar="P",
                    help="stochastic depth (drop-connect) on the MBConv units with a skip connection, torchvision's "
-                        "StochasticDepth(P * i / 16, 'row') for unit i, in training only (--arch efficientnet_b0; the "
+                        "StochasticDepth(P * i / units, 'row') for unit i, in training only (--arch efficientnet_b0 .. b7b; the "
                         "published recipe: 0.2).  Default 0: off")
     return p
 
@@ -555,7 +556,7 @@ def parse_args(argv=None):
                                                  "set_stochastic_depth"):
         parser.error(f"--stochastic-depth is built into the MBConv residual passes: --arch {args.arch} has no "
                      "set_stochastic_depth (the ResNet / WideResNet residual add lives inside conv epilogues); use "
-                     "--arch efficientnet_b0")
+                     "--arch efficientnet_b0 .. efficientnet_b7b")
     if args.use_ema and not (args.eval and args.resume):
         parser.error("--use-ema evaluates a checkpoint's averaged weights: it needs --eval and --resume")
     if args.mixup_alpha > 0 or args.cutmix_alpha > 0:

@@ -218,6 +218,17 @@ SIGNATURES = {
     "nbdt_bn_act_se_bwd_apply": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, c_int32,
                                          _P, _P, _P, _P, _P]),
     "nbdt_dwconv_bwd_weight": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    # padded strided convolutions (nbdt_version() >= 126): (..., k | cpad, stride, pad_top, pad_left, ...)
+    "nbdt_dwconv_fwd_pad": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
+    "nbdt_dwconv_bwd_data_pad": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "nbdt_dwconv_bwd_weight_pad": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "nbdt_stem_conv_pad": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "nbdt_stem_wgrad_pad": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "nbdt_ref_dwconv_fwd_pad": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "nbdt_ref_dwconv_bwd_data_pad": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "nbdt_ref_dwconv_bwd_weight_pad": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "nbdt_ref_stem_conv_pad": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
+    "nbdt_ref_stem_wgrad_pad": (c_int, [_P, _P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, _P, _P]),
     "nbdt_se_gate_fwd": (c_int, [_P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P]),
     "nbdt_se_gate_bwd": (c_int, [_P, _P, _P, _P, _P, _P, c_int32, c_int32, c_int32, c_int32, _P, _P, _P, _P, _P,
                                  _P, _P, _P]),

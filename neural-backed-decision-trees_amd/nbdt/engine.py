@@ -413,8 +413,9 @@ class SegOp:
 
 
 class BatchNorm:
-    def __init__(self, store, name, c_real, scratch_owner, gamma=1.0):
+    def __init__(self, store, name, c_real, scratch_owner, gamma=1.0, eps=ops.BN_EPS):
         self.store, self.name, self.c_real = store, name, c_real
+        self.eps = float(eps)          # one value for the batch statistics, the evaluation transform and eval_affine
         self.C = _pad32(c_real)
         store.add(name + ".weight", (self.C,), lambda v: v.fill_(gamma))
         store.add(name + ".bias", (self.C,), lambda v: v.zero_())
@@ -432,7 +433,7 @@ class BatchNorm:
         """scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale: two [C] vectors computed
         once per parameter / running-statistics version (plumbing on parameters, not on the data path)."""
         if self._affine is None:
-            scale = self.gamma * torch.rsqrt(self.running_var + ops.BN_EPS)
+            scale = self.gamma * torch.rsqrt(self.running_var + self.eps)
             self._affine = (scale.contiguous(), (self.beta - self.running_mean * scale).contiguous())
         return self._affine
 
@@ -451,17 +452,17 @@ class BatchNorm:
             self._affine = None        # running statistics are about to change
             if fused:
                 ops.bn_finalize(x, self.owner.partials(x), self.mean, self.rstd, self.running_mean,
-                                self.running_var)
+                                self.running_var, eps=self.eps)
             elif slots_filled:
                 ops.bn_stats(x, self.owner.scratch(self.C), self.mean, self.rstd, self.running_mean,
-                             self.running_var, slots_filled=True)
+                             self.running_var, eps=self.eps, slots_filled=True)
             else:
                 ops.bn_stats(x, self.owner.scratch(self.C), self.mean, self.rstd, self.running_mean,
-                             self.running_var)
+                             self.running_var, eps=self.eps)
             self.num_batches_tracked += 1
         else:  # eval: running statistics (two [C]-sized plumbing ops, not on the training path)
             self.mean.copy_(self.running_mean)
-            torch.rsqrt(self.running_var + ops.BN_EPS, out=self.rstd)
+            torch.rsqrt(self.running_var + self.eps, out=self.rstd)
 
     def apply(self, x, y, relu=True, residual=None):
         ops.bn_apply(x, self.mean, self.rstd, self.gamma, self.beta, y, relu=relu, residual=residual)
@@ -1005,8 +1006,10 @@ class _Engine:
             comm.finish(self.store.grad)
             self._reserve_for(None)
 
+    bn_eps = ops.BN_EPS        # an engine whose BatchNorms use another eps sets it before it builds them
+
     def bn(self, name, c, gamma=1.0):
-        b = BatchNorm(self.store, name, c, self, gamma)
+        b = BatchNorm(self.store, name, c, self, gamma, eps=self.bn_eps)
         self.bns.append(b)
         return b
 

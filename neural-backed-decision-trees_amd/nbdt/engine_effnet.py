@@ -1,6 +1,7 @@
-"""EfficientNet-B0 execution engine (SURVEY.md row A4 / BASELINE config 5).
+"""EfficientNet execution engine: B0 (SURVEY.md row A4 / BASELINE config 5) and, scaled by ``efficientnet_config``, B1 .. B7
+and the TF-padded b0b .. b7b, at any image side >= 32.
 
-Restates pytorchcv's ``efficientnet_b0`` (the model the reference re-exports at
+Restates pytorchcv's ``efficientnet_b0`` .. ``efficientnet_b7b`` (the models the reference re-exports at
 nbdt/models/__init__.py:3 and names in README.md:141-151) as a fixed launch sequence over the HIP
 kernels: 1x1 expand / project convolutions are the implicit-GEMM kernels (csrc/conv_dma.hip) with the
 following BatchNorm's statistics fused into their epilogue; depthwise convolutions, BatchNorm + swish,
@@ -29,12 +30,90 @@ B0_STAGES = [
 ]
 ACT = ops.ACT_SWISH
 
+# pytorchcv get_efficientnet: the B0 groups, and per version (width factor, depth factor, native input size, dropout rate)
+_BASE_LAYERS = [1, 2, 2, 3, 3, 4, 1]
+_BASE_CHANNELS = [16, 24, 40, 80, 112, 192, 320]
+_BASE_EXPANSION = [1, 6, 6, 6, 6, 6, 6]
+_BASE_KERNEL = [3, 3, 5, 3, 5, 5, 3]
+_BASE_STRIDE = [1, 2, 2, 2, 1, 2, 1]          # of a group's first unit
+EFFNET_SCALING = {
+    "b0": (1.0, 1.0, 224, 0.2), "b1": (1.0, 1.1, 240, 0.2), "b2": (1.1, 1.2, 260, 0.3), "b3": (1.2, 1.4, 300, 0.3),
+    "b4": (1.4, 1.8, 380, 0.4), "b5": (1.6, 2.2, 456, 0.4), "b6": (1.8, 2.6, 528, 0.5), "b7": (2.0, 3.1, 600, 0.5),
+}
+
+
+def round_channels(c, divisor=8):
+    """pytorchcv round_channels: the nearest multiple of 8, never more than 10 % below c."""
+    r = max(int(c + divisor / 2.0) // divisor * divisor, divisor)
+    if float(r) < 0.9 * c:
+        r += divisor
+    return r
+
+
+def efficientnet_config(version, tf_mode=False):
+    """What EfficientNetEngine needs to build pytorchcv's efficientnet_<version> (tf_mode: the `b` names, e.g. b7b):
+    {"stages": in the shape of B0_STAGES, "init_channels", "final_channels", "dropout_rate", "in_size", "bn_eps",
+    "tf_mode"}.  Depth scales a group's unit count by ceil, width its channels by round_channels (the final block only when
+    width > 1); a group whose first unit has stride 1 continues the previous stage (except the first), which fixes the
+    stage / unit numbers and so the state_dict keys.  tf_mode changes the padding rule (ops.conv_padding(same=True)) and the
+    BatchNorm eps (1e-3 instead of 1e-5), nothing else."""
+    if version not in EFFNET_SCALING:
+        raise ValueError(f"unknown EfficientNet version {version!r}: one of {sorted(EFFNET_SCALING)}")
+    width, depth, in_size, dropout = EFFNET_SCALING[version]
+    stages = []
+    for n, c, e, k, s in zip(_BASE_LAYERS, _BASE_CHANNELS, _BASE_EXPANSION, _BASE_KERNEL, _BASE_STRIDE):
+        units = [(round_channels(c * width), k, e)] * int(math.ceil(n * depth))
+        if s != 1 or not stages:
+            stages.append((s, units))
+        else:
+            stages[-1] = (stages[-1][0], stages[-1][1] + units)
+    return {"stages": stages, "init_channels": round_channels(32 * width),
+            "final_channels": round_channels(1280 * width) if width > 1.0 else 1280, "dropout_rate": dropout,
+            "in_size": in_size, "bn_eps": 1e-3 if tf_mode else 1e-5, "tf_mode": bool(tf_mode)}
+
+
+def efficientnet_layout(config, num_classes=1000):
+    """[(state_dict key, logical shape)] of the parameters of the model `config` describes, in pytorchcv's module order
+    -- derived from the configuration alone (no device): what an engine built from it exposes, and what a checkpoint
+    of pytorchcv's model holds.  BatchNorm contributes .weight and .bias (buffers are not listed)."""
+    out = []
+
+    def conv(name, cout, cin, k):
+        out.append((name + ".conv.weight", (cout, cin, k, k)))
+        out.extend([(name + ".bn.weight", (cout,)), (name + ".bn.bias", (cout,))])
+
+    def se(name, c, mid):
+        out.extend([(name + ".conv1.weight", (mid, c, 1, 1)), (name + ".conv1.bias", (mid,)),
+                    (name + ".conv2.weight", (c, mid, 1, 1)), (name + ".conv2.bias", (c,))])
+
+    cin = config["init_channels"]
+    conv("features.init_block.conv", cin, 3, 3)
+    for i, (_, specs) in enumerate(config["stages"]):
+        for j, (cout, k, exp) in enumerate(specs):
+            pre, mid = f"features.stage{i + 1}.unit{j + 1}.", cin * exp
+            if i == 0:
+                conv(pre + "dw_conv", mid, 1, k)
+                se(pre + "se", mid, mid // 4)
+                conv(pre + "pw_conv", cout, mid, 1)
+            else:
+                conv(pre + "conv1", mid, cin, 1)
+                conv(pre + "conv2", mid, 1, k)
+                se(pre + "se", mid, mid // (4 * exp))
+                conv(pre + "conv3", cout, mid, 1)
+            cin = cout
+    out.append(("features.final_block.conv.weight", (config["final_channels"], cin, 1, 1)))
+    out.extend([("features.final_block.bn.weight", (config["final_channels"],)),
+                ("features.final_block.bn.bias", (config["final_channels"],))])
+    out.extend([("output.fc.weight", (num_classes, config["final_channels"])), ("output.fc.bias", (num_classes,))])
+    return out
+
 
 class DepthwiseConv:
     """groups=C Conv2d(k, stride, padding=k//2), bias-free; master weights fp32 [k*k][Cpad]."""
 
-    def __init__(self, store, name, c_real, k, stride, gen):
+    def __init__(self, store, name, c_real, k, stride, gen, same=False):
         self.store, self.name, self.c_real, self.k, self.stride = store, name, c_real, k, stride
+        self.same = same            # TF "SAME" padding (ops.conv_padding) instead of the symmetric k // 2
         self.C = _pad32(c_real)
         bound = math.sqrt(2.0) * math.sqrt(3.0 / (k * k))   # kaiming_uniform_(a=0), fan_in = k*k
 
@@ -49,8 +128,18 @@ class DepthwiseConv:
         v = self.store._view(buf, self.name).view(self.k, self.k, self.C)
         return v[:, :, :self.c_real].permute(2, 0, 1).unsqueeze(1)      # [C, 1, k, k]
 
+    def pad(self, hw):
+        """None: the launches without a padding argument (padding k // 2, extents the stride divides -- every B0 layer at
+        a multiple of 32); else (top, left) for the input extents hw."""
+        h, w = hw
+        if self.stride == 1 or (not self.same and h % 2 == 0 and w % 2 == 0):
+            return None
+        return (ops.conv_padding(h, self.k, self.stride, self.same)[0],
+                ops.conv_padding(w, self.k, self.stride, self.same)[0])
+
     def forward(self, x, y, bn_scratch=None):
-        ops.dwconv_fwd(x, self.store.p(self.name), y, self.k, self.stride, bn_scratch)
+        ops.dwconv_fwd(x, self.store.p(self.name), y, self.k, self.stride, bn_scratch,
+                       pad=self.pad((x.shape[1] - 2, x.shape[2] - 2)))
 
     def backward_data(self, gy, gx, bn=None, bn_x=None):
         """bn/bn_x: `gx` is dL/d(swish(bn(bn_x))) -- also leave that BatchNorm's backward sums in its owner's slots
@@ -59,19 +148,21 @@ class DepthwiseConv:
             assert self.stride == 1
             bn.dwconv_backward_data(gy, self.store.p(self.name), gx, self.k, bn_x)
             return
-        ops.dwconv_bwd_data(gy, self.store.p(self.name), gx, self.k, self.stride)
+        ops.dwconv_bwd_data(gy, self.store.p(self.name), gx, self.k, self.stride,
+                            pad=self.pad((gx.shape[1] - 2, gx.shape[2] - 2)))
 
     def backward_weight(self, x, gy, also):
         """also: a further launch that only feeds the optimizer (the SE block's parameter gradients), issued behind the
         weight gradient on the same stream -- one cross-stream dependency for both."""
         side = self.side_stream
+        pad = self.pad((x.shape[1] - 2, x.shape[2] - 2))
         if side is None:
-            ops.dwconv_bwd_weight(x, gy, self.store.g(self.name), self.k, self.stride)
+            ops.dwconv_bwd_weight(x, gy, self.store.g(self.name), self.k, self.stride, pad=pad)
             also()
             return
         side.wait_stream(torch.cuda.current_stream(x.device))     # second stream: see WRNEngine
         with torch.cuda.stream(side):
-            ops.dwconv_bwd_weight(x, gy, self.store.g(self.name), self.k, self.stride)
+            ops.dwconv_bwd_weight(x, gy, self.store.g(self.name), self.k, self.stride, pad=pad)
             also()
 
 
@@ -114,9 +205,14 @@ class SqueezeExcite:
 
 class EfficientNetEngine(_Engine):
     def __init__(self, num_classes=1000, dropout_rate=0.2, stages=B0_STAGES, init_channels=32,
-                 final_channels=1280, device="cuda", seed=0, stochastic_depth_prob=0.0):
+                 final_channels=1280, device="cuda", seed=0, stochastic_depth_prob=0.0, bn_eps=1e-5, tf_mode=False):
+        """stages / init_channels / final_channels / dropout_rate / bn_eps / tf_mode: efficientnet_config(version,
+        tf_mode) names them all (EfficientNetEngine.from_config); the defaults are B0."""
         super().__init__(device, seed)
         self.num_classes, self.dropout_rate = num_classes, float(dropout_rate)
+        self.bn_eps, self.tf_mode = float(bn_eps), bool(tf_mode)
+        if len(stages) != 5 or len(stages[2][1]) < 1 or sum(len(sp) for _, sp in stages) > ops._C.NBDT_SD_MAX_UNITS:
+            raise ValueError("EfficientNetEngine takes five stages and at most %d units" % ops._C.NBDT_SD_MAX_UNITS)
         gen = self.gen
         self.stem_c = init_channels
         b0 = math.sqrt(2.0) * math.sqrt(3.0 / 27)
@@ -135,7 +231,7 @@ class EfficientNetEngine(_Engine):
                      "index": len(self.units)}
                 if i == 0:   # EffiDwsConvUnit: depthwise -> SE -> pointwise
                     u["conv1"] = u["bn1"] = None
-                    u["dw"] = DepthwiseConv(self.store, pre + "dw_conv.conv.weight", mid, k, stride, gen)
+                    u["dw"] = DepthwiseConv(self.store, pre + "dw_conv.conv.weight", mid, k, stride, gen, self.tf_mode)
                     u["bn2"] = self.bn(pre + "dw_conv.bn", mid)
                     u["se"] = SqueezeExcite(self.store, pre + "se", mid, mid // 4, gen)
                     u["conv3"] = self.conv(pre + "pw_conv.conv.weight", mid, cout, 1, 1)
@@ -143,7 +239,7 @@ class EfficientNetEngine(_Engine):
                 else:        # EffiInvResUnit: expand -> depthwise -> SE -> project
                     u["conv1"] = self.conv(pre + "conv1.conv.weight", cin, mid, 1, 1)
                     u["bn1"] = self.bn(pre + "conv1.bn", mid)
-                    u["dw"] = DepthwiseConv(self.store, pre + "conv2.conv.weight", mid, k, stride, gen)
+                    u["dw"] = DepthwiseConv(self.store, pre + "conv2.conv.weight", mid, k, stride, gen, self.tf_mode)
                     u["bn2"] = self.bn(pre + "conv2.bn", mid)
                     u["se"] = SqueezeExcite(self.store, pre + "se", mid, mid // (exp * 4), gen)
                     u["conv3"] = self.conv(pre + "conv3.conv.weight", mid, cout, 1, 1)
@@ -169,6 +265,28 @@ class EfficientNetEngine(_Engine):
         self.sd_counter = 0            # the counter the NEXT training forward draws with; not saved: a resumed run restarts it
         self._sd_rows = None           # the [units, B] table the last forward drew (None: it drew none) -- what backward reads
         self.set_stochastic_depth(stochastic_depth_prob)
+
+    @classmethod
+    def from_config(cls, config, **kwargs):
+        """An engine from efficientnet_config(version, tf_mode); keywords override (dropout_rate, num_classes, ...)."""
+        args = {k: config[k] for k in ("stages", "init_channels", "final_channels", "dropout_rate", "bn_eps", "tf_mode")}
+        args.update(kwargs)
+        return cls(**args)
+
+    def _stem_pad(self, H, W):
+        """(top, left) of the 3x3/2 stem, or None for the launch without a padding argument (see DepthwiseConv.pad)."""
+        if not self.tf_mode and H % 2 == 0 and W % 2 == 0:
+            return None
+        return (ops.conv_padding(H, 3, 2, self.tf_mode)[0], ops.conv_padding(W, 3, 2, self.tf_mode)[0])
+
+    def _add(self, a, b, out):
+        """out = a + b on padded tensors of one shape, as the BatchNorm + residual pass with the identity transform
+        (x * 1 + 0 is exact): the skip gradient of a stage-1 unit, which has no expand convolution to accumulate it."""
+        C = a.shape[3]
+        if ("ident", C) not in self._bufs:
+            self._bufs[("ident", C)] = (torch.zeros(C, device=self.device), torch.ones(C, device=self.device))
+        zero, one = self._bufs[("ident", C)]
+        ops.bn_act_apply(a, zero, one, one, zero, out, act=ops.ACT_NONE, residual=b)
 
     def set_stochastic_depth(self, prob, stream=0):
         """torchvision's StochasticDepth(p, mode="row") on every unit with a skip connection: in training, image b of unit
@@ -219,14 +337,14 @@ class EfficientNetEngine(_Engine):
                     bn2 + SE elementwise 3D | depthwise
                     weight gradient E + D, data gradient + bn1 sums D + 2E | bn1 elementwise 3E | expand weight gradient
                     X + E, data gradient E + X (+ X when it accumulates onto the skip gradient)"""
-        h = w = size // 2
+        h = w = ops.conv_out_size(size, 2)
         e = lambda hh, ww, c: 2 * B * hh * ww * _pad32(c)       # bytes of one bf16 tensor
         stem = e(h, w, self.stem_c)
         total = 12 * B * size * size + 2 * stem + 2 * stem      # image in, stem conv out, BatchNorm + swish (read + write)
         total += 5 * stem + 12 * B * size * size + stem         # backward of that BatchNorm, stem weight gradient
         for u in self.units:
             s = u["stride"]
-            ho, wo = h // s, w // s
+            ho, wo = ops.conv_out_size(h, s), ops.conv_out_size(w, s)
             X, O = e(h, w, u["cin"]), e(ho, wo, u["cout"])
             E, D = e(h, w, u["mid"]), e(ho, wo, u["mid"])
             res = X if u["residual"] else 0
@@ -235,7 +353,7 @@ class EfficientNetEngine(_Engine):
                 bwd = 5 * O + (D + O) + (O + D) + 2 * D + 3 * D + (E + D) + (D + 2 * E) + 3 * E + (X + E) + (E + X) + res
             else:       # stage 1: depthwise on the unit's input, no expand conv
                 fwd = (X + D) + D + 2 * D + (D + O) + 2 * O + res
-                bwd = 5 * O + (D + O) + (O + D) + 2 * D + 3 * D + (X + D) + (D + X)
+                bwd = 5 * O + (D + O) + (O + D) + 2 * D + 3 * D + (X + D) + (D + X) + 3 * res   # (+ the skip gradient's add)
             total += fwd + bwd
             h, w = ho, wo
         F, L = e(h, w, self.feat_c), e(h, w, self.units[-1]["cout"])
@@ -246,16 +364,17 @@ class EfficientNetEngine(_Engine):
     # ------------------------------------------------------------------ forward
     def forward(self, img, training=None):
         training = self.training if training is None else training
-        if img.shape[2] % 32 or img.shape[3] % 32:
-            raise ValueError("EfficientNet input size must be a multiple of 32")
+        if img.shape[2] < 32 or img.shape[3] < 32:
+            raise ValueError("EfficientNet input sides must be at least 32")
         img = self._input(img)
         B, _, H, W = img.shape
         fuse = training and self.fuse_stats
-        h, w = H // 2, W // 2
+        h, w = ops.conv_out_size(H, 2), ops.conv_out_size(W, 2)
         c0 = _pad32(self.stem_c)
         t0 = self.buf("t0", B, h, w, c0)
         x = self.buf("a0", B, h, w, c0)
-        ops.stem_conv(img, self.store.p("features.init_block.conv.conv.weight"), t0, self.stem_c, stride=2)
+        ops.stem_conv(img, self.store.p("features.init_block.conv.conv.weight"), t0, self.stem_c, stride=2,
+                      pad=self._stem_pad(H, W))
         self.bn0.stats(t0, training)
         self.bn0.act_apply(t0, x, act=ACT)
         self._sd_rows = None
@@ -269,7 +388,7 @@ class EfficientNetEngine(_Engine):
         for u in self.units:
             k, s = u["key"], u["stride"]
             cin, mid, cout = _pad32(u["cin"]), _pad32(u["mid"]), _pad32(u["cout"])
-            ho, wo = h // s, w // s
+            ho, wo = ops.conv_out_size(h, s), ops.conv_out_size(w, s)
             if u["conv1"] is not None:
                 e_raw = self.buf(k + ".e_raw", B, h, w, mid)
                 e_act = self.buf(k + ".e_act", B, h, w, mid)
@@ -425,12 +544,17 @@ class EfficientNetEngine(_Engine):
                     g_in = self.buf(f"g_{cin}_{hi}{tag}", B, hi, wi, cin)
                     u["conv1"].backward_data(ge, g_in)
             else:
-                g_in = self.buf(f"g_{cin}_{hi}{tag}", B, hi, wi, cin)
+                # (a unit with a skip still needs g after the data gradient is written: never the buffer g lives in)
+                skip = f"_s{par}" if u["residual"] else ""
+                g_in = self.buf(f"g_{cin}_{hi}{skip}{tag}", B, hi, wi, cin)
                 u["dw"].backward_weight(x_in, gd, also=se_params)
                 u["dw"].backward_data(gd, g_in)
+                if u["residual"]:      # (B1 and up: stage 1 has a second unit, 16 -> 16 channels) the skip gradient
+                    self._add(g_in, g, g_in)
             u["dbg"] = {"g_out": g, "g_in": g_in, "gp": gp, "gd": gd}
             g, h, w = g_in, hi, wi
         t0 = self.buf("t0", B, h, w, _pad32(self.stem_c))
         self.bn0.act_backward(g, t0, g, act=ACT)
-        ops.stem_wgrad(self._img, g, st.g("features.init_block.conv.conv.weight"), self.stem_c, stride=2)
+        ops.stem_wgrad(self._img, g, st.g("features.init_block.conv.conv.weight"), self.stem_c, stride=2,
+                       pad=self._stem_pad(self._img.shape[2], self._img.shape[3]))
         self._end_backward(comm)

@@ -647,8 +647,38 @@ def pool_bn_bwd_apply(gpooled, x, mean, rstd, gamma, beta, dsum, gx):
                                        B, H, W, C, ptr(gx), st))
 
 
-def stem_conv(img, w, out, cout_real, stride=1):
+def conv_out_size(h, stride):
+    """Output extent of a strided convolution of this package: ceil(h / stride), for both padding rules."""
+    return -(-int(h) // int(stride))
+
+
+def conv_padding(h, k, stride, same=False):
+    """(low, high) zero padding of one axis of a k-tap convolution with conv_out_size(h, stride) outputs.  same=False:
+    PyTorch's symmetric padding=k // 2.  same=True: TensorFlow's "SAME" rule, total = max((out - 1) * stride + k - h, 0)
+    with the odd pixel on the high side; it differs from the symmetric rule only for stride 2 on an even extent
+    (k = 3: (0, 1), k = 5: (1, 2))."""
+    if not same or stride == 1:
+        return k // 2, k // 2
+    total = max((conv_out_size(h, stride) - 1) * stride + k - int(h), 0)
+    return total // 2, total - total // 2
+
+
+def _check_out(x_hw, y, stride):
+    want = (conv_out_size(x_hw[0], stride) + 2, conv_out_size(x_hw[1], stride) + 2)
+    if tuple(y.shape[1:3]) != want:
+        raise ValueError(f"output tensor is {tuple(y.shape[1:3])} with its border, the convolution writes {want}")
+
+
+def stem_conv(img, w, out, cout_real, stride=1, pad=None):
+    """pad: None = padding 1 on extents the stride divides; (top, left) = the low-side padding of
+    nbdt_stem_conv_pad, any extents."""
     B, _, H, W = img.shape
+    if pad is not None:
+        _check_out((H, W), out, stride)
+        fn = lib().nbdt_ref_stem_conv_pad if _ref(out) else lib().nbdt_stem_conv_pad
+        check(fn(ptr(img), ptr(w), B, H, W, cout_real, out.shape[3], stride, int(pad[0]), int(pad[1]), ptr(out),
+                 stream_ptr(img.device)))
+        return
     if _ref(out):
         check(lib().nbdt_ref_stem_conv(ptr(img), ptr(w), B, H, W, cout_real, out.shape[3], stride, ptr(out),
                                        stream_ptr(img.device)))
@@ -657,8 +687,14 @@ def stem_conv(img, w, out, cout_real, stride=1):
                                stream_ptr(img.device)))
 
 
-def stem_wgrad(img, gy, dw, cout_real, stride=1):
+def stem_wgrad(img, gy, dw, cout_real, stride=1, pad=None):
     B, _, H, W = img.shape
+    if pad is not None:
+        _check_out((H, W), gy, stride)
+        fn = lib().nbdt_ref_stem_wgrad_pad if _ref(gy) else lib().nbdt_stem_wgrad_pad
+        check(fn(ptr(img), ptr(gy), B, H, W, cout_real, gy.shape[3], stride, int(pad[0]), int(pad[1]), ptr(dw),
+                 stream_ptr(img.device)))
+        return
     if _ref(gy):
         check(lib().nbdt_ref_stem_wgrad(ptr(img), ptr(gy), B, H, W, cout_real, gy.shape[3], stride, ptr(dw),
                                         stream_ptr(img.device)))
@@ -1232,9 +1268,20 @@ def draw_stochastic_depth(seed, stream, counter, prob, scale, B):
     return np.where(u < prob[:, None], np.float32(0.0), scale[:, None]).astype(np.float32)
 
 
-def dwconv_fwd(x, w, y, k, stride, bn_scratch=None):
-    """bn_scratch: the 32-slot BN scratch; the kernel adds sum(y), sum(y^2) (fold with bn_stats(None, ...))."""
+def dwconv_fwd(x, w, y, k, stride, bn_scratch=None, pad=None):
+    """bn_scratch: the 32-slot BN scratch; the kernel adds sum(y), sum(y^2) (fold with bn_stats(None, ...)).
+    pad: None = padding k // 2 on extents the stride divides; (top, left) = the low-side padding of nbdt_dwconv_fwd_pad
+    (conv_padding), any extents, y holding conv_out_size rows and columns."""
     B, H, W, C = _dims(x)
+    if pad is not None:
+        _check_out((H, W), y, stride)
+        if _ref(x):
+            check(lib().nbdt_ref_dwconv_fwd_pad(ptr(x), ptr(w), B, H, W, C, k, stride, int(pad[0]), int(pad[1]), ptr(y),
+                                                stream_ptr(x.device)))
+            return
+        check(lib().nbdt_dwconv_fwd_pad(ptr(x), ptr(w), B, H, W, C, k, stride, int(pad[0]), int(pad[1]), ptr(y),
+                                        ptr(bn_scratch), stream_ptr(x.device)))
+        return
     if _ref(x):    # (no statistics from the fp32 twin: bn_stats re-reads the tensor in reference mode)
         check(lib().nbdt_ref_dwconv_fwd(ptr(x), ptr(w), B, H, W, C, k, stride, ptr(y), stream_ptr(x.device)))
         return
@@ -1242,8 +1289,13 @@ def dwconv_fwd(x, w, y, k, stride, bn_scratch=None):
                                 stream_ptr(x.device)))
 
 
-def dwconv_bwd_data(gy, w, gx, k, stride):
+def dwconv_bwd_data(gy, w, gx, k, stride, pad=None):
     B, H, W, C = _dims(gx)
+    if pad is not None:
+        _check_out((H, W), gy, stride)
+        fn = lib().nbdt_ref_dwconv_bwd_data_pad if _ref(gx) else lib().nbdt_dwconv_bwd_data_pad
+        check(fn(ptr(gy), ptr(w), B, H, W, C, k, stride, int(pad[0]), int(pad[1]), ptr(gx), stream_ptr(gx.device)))
+        return
     if _ref(gx):
         check(lib().nbdt_ref_dwconv_bwd_data(ptr(gy), ptr(w), B, H, W, C, k, stride, ptr(gx), stream_ptr(gx.device)))
         return
@@ -1290,8 +1342,13 @@ def bn_act_se_bwd_apply(gu, gate, gpool, sums, x, mean, rstd, gamma, beta, dsum,
                                          ptr(gx), stream_ptr(x.device)))
 
 
-def dwconv_bwd_weight(x, gy, dw, k, stride):
+def dwconv_bwd_weight(x, gy, dw, k, stride, pad=None):
     B, H, W, C = _dims(x)
+    if pad is not None:
+        _check_out((H, W), gy, stride)
+        fn = lib().nbdt_ref_dwconv_bwd_weight_pad if _ref(x) else lib().nbdt_dwconv_bwd_weight_pad
+        check(fn(ptr(x), ptr(gy), B, H, W, C, k, stride, int(pad[0]), int(pad[1]), ptr(dw), stream_ptr(x.device)))
+        return
     if _ref(x):
         check(lib().nbdt_ref_dwconv_bwd_weight(ptr(x), ptr(gy), B, H, W, C, k, stride, ptr(dw), stream_ptr(x.device)))
         return
