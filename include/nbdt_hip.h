@@ -52,6 +52,18 @@ const char* nbdt_debug_last_igemm(void);
  * 2>"): what bench.py compares with the kernel names of a committed PMC traffic file before quoting it */
 const char* nbdt_debug_last_igemm_full(void);
 const char* nbdt_debug_last_wgrad(void);      /* same for nbdt_conv_wgrad */
+/* Which form the calling thread's last rules launch took (nbdt_soft_forward, nbdt_soft_backward, the tree losses,
+ * nbdt_hard_forward, nbdt_node_outputs, nbdt_tree_stats_accumulate): "lds" (rows and staged operands in LDS),
+ * "lds-unstaged" (rows in LDS, direct-indexed chains), "global" (rows in global memory), "" before the first launch.
+ * See "Size limits" at nbdt_tree_create.  nbdt_version() >= 127. */
+const char* nbdt_debug_last_rules_path(void);
+/* Form of the per-sample rules kernels (process-wide, default 0; nbdt_version() >= 127).  0: automatic -- the LDS forms
+ * wherever a sample's row fits LDS, exactly as before this switch existed, and the global-row form only where they
+ * cannot run.  1: the global-row form for every hierarchy; for tests and measurements (it is slower wherever the LDS
+ * forms run).  The diagnostics and the fused head have no global-row form and ignore the switch.  Anything else is
+ * NBDT_EINVAL. */
+int nbdt_set_rules_path(int mode);
+int nbdt_get_rules_path(void);
 int nbdt_version(void);
 /* Deterministic mode (process-wide switch, default off).  The reference's CPU path (stock ATen ops,
  * nbdt/models/resnet.py:69-74) gives the same bits on every run; the fast path does not: every cross-block fp32
@@ -121,10 +133,23 @@ int nbdt_weight_tile_batched(const void* src_bf16, const int64_t* table, int32_t
  *   child if it is an inner node, else -(class_index)-1.   All arrays are HOST pointers and are
  *   copied to `device`, together with the order in which a sample's lanes take the slots (longest first, dealt to
  *   the waves by load: csrc/rules.hip build_slot_schedule).
- * Size limits of the rules kernels (NBDT_EINVAL "hierarchy too large for LDS" beyond them): the per-sample rows
- *   (2-3 floats per class and per child slot) plus the offset arrays must fit 160 KB of LDS; when the sum of the
- *   leaf depths L = slot_off[R] also fits, the kernels stage the gathered operands there (ImageNet-1000: L = 11012),
- *   otherwise they index through the maps directly -- same results, slower. */
+ * Size limits of the rules kernels: none for the rules and the losses (nbdt_soft_forward, nbdt_soft_backward,
+ *   nbdt_soft_tree_loss[_ex], nbdt_hard_tree_loss[_ex], nbdt_hard_forward, nbdt_node_outputs,
+ *   nbdt_node_logits_backward).  They take one of three forms, chosen per launch from the hierarchy alone:
+ *   - the per-sample rows (2-3 floats per class and per child slot) plus the offset arrays fit 160 KB of LDS, and so
+ *     does the sum of the leaf depths L = slot_off[R]: the kernels stage the gathered operands in LDS (ImageNet-1000:
+ *     L = 11012);
+ *   - the rows fit but L does not: they index through the maps directly -- same results, slower;
+ *   - the rows do not fit (from roughly 2,300 classes of a binary hierarchy): the rows live in global memory, in the
+ *     library's per-(device, stream) workspace: one row of about 3C + 2R floats per block of a grid of at most one
+ *     block per CU, whatever the batch (0.6 MB per row at 21,841 classes; the workspace allocates at least 64 MB and
+ *     25 % headroom: 187 MB there on 256 CUs).  NBDT_ENOMEM when the workspace cannot be
+ *     allocated; under hipGraph capture the workspace's rule holds (one eager launch first).  Same arithmetic contract:
+ *     node logits, node predictions, hard predictions and decision nodes / children are bit-equal to the LDS forms;
+ *     inner nodes with more than 64 children have their softmax sums folded by the whole block, in a fixed order.
+ *   Still limited (NBDT_EINVAL "hierarchy too large for LDS ..." / "classifier too wide for the fused head ..."):
+ *   nbdt_tree_stats_accumulate keeps its rows and counters in LDS, and nbdt_head_soft_tree_loss takes at most 512
+ *   classes and child slots. */
 typedef struct nbdt_tree nbdt_tree;
 int nbdt_tree_create(int device, int num_classes, int num_inodes, int root,
                      const int32_t* node_off, const int32_t* slot_off, const int32_t* slot_cls,
@@ -235,7 +260,9 @@ int nbdt_node_outputs(const nbdt_tree* t, const void* z, int ztype, int64_t B, i
  *   scores (nullable) fp32 [B,3], WRITTEN: entropy of softmax(z) (Entropy.score), top-1 minus top-2 softmax
  *   probability (TopDifference.score), max minus min of the entropies along the hard walk with the reference's
  *   leading 0 of the root entry included (NBDTEntropyMaxMin.score).
- * Limits: as the other rules kernels, plus 28 bytes of LDS per inner node for the block's counters. */
+ * Limits: the LDS forms' (the sample rows and the offset arrays in 160 KB of LDS: there is no global-row form of the
+ * diagnostics, whose confusion matrices alone are C*C int64), plus 28 bytes of LDS per inner node for the block's
+ * counters.  NBDT_EINVAL "hierarchy too large for LDS: ..." beyond them. */
 typedef struct nbdt_tree_stats {
   int64_t* totals;
   int64_t* confusion_net;

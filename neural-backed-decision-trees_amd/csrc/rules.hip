@@ -18,7 +18,9 @@
 //     and the chains then fold contiguous LDS (chains / long_chain);
 //   - one lane folds one slot, so a wave is busy for its longest slot: the host sorts the slots by length and
 //     deals chunks of 64 to the group's waves longest-processing-time first (build_slot_schedule);
-//   - hierarchies too deep for the staging row (sum of leaf depths > ~35k) take direct-indexed chains.
+//   - hierarchies too deep for the staging row (sum of leaf depths > ~35k) take direct-indexed chains;
+//   - hierarchies whose sample row itself does not fit LDS (from ~2,300 classes of a binary tree) take the kernels of
+//     rules_global.h, included below: the same phases on a row in global memory (rules_take_global).
 // profiles/r02_rules*.{jsonl,txt}: (256, 1000) soft forward 67.6 -> 11.3 us, fused loss 141 -> 23 us.
 //
 // Arithmetic contract (matches oracle/nbdt_oracle.py bit-for-bit on the integer outputs):
@@ -28,6 +30,7 @@
 #include "common.h"
 
 #include <algorithm>
+#include <atomic>
 #include <vector>
 
 namespace nbdt {
@@ -44,6 +47,8 @@ struct nbdt_tree {
   int32_t* d_all;  // one allocation
   const int32_t *node_off, *slot_off, *slot_cls, *cls_off, *cls_slot, *slot_next;
   const int32_t* sched;  // [3][sched_len]: slot id (or -1), first and one-past-last element in slot_cls
+  const int32_t* wide;   // [n_wide] inner nodes with more than kWideFan children (the global-row kernels, rules_global.h)
+  int n_wide;
 };
 
 struct TreeView {
@@ -1446,11 +1451,13 @@ __global__ __launch_bounds__(block_of(TPS)) void tree_stats_kernel(TreeView t, c
       if (ent[i] != 0ull) add_i64(a.node_entropy + i, (long long)ent[i]);
 }
 
+#include "rules_global.h"
+
 // ------------------------------------------------------------------------------------------
 // host side
 
 extern "C" const char* nbdt_last_error(void) { return nbdt::g_err; }
-extern "C" int nbdt_version(void) { return 126; }     // 125: nbdt_conv_group_weight_prep[_batched], nbdt_conv_group_fwd / _dgrad / _wgrad and their nbdt_ref_conv_group_* twins (the grouped 3x3 convolution of ResNeXt as block-diagonal 32 x 32 blocks: csrc/conv_group.hip); 124: nbdt_resized_crop_policy_batch[_sharded] (policy chains and random erasing on the resized-crop path: csrc/resample.hip, csrc/policy_ops.h); 123: nbdt_policy_chain_batch[_sharded] (RandAugment / AutoAugment chains: csrc/policy.hip); 122: nbdt_bn_act_apply_rows, nbdt_bn_act_bwd_rows, their nbdt_ref_* twins, nbdt_stochastic_depth_draw (stochastic depth inside the MBConv residual passes: csrc/effnet.hip); 120: nbdt_arena_opt_create / _destroy, nbdt_adamw_step, nbdt_rmsprop_step (AdamW and RMSprop over the flat arena: csrc/adaptive.hip); 119: nbdt_policy_batch[_sharded] (TrivialAugmentWide + random erasing on device-resident datasets: csrc/policy.hip); 118: nbdt_ema_update / _swap and their _multi forms (weight EMA: the fused shadow update and the in-place exchange for evaluation: csrc/ema.hip); 117: nbdt_lars_create / _destroy / _step / _ratios (LARS over the flat parameter arena: csrc/lars.hip); 116: nbdt_soft_tree_loss_ex, nbdt_hard_tree_loss_ex (label smoothing in both fused tree losses, probability targets in the soft one), nbdt_mix_batch (MixUp / CutMix and their targets in one launch: csrc/mix.hip); 115: nbdt_stem_patches, nbdt_maxpool3x3s2_fwd / _bwd (the 7x7 / 2 stem as a patch gather in front of the 1x1 convolution, and MaxPool2d(3, 2, 1), for torchvision-shaped ResNets: csrc/stem_pool.hip); 114: nbdt_augment_batch_sharded, nbdt_resized_crop_batch_sharded (a rank keeps its contiguous shard of a device-resident dataset: the draw from the dataset index, the gather from index - index_base); 113: nbdt_conv_pw (stride-1 1x1 convolutions as a GEMM: the Bottleneck ResNets); 112: nbdt_tree_stats_accumulate (tree diagnostics: per-node counters, confusion matrices, entropy sums, scores in one launch); 111: nbdt_resized_crop_batch, nbdt_resized_crop_band_rows (RandomResizedCrop / Resize + CenterCrop datasets); 110: nbdt_augment_batch (device-resident datasets: gather + crop + flip + normalise), NBDT_U8; 109: nbdt_set/get_stream_nt_min_bytes, nbdt_debug_last_stream_nt, nbdt_conv_seg_create refuses ntensors > 2; 108: nbdt_se_param_grad, nbdt_se_gate_bwd without parameter gradients; 107: nbdt_bn_act_se_sums / _se_bwd_apply; 106: nbdt_conv_desc.ksplit is live (was reserved), nbdt_conv_seg_*
+extern "C" int nbdt_version(void) { return 127; }     // 127: nbdt_set_rules_path / nbdt_get_rules_path / nbdt_debug_last_rules_path (the rules kernels with the sample row in global memory, for hierarchies too large for LDS: csrc/rules_global.h); 125: nbdt_conv_group_weight_prep[_batched], nbdt_conv_group_fwd / _dgrad / _wgrad and their nbdt_ref_conv_group_* twins (the grouped 3x3 convolution of ResNeXt as block-diagonal 32 x 32 blocks: csrc/conv_group.hip); 124: nbdt_resized_crop_policy_batch[_sharded] (policy chains and random erasing on the resized-crop path: csrc/resample.hip, csrc/policy_ops.h); 123: nbdt_policy_chain_batch[_sharded] (RandAugment / AutoAugment chains: csrc/policy.hip); 122: nbdt_bn_act_apply_rows, nbdt_bn_act_bwd_rows, their nbdt_ref_* twins, nbdt_stochastic_depth_draw (stochastic depth inside the MBConv residual passes: csrc/effnet.hip); 120: nbdt_arena_opt_create / _destroy, nbdt_adamw_step, nbdt_rmsprop_step (AdamW and RMSprop over the flat arena: csrc/adaptive.hip); 119: nbdt_policy_batch[_sharded] (TrivialAugmentWide + random erasing on device-resident datasets: csrc/policy.hip); 118: nbdt_ema_update / _swap and their _multi forms (weight EMA: the fused shadow update and the in-place exchange for evaluation: csrc/ema.hip); 117: nbdt_lars_create / _destroy / _step / _ratios (LARS over the flat parameter arena: csrc/lars.hip); 116: nbdt_soft_tree_loss_ex, nbdt_hard_tree_loss_ex (label smoothing in both fused tree losses, probability targets in the soft one), nbdt_mix_batch (MixUp / CutMix and their targets in one launch: csrc/mix.hip); 115: nbdt_stem_patches, nbdt_maxpool3x3s2_fwd / _bwd (the 7x7 / 2 stem as a patch gather in front of the 1x1 convolution, and MaxPool2d(3, 2, 1), for torchvision-shaped ResNets: csrc/stem_pool.hip); 114: nbdt_augment_batch_sharded, nbdt_resized_crop_batch_sharded (a rank keeps its contiguous shard of a device-resident dataset: the draw from the dataset index, the gather from index - index_base); 113: nbdt_conv_pw (stride-1 1x1 convolutions as a GEMM: the Bottleneck ResNets); 112: nbdt_tree_stats_accumulate (tree diagnostics: per-node counters, confusion matrices, entropy sums, scores in one launch); 111: nbdt_resized_crop_batch, nbdt_resized_crop_band_rows (RandomResizedCrop / Resize + CenterCrop datasets); 110: nbdt_augment_batch (device-resident datasets: gather + crop + flip + normalise), NBDT_U8; 109: nbdt_set/get_stream_nt_min_bytes, nbdt_debug_last_stream_nt, nbdt_conv_seg_create refuses ntensors > 2; 108: nbdt_se_param_grad, nbdt_se_gate_bwd without parameter gradients; 107: nbdt_bn_act_se_sums / _se_bwd_apply; 106: nbdt_conv_desc.ksplit is live (was reserved), nbdt_conv_seg_*
 extern "C" int nbdt_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1552,10 +1559,13 @@ extern "C" int nbdt_tree_create(int device, int C, int N, int root, const int32_
   std::vector<int32_t> sched;
   int sched_len = 0;
   build_slot_schedule(R, slot_off, pick_tps(C, R), &sched, &sched_len);
+  std::vector<int32_t> wide;
+  for (int n = 0; n < N; ++n)
+    if (node_off[n + 1] - node_off[n] > kWideFan) wide.push_back(n);
   nbdt_tree* t = new nbdt_tree();
   t->device = device; t->cus = cus; t->C = C; t->N = N; t->R = R; t->L = L; t->root = root; t->max_depth = max_depth;
   t->sched_len = sched_len;
-  const size_t n_ints = (size_t)(N + 1) + (R + 1) + L + (C + 1) + L + R + sched.size();
+  const size_t n_ints = (size_t)(N + 1) + (R + 1) + L + (C + 1) + L + R + sched.size() + wide.size();
   hipError_t e = hipMalloc((void**)&t->d_all, n_ints * sizeof(int32_t));
   if (e != hipSuccess) {
     delete t;
@@ -1576,6 +1586,8 @@ extern "C" int nbdt_tree_create(int device, int C, int N, int root, const int32_
   put(cls_slot, L, &t->cls_slot);
   put(slot_next, R, &t->slot_next);
   put(sched.data(), sched.size(), &t->sched);
+  put(wide.data(), wide.size(), &t->wide);
+  t->n_wide = (int)wide.size();
   e = hipMemcpy(t->d_all, host, n_ints * sizeof(int32_t), hipMemcpyHostToDevice);
   delete[] host;
   (void)hipSetDevice(prev);
@@ -1605,6 +1617,22 @@ static int pick_tps(const nbdt_tree* t) { return pick_tps(t->C, t->R); }
 constexpr size_t kLdsBytes = 160 * 1024;
 constexpr size_t kStagePad = 4;  // floats of slack behind the last staging row (chain() reads whole blocks)
 
+// Which form the per-sample kernels take (nbdt_set_rules_path): 0 = the LDS form wherever its row fits and the global-row
+// form (rules_global.h) where it does not, 1 = the global-row form for every hierarchy (tests and measurements).
+static std::atomic<int> g_rules_path{0};
+static thread_local int g_last_rules_path = 0;  // nbdt_debug_last_rules_path: 0 none yet, 1 LDS staged, 2 LDS unstaged, 3 global
+
+extern "C" int nbdt_set_rules_path(int mode) {
+  NBDT_REQUIRE(mode == 0 || mode == 1, "rules path must be 0 (automatic) or 1 (global rows)");
+  g_rules_path.store(mode, std::memory_order_relaxed);
+  return NBDT_OK;
+}
+extern "C" int nbdt_get_rules_path(void) { return g_rules_path.load(std::memory_order_relaxed); }
+extern "C" const char* nbdt_debug_last_rules_path(void) {
+  static const char* const names[] = {"", "lds", "lds-unstaged", "global"};
+  return names[g_last_rules_path];
+}
+
 template <typename... KA, typename... A>
 static int launch_rules(void (*kernel)(KA...), unsigned grid, int block, size_t shmem, hipStream_t st,
                         A... args) {
@@ -1627,7 +1655,10 @@ static int launch_rules(void (*kernel)(KA...), unsigned grid, int block, size_t 
     v.staged = ((size_t)v.tl_ints + (size_t)spb * (floats + t->L) + kStagePad) * sizeof(float) <= kLdsBytes; \
     if (v.staged) floats += t->L;                                                                    \
     const size_t shmem = ((size_t)v.tl_ints + (size_t)spb * floats + kStagePad) * sizeof(float);     \
-    NBDT_REQUIRE(shmem <= kLdsBytes, "hierarchy too large for LDS");                                 \
+    NBDT_REQUIRE(shmem <= kLdsBytes, (BLOCKS_PER_CU) > 0 ? "hierarchy too large for LDS: the tree diagnostics "   \
+                 "keep their rows and counters there (the rules and the losses run at any size)"     \
+                 : "hierarchy too large for LDS");                                                   \
+    g_last_rules_path = v.staged ? 1 : 2;                                                            \
     unsigned grid = (unsigned)((B + spb - 1) / spb);                                                 \
     if ((BLOCKS_PER_CU) > 0) {                                                                       \
       const int cus = t->cus;                                                                        \
@@ -1654,6 +1685,51 @@ static int launch_rules(void (*kernel)(KA...), unsigned grid, int block, size_t 
   } while (0)
 #define NBDT_DISPATCH_RULES(KERNEL, NEXT, BASE_FLOATS, ...) NBDT_DISPATCH_RULES_EX(KERNEL, NEXT, BASE_FLOATS, 0, 0, __VA_ARGS__)
 
+// ---- the global-row form (rules_global.h).  The automatic choice: exactly where NBDT_DISPATCH_RULES would refuse, i.e.
+// where the unstaged row of the call (BASE_FLOATS, NEXT as the call passes them) does not fit kLdsBytes.
+static bool rules_take_global(const nbdt_tree* t, bool next, size_t base_floats) {
+  if (g_rules_path.load(std::memory_order_relaxed) == 1) return true;
+  const int tps = pick_tps(t);
+  const size_t spb = (size_t)(block_of(tps) / tps);
+  return ((size_t)tree_lds_ints(t, next) + spb * base_floats + kStagePad) * sizeof(float) > kLdsBytes;
+}
+
+// floats of one block's row: zs, ss, ps and either pq, gx (the soft rules and the losses) or the two per-node int arrays
+// of the hard walk
+static size_t global_row_floats(const nbdt_tree* t) {
+  const size_t tail = std::max((size_t)2 * t->C, (size_t)2 * t->N);
+  return ((size_t)t->C + 2 * (size_t)t->R + tail + 3) & ~(size_t)3;
+}
+
+// The grid and its rows: one row per block, one block per CU (the loss and hard kernels take 60-97 VGPRs, so a CU holds
+// one 1024-lane block of them), never more blocks than samples.  The rows come from the per-(device, stream) workspace
+// (which allocates at least 64 MB and 25 % headroom), so the launch is stream-ordered behind its other users and follows
+// their rule under hipGraph capture (one eager launch first).
+static int global_rows(const nbdt_tree* t, int64_t B, hipStream_t st, GlobalRows* g, unsigned* grid) {
+  const size_t row = global_row_floats(t);
+  const size_t cus = (size_t)std::max(t->cus, 1);
+  const size_t blocks = std::min<size_t>((size_t)B, cus);
+  float* rows = det_rows(st, blocks * row);
+  if (!rows) return nbdt::fail(NBDT_ENOMEM, "rules: %s (%s)", "no workspace for the global sample rows", nbdt::det_rows_why());
+  g->rows = rows; g->row_floats = row; g->wide = t->wide; g->n_wide = t->n_wide;
+  *grid = (unsigned)blocks;
+  return NBDT_OK;
+}
+
+#define NBDT_DISPATCH_GLOBAL(KERNEL, ...)                                                             \
+  do {                                                                                                \
+    GlobalRows gr;                                                                                    \
+    unsigned ggrid = 0;                                                                               \
+    hipStream_t gst = (hipStream_t)stream;                                                            \
+    const int grc = global_rows(t, B, gst, &gr, &ggrid);                                              \
+    if (grc) return grc;                                                                              \
+    if (ztype == NBDT_F32) hipLaunchKernelGGL(KERNEL<LoadF32>, dim3(ggrid), dim3(kGlobalBlock), 0, gst, v, gr, __VA_ARGS__); \
+    else if (ztype == NBDT_BF16) hipLaunchKernelGGL(KERNEL<LoadBF16>, dim3(ggrid), dim3(kGlobalBlock), 0, gst, v, gr, __VA_ARGS__); \
+    else hipLaunchKernelGGL(KERNEL<LoadF16>, dim3(ggrid), dim3(kGlobalBlock), 0, gst, v, gr, __VA_ARGS__); \
+    NBDT_LAUNCH_CHECK();                                                                              \
+    g_last_rules_path = 3;                                                                            \
+  } while (0)
+
 static int check_common(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz) {
   NBDT_REQUIRE(t != nullptr, "null tree handle");
   NBDT_REQUIRE(z != nullptr || B == 0, "null logits");
@@ -1669,6 +1745,10 @@ extern "C" int nbdt_soft_forward(const nbdt_tree* t, const void* z, int ztype, i
   if (B == 0) return NBDT_OK;
   NBDT_REQUIRE(P != nullptr, "null output");
   TreeView v = view_of(t);
+  if (rules_take_global(t, false, t->C + 2 * t->R)) {
+    NBDT_DISPATCH_GLOBAL(global_soft_fwd_kernel, z, B, ldz, P);
+    return NBDT_OK;
+  }
   NBDT_DISPATCH_RULES(soft_fwd_kernel, false, t->C + 2 * t->R, v, z, B, ldz, P);
   return NBDT_OK;
 }
@@ -1680,6 +1760,10 @@ extern "C" int nbdt_soft_backward(const nbdt_tree* t, const void* z, int ztype, 
   if (B == 0) return NBDT_OK;
   NBDT_REQUIRE(gP != nullptr && gz != nullptr, "null gradient buffer");
   TreeView v = view_of(t);
+  if (rules_take_global(t, false, 2 * t->C + 2 * t->R)) {
+    NBDT_DISPATCH_GLOBAL(global_soft_bwd_kernel, z, B, ldz, gP, gz);
+    return NBDT_OK;
+  }
   NBDT_DISPATCH_RULES(soft_bwd_kernel, false, 2 * t->C + 2 * t->R, v, z, B, ldz, gP, gz);
   return NBDT_OK;
 }
@@ -1700,12 +1784,20 @@ extern "C" int nbdt_soft_tree_loss_ex(const nbdt_tree* t, const void* z, int zty
   NBDT_REQUIRE(B > 0, "empty batch has no mean loss");
   TreeView v = view_of(t);
   const float scale = grad_scale / (float)B;
-  if (y && smoothing == 0.f)
+  if (rules_take_global(t, false, NBDT_SOFT_LOSS_ROW_FLOATS(t->C, t->R))) {
+    if (y && smoothing == 0.f) {
+      NBDT_DISPATCH_GLOBAL(global_soft_loss_kernel, z, B, ldz, y, w_xent, w_tree, scale, row_loss, gz);
+    } else {
+      NBDT_DISPATCH_GLOBAL(global_soft_target_loss_kernel, z, B, ldz, y, tprob, ldt, smoothing, w_xent, w_tree, scale,
+                           row_loss, gz);
+    }
+  } else if (y && smoothing == 0.f) {
     NBDT_DISPATCH_RULES(soft_loss_kernel, false, NBDT_SOFT_LOSS_ROW_FLOATS(t->C, t->R), v, z, B, ldz, y, w_xent, w_tree, scale,
                         row_loss, gz);
-  else
+  } else {
     NBDT_DISPATCH_RULES(soft_target_loss_kernel, false, NBDT_SOFT_LOSS_ROW_FLOATS(t->C, t->R), v, z, B, ldz, y, tprob, ldt, smoothing,
                         w_xent, w_tree, scale, row_loss, gz);
+  }
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, row_loss, B, loss);
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;
@@ -1797,8 +1889,12 @@ extern "C" int nbdt_hard_tree_loss_ex(const nbdt_tree* t, const void* z, int zty
   NBDT_REQUIRE(B > 0, "empty batch has no mean loss");
   TreeView v = view_of(t);
   const float scale = grad_scale / (float)B;
-  NBDT_DISPATCH_RULES(hard_loss_kernel, false, 2 * t->C + 2 * t->R + 16, v, z, B, ldz, y, smoothing, w_xent, w_node,
-                      scale, row_loss, gz);
+  if (rules_take_global(t, false, 2 * t->C + 2 * t->R + 16)) {
+    NBDT_DISPATCH_GLOBAL(global_hard_loss_kernel, z, B, ldz, y, smoothing, w_xent, w_node, scale, row_loss, gz);
+  } else {
+    NBDT_DISPATCH_RULES(hard_loss_kernel, false, 2 * t->C + 2 * t->R + 16, v, z, B, ldz, y, smoothing, w_xent, w_node,
+                        scale, row_loss, gz);
+  }
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(kBlock), 0, (hipStream_t)stream, row_loss, B, loss);
   NBDT_LAUNCH_CHECK();
   return NBDT_OK;
@@ -1830,6 +1926,10 @@ extern "C" int nbdt_hard_forward(const nbdt_tree* t, const void* z, int ztype, i
                "decision buffers must be all set or all NULL");
   if (B == 0) return NBDT_OK;
   TreeView v = view_of(t);
+  if (rules_take_global(t, true, t->C + t->R + 8 + 2 * t->N)) {
+    NBDT_DISPATCH_GLOBAL(global_hard_fwd_kernel, z, B, ldz, pred, onehot, path_node, path_child, path_prob, path_entropy);
+    return NBDT_OK;
+  }
   NBDT_DISPATCH_RULES(hard_fwd_kernel, true, t->C + t->R + 8 + 2 * t->N, v, z, B, ldz, pred, onehot, path_node, path_child,
                       path_prob, path_entropy);
   return NBDT_OK;
@@ -1841,6 +1941,10 @@ extern "C" int nbdt_node_outputs(const nbdt_tree* t, const void* z, int ztype, i
   if (rc) return rc;
   if (B == 0) return NBDT_OK;
   TreeView v = view_of(t);
+  if (rules_take_global(t, false, t->C + 2 * t->R)) {
+    NBDT_DISPATCH_GLOBAL(global_node_outputs_kernel, z, B, ldz, logits, probs, preds, entropy);
+    return NBDT_OK;
+  }
   NBDT_DISPATCH_RULES(node_outputs_kernel, false, t->C + 2 * t->R, v, z, B, ldz, logits, probs, preds, entropy);
   return NBDT_OK;
 }

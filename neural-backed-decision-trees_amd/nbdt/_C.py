@@ -117,6 +117,9 @@ SIGNATURES = {
     "nbdt_debug_last_igemm": (c_char_p, []),
     "nbdt_debug_last_igemm_full": (c_char_p, []),
     "nbdt_debug_last_wgrad": (c_char_p, []),
+    "nbdt_debug_last_rules_path": (c_char_p, []),
+    "nbdt_set_rules_path": (c_int, [c_int]),
+    "nbdt_get_rules_path": (c_int, []),
     "nbdt_conv_wgrad_blocks": (c_int, [_P]),
     "nbdt_conv_plan": (c_int, [_P, _P, _P]),
     "nbdt_soft_forward": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P]),
@@ -409,6 +412,11 @@ class TreeHandle:
                 _lib.nbdt_tree_destroy(self.h)
         except Exception:
             pass
+
+
+def last_rules_path():
+    """Which form the calling thread's last rules launch took: "lds", "lds-unstaged" or "global" ("" before the first)."""
+    return lib().nbdt_debug_last_rules_path().decode()
 
 
 def _rows(z, handle):

@@ -34,6 +34,22 @@ def is_deterministic():
     return bool(lib().nbdt_get_deterministic())
 
 
+RULES_PATHS = ("auto", "global")
+
+
+def set_rules_path(name):
+    """Process-wide: "auto" (default) = the tree rules and losses keep a sample's row in LDS wherever it fits and take
+    the global-row kernels only for hierarchies too large for that; "global" = the global-row kernels for every
+    hierarchy, for tests and measurements (nbdt_set_rules_path in include/nbdt_hip.h)."""
+    if name not in RULES_PATHS:
+        raise ValueError(f"unknown rules path {name!r}: expected one of {RULES_PATHS}")
+    check(lib().nbdt_set_rules_path(RULES_PATHS.index(name)))
+
+
+def rules_path():
+    return RULES_PATHS[lib().nbdt_get_rules_path()]
+
+
 def set_wgrad_store_epilogue(on):
     """K-split weight gradient: 1 (default) = plain stores into per-split copies + a fold pass, 0 = fp32 atomics into dw
     (nbdt_set_wgrad_store_epilogue in include/nbdt_hip.h)."""
