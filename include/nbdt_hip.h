@@ -1390,6 +1390,36 @@ int nbdt_ref_stem_conv_pad(const float* img, const float* w, int32_t B, int32_t 
 int nbdt_ref_stem_wgrad_pad(const float* img, const float* gy, int32_t B, int32_t H, int32_t W, int32_t cout_real,
                             int32_t cpad, int32_t stride, int32_t pad_top, int32_t pad_left, float* dw, void* stream);
 
+/* ------------------------------------------------------------------ agglomerative clustering (nbdt_version() >= 128)
+ * What scipy.cluster.hierarchy.linkage / sklearn's AgglomerativeClustering compute for an induced hierarchy, on the
+ * device in fp64 (csrc/linkage.hip): one launch writes the full pairwise distance matrix of the n rows of `centers`
+ * (fp32 [n][d], contiguous, device memory) into the workspace, a second one -- a single workgroup -- runs the
+ * nearest-neighbour chain over it and writes the n - 1 merges in the order it found them:
+ *   merges_out  int32 [n-1][2]   (retired index, kept index): the two clusters merged, smaller index first; the merged
+ *                                cluster lives on under the larger index
+ *   heights_out fp64  [n-1]      the linkage distance of the merge
+ *   sizes_out   int32 [n-1]      leaves of the merged cluster (0 in every row of a run that did not finish, which only
+ *                                NaN distances can cause)
+ * Sorting the rows by height (stable) and relabelling with a union-find in which merge i creates cluster n + i gives
+ * scipy's linkage matrix (nbdt.graph.linkage_children does that on the host).  Ties are resolved towards the previous
+ * chain element, then the lowest index: same inputs, same bits.
+ * The workspace holds the matrix (8 n^2 bytes) and two int32 [n] arrays (cluster sizes, the chain);
+ * nbdt_linkage_workspace_bytes gives its size.  Its contents after a call are scratch, except that the first int32 of
+ * the second array (byte offset 8 n^2 + 4 n) holds the number of chain steps taken, for profiles.
+ * NBDT_EINVAL before any device call, outputs untouched: null pointers, n < 2 (or above 2^20), d < 1 (or above 2^24),
+ * an unknown method or metric, ward with another metric than euclidean, a workspace smaller than that size, misaligned
+ * pointers (8 bytes for workspace and heights_out, 4 for the others). */
+#define NBDT_LINKAGE_WARD 0
+#define NBDT_LINKAGE_COMPLETE 1
+#define NBDT_LINKAGE_SINGLE 2
+#define NBDT_LINKAGE_AVERAGE 3
+#define NBDT_METRIC_EUCLIDEAN 0
+#define NBDT_METRIC_MANHATTAN 1     /* sklearn's l1 / manhattan / cityblock */
+#define NBDT_METRIC_COSINE 2        /* 1 - x.y / (|x| |y|), the cosine clipped to [-1, 1] as scipy's pdist does */
+int nbdt_linkage_workspace_bytes(int64_t n, int64_t* bytes);
+int nbdt_linkage(const float* centers, int64_t n, int64_t d, int32_t method, int32_t metric, void* workspace,
+                 int64_t workspace_bytes, int32_t* merges_out, double* heights_out, int32_t* sizes_out, void* stream);
+
 /* ------------------------------------------------------------------ measurement probe (not on the product path) */
 /* A register-only stream of independent v_mfma_f32_32x32x16_bf16 on `blocks` CUs (one 512-thread block each, two waves
  * per SIMD): every wave issues iters x 16 of them (x 32768 flop).  bench.py times the launch for `roofline.mfma_stream`

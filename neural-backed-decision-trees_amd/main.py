@@ -172,7 +172,13 @@ def build_parser():
     p.add_argument("--hierarchy")
     p.add_argument("--path-graph")
     p.add_argument("--path-wnids")
-    losses.add_arguments(p)      # --xent-weight* / --tree-supervision-weight* / --tree-*-epochs (reference nbdt/loss.py:27-80)
+    p.add_argument("--induce-hierarchy", action="store_true",
+                   help="with --resume --path-resume FILE: write the hierarchy induced-<arch> (or --path-graph) from that "
+                        "checkpoint's classifier before the tree is built -- agglomerative clustering on the GPU "
+                        "(csrc/linkage.hip) -- then go on as usual")
+    p.add_argument("--induced-linkage", default="ward", choices=("ward", "complete", "single", "average"),
+                   help="--induce-hierarchy: the linkage (ward is what every shipped hierarchy uses)")
+    losses.add_arguments(p)     # --xent-weight* / --tree-supervision-weight* / --tree-*-epochs (reference nbdt/loss.py:27-80)
     # data source (see module docstring)
     p.add_argument("--data-file", help="torch.save'd dict: train_x, train_y, test_x, test_y")
     p.add_argument("--synthetic", type=int, default=0, help="number of synthetic training samples")
@@ -559,6 +565,11 @@ def parse_args(argv=None):
                      "--arch efficientnet_b0 .. efficientnet_b7b")
     if args.use_ema and not (args.eval and args.resume):
         parser.error("--use-ema evaluates a checkpoint's averaged weights: it needs --eval and --resume")
+    if args.induce_hierarchy:
+        if not (args.resume and args.path_resume):
+            parser.error("--induce-hierarchy clusters a trained classifier: it needs --resume --path-resume FILE")
+        if args.hierarchy and args.hierarchy != f"induced-{args.arch}":
+            parser.error(f"--induce-hierarchy writes induced-{args.arch} (or --path-graph), not --hierarchy {args.hierarchy}")
     if args.mixup_alpha > 0 or args.cutmix_alpha > 0:
         name = args.loss[-1]            # the loss the training step calls
         if name != "CrossEntropyLoss" and not hasattr(getattr(losses, name), "soft_target_loss_and_grad"):
@@ -566,6 +577,25 @@ def parse_args(argv=None):
                              f"(it has no soft_target_loss_and_grad; the reference's {name} cannot either): use "
                              "SoftTreeSupLoss, SoftTreeLoss or CrossEntropyLoss")
     return args
+
+
+def induce_hierarchy(args, rank, world, log):
+    """--induce-hierarchy: the step the README's "resolves only after generate_hierarchy(...)" asks for, in the run
+    itself.  Rank 0 clusters the checkpoint's classifier rows on its GPU and writes the file (atomically), the others
+    wait for it."""
+    from nbdt.hierarchy import generate_hierarchy
+    if not os.path.exists(args.path_resume):
+        raise SystemExit(f"--induce-hierarchy: no checkpoint at {args.path_resume}")
+    if rank == 0:
+        path = generate_hierarchy(args.dataset, "induced", arch=args.arch, checkpoint=args.path_resume,
+                                  induced_linkage=args.induced_linkage, path=args.path_graph or "",
+                                  fname=f"graph-induced-{args.arch}", path_wnids=args.path_wnids,
+                                  induced_backend="device")
+        log(f"==> --induce-hierarchy: {path} from the classifier of {args.path_resume}")
+    if world > 1:
+        torch.distributed.barrier()
+    if not args.path_graph:
+        args.hierarchy = f"induced-{args.arch}"
 
 
 def main(argv=None):
@@ -660,6 +690,8 @@ def main(argv=None):
 
     if not args.hierarchy and not args.path_graph and any("Tree" in l for l in args.loss) or args.analysis or args.diagnostics:
         args.hierarchy = args.hierarchy or f"induced-{args.arch}"       # reference nbdt/model.py:296-298 default
+    if args.induce_hierarchy:
+        induce_hierarchy(args, rank, world, log)
     tree = Tree.create_from_args(args)
     ck_args = dict(vars(args))
     ck_args["path_graph"] = tree.path_graph

@@ -31,6 +31,8 @@ NBDT_CHAIN_MAX_SUBPOLICIES = 1024
 NBDT_CHAIN_RAND, NBDT_CHAIN_SUBPOLICY = 0, 1
 NBDT_CHAIN_TA_WIDE = 2              # nbdt_resized_crop_policy_batch only: one slot, nbdt_policy_batch's draw
 NBDT_RESIZED_CROP_POLICY_MAX_SIDE = 512
+NBDT_LINKAGE = {"ward": 0, "complete": 1, "single": 2, "average": 3}        # nbdt_linkage's method ...
+NBDT_METRIC = {"euclidean": 0, "l2": 0, "manhattan": 1, "l1": 1, "cityblock": 1, "cosine": 2}     # ... and metric
 _ZTYPE = {torch.float32: NBDT_F32, torch.bfloat16: NBDT_BF16, torch.float16: NBDT_F16}
 
 
@@ -315,6 +317,9 @@ SIGNATURES = {
     "nbdt_clip_apply": (c_int, [c_void_p, _P, _P]),
     "nbdt_clip_record": (c_void_p, [c_void_p]),
     "nbdt_clip_record_to_host": (c_int, [c_void_p, _P, _P]),
+    # agglomerative clustering (nbdt_version() >= 128): (centers, n, d, method, metric, workspace, workspace_bytes, ...)
+    "nbdt_linkage_workspace_bytes": (c_int, [c_int64, POINTER(c_int64)]),
+    "nbdt_linkage": (c_int, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P]),
 }
 
 

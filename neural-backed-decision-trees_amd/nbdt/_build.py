@@ -45,7 +45,9 @@ FLAGS = {
     "adaptive.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # global-norm clipping: the five fp32 operations behind norm and coef are single IEEE operations, root and division included
     "clip.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
-    "ema.hip": ["-ffp-contract=off"],          # e + omd * (p - e): a subtract, a multiply and an add, never a fused multiply-add
+    # fp64 sums and Lance-Williams updates as the separate IEEE operations tests/_linkage_ref.py restates: merge order is decided by them
+    "linkage.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    "ema.hip": ["-ffp-contract=off"],         # e + omd * (p - e): a subtract, a multiply and an add, never a fused multiply-add
 }
 
 

@@ -10,7 +10,7 @@ from nbdt.utils import dataset_to_default_path_wnids
 
 def generate_hierarchy(dataset, method, seed=0, branching_factor=2, extra=0, no_prune=False, fname="", path="",
                        single_path=False, induced_linkage="ward", induced_affinity="euclidean", checkpoint=None,
-                       arch=None, model=None, path_wnids=None, **kwargs):
+                       arch=None, model=None, path_wnids=None, induced_backend=None, **kwargs):
     if method != "induced":
         raise NotImplementedError(f'Method "{method}" is not built (only induced hierarchies are in scope)')
     if extra:
@@ -19,7 +19,7 @@ def generate_hierarchy(dataset, method, seed=0, branching_factor=2, extra=0, no_
     G = build_induced_graph(wnids, dataset=dataset, checkpoint=checkpoint,
                             model=None if model is not None else arch, linkage=induced_linkage,
                             affinity=induced_affinity, branching_factor=branching_factor,
-                            state_dict=model.state_dict() if model is not None else None)
+                            state_dict=model.state_dict() if model is not None else None, backend=induced_backend)
     assert all(w in G.nodes for w in wnids)
     # The reference prunes single-successor nodes here unless --no-prune (nbdt/hierarchy.py:96-98).  Agglomerative
     # clustering merges exactly two clusters per step whatever the linkage, so an induced hierarchy never has such a

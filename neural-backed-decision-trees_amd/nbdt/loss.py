@@ -339,8 +339,9 @@ class HardTreeSupLoss(TreeSupLoss):
 class SoftTreeLoss(SoftTreeSupLoss):
     """reference nbdt/loss.py:269-315: plain cross entropy until `tree_start_epochs`, then soft tree
     supervision on a hierarchy RE-INDUCED from the network's own classifier weights every
-    `tree_update_every_epochs` epochs (until `tree_update_end_epochs`).  Re-induction is host-side ward
-    clustering (nbdt/graph.py); the kernels pick the new hierarchy up through a fresh tree handle."""
+    `tree_update_every_epochs` epochs (until `tree_update_end_epochs`).  Re-induction is ward clustering
+    (nbdt/graph.py): sklearn on the host by default, csrc/linkage.hip on the classifier where it lives with
+    `tree_update_backend="device"`; the kernels pick the new hierarchy up through a fresh tree handle."""
 
     accepts_tree_start_epochs = True
     accepts_tree_update_every_epochs = True
@@ -350,11 +351,12 @@ class SoftTreeLoss(SoftTreeSupLoss):
     accepts_checkpoint_path = lambda checkpoint_path, **kwargs: checkpoint_path
 
     def __init__(self, *args, arch=None, checkpoint_path="./", net=None, tree_start_epochs=67,
-                 tree_update_every_epochs=10, tree_update_end_epochs=120, **kwargs):
+                 tree_update_every_epochs=10, tree_update_end_epochs=120, tree_update_backend=None, **kwargs):
         super().__init__(*args, **kwargs)
         self.start_epochs = tree_start_epochs
         self.update_every_epochs = tree_update_every_epochs
         self.update_end_epochs = tree_update_end_epochs
+        self.update_backend = tree_update_backend     # nbdt.graph.linkage_children: None | "sklearn" | "device"
         self.net = net
         self.arch = arch
         self.checkpoint_path = checkpoint_path
@@ -402,7 +404,8 @@ class SoftTreeLoss(SoftTreeSupLoss):
             # writes (atomically, Tree.update_from_model), the others wait and then load what it wrote.
             multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
             if not multi or dist.get_rank() == 0:
-                self.tree.update_from_model(self.net, self.arch, self.tree.dataset, path_graph=path_graph)
+                self.tree.update_from_model(self.net, self.arch, self.tree.dataset, path_graph=path_graph,
+                                            backend=self.update_backend)
             if multi:
                 dist.barrier()
                 if dist.get_rank() != 0:
