@@ -54,7 +54,8 @@ const char* nbdt_debug_last_igemm_full(void);
 const char* nbdt_debug_last_wgrad(void);      /* same for nbdt_conv_wgrad */
 /* Which form the calling thread's last rules launch took (nbdt_soft_forward, nbdt_soft_backward, the tree losses,
  * nbdt_hard_forward, nbdt_node_outputs, nbdt_tree_stats_accumulate): "lds" (rows and staged operands in LDS),
- * "lds-unstaged" (rows in LDS, direct-indexed chains), "global" (rows in global memory), "" before the first launch.
+ * "lds-unstaged" (rows in LDS, direct-indexed chains), "global" (rows in global memory), "pixel" (the nbdt_seg_*
+ * entries: one lane per pixel of an NCHW tensor, nbdt_version() >= 129), "" before the first launch.
  * See "Size limits" at nbdt_tree_create.  nbdt_version() >= 127. */
 const char* nbdt_debug_last_rules_path(void);
 /* Form of the per-sample rules kernels (process-wide, default 0; nbdt_version() >= 127).  0: automatic -- the LDS forms
@@ -274,6 +275,44 @@ typedef struct nbdt_tree_stats {
 } nbdt_tree_stats;
 int nbdt_tree_stats_accumulate(const nbdt_tree* t, const void* z, int ztype, int64_t B, int64_t ldz,
                                const int64_t* y, const nbdt_tree_stats* stats, float* scores, void* stream);
+
+/* ---- the rules on NCHW logits, one lane per pixel (nbdt_version() >= 129; csrc/rules_pixel.h): SegNBDT, HardSegNBDT,
+ * SoftSegNBDT (nbdt/model.py:376-399) and SoftSegTreeSupLoss (nbdt/loss.py:318-327) without the reference's permutes
+ * to [N*H*W, C] rows and back.
+ *   z: [N, C, HW] logits of type ztype; the HW pixels of a plane are contiguous, image n / channel c starts at element
+ *   n*zi + c*zc (int64 element strides, so a channel-sliced view works; zc >= HW, zi >= (C-1)*zc + HW).  Every offset is
+ *   64-bit.  Outputs are dense fp32 / int64 in the same [N, C, HW] / [N, HW] order and must not alias the inputs.
+ * Same arithmetic contract as the row kernels: child logits, node decisions and hard predictions are bit-equal to theirs
+ * on the coerced tensor; P, losses and gradients agree to rounding (the cross-entropy sums run sequentially per pixel
+ * here and as a butterfly over lanes there).  nbdt_debug_last_rules_path() reports "pixel".
+ * Size limit: R + F <= 640, with R child slots and F the largest fan-out of an inner node -- a pixel's R + F floats of
+ * LDS times 64 lanes within 160 KB.  F <= R, so 2R <= 640 always fits; a binary hierarchy fits up to 320 classes
+ * (ADE20K: C 150, R 298, F 2).  Every class must lie under at least one child slot.  Beyond it every entry returns NBDT_EINVAL and nbdt_seg_pixel_fits() returns 0: run the
+ * row kernels on the coerced tensor (what nbdt.model / nbdt.loss do).  nbdt_set_rules_path does not apply here.
+ *
+ * nbdt_seg_soft_forward: P [N, C, HW] path probabilities.  One launch.
+ * nbdt_seg_soft_backward: gz [N, C, HW] = d<gP, P>/dz, the forward recomputed from z; the path for any criterion that
+ *   is not a plain cross entropy.  One launch; gz doubles as the kernel's per-class scratch.
+ * nbdt_seg_soft_tree_loss: criterion = nn.CrossEntropyLoss(ignore_index, label_smoothing = smoothing), mean reduction:
+ *   loss = w_xent*CE(z, y) + w_tree*CE(P, y), each a mean over the pixels with y != ignore_index (y: [N, HW] int64);
+ *   gz = grad_scale * dloss/dz, exactly 0 at ignored pixels.  A label outside [0, C) other than ignore_index gives a NaN
+ *   loss; no valid pixel at all gives a NaN loss and a zero gradient, like torch.  THREE launches behind a 4-byte
+ *   memset, no host read-back: a count of the valid pixels over y (integer atomics), the main kernel (one row-loss sum
+ *   per block of 64 pixels, by a fixed butterfly), and a one-block fold that adds those sums in block order and divides
+ *   by the count -- no floating-point atomics, so two calls on the same input give the same bits.
+ *   workspace: nbdt_seg_loss_workspace_floats(N, HW) fp32 of scratch; loss: 1 fp32.
+ * nbdt_seg_hard_forward: pred [N, HW] int64, optional onehot [N, C, HW] fp32 (NULL: not written).  One launch. */
+int nbdt_seg_pixel_fits(const nbdt_tree* t);
+int64_t nbdt_seg_loss_workspace_floats(int64_t N, int64_t HW);
+int nbdt_seg_soft_forward(const nbdt_tree* t, const void* z, int ztype, int64_t N, int64_t HW, int64_t zi, int64_t zc,
+                          float* P, void* stream);
+int nbdt_seg_soft_backward(const nbdt_tree* t, const void* z, int ztype, int64_t N, int64_t HW, int64_t zi, int64_t zc,
+                           const float* gP, float* gz, void* stream);
+int nbdt_seg_soft_tree_loss(const nbdt_tree* t, const void* z, int ztype, int64_t N, int64_t HW, int64_t zi, int64_t zc,
+                            const int64_t* y, int64_t ignore_index, float smoothing, float w_xent, float w_tree,
+                            float grad_scale, float* workspace, float* loss, float* gz, void* stream);
+int nbdt_seg_hard_forward(const nbdt_tree* t, const void* z, int ztype, int64_t N, int64_t HW, int64_t zi, int64_t zc,
+                          int64_t* pred, float* onehot, void* stream);
 
 /* ------------------------------------------------------------------ backbone: implicit-GEMM conv
  * One launch = one "tap table": out[pix(m)][n] (+)= sum_t sum_c in[pix_in(m) + tap_off[t]][c] *

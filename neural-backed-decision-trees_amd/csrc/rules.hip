@@ -47,6 +47,10 @@ struct nbdt_tree {
   int32_t* d_all;  // one allocation
   const int32_t *node_off, *slot_off, *slot_cls, *cls_off, *cls_slot, *slot_next;
   const int32_t* sched;  // [3][sched_len]: slot id (or -1), first and one-past-last element in slot_cls
+  int max_fan;     // largest fan-out of an inner node (the T rows of the pixel form, rules_pixel.h)
+  int binary;      // every inner node has two children
+  int pix_ok;      // the packed maps below exist: every class lies under a slot, every index fits 16 bits
+  const int32_t *pix_slot, *pix_cls;  // [L] each: slot_cls / cls_slot with their segment ends folded in (rules_pixel.h, flat_chains)
   const int32_t* wide;   // [n_wide] inner nodes with more than kWideFan children (the global-row kernels, rules_global.h)
   int n_wide;
 };
@@ -1457,7 +1461,7 @@ __global__ __launch_bounds__(block_of(TPS)) void tree_stats_kernel(TreeView t, c
 // host side
 
 extern "C" const char* nbdt_last_error(void) { return nbdt::g_err; }
-extern "C" int nbdt_version(void) { return 128; }     // 128: nbdt_linkage / nbdt_linkage_workspace_bytes (agglomerative clustering for induced hierarchies: csrc/linkage.hip); 127: nbdt_set_rules_path / nbdt_get_rules_path / nbdt_debug_last_rules_path (the rules kernels with the sample row in global memory, for hierarchies too large for LDS: csrc/rules_global.h); 125: nbdt_conv_group_weight_prep[_batched], nbdt_conv_group_fwd / _dgrad / _wgrad and their nbdt_ref_conv_group_* twins (the grouped 3x3 convolution of ResNeXt as block-diagonal 32 x 32 blocks: csrc/conv_group.hip); 124: nbdt_resized_crop_policy_batch[_sharded] (policy chains and random erasing on the resized-crop path: csrc/resample.hip, csrc/policy_ops.h); 123: nbdt_policy_chain_batch[_sharded] (RandAugment / AutoAugment chains: csrc/policy.hip); 122: nbdt_bn_act_apply_rows, nbdt_bn_act_bwd_rows, their nbdt_ref_* twins, nbdt_stochastic_depth_draw (stochastic depth inside the MBConv residual passes: csrc/effnet.hip); 120: nbdt_arena_opt_create / _destroy, nbdt_adamw_step, nbdt_rmsprop_step (AdamW and RMSprop over the flat arena: csrc/adaptive.hip); 119: nbdt_policy_batch[_sharded] (TrivialAugmentWide + random erasing on device-resident datasets: csrc/policy.hip); 118: nbdt_ema_update / _swap and their _multi forms (weight EMA: the fused shadow update and the in-place exchange for evaluation: csrc/ema.hip); 117: nbdt_lars_create / _destroy / _step / _ratios (LARS over the flat parameter arena: csrc/lars.hip); 116: nbdt_soft_tree_loss_ex, nbdt_hard_tree_loss_ex (label smoothing in both fused tree losses, probability targets in the soft one), nbdt_mix_batch (MixUp / CutMix and their targets in one launch: csrc/mix.hip); 115: nbdt_stem_patches, nbdt_maxpool3x3s2_fwd / _bwd (the 7x7 / 2 stem as a patch gather in front of the 1x1 convolution, and MaxPool2d(3, 2, 1), for torchvision-shaped ResNets: csrc/stem_pool.hip); 114: nbdt_augment_batch_sharded, nbdt_resized_crop_batch_sharded (a rank keeps its contiguous shard of a device-resident dataset: the draw from the dataset index, the gather from index - index_base); 113: nbdt_conv_pw (stride-1 1x1 convolutions as a GEMM: the Bottleneck ResNets); 112: nbdt_tree_stats_accumulate (tree diagnostics: per-node counters, confusion matrices, entropy sums, scores in one launch); 111: nbdt_resized_crop_batch, nbdt_resized_crop_band_rows (RandomResizedCrop / Resize + CenterCrop datasets); 110: nbdt_augment_batch (device-resident datasets: gather + crop + flip + normalise), NBDT_U8; 109: nbdt_set/get_stream_nt_min_bytes, nbdt_debug_last_stream_nt, nbdt_conv_seg_create refuses ntensors > 2; 108: nbdt_se_param_grad, nbdt_se_gate_bwd without parameter gradients; 107: nbdt_bn_act_se_sums / _se_bwd_apply; 106: nbdt_conv_desc.ksplit is live (was reserved), nbdt_conv_seg_*
+extern "C" int nbdt_version(void) { return 129; }     // 129: nbdt_seg_soft_forward / _soft_backward / _soft_tree_loss / _hard_forward, nbdt_seg_pixel_fits, nbdt_seg_loss_workspace_floats (the rules and the fused soft loss on NCHW logits, one lane per pixel: csrc/rules_pixel.h), "pixel" from nbdt_debug_last_rules_path; 128: nbdt_linkage / nbdt_linkage_workspace_bytes (agglomerative clustering for induced hierarchies: csrc/linkage.hip); 127: nbdt_set_rules_path / nbdt_get_rules_path / nbdt_debug_last_rules_path (the rules kernels with the sample row in global memory, for hierarchies too large for LDS: csrc/rules_global.h); 125: nbdt_conv_group_weight_prep[_batched], nbdt_conv_group_fwd / _dgrad / _wgrad and their nbdt_ref_conv_group_* twins (the grouped 3x3 convolution of ResNeXt as block-diagonal 32 x 32 blocks: csrc/conv_group.hip); 124: nbdt_resized_crop_policy_batch[_sharded] (policy chains and random erasing on the resized-crop path: csrc/resample.hip, csrc/policy_ops.h); 123: nbdt_policy_chain_batch[_sharded] (RandAugment / AutoAugment chains: csrc/policy.hip); 122: nbdt_bn_act_apply_rows, nbdt_bn_act_bwd_rows, their nbdt_ref_* twins, nbdt_stochastic_depth_draw (stochastic depth inside the MBConv residual passes: csrc/effnet.hip); 120: nbdt_arena_opt_create / _destroy, nbdt_adamw_step, nbdt_rmsprop_step (AdamW and RMSprop over the flat arena: csrc/adaptive.hip); 119: nbdt_policy_batch[_sharded] (TrivialAugmentWide + random erasing on device-resident datasets: csrc/policy.hip); 118: nbdt_ema_update / _swap and their _multi forms (weight EMA: the fused shadow update and the in-place exchange for evaluation: csrc/ema.hip); 117: nbdt_lars_create / _destroy / _step / _ratios (LARS over the flat parameter arena: csrc/lars.hip); 116: nbdt_soft_tree_loss_ex, nbdt_hard_tree_loss_ex (label smoothing in both fused tree losses, probability targets in the soft one), nbdt_mix_batch (MixUp / CutMix and their targets in one launch: csrc/mix.hip); 115: nbdt_stem_patches, nbdt_maxpool3x3s2_fwd / _bwd (the 7x7 / 2 stem as a patch gather in front of the 1x1 convolution, and MaxPool2d(3, 2, 1), for torchvision-shaped ResNets: csrc/stem_pool.hip); 114: nbdt_augment_batch_sharded, nbdt_resized_crop_batch_sharded (a rank keeps its contiguous shard of a device-resident dataset: the draw from the dataset index, the gather from index - index_base); 113: nbdt_conv_pw (stride-1 1x1 convolutions as a GEMM: the Bottleneck ResNets); 112: nbdt_tree_stats_accumulate (tree diagnostics: per-node counters, confusion matrices, entropy sums, scores in one launch); 111: nbdt_resized_crop_batch, nbdt_resized_crop_band_rows (RandomResizedCrop / Resize + CenterCrop datasets); 110: nbdt_augment_batch (device-resident datasets: gather + crop + flip + normalise), NBDT_U8; 109: nbdt_set/get_stream_nt_min_bytes, nbdt_debug_last_stream_nt, nbdt_conv_seg_create refuses ntensors > 2; 108: nbdt_se_param_grad, nbdt_se_gate_bwd without parameter gradients; 107: nbdt_bn_act_se_sums / _se_bwd_apply; 106: nbdt_conv_desc.ksplit is live (was reserved), nbdt_conv_seg_*
 extern "C" int nbdt_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -1565,7 +1569,22 @@ extern "C" int nbdt_tree_create(int device, int C, int N, int root, const int32_
   nbdt_tree* t = new nbdt_tree();
   t->device = device; t->cus = cus; t->C = C; t->N = N; t->R = R; t->L = L; t->root = root; t->max_depth = max_depth;
   t->sched_len = sched_len;
-  const size_t n_ints = (size_t)(N + 1) + (R + 1) + L + (C + 1) + L + R + sched.size() + wide.size();
+  t->max_fan = 0;
+  t->binary = 1;
+  for (int n = 0; n < N; ++n) {
+    t->max_fan = std::max(t->max_fan, node_off[n + 1] - node_off[n]);
+    if (node_off[n + 1] - node_off[n] != 2) t->binary = 0;
+  }
+  // the maps as the pixel kernels walk them: index | last element of its slot / class (bit 31) | of its node (bit 30)
+  std::vector<int32_t> pix_slot(slot_cls, slot_cls + L), pix_cls(cls_slot, cls_slot + L);
+  t->pix_ok = C < 65536 && R < 65536 && slot_off[0] == 0 && cls_off[0] == 0 && node_off[0] == 0;
+  for (int c = 0; c < C && t->pix_ok; ++c) t->pix_ok = cls_off[c + 1] > cls_off[c];
+  if (t->pix_ok) {
+    for (int s = 0; s < R; ++s) pix_slot[slot_off[s + 1] - 1] |= (int32_t)0x80000000u;
+    for (int n = 0; n < N; ++n) pix_slot[slot_off[node_off[n + 1]] - 1] |= 0x40000000;
+    for (int c = 0; c < C; ++c) pix_cls[cls_off[c + 1] - 1] |= (int32_t)0x80000000u;
+  }
+  const size_t n_ints = (size_t)(N + 1) + (R + 1) + L + (C + 1) + L + R + sched.size() + wide.size() + 2 * (size_t)L;
   hipError_t e = hipMalloc((void**)&t->d_all, n_ints * sizeof(int32_t));
   if (e != hipSuccess) {
     delete t;
@@ -1587,6 +1606,8 @@ extern "C" int nbdt_tree_create(int device, int C, int N, int root, const int32_
   put(slot_next, R, &t->slot_next);
   put(sched.data(), sched.size(), &t->sched);
   put(wide.data(), wide.size(), &t->wide);
+  put(pix_slot.data(), L, &t->pix_slot);
+  put(pix_cls.data(), L, &t->pix_cls);
   t->n_wide = (int)wide.size();
   e = hipMemcpy(t->d_all, host, n_ints * sizeof(int32_t), hipMemcpyHostToDevice);
   delete[] host;
@@ -1620,7 +1641,7 @@ constexpr size_t kStagePad = 4;  // floats of slack behind the last staging row 
 // Which form the per-sample kernels take (nbdt_set_rules_path): 0 = the LDS form wherever its row fits and the global-row
 // form (rules_global.h) where it does not, 1 = the global-row form for every hierarchy (tests and measurements).
 static std::atomic<int> g_rules_path{0};
-static thread_local int g_last_rules_path = 0;  // nbdt_debug_last_rules_path: 0 none yet, 1 LDS staged, 2 LDS unstaged, 3 global
+static thread_local int g_last_rules_path = 0;  // nbdt_debug_last_rules_path: 0 none yet, 1 LDS staged, 2 LDS unstaged, 3 global, 4 pixel
 
 extern "C" int nbdt_set_rules_path(int mode) {
   NBDT_REQUIRE(mode == 0 || mode == 1, "rules path must be 0 (automatic) or 1 (global rows)");
@@ -1629,7 +1650,7 @@ extern "C" int nbdt_set_rules_path(int mode) {
 }
 extern "C" int nbdt_get_rules_path(void) { return g_rules_path.load(std::memory_order_relaxed); }
 extern "C" const char* nbdt_debug_last_rules_path(void) {
-  static const char* const names[] = {"", "lds", "lds-unstaged", "global"};
+  static const char* const names[] = {"", "lds", "lds-unstaged", "global", "pixel"};
   return names[g_last_rules_path];
 }
 
@@ -1972,3 +1993,8 @@ extern "C" int nbdt_tree_stats_accumulate(const nbdt_tree* t, const void* z, int
                          stats_block_ints(t->N, t->max_depth), 2, v, z, B, ldz, a);
   return NBDT_OK;
 }
+
+// ------------------------------------------------------------------------------------------
+// the same layer on NCHW logits, one lane per pixel (segmentation)
+
+#include "rules_pixel.h"

@@ -122,7 +122,7 @@ from nbdt.data import (DATASET_STATS, RESIZED_CROP_STATS, DeviceDataset, Resized
 from nbdt.engine import train_step  # noqa: E402
 from nbdt.model import coerce_state_dict  # noqa: E402
 from nbdt.tree import Tree  # noqa: E402
-from nbdt.utils import DATASET_TO_NUM_CLASSES, DATASETS  # noqa: E402
+from nbdt.utils import DATASET_TO_NUM_CLASSES, DATASETS, SEGMENTATION_DATASETS  # noqa: E402
 
 CIFAR_MEAN, CIFAR_STD = (0.4914, 0.4822, 0.4465), (0.2023, 0.1994, 0.2010)   # reference nbdt/data/cifar.py:17-19
 METRICS = {"top1": 1, "top2": 2, "top5": 5, "top10": 10}      # the reference's --metric names -> k
@@ -153,7 +153,8 @@ def build_parser():
     p = argparse.ArgumentParser(description="NBDT training on MI355X (reference main.py command line)")
     p.add_argument("--batch-size", default=512, type=int, help="GLOBAL batch size (split over ranks)")
     p.add_argument("--epochs", "-e", default=200, type=int, help="lr schedule is scaled accordingly")
-    p.add_argument("--dataset", default="CIFAR10", choices=DATASETS)
+    p.add_argument("--dataset", default="CIFAR10",
+                   choices=[d for d in DATASETS if d not in SEGMENTATION_DATASETS])     # a classification driver
     p.add_argument("--arch", default="ResNet18", choices=models.get_model_choices())
     p.add_argument("--lr", default=0.1, type=float)
     p.add_argument("--weight-decay", default=5e-4, type=float, help="SGD weight decay (the reference's ImageNet recipe: 1e-4)")

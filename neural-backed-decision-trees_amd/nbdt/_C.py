@@ -142,6 +142,13 @@ SIGNATURES = {
     "nbdt_hard_forward": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P]),
     "nbdt_node_outputs": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "nbdt_tree_stats_accumulate": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, _P, _P]),
+    "nbdt_seg_pixel_fits": (c_int, [c_void_p]),
+    "nbdt_seg_loss_workspace_floats": (c_int64, [c_int64, c_int64]),
+    "nbdt_seg_soft_forward": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, c_int64, c_int64, _P, _P]),
+    "nbdt_seg_soft_backward": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, c_int64, c_int64, _P, _P, _P]),
+    "nbdt_seg_soft_tree_loss": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, c_int64, c_int64, _P, c_int64, c_float,
+                                        c_float, c_float, c_float, _P, _P, _P, _P]),
+    "nbdt_seg_hard_forward": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, c_int64, c_int64, _P, _P, _P]),
     "nbdt_conv_igemm": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "nbdt_conv_pw": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "nbdt_conv_igemm_multi": (c_int, [_P, c_int32, _P, _P, _P, _P]),
@@ -584,3 +591,149 @@ def node_outputs(handle, z):
     check(lib().nbdt_node_outputs(handle.h, ptr(z), ztype_of(z), B, ld, ptr(logits), ptr(probs),
                                   ptr(preds), ptr(ent), stream_of(z)))
     return logits, probs, preds, ent
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the rules on NCHW logits (segmentation): csrc/rules_pixel.h, one lane per pixel
+
+SEG_PIXEL_MAX_ROWS = 640      # kPixMaxRows: child slots + largest fan-out, at 64 lanes x 4 bytes each within 160 KB of LDS
+
+
+def seg_pixel_fits(flat):
+    """The pixel form's size limit (include/nbdt_hip.h, nbdt_seg_*): R + F <= 640 -- a pure function of the hierarchy."""
+    fan = int((flat.node_off[1:] - flat.node_off[:-1]).max())
+    on_a_path = bool((flat.cls_off[1:] > flat.cls_off[:-1]).all())      # a class under no child has no chain to walk
+    return on_a_path and flat.num_slots + fan <= SEG_PIXEL_MAX_ROWS
+
+
+def _dense_planes(shape, strides):
+    """[N, C, H, W] whose planes are contiguous over pixels and do not overlap (a channel-sliced view qualifies)."""
+    (N, C, H, W), (sn, sc, sh, sw) = shape, strides
+    return ((W == 1 or sw == 1) and (H == 1 or sh == W) and (C == 1 or sc >= H * W)
+            and (N == 1 or sn >= (C - 1) * (sc if C > 1 else 0) + H * W))
+
+
+def _pixel_rows(shape, strides):
+    """[N, C, H, W] whose memory is already [N*H*W, C] rows of unit column stride (channels_last)."""
+    (N, C, H, W), (sn, sc, sh, sw) = shape, strides
+    ld = sw if W > 1 else (sh if H > 1 else (sn if N > 1 else C))
+    return ((C == 1 or sc == 1) and ld >= C and (W == 1 or sw == ld) and (H == 1 or sh == W * ld)
+            and (N == 1 or sn == H * W * ld))
+
+
+def seg_dispatch(shape, strides, dtype, flat):
+    """Which way 4-D logits take through the rules -- a pure host function of (shape, strides, dtype, hierarchy):
+      "pixel"       contiguous NCHW planes: the pixel kernels, as they are
+      "rows"        channels_last memory is already [N*H*W, C] rows: the row kernels with ldz = C, no copy
+      "contiguous"  anything else: one .contiguous(), then the pixel kernels
+      "coerced"     a hierarchy beyond the pixel form's limit: the row kernels on one channels_last copy
+    """
+    if len(shape) != 4:
+        raise NBDTHipError(f"segmentation rules expect [N, C, H, W] logits, got shape {tuple(shape)}")
+    if shape[1] != flat.num_classes:
+        raise NBDTHipError(f"logits have {shape[1]} channels but the hierarchy has {flat.num_classes} classes")
+    if dtype not in _ZTYPE:
+        raise NBDTHipError(f"unsupported logits dtype {dtype}")
+    if _pixel_rows(shape, strides) and not (_dense_planes(shape, strides) and seg_pixel_fits(flat)):
+        return "rows"
+    if not seg_pixel_fits(flat):
+        return "coerced"
+    return "pixel" if _dense_planes(shape, strides) else "contiguous"
+
+
+def _seg_route(z, handle):
+    """-> ("pixel", z with dense planes) or ("rows", the [N*H*W, C] view of channels_last memory)."""
+    how = seg_dispatch(tuple(z.shape), tuple(z.stride()), z.dtype, handle.flat)
+    if how == "contiguous":
+        z, how = z.contiguous(), "pixel"
+    elif how == "coerced":
+        z, how = z.contiguous(memory_format=torch.channels_last), "rows"
+    if how == "rows":
+        return how, z.permute(0, 2, 3, 1).reshape(-1, z.shape[1])
+    return how, z
+
+
+def _seg_geom(z):
+    N, C, H, W = z.shape
+    zc = z.stride(1) if C > 1 else H * W
+    zi = z.stride(0) if N > 1 else max(C - 1, 0) * zc + H * W
+    return N, H * W, zi, zc
+
+
+def _rows_to_nchw(rows, shape):
+    """[N*H*W, K] -> [N, K, H, W] (a channels_last-strided view, no copy)."""
+    N, _, H, W = shape
+    return rows.view(N, H, W, rows.shape[1]).permute(0, 3, 1, 2)
+
+
+def seg_soft_forward(handle, z):
+    """P [N, C, H, W] fp32 path probabilities of NCHW logits."""
+    require_gpu(z, "seg_soft_forward")
+    handle.flat.require_single_path()
+    how, zz = _seg_route(z, handle)
+    if how == "rows":
+        return _rows_to_nchw(soft_forward(handle, zz), z.shape)
+    N, HW, zi, zc = _seg_geom(zz)
+    P = torch.empty(tuple(z.shape), dtype=torch.float32, device=z.device)
+    check(lib().nbdt_seg_soft_forward(handle.h, ptr(zz), ztype_of(zz), N, HW, zi, zc, ptr(P), stream_of(zz)))
+    return P
+
+
+def seg_soft_backward(handle, z, gP):
+    """gz [N, C, H, W] fp32 = d<gP, P>/dz, the forward recomputed from z."""
+    require_gpu(z, "seg_soft_backward")
+    handle.flat.require_single_path()
+    how, zz = _seg_route(z, handle)
+    if how == "rows":
+        g = gP.float().permute(0, 2, 3, 1).reshape(-1, z.shape[1])
+        return _rows_to_nchw(soft_backward(handle, zz, g), z.shape)
+    N, HW, zi, zc = _seg_geom(zz)
+    gP = gP.float().contiguous()
+    gz = torch.empty(tuple(z.shape), dtype=torch.float32, device=z.device)
+    check(lib().nbdt_seg_soft_backward(handle.h, ptr(zz), ztype_of(zz), N, HW, zi, zc, ptr(gP), ptr(gz), stream_of(zz)))
+    return gz
+
+
+def seg_soft_tree_loss(handle, z, y, ignore_index, w_xent, w_tree, grad_scale=1.0, smoothing=0.0):
+    """SoftSegTreeSupLoss for nn.CrossEntropyLoss(ignore_index, label_smoothing=smoothing): (loss, gz [N, C, H, W] fp32),
+    both means over the pixels with y != ignore_index; gz is 0 at the others."""
+    require_gpu(z, "seg_soft_tree_loss")
+    handle.flat.require_single_path()
+    if y.is_floating_point() or y.dim() != 3 or (y.shape[0],) + tuple(y.shape[1:]) != (z.shape[0],) + tuple(z.shape[2:]):
+        raise NBDTHipError(f"segmentation targets must be class indices [N, H, W] = "
+                           f"{(z.shape[0],) + tuple(z.shape[2:])}, got {y.dtype} {tuple(y.shape)}")
+    y = y.to(device=z.device, dtype=torch.int64).contiguous()
+    how, zz = _seg_route(z, handle)
+    if how == "rows":
+        # the row losses take no ignore_index: they run on the valid rows alone (their mean is the mean over those)
+        keep = (y.reshape(-1) != ignore_index).nonzero().squeeze(1)
+        gz = torch.zeros((zz.shape[0], zz.shape[1]), dtype=torch.float32, device=z.device)
+        if keep.numel() == 0:
+            return torch.full((), float("nan"), dtype=torch.float32, device=z.device), _rows_to_nchw(gz, z.shape)
+        loss, g = soft_tree_loss(handle, zz[keep], y.reshape(-1)[keep], w_xent, w_tree, grad_scale, smoothing)
+        gz[keep] = g
+        return loss, _rows_to_nchw(gz, z.shape)
+    N, HW, zi, zc = _seg_geom(zz)
+    ws = torch.empty((int(lib().nbdt_seg_loss_workspace_floats(N, HW)),), dtype=torch.float32, device=z.device)
+    loss = torch.empty((), dtype=torch.float32, device=z.device)
+    gz = torch.empty(tuple(z.shape), dtype=torch.float32, device=z.device)
+    check(lib().nbdt_seg_soft_tree_loss(handle.h, ptr(zz), ztype_of(zz), N, HW, zi, zc, ptr(y), int(ignore_index),
+                                        float(smoothing), float(w_xent), float(w_tree), float(grad_scale), ptr(ws),
+                                        ptr(loss), ptr(gz), stream_of(zz)))
+    return loss, gz
+
+
+def seg_hard_forward(handle, z, want_onehot=True):
+    """(pred [N, H, W] int64, onehot [N, C, H, W] fp32 or None) of NCHW logits."""
+    require_gpu(z, "seg_hard_forward")
+    how, zz = _seg_route(z, handle)
+    N, C, H, W = z.shape
+    if how == "rows":
+        pred, onehot, _ = hard_forward(handle, zz, want_onehot=want_onehot)
+        return pred.view(N, H, W), (_rows_to_nchw(onehot, z.shape) if want_onehot else None)
+    N, HW, zi, zc = _seg_geom(zz)
+    pred = torch.empty((N, H, W), dtype=torch.int64, device=z.device)
+    onehot = torch.empty(tuple(z.shape), dtype=torch.float32, device=z.device) if want_onehot else None
+    check(lib().nbdt_seg_hard_forward(handle.h, ptr(zz), ztype_of(zz), N, HW, zi, zc, ptr(pred), ptr(onehot),
+                                      stream_of(zz)))
+    return pred, onehot

@@ -13,6 +13,9 @@ criterion composes the fused rules kernel (autograd-enabled) with the user's cri
 
 ``HardTreeSupLoss`` (reference :212-257) gets the same treatment (hard_loss_kernel).  ``SoftTreeLoss``
 (:269-315) adds mid-training re-induction of the hierarchy (nbdt/graph.py, nbdt/hierarchy.py).
+
+``SoftSegTreeSupLoss`` (:318-327) is the soft loss on ``[N, C, H, W]`` logits and ``[N, H, W]`` targets; with a
+cross-entropy criterion of any ``ignore_index`` it is one fused launch on the pixel kernels (csrc/rules_pixel.h).
 """
 import torch
 import torch.nn as nn
@@ -22,7 +25,7 @@ from nbdt.model import HardEmbeddedDecisionRules, SoftEmbeddedDecisionRules
 from nbdt.tree import Tree
 from nbdt.utils import dataset_to_default_path_graph, dataset_to_default_path_wnids, hierarchy_to_path_graph
 
-__all__ = names = ("HardTreeSupLoss", "SoftTreeSupLoss", "SoftTreeLoss", "CrossEntropyLoss")
+__all__ = names = ("HardTreeSupLoss", "SoftTreeSupLoss", "SoftTreeLoss", "SoftSegTreeSupLoss", "CrossEntropyLoss")
 
 CrossEntropyLoss = nn.CrossEntropyLoss
 
@@ -410,3 +413,69 @@ class SoftTreeLoss(SoftTreeSupLoss):
                 dist.barrier()
                 if dist.get_rank() != 0:
                     self.tree.load_hierarchy(self.tree.dataset, path_graph, self.tree.path_wnids, self.tree.classes)
+
+
+def _seg_fusable(criterion):
+    """(ignore_index, label_smoothing) of a criterion nbdt_seg_soft_tree_loss implements -- an nn.CrossEntropyLoss
+    without class weights, mean reduction, ANY ignore_index, label_smoothing in [0, 1) -- or None."""
+    if not (type(criterion) is nn.CrossEntropyLoss and criterion.weight is None and criterion.reduction == "mean"):
+        return None
+    smoothing = float(getattr(criterion, "label_smoothing", 0.0))
+    return (int(criterion.ignore_index), smoothing) if 0.0 <= smoothing < 1.0 else None
+
+
+class _FusedSoftSegTreeLossFn(torch.autograd.Function):
+    """loss, and dloss/dz [N, C, H, W] computed in the same call (saved for backward)."""
+
+    @staticmethod
+    def forward(ctx, z, y, tree, w_xent, w_tree, ignore_index, smoothing):
+        handle = tree.device_handle(z.device.index)
+        loss, gz = _C.seg_soft_tree_loss(handle, z, y, ignore_index, w_xent, w_tree, smoothing=smoothing)
+        ctx.save_for_backward(gz)
+        ctx.z_dtype = z.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        (gz,) = ctx.saved_tensors
+        return (gz * gloss).to(ctx.z_dtype), None, None, None, None, None, None
+
+
+class SoftSegTreeSupLoss(SoftTreeSupLoss):
+    """reference nbdt/loss.py:318-327, on ``[N, C, H, W]`` logits and ``[N, H, W]`` targets:
+
+        loss = criterion(z, y) + criterion(rules(z), y) * tree_supervision_weight            (:322-326)
+
+    Faithful to the reference, including what it leaves out: its ``forward`` replaces ``TreeSupLoss.forward`` (:195-203),
+    so ``xent_weight`` and its schedule, ``tree_supervision_weight_end`` / ``_power`` and ``set_epoch`` have NO effect
+    here -- the cross-entropy term always weighs 1 and the tree term the constructor's ``tree_supervision_weight``.
+
+    With an ``nn.CrossEntropyLoss`` without class weights (mean reduction, any ``ignore_index``, ``label_smoothing`` in
+    [0, 1)) the whole loss and its gradient are one call of ``nbdt_seg_soft_tree_loss``.  Any other criterion (OHEM and
+    the like) is applied by torch to the output of the autograd-enabled pixel rules."""
+
+    def weights(self):
+        return 1.0, float(self.tree_supervision_weight)
+
+    def forward(self, outputs, targets):
+        self.assert_output_not_nbdt(outputs)
+        assert len(outputs.shape) == 4, "Input must be of shape (N,C,H,W) for segmentation"
+        _C.require_gpu(outputs, "SoftSegTreeSupLoss")
+        w_xent, w_tree = self.weights()
+        fusable = _seg_fusable(self.criterion)
+        if fusable is not None and targets.dim() == 3 and not targets.is_floating_point():
+            return _FusedSoftSegTreeLossFn.apply(outputs, targets, self.tree, w_xent, w_tree, *fusable)
+        loss = self.criterion(outputs, targets)
+        return loss + self.criterion(self.rules.forward_pixels(outputs), targets) * w_tree
+
+    def loss_and_grad(self, outputs, targets, grad_scale=1.0):
+        """(loss, dloss/dz * grad_scale) from the fused call, no autograd (NBDTHipError for a criterion it does not
+        implement)."""
+        self.assert_output_not_nbdt(outputs)
+        fusable = _seg_fusable(self.criterion)
+        if fusable is None:
+            raise _C.NBDTHipError("SoftSegTreeSupLoss.loss_and_grad: the fused loss takes an nn.CrossEntropyLoss without "
+                                  "class weights and with mean reduction; call the module itself for any other criterion")
+        w_xent, w_tree = self.weights()
+        handle = self.tree.device_handle(outputs.device.index)
+        return _C.seg_soft_tree_loss(handle, outputs, targets, fusable[0], w_xent, w_tree, grad_scale, fusable[1])

@@ -7,8 +7,12 @@ behavioural contracts (``_nbdt_output_flag``, eval-on-init, state_dict proxying,
 Every forward dispatches to one fused HIP kernel in libnbdt_hip.so (csrc/rules.hip) instead of
 the reference's per-node Python loop; there is no CPU path.
 
-Out of scope here: the segmentation variants (SegNBDT*) and pretrained
-checkpoint download (`pretrained=True` needs network access the target box does not have).
+``SegNBDT``, ``HardSegNBDT``, ``SoftSegNBDT`` (:376-399) apply the same rules to every pixel of ``[N, C, H, W]``
+logits, on kernels that give one lane to one pixel instead of the reference's permute to rows and back
+(csrc/rules_pixel.h; the dispatch by memory layout is ``seg_dispatch``).
+
+Out of scope here: pretrained checkpoint download (`pretrained=True` needs network
+access the target box does not have).
 """
 import torch
 import torch.nn as nn
@@ -196,6 +200,22 @@ class HardEmbeddedDecisionRules(EmbeddedDecisionRules):
         pred, _, _ = _C.hard_forward(handle, outputs.detach(), want_onehot=False)
         return pred
 
+    def forward_pixels(self, outputs):
+        """forward on [N, C, H, W] logits (segmentation): one-hot [N, C, H, W], detached."""
+        _require_nchw(outputs)
+        _C.require_gpu(outputs, "HardEmbeddedDecisionRules")
+        handle = self.tree.device_handle(outputs.device.index)
+        _, onehot = _C.seg_hard_forward(handle, outputs.detach(), want_onehot=True)
+        onehot._nbdt_output_flag = True
+        return onehot
+
+    def predict_pixels(self, outputs):
+        """[N, H, W] int64 predicted classes of [N, C, H, W] logits; the one-hot tensor is never materialised."""
+        _require_nchw(outputs)
+        _C.require_gpu(outputs, "HardEmbeddedDecisionRules")
+        handle = self.tree.device_handle(outputs.device.index)
+        return _C.seg_hard_forward(handle, outputs.detach(), want_onehot=False)[0]
+
 
 class SoftEmbeddedDecisionRules(EmbeddedDecisionRules):
     """Path-probability product over the hierarchy (reference :206-273); differentiable."""
@@ -245,6 +265,18 @@ class SoftEmbeddedDecisionRules(EmbeddedDecisionRules):
         logits = _SoftRulesFn.apply(outputs, self.tree)
         logits._nbdt_output_flag = True  # checked in nbdt losses, to prevent mistakes
         return logits
+
+    def forward_pixels(self, outputs):
+        """forward on [N, C, H, W] logits (segmentation): path probabilities [N, C, H, W], differentiable."""
+        _require_nchw(outputs)
+        _C.require_gpu(outputs, "SoftEmbeddedDecisionRules")
+        probs = _SegSoftRulesFn.apply(outputs, self.tree)
+        probs._nbdt_output_flag = True
+        return probs
+
+    def predict_pixels(self, outputs):
+        """[N, H, W] int64: the class of the largest path probability (first maximum)."""
+        return self.forward_pixels(outputs.detach()).max(1)[1]
 
 
 def coerce_state_dict(state_dict, reference_state_dict):
@@ -314,6 +346,64 @@ class HardNBDT(NBDT):
 
 
 class SoftNBDT(NBDT):
+    def __init__(self, *args, **kwargs):
+        kwargs.update({"Rules": SoftEmbeddedDecisionRules})
+        super().__init__(*args, **kwargs)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# segmentation (reference nbdt/model.py:376-399): the same rules on [N, C, H, W] logits.  The reference permutes to
+# [N*H*W, C] rows, runs the row rules and permutes back (coerce_tensor / uncoerce_tensor); here contiguous NCHW goes to
+# kernels that give one lane to one pixel (csrc/rules_pixel.h), channels_last memory -- already rows -- goes to the row
+# kernels without a copy, and anything else through one .contiguous() (nbdt._C.seg_dispatch, a pure host function).
+
+seg_dispatch = _C.seg_dispatch
+
+
+class _SegSoftRulesFn(torch.autograd.Function):
+    """P = soft_rules(z) per pixel of NCHW logits; backward recomputes the forward in-kernel from z."""
+
+    @staticmethod
+    def forward(ctx, z, tree):
+        handle = tree.device_handle(z.device.index)
+        ctx.tree = tree
+        ctx.save_for_backward(z)
+        return _C.seg_soft_forward(handle, z)
+
+    @staticmethod
+    def backward(ctx, gP):
+        (z,) = ctx.saved_tensors
+        handle = ctx.tree.device_handle(z.device.index)
+        return _C.seg_soft_backward(handle, z, gP).to(z.dtype), None
+
+
+def _require_nchw(x):
+    assert len(x.shape) == 4, "Input must be of shape (N,C,H,W) for segmentation"
+
+
+class SegNBDT(NBDT):
+    """reference nbdt/model.py:376-387: backbone + decision rules per pixel.  forward returns [N, C, H, W] like the
+    reference (one-hot for the hard rules, path probabilities for the soft ones); predict returns [N, H, W] labels."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+
+    def forward(self, x):
+        _require_nchw(x)
+        return self.rules.forward_pixels(self.model(x))
+
+    def predict(self, x):
+        _require_nchw(x)
+        return self.rules.predict_pixels(self.model(x))
+
+
+class HardSegNBDT(SegNBDT):
+    def __init__(self, *args, **kwargs):
+        kwargs.update({"Rules": HardEmbeddedDecisionRules})
+        super().__init__(*args, **kwargs)
+
+
+class SoftSegNBDT(SegNBDT):
     def __init__(self, *args, **kwargs):
         kwargs.update({"Rules": SoftEmbeddedDecisionRules})
         super().__init__(*args, **kwargs)

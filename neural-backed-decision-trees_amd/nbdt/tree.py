@@ -24,6 +24,7 @@ import numpy as np
 from nbdt.utils import (
     DATASETS,
     DATASET_TO_NUM_CLASSES,
+    SEGMENTATION_DATASETS,
     dataset_to_default_path_graph,
     dataset_to_default_path_wnids,
     hierarchy_to_path_graph,
@@ -226,6 +227,13 @@ class Tree:
         self.path_graph = path_graph
         self.path_wnids = path_wnids
         self.classes = classes
+        if dataset in SEGMENTATION_DATASETS:
+            for what, path in (("path_graph", path_graph), ("path_wnids", path_wnids)):
+                if not os.path.exists(path):
+                    raise FileNotFoundError(
+                        f"No such hierarchy file: {path} -- this package ships no graph or wnid files for the "
+                        f"segmentation datasets ({', '.join(SEGMENTATION_DATASETS)}); pass {what}= explicitly "
+                        "(or `classes` and a `path_graph`)")
         self._order, self._succ, self._pred, self._labels = read_graph(path_graph)
         self.wnids_leaves = get_wnids(path_wnids)
         self.wnid_to_class = {w: c for w, c in zip(self.wnids_leaves, self.classes)}

@@ -9,12 +9,19 @@ import os
 from pathlib import Path
 
 METHODS = ("wordnet", "random", "induced")
-DATASETS = ("CIFAR10", "CIFAR100", "TinyImagenet200", "Imagenet1000")
+# The segmentation datasets of the reference's hierarchies (SegNBDT / SoftSegTreeSupLoss).  Their graph and wnid files
+# are not shipped with this package: pass path_graph / path_wnids (or classes and a graph) to the constructors.
+SEGMENTATION_DATASETS = ("LookIntoPerson", "PascalContext", "ADE20K", "Cityscapes")
+DATASETS = ("CIFAR10", "CIFAR100", "TinyImagenet200", "Imagenet1000") + SEGMENTATION_DATASETS
 DATASET_TO_NUM_CLASSES = {
     "CIFAR10": 10,
     "CIFAR100": 100,
     "TinyImagenet200": 200,
     "Imagenet1000": 1000,
+    "LookIntoPerson": 20,
+    "PascalContext": 59,
+    "ADE20K": 150,
+    "Cityscapes": 19,
 }
 
 
