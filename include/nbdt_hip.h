@@ -24,6 +24,26 @@
  *   - activations are "padded NHWC bf16": [B][H+2][W+2][C] with a zero one-pixel border
  *     (so every 3x3 tap is in-bounds); kernels write interiors only.
  *   - conv weights are [Cout][taps][Cin] bf16 ("KRSC"), fp32 masters in the same order.
+ *
+ * Size limits (nbdt_version() >= 130; DESIGN.md section 26 has the derivation of each).  A tensor at or past its limit is
+ * refused with NBDT_EINVAL before any HIP call -- nothing is truncated and no wrapped address is formed.  "Elements" are
+ * elements of the tensor's type; most kernels keep signed 32-bit element offsets from the tensor's base:
+ *   nbdt_conv_igemm[_stats|_affine|_bnbwd|_multi], nbdt_conv_plan
+ *                          output (= residual, accumulate, bn_x) elements B*out_bs + out_base < 2^31; input elements
+ *                          B*in_bs + in_base + max tap_off < 2^31; weight elements cout*w_ntaps*cin < 2^31; pixels
+ *                          B*gh*gw < 2^31
+ *   nbdt_conv_wgrad        B*x_bs + x_base + max tap_off < 2^31, B*g_bs + g_base < 2^31, cout*w_ntaps*cin < 2^31, pixels < 2^31
+ *   nbdt_conv_pw           B*in_bs + tap_off < 2^31, B*out_bs < 2^31, cin*cout < 2^31, pixels < 2^31
+ *   nbdt_conv_seg_create   input bytes B*(gh+2)*(gw+2)*pix_stride*2 < 2^32; per class B*out_bs + out_base < 2^31; pixels < 2^31
+ *   nbdt_conv_group_*      padded pixels B*(H+2)*(W+2) < 2^31 (no limit on elements: 64-bit addresses)
+ *   nbdt_bn_*, nbdt_pool_bn_bwd_*, nbdt_bn_act_*, nbdt_dwconv_*
+ *                          padded elements B*(H+2)*(W+2)*C < 2^31 (the depthwise entries: of the input-side tensor);
+ *                          nbdt_bn_apply_s2d also B*(H/2+2)*(W/2+2)*4C < 2^31 for its output
+ *   nbdt_stem_wgrad        output pixels B*Ho*Wo < 2^31 - 2^22;  nbdt_stem_conv_pad / nbdt_stem_wgrad_pad: < 2^25
+ *   nbdt_seg_*             blocks N*ceil(HW/64) < 2^31; nbdt_seg_soft_tree_loss also pixels N*HW < 2^31
+ *   no limit below the launch grid (64-bit offsets throughout): nbdt_stem_conv, nbdt_stem_patches, nbdt_maxpool3x3s2_*,
+ *   nbdt_dropout_*, nbdt_linear_*, nbdt_se_*, nbdt_mix_batch, nbdt_augment_batch*, nbdt_policy_*batch*,
+ *   nbdt_resized_crop_*batch* (datasets and batches past 4 GiB are fine; one image has H, W <= 4096).
  */
 #ifndef NBDT_HIP_H
 #define NBDT_HIP_H
@@ -716,7 +736,8 @@ int nbdt_se_gate_bwd(const float* dgate, const float* gate, const float* pre1, c
 int nbdt_se_param_grad(const float* dpre2, const float* dpre1, const float* pre1, const float* pooled,
                        int32_t B, int32_t C, int32_t C_real, int32_t S, float* dw1, float* db1, float* dw2,
                        float* db2, void* stream);
-/* nn.Dropout(p) on n fp32 values: mask[i] in {0,1} from a counter hash of (seed, i); y = x*mask/(1-p) */
+/* nn.Dropout(p) on n fp32 values: mask[i] in {0,1} from a counter hash of (seed, i); y = x*mask/(1-p).
+ * n <= 256 * (2^31 - 1): one block per 256 elements (NBDT_EINVAL beyond). */
 int nbdt_dropout_fwd(const float* x, int64_t n, float p, uint32_t seed, uint8_t* mask, float* y,
                      void* stream);
 int nbdt_dropout_bwd(const float* gy, int64_t n, float p, const uint8_t* mask, float* gx, void* stream);

@@ -716,6 +716,10 @@ extern "C" int nbdt_bn_apply_s2d(const void* x, const float* save_mean, const fl
   NBDT_REQUIRE(H % 2 == 0 && W % 2 == 0, "space-to-depth needs even H and W");
   int rc = check_shape(B, H, W, C);
   if (rc) return rc;
+  // the space-to-depth copy has more border than x: B * (H/2 + 2) * (W/2 + 2) * 4C = B * (H + 4) * (W + 4) * C elements,
+  // and bn_apply_s2d_kernel keeps its offset `o2` in an int
+  NBDT_REQUIRE((long long)B * (H / 2 + 2) * (W / 2 + 2) * 4 * C < (1ll << 31),
+               "space-to-depth output elements: B * (H/2 + 2) * (W/2 + 2) * 4C must stay below 2^31 (32-bit element offsets)");
   hipStream_t st = (hipStream_t)stream;
   const PadGeom g = make_geom(B, H, W, C);
   const Layout l = layout_for(C);

@@ -15,7 +15,7 @@ constexpr int kSlots = NBDT_BN_SLOTS;
 int check_shape(int B, int H, int W, int C) {
   NBDT_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "empty tensor");
   NBDT_REQUIRE(C % 8 == 0 && C / 8 <= 256, "C must be a multiple of 8 and <= 2048");
-  NBDT_REQUIRE((long long)B * (H + 2) * (W + 2) * C < (1ll << 31), "tensor too large for 32-bit offsets");
+  NBDT_REQUIRE((long long)B * (H + 2) * (W + 2) * C < (1ll << 31), "padded tensor elements: B * (H+2) * (W+2) * C must stay below 2^31 (32-bit element offsets)");
   return NBDT_OK;
 }
 
@@ -24,7 +24,7 @@ int check_shape(int B, int H, int W, int C) {
 int check_shape_wide(int B, int H, int W, int C) {
   NBDT_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0, "empty tensor");
   NBDT_REQUIRE(C % 8 == 0, "C must be a multiple of 8");
-  NBDT_REQUIRE((long long)B * (H + 2) * (W + 2) * C < (1ll << 31), "tensor too large for 32-bit offsets");
+  NBDT_REQUIRE((long long)B * (H + 2) * (W + 2) * C < (1ll << 31), "padded tensor elements: B * (H+2) * (W+2) * C must stay below 2^31 (32-bit element offsets)");
   return NBDT_OK;
 }
 

@@ -62,6 +62,25 @@ static int check_desc(const nbdt_conv_desc* d) {
                "output pixel offsets must be 8-byte aligned");
   for (int t = 0; t < d->ntaps; ++t) NBDT_REQUIRE(d->tap_off[t] % 8 == 0, "tap offsets must be 16-byte aligned");
   NBDT_REQUIRE((int64_t)d->B * d->gh * d->gw < (1ll << 31), "pixel grid too large");
+  // Every kernel behind these entry points keeps ELEMENT offsets in a signed 32-bit int: pix_offset() and the epilogue's
+  // row_off[] (conv_common.h; a negative entry means "row past M", so a wrapped one silently skips its store),
+  // conv_dma.hip's a_src[] / w_src[], and the halo kernels' 32-bit byte lane offsets (2 * elements < 2^32).  The residual
+  // and the BatchNorm input of the fused backward sums are addressed with the output's offsets.
+  {
+    int64_t tap_hi = 0;
+    for (int t = 0; t < d->ntaps; ++t) tap_hi = d->tap_off[t] > tap_hi ? d->tap_off[t] : tap_hi;
+    const int64_t out_last = (int64_t)(d->B - 1) * d->out_bs + (int64_t)(d->gh - 1) * d->out_hs +
+                             (int64_t)(d->gw - 1) * d->out_ws + d->cout;
+    const int64_t in_last = (int64_t)(d->B - 1) * d->in_bs + (int64_t)(d->gh - 1) * d->in_hs +
+                            (int64_t)(d->gw - 1) * d->in_ws + d->cin;
+    const int64_t out_all = (int64_t)d->B * d->out_bs, in_all = (int64_t)d->B * d->in_bs;
+    NBDT_REQUIRE((out_all > out_last ? out_all : out_last) + d->out_base < (1ll << 31),
+                 "output elements: B * out_bs + out_base must stay below 2^31 (32-bit element offsets; the residual shares them)");
+    NBDT_REQUIRE((in_all > in_last ? in_all : in_last) + d->in_base + tap_hi < (1ll << 31),
+                 "input elements: B * in_bs + in_base + max tap_off must stay below 2^31 (32-bit element offsets)");
+    NBDT_REQUIRE((int64_t)d->cout * d->w_ntaps * d->cin < (1ll << 31),
+                 "weight elements: cout * w_ntaps * cin must stay below 2^31 (32-bit element offsets)");
+  }
   // (ksplit was a reserved, ignored field before version 106: descriptors must be zero-initialised)
   NBDT_REQUIRE(d->ksplit >= 0, "ksplit: 0 (automatic), 1 (never) or n blocks per tile");
   NBDT_REQUIRE(d->ksplit <= 1 || d->wide_tile == 5, "ksplit > 1 goes with wide_tile = 5 (forced half tiles; tests, A/B)");

@@ -324,8 +324,19 @@ extern "C" int nbdt_conv_pw(const nbdt_conv_desc* d, const void* in, const void*
   NBDT_REQUIRE(!(bn_partials != nullptr && d->accumulate), "fused statistics are for plain outputs");
   const int64_t M64 = (int64_t)d->B * d->gh * d->gw;
   NBDT_REQUIRE(M64 < (1ll << 31), "pixel grid too large");
-  NBDT_REQUIRE((int64_t)d->B * d->in_bs + d->tap_off[0] < (1ll << 31) && (int64_t)d->B * d->out_bs < (1ll << 31) &&
-               (int64_t)d->cin * d->cout < (1ll << 31), "tensor too large for 32-bit element offsets");
+  {   // signed 32-bit ELEMENT offsets: a_src[] here, row_off[] in the shared epilogue (conv_common.h), w_src[]
+    const int64_t out_last = (int64_t)(d->B - 1) * d->out_bs + (int64_t)(d->gh - 1) * d->out_hs +
+                             (int64_t)(d->gw - 1) * d->out_ws + d->cout;
+    const int64_t in_last = (int64_t)(d->B - 1) * d->in_bs + (int64_t)(d->gh - 1) * d->in_hs +
+                            (int64_t)(d->gw - 1) * d->in_ws + d->cin;
+    const int64_t out_all = (int64_t)d->B * d->out_bs, in_all = (int64_t)d->B * d->in_bs;
+    // (B * bs bounds every pixel of a padded NHWC map, base included; the last pixel's own end covers any other map)
+    NBDT_REQUIRE((in_all > in_last + d->in_base ? in_all : in_last + d->in_base) + d->tap_off[0] < (1ll << 31),
+                 "input elements: B * in_bs + tap_off must stay below 2^31 (32-bit element offsets)");
+    NBDT_REQUIRE((out_all > out_last + d->out_base ? out_all : out_last + d->out_base) < (1ll << 31),
+                 "output elements: B * out_bs must stay below 2^31 (32-bit element offsets)");
+    NBDT_REQUIRE((int64_t)d->cin * d->cout < (1ll << 31), "weight elements: cin * cout must stay below 2^31");
+  }
   nbdt::ConvDmaParams p{};
   p.d = *d;
   p.in = (const bf16_t*)in;

@@ -838,6 +838,13 @@ extern "C" int nbdt_conv_seg_create(const nbdt_conv_seg_desc* d, void** plan) {
     NBDT_REQUIRE(k.nslices >= 1 && k.nslices <= NBDT_SEG_MAX_SLICES && k.slices, "1..NBDT_SEG_MAX_SLICES slices per class");
     NBDT_REQUIRE((k.out_base % 4) == 0 && (k.out_ws % 4) == 0 && (k.out_hs % 4) == 0 && (k.out_bs % 4) == 0,
                  "output pixel offsets must be 8-byte aligned");
+    {   // the shared epilogue (conv_common.h) keeps output element offsets in a signed int: negative = "row past M"
+      const long long out_last = (long long)(d->B - 1) * k.out_bs + (long long)(d->gh - 1) * k.out_hs +
+                                 (long long)(d->gw - 1) * k.out_ws + d->cout;
+      const long long out_all = (long long)d->B * k.out_bs;
+      NBDT_REQUIRE((out_all > out_last ? out_all : out_last) + k.out_base < (1ll << 31),
+                   "output elements: B * out_bs + out_base must stay below 2^31 (32-bit element offsets; the residual shares them)");
+    }
     for (int s = 0; s < k.nslices; ++s) {
       const nbdt_conv_seg_slice& sl = k.slices[s];
       NBDT_REQUIRE(sl.tensor >= 0 && sl.tensor < d->ntensors && sl.w_matrix >= 0 && sl.w_matrix < d->nmatrices, "bad tensor / matrix index");

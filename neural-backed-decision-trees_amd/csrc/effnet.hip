@@ -1399,6 +1399,7 @@ extern "C" int nbdt_dropout_fwd(const float* x, int64_t n, float p, uint32_t see
                                 void* stream) {
   NBDT_REQUIRE(x && mask && y, "null argument");
   NBDT_REQUIRE(n > 0 && p >= 0.f && p < 1.f, "bad dropout arguments");
+  NBDT_REQUIRE((n + 255) / 256 <= 0x7fffffffll, "too many dropout elements for one launch (one block per 256)");
   hipLaunchKernelGGL(dropout_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x,
                      (long long)n, p, 1.f / (1.f - p), seed, mask, y);
   NBDT_LAUNCH_CHECK();
@@ -1408,6 +1409,7 @@ extern "C" int nbdt_dropout_fwd(const float* x, int64_t n, float p, uint32_t see
 extern "C" int nbdt_dropout_bwd(const float* gy, int64_t n, float p, const uint8_t* mask, float* gx, void* stream) {
   NBDT_REQUIRE(gy && mask && gx, "null argument");
   NBDT_REQUIRE(n > 0 && p >= 0.f && p < 1.f, "bad dropout arguments");
+  NBDT_REQUIRE((n + 255) / 256 <= 0x7fffffffll, "too many dropout elements for one launch (one block per 256)");
   hipLaunchKernelGGL(dropout_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, gy,
                      (long long)n, 1.f / (1.f - p), mask, gx);
   NBDT_LAUNCH_CHECK();

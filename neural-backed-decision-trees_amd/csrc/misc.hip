@@ -330,7 +330,8 @@ __global__ __launch_bounds__(256) void stem_wgrad_mfma_kernel(const float* __res
 static int stem_conv_impl(const float* img, const float* w, int B, int H, int W, int cout_real, int cpad, int stride,
                           int pad_t, int pad_l, void* out, void* stream) {
   const int Ho = (H + stride - 1) / stride, Wo = (W + stride - 1) / stride;
-  const long long total = (long long)B * Ho * Wo;      // one thread per output pixel
+  const long long total = (long long)B * Ho * Wo;      // one thread per output pixel (64-bit indices in the kernel)
+  NBDT_REQUIRE((total + 255) / 256 <= 0x7fffffffll, "output pixels: B * Ho * Wo needs more than 2^31 - 1 blocks of 256");
   hipLaunchKernelGGL(stem_conv_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), cout_real * 27 * sizeof(float),
                      (hipStream_t)stream, img, w, B, H, W, cout_real, cpad, stride, pad_t, pad_l, (bf16_t*)out);
   NBDT_LAUNCH_CHECK();
@@ -367,7 +368,11 @@ extern "C" int nbdt_stem_conv_pad(const float* img, const float* w, int32_t B, i
 
 static int stem_wgrad_impl(const float* img, const void* gy, int B, int H, int W, int cout_real, int cpad, int stride,
                            int pad_t, int pad_l, float* dw, void* stream) {
-  const int npix = B * ((H + stride - 1) / stride) * ((W + stride - 1) / stride);
+  // stem_wgrad_mfma_kernel counts output pixels in `int`: npix, and (blockIdx.x * tiles_per_block + t) * 64, which runs
+  // past npix by at most 64 * (tiles_per_block + 1) <= 2^21 + 128 before the kernel's `p0 >= npix` test sees it
+  const long long npix64 = (long long)B * ((H + stride - 1) / stride) * ((W + stride - 1) / stride);
+  NBDT_REQUIRE(npix64 < (1ll << 31) - (1ll << 22), "output pixels: B * Ho * Wo must stay below 2^31 - 2^22 (32-bit pixel index)");
+  const int npix = (int)npix64;
   const int tiles = (npix + 63) / 64;
   int blocks = tiles < 1024 ? tiles : 1024;
   const int tpb = (tiles + blocks - 1) / blocks;

@@ -487,6 +487,8 @@ extern "C" int nbdt_seg_soft_tree_loss(const nbdt_tree* t, const void* z, int zt
   NBDT_REQUIRE(N > 0, "empty batch has no mean loss");
   NBDT_REQUIRE(y && workspace && loss && gz && (const void*)gz != z, "null or aliased buffer");
   NBDT_REQUIRE(smoothing >= 0.f && smoothing < 1.f, "label smoothing must be in [0, 1)");
+  // (addresses are 64-bit throughout; the count of valid pixels -- pix_count_kernel, the loss's divisor -- is an int)
+  NBDT_REQUIRE(HW < (1ll << 31) && N <= ((1ll << 31) - 1) / HW, "pixels: N * HW must stay below 2^31 (the valid-pixel count is a 32-bit integer)");
   TreeView v = view_of(t);
   int* n_valid = (int*)workspace;
   float* partial = workspace + 4;

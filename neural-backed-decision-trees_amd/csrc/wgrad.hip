@@ -31,6 +31,23 @@ extern "C" int nbdt_conv_wgrad(const nbdt_wgrad_desc* d, const void* x, const vo
   NBDT_REQUIRE(d->cu_budget == 0 || (d->cu_budget >= 32 && d->cu_budget <= 256), "cu_budget must be 0 or 32..256");
   const int64_t M_all = (int64_t)d->B * d->gh * d->gw;
   NBDT_REQUIRE(M_all < (1ll << 31), "pixel grid too large");
+  // All three kernels form `(int)b * x_bs + ...` / `(int)b * g_bs + ...`: signed 32-bit ELEMENT offsets from the tensor
+  // base (the 8-wave kernels add a 32-bit byte lane offset on top: 2 * elements < 2^32, the same bound).
+  {
+    int64_t tap_hi = 0;
+    for (int t = 0; t < d->ntaps; ++t) tap_hi = d->tap_off[t] > tap_hi ? d->tap_off[t] : tap_hi;
+    const int64_t x_last = (int64_t)(d->B - 1) * d->x_bs + (int64_t)(d->gh - 1) * d->x_hs +
+                           (int64_t)(d->gw - 1) * d->x_ws + d->cin;
+    const int64_t g_last = (int64_t)(d->B - 1) * d->g_bs + (int64_t)(d->gh - 1) * d->g_hs +
+                           (int64_t)(d->gw - 1) * d->g_ws + d->cout;
+    const int64_t x_all = (int64_t)d->B * d->x_bs, g_all = (int64_t)d->B * d->g_bs;
+    NBDT_REQUIRE((x_all > x_last ? x_all : x_last) + d->x_base + tap_hi < (1ll << 31),
+                 "input elements: B * x_bs + x_base + max tap_off must stay below 2^31 (32-bit element offsets)");
+    NBDT_REQUIRE((g_all > g_last ? g_all : g_last) + d->g_base < (1ll << 31),
+                 "output-gradient elements: B * g_bs + g_base must stay below 2^31 (32-bit element offsets)");
+    NBDT_REQUIRE((int64_t)d->cout * d->w_ntaps * d->cin < (1ll << 31),
+                 "weight-gradient elements: cout * w_ntaps * cin must stay below 2^31");
+  }
   if (nbdt::wgrad_taps_applicable(d)) return nbdt::wgrad_taps(d, x, gy, dw, (hipStream_t)stream);
   // 3x3 stride-2 over the space-to-depth copy of the input (round 6; variant 3 = the first-generation kernel, A/B and tests)
   if (d->variant != 3 && nbdt::wgrad_s2d_applicable(d)) return nbdt::wgrad_s2d(d, x, gy, dw, (hipStream_t)stream);
