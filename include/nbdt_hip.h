@@ -43,7 +43,8 @@
  *   nbdt_seg_*             blocks N*ceil(HW/64) < 2^31; nbdt_seg_soft_tree_loss also pixels N*HW < 2^31
  *   no limit below the launch grid (64-bit offsets throughout): nbdt_stem_conv, nbdt_stem_patches, nbdt_maxpool3x3s2_*,
  *   nbdt_dropout_*, nbdt_linear_*, nbdt_se_*, nbdt_mix_batch, nbdt_augment_batch*, nbdt_policy_*batch*,
- *   nbdt_resized_crop_*batch* (datasets and batches past 4 GiB are fine; one image has H, W <= 4096).
+ *   nbdt_resized_crop_*batch* (datasets and batches past 4 GiB are fine; one image has H, W <= 4096),
+ *   nbdt_group_logits[_backward], nbdt_superclass_accumulate (grid-stride loops over the batch).
  */
 #ifndef NBDT_HIP_H
 #define NBDT_HIP_H
@@ -333,6 +334,52 @@ int nbdt_seg_soft_tree_loss(const nbdt_tree* t, const void* z, int ztype, int64_
                             float grad_scale, float* workspace, float* loss, float* gz, void* stream);
 int nbdt_seg_hard_forward(const nbdt_tree* t, const void* z, int ztype, int64_t N, int64_t HW, int64_t zi, int64_t zc,
                           int64_t* pred, float* onehot, void* stream);
+
+/* ------------------------------------------------------------------ superclass evaluation (nbdt_version() >= 131)
+ * Zero-shot evaluation on superclasses (reference nbdt/analysis.py:430-559, Superclass / SuperclassNBDT) and
+ * get_node_logits over an ad-hoc grouping of the classes (nbdt/model.py:84-99 with new_to_old_classes), csrc/superclass.hip.
+ *
+ * Grouping handle.  G groups over C classes: group g lists the classes group_cls[group_off[g] .. group_off[g+1]), in the
+ * order its sums run.  A class may lie in several groups or in none; a group may be empty.  Both arrays are HOST pointers
+ * and are copied to `device`, together with the transposed map (class -> the groups holding it, ascending group index)
+ * that the backward pass walks.  NBDT_EINVAL with a message: a class twice within one group, a class index outside
+ * [0, C), offsets that do not start at 0 or decrease, C <= 0 or G <= 0.
+ *
+ * Arithmetic contract (that of the rules layer): a group's logit is the sequential fp32 sum of its members in the listed
+ * order, starting from 0.0f, followed by one IEEE division by the member count; an empty group gives NaN (0 / 0), as
+ * torch's mean of an empty slice does; bf16 / fp16 logits are widened exactly.  A maximum is torch's: NaN is the largest
+ * value and the first of equal values wins.  No floating-point atomics: two calls on the same input give the same bits.
+ *
+ * Size limits: none.  Rows are not staged in LDS whole: the member list is walked in chunks of 2048 entries (8 KB of
+ * static LDS), and every row offset (b * ldz, b * G, b * C) is 64-bit.  C = 21,841 runs like C = 10.
+ *
+ * nbdt_group_logits: out [B, G] fp32, every element written.  z: [B, C] logits of type ztype, row stride ldz >= C.
+ * nbdt_group_logits_backward: gz [B, C] fp32 from gs [B, G] fp32: gz[b][c] = the sequential sum, over the groups g
+ *   holding c in ascending g and starting from 0.0f, of gs[b][g] / n_g (one division per term, then the add).  A class
+ *   in no group gets exactly 0.  gz is WRITTEN, every element, never added to.
+ * nbdt_superclass_accumulate: one evaluation batch in ONE launch, no host read-back.
+ *   y [B] int64 labels of the TEST label set; map_target int32 [C_test]: test class -> superclass or -1;
+ *   map_pred int32 [C]: training class -> superclass or -1 (required by NBDT_SUPER_MASKED, unused otherwise).
+ *   mode NBDT_SUPER_MASKED (Superclass.forward): every class with map_pred[c] < 0 takes the value -100.0f (the
+ *     reference's constant, not -inf), the first maximum over all C classes wins, and the prediction is
+ *     map_pred[argmax]: -1 when every mapped logit lies below -100.
+ *   mode NBDT_SUPER_GROUP_MEAN (SuperclassNBDT.forward): the prediction is the first maximum of the G group logits.
+ *   Both: t = map_target[y[b]]; a sample with y[b] outside [0, C_test), or with t outside [0, G), counts nowhere;
+ *   otherwise totals[0] += 1, totals[1] += (prediction == t), and, when 0 <= prediction < G,
+ *   confusion[t * G + prediction] += 1.  pred (nullable) [B] int64 is written for EVERY row, whatever its target.
+ *   totals [2] and confusion [G * G] (nullable) are int64 and ADDED TO, never overwritten: the caller zeroes them once
+ *   per pass; all sums are integer sums, so any split of the pass into batches gives the same bits. */
+#define NBDT_SUPER_MASKED 0
+#define NBDT_SUPER_GROUP_MEAN 1
+typedef struct nbdt_groups nbdt_groups;
+int nbdt_groups_create(int device, int num_classes, int num_groups, const int32_t* group_off, const int32_t* group_cls,
+                       nbdt_groups** out);
+int nbdt_groups_destroy(nbdt_groups* g);
+int nbdt_group_logits(const nbdt_groups* g, const void* z, int ztype, int64_t B, int64_t ldz, float* out, void* stream);
+int nbdt_group_logits_backward(const nbdt_groups* g, const float* gs, int64_t B, float* gz, void* stream);
+int nbdt_superclass_accumulate(const nbdt_groups* g, const void* z, int ztype, int64_t B, int64_t ldz, const int64_t* y,
+                               const int32_t* map_target, int32_t C_test, const int32_t* map_pred, int32_t mode,
+                               int64_t* totals, int64_t* confusion, int64_t* pred, void* stream);
 
 /* ------------------------------------------------------------------ backbone: implicit-GEMM conv
  * One launch = one "tap table": out[pix(m)][n] (+)= sum_t sum_c in[pix_in(m) + tap_off[t]][c] *

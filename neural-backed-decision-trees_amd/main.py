@@ -39,6 +39,18 @@ recipes in the reference's ``scripts/*.sh`` keep their arguments.  What differs,
   analyzers of ``nbdt.diagnostics`` beside the ``--analysis`` analyzer, in a ``diagnostics.Chain``: per-node accuracy and
   entropy, the depth of the first wrong turn, confusion matrices and entropy rankings from one fused launch per
   evaluation batch; ``--diagnostics-out FILE`` writes the last evaluation's report as JSON.
+* ``--analysis Superclass | SuperclassNBDT --superclass-wnids W1 W2 ...`` is the reference's zero-shot evaluation on
+  superclasses (``nbdt.superclass``, one launch per evaluation batch): ``--dataset-test D`` names the label set of the
+  evaluation split, which comes from ``--data-file-test F`` (its ``test_x`` / ``test_y``) or, with ``--synthetic``, is a
+  synthetic split with labels in ``[0, C_test)``; ``--disable-test-eval`` (required when the two label sets differ) skips
+  the criterion and the backbone's hit counter, whose labels would index another label set; in a training run the best
+  checkpoint is then kept by the analyzer's accuracy (its ``acc`` field holds that), so the run needs an ``--analysis``
+  that reports one.  ``--superclass-file`` is an
+  explicit hypernym table; without it and without nltk the mapping comes from the shipped WordNet graph, lossily.
+* ``--include-labels`` / ``--exclude-labels`` / ``--probability-labels`` / ``--include-classes`` (reference
+  nbdt/data/custom.py) restrict the TRAINING split: ``nbdt.data.label_subset`` picks the kept samples once, with the
+  reference's draw, and every epoch's permutation is drawn over them (``nbdt.dist.epoch_indices(subset=)``) -- with the
+  device-resident datasets too, and within each rank's range under ``--shard-data``.  Labels keep their numbering.
 * Evaluation is distributed whenever there is more than one rank: rank r of w evaluates the samples
   ``nbdt.data.shard_range(N, r, w)`` of the test split, the hit counts and the loss are summed over ranks with one
   all-reduce, and every analyzer's ``reduce()`` merges the ranks' statistics, so what rank 0 prints, writes and
@@ -117,12 +129,13 @@ from nbdt import diagnostics  # noqa: E402
 from nbdt import dist as ndist  # noqa: E402
 from nbdt import loss as losses  # noqa: E402
 from nbdt import models  # noqa: E402
-from nbdt.data import (DATASET_STATS, RESIZED_CROP_STATS, DeviceDataset, ResizedCropDataset, draw_mix, mix_batch,  # noqa: E402
-                       shard_range)
+from nbdt import superclass  # noqa: E402
+from nbdt.data import (DATASET_STATS, RESIZED_CROP_STATS, DeviceDataset, ResizedCropDataset, draw_mix, label_subset,  # noqa: E402
+                       mix_batch, shard_range)
 from nbdt.engine import train_step  # noqa: E402
 from nbdt.model import coerce_state_dict  # noqa: E402
-from nbdt.tree import Tree  # noqa: E402
-from nbdt.utils import DATASET_TO_NUM_CLASSES, DATASETS, SEGMENTATION_DATASETS  # noqa: E402
+from nbdt.tree import Tree, get_wnids  # noqa: E402
+from nbdt.utils import DATASET_TO_NUM_CLASSES, DATASETS, SEGMENTATION_DATASETS, dataset_to_default_path_wnids  # noqa: E402
 
 CIFAR_MEAN, CIFAR_STD = (0.4914, 0.4822, 0.4465), (0.2023, 0.1994, 0.2010)   # reference nbdt/data/cifar.py:17-19
 METRICS = {"top1": 1, "top2": 2, "top5": 5, "top10": 10}      # the reference's --metric names -> k
@@ -165,7 +178,23 @@ def build_parser():
     p.add_argument("--eval", action="store_true")
     p.add_argument("--loss", choices=losses.names, default=["CrossEntropyLoss"], nargs="+")
     p.add_argument("--metric", choices=sorted(METRICS), default="top1")
-    p.add_argument("--analysis", choices=analysis.names, help="analyzer run during every evaluation (nbdt.analysis)")
+    p.add_argument("--analysis", choices=analysis.names + superclass.names,
+                   help="analyzer run during every evaluation (nbdt.analysis; Superclass / SuperclassNBDT: nbdt.superclass)")
+    p.add_argument("--dataset-test", choices=[d for d in DATASETS if d not in SEGMENTATION_DATASETS],
+                   help="the label set of the evaluation split (default: --dataset); another one needs --disable-test-eval")
+    p.add_argument("--data-file-test", metavar="F",
+                   help="with --dataset-test: torch.save'd dict whose test_x / test_y are the evaluation split")
+    p.add_argument("--disable-test-eval", action="store_true",
+                   help="evaluation skips the criterion and the backbone's hit counter (their labels would index another "
+                        "label set); use --analysis to define the metric")
+    superclass.add_arguments(p)     # --superclass-wnids / --superclass-file
+    # label subsets of the training split (reference nbdt/data/custom.py:37-41)
+    p.add_argument("--probability-labels", nargs="*", type=float, metavar="P",
+                   help="keep a training sample of label c with probability P[c] (one value: every label)")
+    p.add_argument("--include-labels", nargs="*", type=int, metavar="C", help="train on these labels only")
+    p.add_argument("--exclude-labels", nargs="*", type=int, metavar="C", help="train on every label but these")
+    p.add_argument("--include-classes", nargs="*", metavar="WNID",
+                   help="--include-labels by name: the WordNet ids of the dataset's classes (nbdt/wnids/<dataset>.txt)")
     p.add_argument("--diagnostics", choices=diagnostics.names, nargs="+", default=[],
                    help="tree diagnostics run beside --analysis during every evaluation (nbdt.diagnostics)")
     p.add_argument("--diagnostics-out", metavar="FILE", help="write the diagnostics of the last evaluation as JSON")
@@ -440,6 +469,56 @@ def load_data(args, num_classes, device, raw=False):
     return [*make(n), *make(max(n // 4, args.batch_size))]
 
 
+def synthetic_test_labels(seed, num_classes_test, count):
+    """(labels, generator): the labels of the synthetic --dataset-test split, uniform in [0, num_classes_test), drawn first
+    from a generator of their own so that they are a function of (seed, label set, count) alone."""
+    g = torch.Generator().manual_seed(int(seed) + 29)
+    return torch.randint(0, int(num_classes_test), (int(count),), generator=g), g
+
+
+def load_test_data(args, num_classes_test, like_x, raw=False):
+    """The evaluation split of --dataset-test on the host: test_x / test_y of --data-file-test, prepared as load_data
+    prepares a split, or with --synthetic a synthetic split shaped like the training images (`like_x`, whose count the
+    usual quarter is taken of) with labels in [0, num_classes_test)."""
+    if args.data_file_test:
+        blob = torch.load(args.data_file_test, map_location="cpu")
+        x, y = blob["test_x"], blob["test_y"].long()
+        if raw and x.dtype == torch.uint8:
+            return x.contiguous(), y
+        if resized_crop_family(args):
+            raise SystemExit(f"--augment {args.augment} resamples bytes: test_x of {args.data_file_test} must be uint8, "
+                             f"not {x.dtype}")
+        if x.dtype == torch.uint8:
+            # deliberate: whatever --dataset-test is, its images are normalised as load_data normalises the images the
+            # model was trained on (the CIFAR statistics, on this host path), not with the test set's own statistics
+            x = x.float().div_(255.0)
+            x = (x - torch.tensor(CIFAR_MEAN).view(1, 3, 1, 1)) / torch.tensor(CIFAR_STD).view(1, 3, 1, 1)
+        return x.float().contiguous(), y
+    if not args.synthetic:
+        raise SystemExit("--dataset-test needs its evaluation split: --data-file-test F (test_x, test_y), or --synthetic")
+    m = max(like_x.shape[0] // 4, args.batch_size)
+    y, g = synthetic_test_labels(args.seed, num_classes_test, m)
+    proto = torch.randn(num_classes_test, *like_x.shape[1:], generator=g)
+    x = proto[y] + torch.randn(m, *like_x.shape[1:], generator=g)
+    if like_x.dtype == torch.uint8:
+        x = (128.0 + 40.0 * x).round_().clamp_(0, 255).to(torch.uint8)
+    return x.contiguous(), y
+
+
+def training_subset(args, train_y, num_classes):
+    """--include-labels / --exclude-labels / --probability-labels / --include-classes: the kept training samples as an
+    ascending int64 index tensor (nbdt.data.label_subset, seeded with --seed), or None without such a flag."""
+    if not args.label_subset:
+        return None
+    kwargs = {args.label_subset: getattr(args, args.label_subset)}
+    if args.label_subset == "include_classes":
+        kwargs["classes"] = get_wnids(args.path_wnids or dataset_to_default_path_wnids(args.dataset))
+    try:
+        return label_subset(train_y, num_classes, seed=args.seed, **kwargs)
+    except ValueError as e:
+        raise SystemExit(f"--{args.label_subset.replace('_', '-')}: {e}") from e
+
+
 def build_diagnostic(name, tree):
     """One analyzer of nbdt.diagnostics on the run's hierarchy (ConfusionMatrix: the backbone's own predictions)."""
     cls = getattr(diagnostics, name)
@@ -448,11 +527,12 @@ def build_diagnostic(name, tree):
     return cls(tree.classes)
 
 
-def evaluate_part(net, criterion_module, analyzer, k, x, y, batch, device, rank=0, world=1):
+def evaluate_part(net, criterion_module, analyzer, k, x, y, batch, device, rank=0, world=1, plain_eval=True):
     """One rank's part of an evaluation, nothing exchanged: the samples ``shard_range(N, rank, world)`` of (x, y) in
     batches of `batch`; every batch's logits also go to the analyzer (update_batch).  Returns (HitCounter, loss sum as a
     device scalar, number of batches).  x is a device-resident dataset -- sharded (it must be this rank's shard) or whole
-    -- or a host tensor."""
+    -- or a host tensor.  plain_eval=False (--disable-test-eval): the criterion and the hit counter are skipped -- the
+    labels belong to another label set than the logits' columns -- and only the analyzer sees the batches."""
     net.eval()
     plain = HitCounter(k, device)
     loss_sum = torch.zeros((), device=device)
@@ -472,19 +552,21 @@ def evaluate_part(net, criterion_module, analyzer, k, x, y, batch, device, rank=
                 j = min(lo + i + batch, hi)
                 xb, yb = x[lo + i:j].to(device), y[lo + i:j].to(device)
             z = net(xb)
-            loss_sum += criterion_module(z, yb)
             batches += 1
-            plain.add(z, yb)
+            if plain_eval:
+                loss_sum += criterion_module(z, yb)
+                plain.add(z, yb)
             analyzer.update_batch(z, yb, xb)
     return plain, loss_sum, batches
 
 
-def evaluate(net, criterion_module, analyzer, k, x, y, batch, device, rank=0, world=1, group=None):
+def evaluate(net, criterion_module, analyzer, k, x, y, batch, device, rank=0, world=1, group=None, plain_eval=True):
     """reference main.py:262-277: top-k accuracy of the backbone's logits and the mean loss over (x, y); every batch's
     logits also go to the analyzer (update_batch), which keeps its own statistic.  With world > 1 every rank evaluates its
     part (evaluate_part), hits / seen / loss sum / batch count are summed over ranks with ONE all-reduce and the analyzer
     is reduced (analyzer.reduce): every rank returns, and its analyzer holds, the numbers of the whole split."""
-    plain, loss_sum, batches = evaluate_part(net, criterion_module, analyzer, k, x, y, batch, device, rank, world)
+    plain, loss_sum, batches = evaluate_part(net, criterion_module, analyzer, k, x, y, batch, device, rank, world,
+                                             plain_eval=plain_eval)
     if world > 1:
         # one fp64 vector: the counts are integers far below 2^53, so their sums are exact
         part = torch.tensor([0.0, 0.0, plain.seen, batches], dtype=torch.float64, device=device)
@@ -505,6 +587,26 @@ def parse_args(argv=None):
                      "pass (its start_train raises NotImplementedError)")
     if args.diagnostics_out and not args.diagnostics:
         parser.error("--diagnostics-out needs --diagnostics")
+    if args.dataset_test and args.dataset_test != args.dataset and not args.disable_test_eval:
+        parser.error(f"--dataset-test {args.dataset_test} differs from --dataset {args.dataset}: the criterion and the "
+                     "backbone's hit counter would index another label set; pass --disable-test-eval and an --analysis")
+    if args.disable_test_eval and not args.eval and args.analysis in (None, "Noop"):
+        parser.error("--disable-test-eval in a training run needs an --analysis that reports an accuracy: nothing else "
+                     "evaluates the epochs, and the best checkpoint is kept by it")
+    if args.data_file_test and not args.dataset_test:
+        parser.error("--data-file-test holds the evaluation split of --dataset-test: it needs --dataset-test")
+    if args.analysis in superclass.names and not args.superclass_wnids:
+        parser.error(f"--analysis {args.analysis} needs --superclass-wnids")
+    if (args.superclass_wnids or args.superclass_file) and args.analysis not in superclass.names:
+        parser.error("--superclass-wnids / --superclass-file belong to --analysis Superclass | SuperclassNBDT")
+    subsets = [f for f in ("probability_labels", "include_labels", "exclude_labels", "include_classes")
+               if getattr(args, f) is not None]
+    if len(subsets) > 1:
+        parser.error("--probability-labels, --include-labels, --exclude-labels and --include-classes each select the "
+                     f"training subset: pass one of them, not {len(subsets)}")
+    if subsets and not getattr(args, subsets[0]):
+        parser.error(f"--{subsets[0].replace('_', '-')} needs at least one value")
+    args.label_subset = subsets[0] if subsets else None
     if args.shard_data and not (args.augment == "reference" or resized_crop_family(args)):
         parser.error("--shard-data shards the device-resident datasets: it needs --augment reference, resized-crop or "
                      "resized-crop-policy")
@@ -627,6 +729,10 @@ def main(argv=None):
     num_classes = DATASET_TO_NUM_CLASSES[args.dataset]
     log("==> Preparing data..")
     train_x, train_y, test_x, test_y = load_data(args, num_classes, device, raw=on_device)
+    if args.dataset_test and (args.dataset_test != args.dataset or args.data_file_test):
+        # the evaluation split carries the labels of another label set (or is another file of the same one)
+        test_x, test_y = load_test_data(args, DATASET_TO_NUM_CLASSES[args.dataset_test], train_x, raw=on_device)
+    kept = training_subset(args, train_y, num_classes)     # before the labels move to the device: a host pass over them
     shard = (rank, world) if args.shard_data else None         # each rank keeps its contiguous part of both splits
     if args.augment == "reference":
         stats = DATASET_STATS[args.dataset]
@@ -676,6 +782,12 @@ def main(argv=None):
     n_test = test_x.global_size if on_device else test_x.shape[0]
     log(f"Training with dataset {args.dataset} and {num_classes} classes: {n_train} train / "
         f"{n_test} test samples of shape {tuple(train_x.shape[1:])}")
+    if args.dataset_test:
+        log(f"Testing with dataset {args.dataset_test} and {DATASET_TO_NUM_CLASSES[args.dataset_test]} classes")
+    if kept is not None:
+        log(f"--{args.label_subset.replace('_', '-')}: training on {kept.numel()} of the {n_train} training samples")
+    if args.disable_test_eval and args.analysis in (None, "Noop"):
+        log(" * Warning: --disable-test-eval without an --analysis: nothing measures the evaluation pass")
     if shard is not None:
         log(f"--shard-data: rank {rank} of {world} holds train samples {tuple(train_x.shard_range)} and test samples "
             f"{tuple(test_x.shard_range)}")
@@ -738,8 +850,19 @@ def main(argv=None):
 
     criterion = build_criterion(args, tree, net=net, checkpoint_path=checkpoint_path)
     fast = criterion if hasattr(criterion, "loss_and_grad") else _PlainCE(tree, args.label_smoothing)
-    analyzer_cls = getattr(analysis, args.analysis or "Noop")
-    analyzer = analyzer_cls(tree=tree, metric=args.metric) if args.analysis not in (None, "Noop") else analyzer_cls(tree.classes)
+    if args.analysis in superclass.names:
+        try:
+            analyzer = getattr(superclass, args.analysis)(tree=tree, superclass_wnids=args.superclass_wnids,
+                                                          dataset_test=args.dataset_test, metric=args.metric,
+                                                          hypernyms=args.superclass_file)
+        except (ValueError, KeyError, RuntimeError) as e:
+            raise SystemExit(f"--analysis {args.analysis}: {e}") from e
+        log(f"==> Mapped {len(analyzer.mapped_classes)} of the {len(analyzer.wnids_test)} {analyzer.dataset_test} classes "
+            f"to your superclasses; {[len(g) for g in analyzer.groups]} {args.dataset} classes under each")
+    else:
+        analyzer_cls = getattr(analysis, args.analysis or "Noop")
+        analyzer = analyzer_cls(tree=tree, metric=args.metric) if args.analysis not in (None, "Noop") \
+            else analyzer_cls(tree.classes)
     extras = [build_diagnostic(name, tree) for name in args.diagnostics]
     if extras:                                    # every rank ends up with the reduced statistic: rank 0 reports
         analyzer = diagnostics.Chain(analyzer, *extras)
@@ -772,7 +895,7 @@ def main(argv=None):
         # unsharded: the same shuffle of the whole set on every rank, each takes its slice of every global batch;
         # --shard-data: every rank shuffles the part it holds
         plan = ndist.epoch_indices(n_train, args.batch_size, rank, world, args.seed, epoch,
-                                   sharded=shard is not None)
+                                   sharded=shard is not None, subset=kept)
         steps = plan.shape[0]
         lrs = None
         if per_step_lr:          # warm-up / per-step decay: one learning rate per step of this epoch
@@ -808,26 +931,32 @@ def main(argv=None):
         nonlocal best_acc
         analyzer.start_test(epoch)
         acc, loss = evaluate(net, criterion, analyzer, METRICS[args.metric], test_x, test_y, 100, device, rank=rank,
-                             world=world)
+                             world=world, plain_eval=not args.disable_test_eval)
         nbdt_acc = analyzer.accuracy() if hasattr(analyzer, "accuracy") else None
         extra = f" | {analyzer.name}: {nbdt_acc:.3f}%" if nbdt_acc is not None else ""
-        log("Loss: %.3f | Acc: %.3f%%%s" % (loss, acc, extra))
+        if args.disable_test_eval:
+            log("Loss and Acc not evaluated (--disable-test-eval)" + extra)
+        else:
+            log("Loss: %.3f | Acc: %.3f%%%s" % (loss, acc, extra))
         analyzer.end_test(epoch)
-        log(f"Accuracy: {acc} | Best Accuracy: {best_acc}")
+        # what "best" is measured by: the backbone's accuracy, or with --disable-test-eval (nothing evaluated the backbone)
+        # the analyzer's -- parse_args refuses a training run that would have neither
+        score = nbdt_acc if args.disable_test_eval and nbdt_acc is not None else acc
+        log(f"Accuracy: {score} | Best Accuracy: {best_acc}" + (f" ({analyzer.name})" if score is not acc else ""))
         acc_ema = None
         if ema_on:       # every rank swaps: the evaluation is distributed.  Swapped back before anything is saved
             with engine.ema_weights():
                 acc_ema, loss_ema = evaluate(net, criterion, ema_analyzer, METRICS[args.metric], test_x, test_y, 100,
-                                             device, rank=rank, world=world)
+                                             device, rank=rank, world=world, plain_eval=not args.disable_test_eval)
             log(f"EMA Accuracy: {acc_ema} | EMA Loss: {loss_ema:.3f} | {engine.ema_updates} updates")
-        if acc > best_acc and checkpoint and rank == 0:
-            log(f"Saving to {checkpoint_fname} ({acc})..")
+        if score > best_acc and checkpoint and rank == 0:
+            log(f"Saving to {checkpoint_fname} ({score})..")
             os.makedirs("checkpoint", exist_ok=True)
-            blob = {"net": {k: v.cpu() for k, v in net.state_dict().items()}, "acc": acc, "epoch": epoch}
+            blob = {"net": {k: v.cpu() for k, v in net.state_dict().items()}, "acc": score, "epoch": epoch}
             if ema_on:
                 blob.update(ema_checkpoint_fields(engine, acc_ema))
             torch.save(blob, checkpoint_path)
-        best_acc = max(best_acc, acc)
+        best_acc = max(best_acc, score)
         if extras and args.diagnostics_out and rank == 0:
             with open(args.diagnostics_out, "w") as f:
                 json.dump({a.name: a.report() for a in extras}, f, indent=1)

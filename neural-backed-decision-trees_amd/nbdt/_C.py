@@ -327,6 +327,13 @@ SIGNATURES = {
     # agglomerative clustering (nbdt_version() >= 128): (centers, n, d, method, metric, workspace, workspace_bytes, ...)
     "nbdt_linkage_workspace_bytes": (c_int, [c_int64, POINTER(c_int64)]),
     "nbdt_linkage": (c_int, [_P, c_int64, c_int64, c_int32, c_int32, _P, c_int64, _P, _P, _P, _P]),
+    # superclass evaluation (nbdt_version() >= 131): (groups, z, ztype, B, ldz, ...)
+    "nbdt_groups_create": (c_int, [c_int, c_int, c_int, _I32P, _I32P, POINTER(c_void_p)]),
+    "nbdt_groups_destroy": (c_int, [c_void_p]),
+    "nbdt_group_logits": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P]),
+    "nbdt_group_logits_backward": (c_int, [c_void_p, _P, c_int64, _P, _P]),
+    "nbdt_superclass_accumulate": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, c_int32, _P, c_int32, _P, _P,
+                                           _P, _P]),
 }
 
 
@@ -591,6 +598,108 @@ def node_outputs(handle, z):
     check(lib().nbdt_node_outputs(handle.h, ptr(z), ztype_of(z), B, ld, ptr(logits), ptr(probs),
                                   ptr(preds), ptr(ent), stream_of(z)))
     return logits, probs, preds, ent
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# ad-hoc class groupings and superclass evaluation: csrc/superclass.hip
+
+NBDT_SUPER_MASKED, NBDT_SUPER_GROUP_MEAN = 0, 1
+
+
+class GroupsHandle:
+    """Owns one nbdt_groups on one device.  groups: a sequence of G class-index sequences (the order of each is the
+    order its sum runs in) over num_classes classes."""
+
+    def __init__(self, groups, num_classes, device_index):
+        self.groups = tuple(tuple(int(c) for c in g) for g in groups)
+        self.num_classes, self.num_groups, self.device_index = int(num_classes), len(self.groups), device_index
+        off = np.zeros(self.num_groups + 1, dtype=np.int32)
+        off[1:] = np.cumsum([len(g) for g in self.groups])
+        cls = np.array([c for g in self.groups for c in g] or [0], dtype=np.int32)
+        out = c_void_p()
+        check(lib().nbdt_groups_create(int(device_index), self.num_classes, self.num_groups, off.ctypes.data_as(_I32P),
+                                       cls.ctypes.data_as(_I32P), ctypes.byref(out)))
+        self.h = out
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and _lib is not None:
+                _lib.nbdt_groups_destroy(self.h)
+        except Exception:
+            pass
+
+
+_groups_cache = {}
+GROUPS_CACHE_MAX = 64       # handles kept: a caller that keeps inventing groupings must not pin device memory for good
+
+
+def groups_handle(groups, num_classes, device_index):
+    """The cached handle of one (grouping, class count, device), the way a Tree caches its handle per device.  The cache
+    holds the GROUPS_CACHE_MAX most recently used handles; one that falls out is destroyed when its last user (an
+    analyzer, an autograd graph) lets go of it."""
+    key = (tuple(tuple(int(c) for c in g) for g in groups), int(num_classes), device_index)
+    h = _groups_cache.pop(key, None)
+    if h is None:
+        h = GroupsHandle(key[0], num_classes, device_index)
+    _groups_cache[key] = h              # (re)inserted last: dicts keep insertion order, the first key is the oldest
+    while len(_groups_cache) > GROUPS_CACHE_MAX:
+        del _groups_cache[next(iter(_groups_cache))]
+    return h
+
+
+def _group_rows(z, handle):
+    if z.dim() != 2:
+        raise NBDTHipError(f"group logits expect [B, C] logits, got shape {tuple(z.shape)}")
+    if z.shape[1] != handle.num_classes:
+        raise NBDTHipError(f"logits have {z.shape[1]} columns but the grouping is over {handle.num_classes} classes")
+    if z.stride(1) != 1 or (z.shape[0] > 1 and z.stride(0) < z.shape[1]):
+        z = z.contiguous()
+    return z, z.shape[0], (z.stride(0) if z.shape[0] > 1 else z.shape[1])
+
+
+def group_logits(handle, z):
+    """[B, G] fp32: the mean of the logits of every group's classes (nbdt_group_logits)."""
+    require_gpu(z, "group_logits")
+    z, B, ld = _group_rows(z, handle)
+    out = torch.empty((B, handle.num_groups), dtype=torch.float32, device=z.device)
+    check(lib().nbdt_group_logits(handle.h, ptr(z), ztype_of(z), B, ld, ptr(out), stream_of(z)))
+    return out
+
+
+def group_logits_backward(handle, gs):
+    require_gpu(gs, "group_logits_backward")
+    gs = gs.contiguous().float()
+    gz = torch.empty((gs.shape[0], handle.num_classes), dtype=torch.float32, device=gs.device)
+    check(lib().nbdt_group_logits_backward(handle.h, ptr(gs), gs.shape[0], ptr(gz), stream_of(gs)))
+    return gz
+
+
+def superclass_accumulate(handle, z, y, map_target, map_pred, mode, totals, confusion=None, want_pred=False):
+    """One evaluation batch added into the int64 device counters totals [2] and confusion [G, G] (nullable) by ONE launch
+    (nbdt_superclass_accumulate); nothing here waits for the GPU.  map_target / map_pred: int32 device tensors.  Returns
+    the predicted superclass of every row [B] int64 when want_pred, else None."""
+    require_gpu(z, "superclass_accumulate")
+    z, B, ld = _group_rows(z, handle)
+    for name, t, dt in (("targets", y, torch.int64), ("map_target", map_target, torch.int32),
+                        ("map_pred", map_pred, torch.int32), ("totals", totals, torch.int64),
+                        ("confusion", confusion, torch.int64)):
+        if t is None and name in ("map_pred", "confusion"):
+            continue
+        if t.dtype != dt or t.device != z.device or not t.is_contiguous():
+            raise NBDTHipError(f"superclass_accumulate: {name} must be a contiguous {dt} tensor on {z.device}, got "
+                               f"{t.dtype} on {t.device}")
+    if y.shape != (B,):
+        raise NBDTHipError(f"superclass_accumulate: {B} rows of logits but targets of shape {tuple(y.shape)}")
+    if map_pred is not None and map_pred.numel() != handle.num_classes:
+        raise NBDTHipError(f"map_pred has {map_pred.numel()} entries, the grouping is over {handle.num_classes} classes")
+    G = handle.num_groups
+    if totals.numel() != 2 or (confusion is not None and confusion.numel() != G * G):
+        raise NBDTHipError(f"superclass_accumulate: totals must hold 2 counters and confusion {G} x {G}")
+    pred = torch.empty((B,), dtype=torch.int64, device=z.device) if want_pred else None
+    check(lib().nbdt_superclass_accumulate(handle.h, ptr(z), ztype_of(z), B, ld, ptr(y), ptr(map_target),
+                                           int(map_target.numel()), ptr(map_pred), int(mode), ptr(totals),
+                                           ptr(confusion), ptr(pred), stream_of(z)))
+    return pred
 
 
 # ---------------------------------------------------------------------------------------------------------------

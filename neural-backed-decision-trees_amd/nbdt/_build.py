@@ -47,7 +47,9 @@ FLAGS = {
     "clip.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # fp64 sums and Lance-Williams updates as the separate IEEE operations tests/_linkage_ref.py restates: merge order is decided by them
     "linkage.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
-    "ema.hip": ["-ffp-contract=off"],         # e + omd * (p - e): a subtract, a multiply and an add, never a fused multiply-add
+    # group means and their gradient terms: ordered fp32 sums and one IEEE division each, the contract of rules.hip
+    "superclass.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    "ema.hip": ["-ffp-contract=off"],        # e + omd * (p - e): a subtract, a multiply and an add, never a fused multiply-add
 }
 
 

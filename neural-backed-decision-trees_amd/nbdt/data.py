@@ -68,6 +68,53 @@ def shard_range(n, rank, world):
     return rank * n // world, (rank + 1) * n // world
 
 
+def label_subset(labels, num_classes, probability_labels=None, include_labels=None, exclude_labels=None,
+                 include_classes=None, classes=None, seed=0):
+    """The samples the reference's label-subset datasets keep (nbdt/data/custom.py: ResampleLabels / IncludeLabels /
+    ExcludeLabels / IncludeClasses), as an ascending int64 tensor of indices into `labels`.
+
+    Its rule (build_index_mapping): ``random.seed(seed)``, one ``random.random()`` draw per sample in dataset order, and
+    the sample is kept when the draw is below ``p[label]``.  ``probability_labels`` is p -- a scalar or a one-element list
+    broadcasts, any other length must be num_classes; include / exclude are the p of ones and zeros (a draw is always
+    below 1 and never below 0); ``include_classes`` names entries of ``classes``.  Exactly one of the four selects.  The
+    labels keep their num_classes-way numbering: a training loop indexes the dataset through the result."""
+    import random
+    given = [k for k, v in (("probability_labels", probability_labels), ("include_labels", include_labels),
+                            ("exclude_labels", exclude_labels), ("include_classes", include_classes)) if v is not None]
+    if len(given) != 1:
+        raise ValueError(f"label_subset takes exactly one of probability_labels, include_labels, exclude_labels and "
+                         f"include_classes, got {given or 'none'}")
+    k = int(num_classes)
+    if include_classes is not None:
+        if classes is None:
+            raise ValueError("include_classes needs the dataset's class names (classes=)")
+        names = list(classes)
+        include_labels = [names.index(c) for c in include_classes]
+    if exclude_labels is not None:
+        include_labels = set(range(k)) - set(int(c) for c in exclude_labels)
+    if include_labels is not None:
+        keep = set(int(c) for c in include_labels)
+        p = [int(c in keep) for c in range(k)]
+    else:
+        p = probability_labels
+        if not isinstance(p, (tuple, list)):
+            p = [p] * k
+        elif len(p) == 1:
+            p = list(p) * k
+        if len(p) != k:
+            raise ValueError(f"Length of probabilities vector {len(p)} must equal that of the dataset classes {k}.")
+    if isinstance(labels, torch.Tensor):
+        labels = labels.cpu().numpy()
+    labels = np.asarray(labels).astype(np.int64).reshape(-1)
+    if labels.size and (int(labels.min()) < 0 or int(labels.max()) >= k):
+        raise ValueError(f"labels must lie in [0, {k}), got min {int(labels.min())}, max {int(labels.max())}")
+    rng = random.Random(seed)          # random.seed(seed) + random.random(), without touching the global generator
+    kept = [i for i, label in enumerate(labels.tolist()) if rng.random() < p[label]]
+    if not kept:
+        raise ValueError("the label subset is empty: no sample of the dataset was kept")
+    return torch.tensor(kept, dtype=torch.int64)
+
+
 def _place(name, x, y, shard, device):
     """(x, y on the device, (lo, hi), N): the whole of the N samples, or with shard = (rank, world) only the rank's
     range of them -- sliced on the host, so the rest of `x` (a memory-mapped file, say) is never read or copied."""

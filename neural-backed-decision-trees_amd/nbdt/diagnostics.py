@@ -10,7 +10,8 @@ launch and one block of counters.  ``update_batch`` only enqueues work, the firs
 an explicit accessor.
 
 Not here: image dumps (``highest`` / ``lowest`` return tensors; writing JPEGs is presentation), ``TopEntropy``,
-``NBDTEntropyBottom`` (scores only the last sample of a batch in the reference), ``IgnoredSamples``, ``Superclass*``.
+``NBDTEntropyBottom`` (scores only the last sample of a batch in the reference), ``IgnoredSamples``.  ``Superclass`` and
+``SuperclassNBDT`` (zero-shot evaluation on superclasses) are in ``nbdt.superclass``.
 """
 import json
 import math

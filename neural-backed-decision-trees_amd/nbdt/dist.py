@@ -111,7 +111,7 @@ def shard_batch(t, rank, world):
     return t[rank * per:(rank + 1) * per]
 
 
-def epoch_indices(n, batch_size, rank, world, seed, epoch, sharded=False):
+def epoch_indices(n, batch_size, rank, world, seed, epoch, sharded=False, subset=None):
     """This rank's sample indices for every step of one epoch over n samples: int64 ``[steps, batch_size // world]`` on the
     host, indices into the whole dataset.  batch_size is the GLOBAL batch and must divide by world.
 
@@ -123,11 +123,33 @@ def epoch_indices(n, batch_size, rank, world, seed, epoch, sharded=False):
     its own range, with a generator seeded from (seed, epoch, rank), and every rank runs the same number of steps, the one
     the smallest shard (``n // world`` samples) allows.  Every index lies in the rank's range and none repeats within the
     epoch.  The shuffle is within shards, not across the whole set: a global batch is always made of ``batch_size //
-    world`` samples from each rank's part.  That is the price of never moving an image between GPUs."""
+    world`` samples from each rank's part.  That is the price of never moving an image between GPUs.
+
+    subset (an ascending int64 tensor of sample indices, nbdt.data.label_subset; None: all n) -- the epoch runs over those
+    samples only: the same generators permute the kept indices instead of the whole range, sharded=True those of them that
+    lie in the rank's range, with the step count the rank keeping the fewest allows (every rank computes it from the whole
+    subset, which all of them hold).  No index outside the subset is ever returned."""
     n, batch_size, rank, world = int(n), int(batch_size), int(rank), int(world)
     if batch_size <= 0 or batch_size % world:
         raise ValueError(f"global batch {batch_size} is not divisible by world size {world}")
     per = batch_size // world
+    if subset is not None:
+        kept = torch.as_tensor(subset, dtype=torch.int64)
+        if kept.numel() and (int(kept.min()) < 0 or int(kept.max()) >= n):
+            raise ValueError(f"subset indices must lie in [0, {n})")
+        if not sharded:
+            g = torch.Generator().manual_seed(int(seed) * 1000 + int(epoch))
+            order = kept[torch.randperm(kept.numel(), generator=g)]
+            steps = kept.numel() // batch_size
+            return order[:steps * batch_size].view(steps, batch_size)[:, rank * per:(rank + 1) * per].contiguous()
+        spans = [shard_range(n, r, world) for r in range(world)]
+        counts = [int(((kept >= lo) & (kept < hi)).sum()) for lo, hi in spans]
+        steps = min(counts) // per
+        lo, hi = spans[rank]
+        mine = kept[(kept >= lo) & (kept < hi)]
+        g = torch.Generator().manual_seed((((int(seed) * 1000 + int(epoch)) << 20) + rank) & ((1 << 63) - 1))
+        order = mine[torch.randperm(mine.numel(), generator=g)]
+        return order[:steps * per].view(steps, per).contiguous()
     if not sharded:
         g = torch.Generator().manual_seed(int(seed) * 1000 + int(epoch))
         perm = torch.randperm(n, generator=g)

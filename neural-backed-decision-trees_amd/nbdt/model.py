@@ -56,6 +56,19 @@ class _NodeLogitsFn(torch.autograd.Function):
         return _C.node_logits_backward(handle, gs).to(ctx.z_dtype), None
 
 
+class _GroupLogitsFn(torch.autograd.Function):
+    """[B,G] mean logits of an ad-hoc grouping of the classes (nbdt_group_logits); the VJP walks the transposed map."""
+
+    @staticmethod
+    def forward(ctx, z, handle):
+        ctx.handle, ctx.z_dtype = handle, z.dtype
+        return _C.group_logits(handle, z)
+
+    @staticmethod
+    def backward(ctx, gs):
+        return _C.group_logits_backward(ctx.handle, gs).to(ctx.z_dtype), None
+
+
 class EmbeddedDecisionRules(nn.Module):
     """reference nbdt/model.py:65-123."""
 
@@ -76,12 +89,20 @@ class EmbeddedDecisionRules(nn.Module):
         Kept for API parity (analysis code calls it per node).  It runs the fused node kernel for
         the node's hierarchy and slices out this node's columns; callers that need every node
         should use ``forward_nodes``.
+
+        Without a node, ``new_to_old_classes`` ({new class: [old classes]}) and ``num_classes`` name an ad-hoc
+        grouping of the columns: [B, num_classes] fp32 means, one launch (csrc/superclass.hip), differentiable.
         """
         assert node or (new_to_old_classes and num_classes), \
             "Either pass node or (new_to_old_classes mapping and num_classes)"
         if node is None:
-            raise NotImplementedError(
-                "get_node_logits without a node (ad-hoc class mapping) is not part of the HIP path")
+            # an ad-hoc grouping {new class: [old classes]} (what SuperclassNBDT.forward passes): one launch of
+            # nbdt_group_logits.  Keys outside range(num_classes) -- the reference's -1 bucket of unmapped classes -- are
+            # never looked up by its loop and are ignored here; a key that is missing is an empty group (a NaN column).
+            _C.require_gpu(outputs, "get_node_logits")
+            groups = [new_to_old_classes[new] if new in new_to_old_classes else () for new in range(int(num_classes))]
+            handle = _C.groups_handle(groups, outputs.shape[-1], outputs.device.index)
+            return _GroupLogitsFn.apply(outputs, handle)
         tree = node.tree
         _C.require_gpu(outputs, "get_node_logits")
         logits = _NodeLogitsFn.apply(outputs, tree)   # differentiable, like the reference's mean
