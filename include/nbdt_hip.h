@@ -40,7 +40,8 @@
  *                          padded elements B*(H+2)*(W+2)*C < 2^31 (the depthwise entries: of the input-side tensor);
  *                          nbdt_bn_apply_s2d also B*(H/2+2)*(W/2+2)*4C < 2^31 for its output
  *   nbdt_stem_wgrad        output pixels B*Ho*Wo < 2^31 - 2^22;  nbdt_stem_conv_pad / nbdt_stem_wgrad_pad: < 2^25
- *   nbdt_seg_*             blocks N*ceil(HW/64) < 2^31; nbdt_seg_soft_tree_loss also pixels N*HW < 2^31
+ *   nbdt_seg_*             blocks N*ceil(HW/64) < 2^31; nbdt_seg_soft_tree_loss and nbdt_seg_stats_accumulate also pixels
+ *                          N*HW < 2^31 (the loss counts the valid pixels, the statistics count per block, in 32 bits)
  *   no limit below the launch grid (64-bit offsets throughout): nbdt_stem_conv, nbdt_stem_patches, nbdt_maxpool3x3s2_*,
  *   nbdt_dropout_*, nbdt_linear_*, nbdt_se_*, nbdt_mix_batch, nbdt_augment_batch*, nbdt_policy_*batch*,
  *   nbdt_resized_crop_*batch* (datasets and batches past 4 GiB are fine; one image has H, W <= 4096),
@@ -76,7 +77,8 @@ const char* nbdt_debug_last_wgrad(void);      /* same for nbdt_conv_wgrad */
 /* Which form the calling thread's last rules launch took (nbdt_soft_forward, nbdt_soft_backward, the tree losses,
  * nbdt_hard_forward, nbdt_node_outputs, nbdt_tree_stats_accumulate): "lds" (rows and staged operands in LDS),
  * "lds-unstaged" (rows in LDS, direct-indexed chains), "global" (rows in global memory), "pixel" (the nbdt_seg_*
- * entries: one lane per pixel of an NCHW tensor, nbdt_version() >= 129), "" before the first launch.
+ * entries: one lane per pixel of an NCHW tensor, nbdt_version() >= 129; nbdt_seg_stats_accumulate among them,
+ * nbdt_version() >= 132), "" before the first launch.
  * See "Size limits" at nbdt_tree_create.  nbdt_version() >= 127. */
 const char* nbdt_debug_last_rules_path(void);
 /* Form of the per-sample rules kernels (process-wide, default 0; nbdt_version() >= 127).  0: automatic -- the LDS forms
@@ -334,6 +336,38 @@ int nbdt_seg_soft_tree_loss(const nbdt_tree* t, const void* z, int ztype, int64_
                             float grad_scale, float* workspace, float* loss, float* gz, void* stream);
 int nbdt_seg_hard_forward(const nbdt_tree* t, const void* z, int ztype, int64_t N, int64_t HW, int64_t zi, int64_t zc,
                           int64_t* pred, float* onehot, void* stream);
+
+/* Segmentation evaluation in ONE launch (nbdt_version() >= 132; csrc/seg_stats.h): nbdt_tree_stats_accumulate for NCHW
+ * logits -- the three predictions of every pixel (backbone argmax, hard walk, argmax of the soft path product) against
+ * its label, from one set of child logits in LDS; no [N, C, HW] probability tensor is written.
+ *   z, N, HW, zi, zc: as for nbdt_seg_hard_forward.  y: [N, HW] int64 labels (required when a counter is requested).  A
+ *   pixel whose label equals ignore_index, or lies outside [0, C), counts NOWHERE.
+ *   stats (host pointer, nullable): the struct of nbdt_tree_stats_accumulate with the meanings documented there, per
+ *   pixel instead of per sample -- totals[4] (valid pixels, backbone / hard / soft hits), confusion_net / _hard / _soft
+ *   [C*C] (entry [label * C + prediction]), node_counts [N_inner * 5], first_error_depth [max_depth + 1].  Every pointer
+ *   may be NULL; everything is int64 and ADDED TO.  node_entropy must be NULL (NBDT_EINVAL otherwise): the fixed-point
+ *   entropy sums have no per-pixel form.  The first maximum wins in every argmax (class order, slot order).  The soft
+ *   prediction is argmax over classes of what nbdt_seg_soft_forward writes, bit for bit; in a multi-parent graph the
+ *   product runs over every slot that holds the class, as in nbdt_tree_stats_accumulate.
+ *   pred_net / pred_hard / pred_soft (nullable) are WRITTEN as [N, HW] int64: the prediction of every pixel, ignored
+ *   ones included, as nbdt_seg_hard_forward does.
+ * One launch on a persistent grid, no floating-point atomics, no host read-back; all sums are integer sums, so the
+ * counters are bit-identical however the pass is cut into calls.  A block keeps totals, node_counts and
+ * first_error_depth in LDS and adds them once; a confusion entry costs one atomic per distinct (label, prediction) pair
+ * of a wave's 64 pixels.  nbdt_debug_last_rules_path() reports "pixel".
+ * Size limit: the (R + F) * 256 bytes of the pixel form's rows plus 4 * (5 * N_inner + max_depth + 5) bytes of block
+ * counters (rounded up to 8) within 160 KB of LDS -- slightly tighter than nbdt_seg_pixel_fits (ADE20K: 75 KB + 3 KB).
+ * nbdt_seg_stats_fits() returns 0 beyond it and the entry NBDT_EINVAL: run nbdt_tree_stats_accumulate on the coerced
+ * tensor.  Refused with NBDT_EINVAL before any device call: such a hierarchy, y == NULL while a counter is requested,
+ * non-NULL node_entropy, nothing requested at all, and tensors past the nbdt_seg_* limits or with N*HW >= 2^31.
+ * nbdt_set_seg_stats_max_blocks (process-wide, default 0 = one block per resident wave slot, at most 16 per CU) caps the
+ * persistent grid: for tests that want a block to stride over several chunks; negative values are NBDT_EINVAL. */
+int nbdt_seg_stats_fits(const nbdt_tree* t);
+int nbdt_seg_stats_accumulate(const nbdt_tree* t, const void* z, int ztype, int64_t N, int64_t HW, int64_t zi, int64_t zc,
+                              const int64_t* y, int64_t ignore_index, const nbdt_tree_stats* stats, int64_t* pred_net,
+                              int64_t* pred_hard, int64_t* pred_soft, void* stream);
+int nbdt_set_seg_stats_max_blocks(int blocks);
+int nbdt_get_seg_stats_max_blocks(void);
 
 /* ------------------------------------------------------------------ superclass evaluation (nbdt_version() >= 131)
  * Zero-shot evaluation on superclasses (reference nbdt/analysis.py:430-559, Superclass / SuperclassNBDT) and

@@ -149,6 +149,11 @@ SIGNATURES = {
     "nbdt_seg_soft_tree_loss": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, c_int64, c_int64, _P, c_int64, c_float,
                                         c_float, c_float, c_float, _P, _P, _P, _P]),
     "nbdt_seg_hard_forward": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, c_int64, c_int64, _P, _P, _P]),
+    "nbdt_seg_stats_fits": (c_int, [c_void_p]),
+    "nbdt_seg_stats_accumulate": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, _P,
+                                          _P, _P]),
+    "nbdt_set_seg_stats_max_blocks": (c_int, [c_int]),
+    "nbdt_get_seg_stats_max_blocks": (c_int, []),
     "nbdt_conv_igemm": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "nbdt_conv_pw": (c_int, [POINTER(ConvDesc), _P, _P, _P, _P, _P]),
     "nbdt_conv_igemm_multi": (c_int, [_P, c_int32, _P, _P, _P, _P]),
@@ -746,6 +751,97 @@ def seg_dispatch(shape, strides, dtype, flat):
     if _pixel_rows(shape, strides) and not (_dense_planes(shape, strides) and seg_pixel_fits(flat)):
         return "rows"
     if not seg_pixel_fits(flat):
+        return "coerced"
+    return "pixel" if _dense_planes(shape, strides) else "contiguous"
+
+
+# ---- segmentation evaluation (nbdt_seg_stats_accumulate, csrc/seg_stats.h): the same layouts, one more limit
+
+LDS_BYTES = 160 * 1024        # kLdsBytes
+
+
+def flat_max_depth(flat):
+    """Inner nodes on the longest walk from the root: nbdt_tree_max_depth, on the host."""
+    children = lambda n: [int(v) for v in flat.slot_next[flat.node_off[n]:flat.node_off[n + 1]] if v >= 0]  # noqa: E731
+    depth, stack = {}, [(int(flat.root), False)]
+    while stack:
+        n, done = stack.pop()
+        if done:
+            depth[n] = 1 + max((depth.get(m, 0) for m in children(n)), default=0)
+        elif n not in depth:
+            depth[n] = 0                 # (a cycle is refused by nbdt_tree_create; it must not loop for ever here)
+            stack.append((n, True))
+            stack.extend((m, False) for m in children(n) if m not in depth)
+    return depth[int(flat.root)]
+
+
+def seg_stats_lds_bytes(flat):
+    """LDS of one block of the statistics kernel: the pixel form's (R + F) rows of 64 floats plus the block's int32
+    counters [5 N][4 totals][max_depth + 1], padded to an even count."""
+    fan = int((flat.node_off[1:] - flat.node_off[:-1]).max())
+    small = (5 * int(flat.num_inodes) + 4 + flat_max_depth(flat) + 1 + 1) & ~1
+    return (int(flat.num_slots) + fan) * 256 + 4 * small
+
+
+def seg_stats_fits(flat):
+    """nbdt_seg_stats_fits as a pure function of the hierarchy: the pixel form's limit and rows + counters <= 160 KB."""
+    return seg_pixel_fits(flat) and seg_stats_lds_bytes(flat) <= LDS_BYTES
+
+
+def _slot_schedule_len(slot_off, lanes):
+    """sched_len of build_slot_schedule (csrc/rules.hip): passes of the busiest wave times the group's lanes."""
+    R = len(slot_off) - 1
+    length = np.diff(np.asarray(slot_off, dtype=np.int64))
+    order = np.argsort(-length, kind="stable")
+    waves, load, count = lanes // 64, [0] * (lanes // 64), [0] * (lanes // 64)
+    for c in range((R + 63) // 64):
+        w = min(range(waves), key=lambda i: (load[i], i))
+        count[w] += 1
+        load[w] += 64 + 8 * int(length[order[c * 64]])
+    return max(count) * lanes
+
+
+def tree_stats_fits(flat):
+    """The limit of the row diagnostics (nbdt_tree_stats_accumulate: offset arrays, block counters and the unstaged
+    sample rows of a block within 160 KB of LDS) as a pure function of the hierarchy."""
+    C, N, R = int(flat.num_classes), int(flat.num_inodes), int(flat.num_slots)
+    tps = 64 if (C <= 64 and R <= 64) else 256 if (C <= 512 and R <= 512) else 1024
+    spb = max(tps, 256) // tps
+    tl = ((N + 1) + (R + 1) + (C + 1) + 3 * _slot_schedule_len(flat.slot_off, tps) + 3) & ~3
+    small = (5 * N + 4 + flat_max_depth(flat) + 1 + 1) & ~1
+    tl += (small + 4 * N + 3) & ~3
+    return (tl + spb * (C + 2 * R + 2 * N + 32) + 4) * 4 <= LDS_BYTES
+
+
+def seg_stats_dispatch(shape, strides, dtype, flat):
+    """Which way 4-D logits take through the segmentation statistics -- a pure host function like seg_dispatch:
+      "pixel"       contiguous NCHW planes, hierarchy within nbdt_seg_stats_fits: nbdt_seg_stats_accumulate as it is
+      "rows"        channels_last memory: nbdt_tree_stats_accumulate with ldz = C on the [N*H*W, C] view, no copy
+      "contiguous"  other strides: one .contiguous(), then "pixel"
+      "coerced"     beyond the pixel limit but within the row diagnostics': the rows of one channels_last copy
+    and an error that names both limits beyond both."""
+    if len(shape) != 4:
+        raise NBDTHipError(f"segmentation statistics expect [N, C, H, W] logits, got shape {tuple(shape)}")
+    if shape[1] != flat.num_classes:
+        raise NBDTHipError(f"logits have {shape[1]} channels but the hierarchy has {flat.num_classes} classes")
+    if dtype not in _ZTYPE:
+        raise NBDTHipError(f"unsupported logits dtype {dtype}")
+    limits = getattr(flat, "_seg_stats_limits", None)          # a function of the hierarchy alone: worked out once
+    if limits is None:
+        limits = (seg_stats_fits(flat), tree_stats_fits(flat))
+        try:
+            flat._seg_stats_limits = limits
+        except AttributeError:
+            pass
+    pixel, rows = limits
+    if not pixel and not rows:
+        raise NBDTHipError(
+            f"hierarchy too large for the segmentation statistics: the pixel form needs {seg_stats_lds_bytes(flat)} bytes "
+            f"of LDS (rows (R + F) * 256 plus the block's counters; R + F <= {SEG_PIXEL_MAX_ROWS}) and the row diagnostics "
+            f"(nbdt_tree_stats_accumulate) do not fit their sample rows either; both are limited to {LDS_BYTES} bytes")
+    if rows and _pixel_rows(shape, strides) and not (_dense_planes(shape, strides) and pixel):
+        return "rows"
+    if not pixel:
         return "coerced"
     return "pixel" if _dense_planes(shape, strides) else "contiguous"
 

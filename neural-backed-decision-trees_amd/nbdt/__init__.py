@@ -6,3 +6,13 @@ HardNBDT, decision rules), ``nbdt.loss`` (SoftTreeSupLoss), ``nbdt.tree`` (Tree,
 (hand-written HIP for gfx950); there is no CPU fallback.
 """
 __version__ = "0.1.0"
+
+__all__ = ["segmentation"]
+
+
+def __getattr__(name):
+    """``nbdt.segmentation`` (evaluation of segmentation NBDTs) on first use: importing the package stays free of torch."""
+    if name == "segmentation":
+        import importlib
+        return importlib.import_module("nbdt.segmentation")
+    raise AttributeError(f"module 'nbdt' has no attribute {name!r}")

@@ -940,6 +940,64 @@ def tree_stats_accumulate(handle, z, y, stats=None, scores=None):
                                            ptr(scores), _C.stream_of(z)))
 
 
+seg_stats_dispatch = _C.seg_stats_dispatch
+SEG_STATS_FIELDS = tuple(f for f in STATS_FIELDS if f != "node_entropy")
+
+
+def seg_stats_accumulate(handle, z, y, ignore_index, stats=None, want_pred=False):
+    """Segmentation evaluation of one batch: ADDS the statistics of logits z [N, C, H, W] against labels y [N, H, W] to
+    the int64 device tensors in ``stats`` (a dict by nbdt_tree_stats field name without node_entropy; a missing or None
+    entry is not computed).  A pixel whose label is ``ignore_index`` or outside [0, C) counts nowhere.  ONE launch of
+    nbdt_seg_stats_accumulate for contiguous planes; channels_last memory and hierarchies beyond the pixel limit go
+    through nbdt_tree_stats_accumulate on the [N*H*W, C] rows (seg_stats_dispatch).  Enqueues only: no host
+    synchronisation.  want_pred: returns (pred_net, pred_hard, pred_soft), int64 [N, H, W] each, else None."""
+    _C.require_gpu(z, "seg_stats_accumulate")
+    how = seg_stats_dispatch(tuple(z.shape), tuple(z.stride()), z.dtype, handle.flat)
+    N, C, H, W = z.shape
+    sizes = tree_stats_sizes(handle)
+    block = _C.TreeStats()
+    wanted = {}
+    for name, t in (stats or {}).items():
+        if name not in SEG_STATS_FIELDS:
+            raise _C.NBDTHipError(f"unknown segmentation statistic {name!r}; there are {', '.join(SEG_STATS_FIELDS)}")
+        if t is None:
+            continue
+        if t.dtype != torch.int64 or t.device != z.device or not t.is_contiguous() or t.numel() != sizes[name]:
+            raise _C.NBDTHipError(f"{name}: expected a contiguous int64 tensor of {sizes[name]} elements on {z.device}, "
+                                  f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        setattr(block, name, t.data_ptr())
+        wanted[name] = t
+    if y is not None:
+        if y.is_floating_point() or tuple(y.shape) != (N, H, W):
+            raise _C.NBDTHipError(f"segmentation targets must be class indices [N, H, W] = {(N, H, W)}, got {y.dtype} "
+                                  f"{tuple(y.shape)}")
+        y = y.to(device=z.device, dtype=torch.int64).contiguous()
+    elif wanted:
+        raise _C.NBDTHipError("seg_stats_accumulate: statistics against the labels need the labels")
+    if not wanted and not want_pred:
+        return None
+    if how in ("rows", "coerced"):
+        zl = z if how == "rows" else z.contiguous(memory_format=torch.channels_last)
+        rows = zl.permute(0, 2, 3, 1).reshape(-1, C)
+        if wanted:
+            labels = y.reshape(-1)
+            labels = torch.where(labels == int(ignore_index), torch.full_like(labels, -1), labels)   # a copy
+            tree_stats_accumulate(handle, rows, labels, wanted)
+        if not want_pred:
+            return None
+        pred_hard = _C.hard_forward(handle, rows, want_onehot=False)[0]
+        P = _C.soft_forward(handle, rows)                         # (single-parent hierarchies, like SoftSegNBDT)
+        return tuple(p.view(N, H, W) for p in (rows.float().argmax(1), pred_hard, P.argmax(1)))
+    zz = z.contiguous() if how == "contiguous" else z
+    n, HW, zi, zc = _C._seg_geom(zz)
+    preds = tuple(torch.empty((N, H, W), dtype=torch.int64, device=z.device) for _ in range(3)) if want_pred \
+        else (None, None, None)
+    check(lib().nbdt_seg_stats_accumulate(handle.h, ptr(zz), _C.ztype_of(zz), n, HW, zi, zc, ptr(y), int(ignore_index),
+                                          ctypes.byref(block), ptr(preds[0]), ptr(preds[1]), ptr(preds[2]),
+                                          _C.stream_of(zz)))
+    return preds if want_pred else None
+
+
 def sgd_step(p, g, buf, lr, momentum, weight_decay, grad_scale=1.0, p_bf16=None, zero_grad=False):
     """zero_grad: the same pass leaves g zeroed (the next step's zero_grad())."""
     check(lib().nbdt_sgd_step(ptr(p), ptr(g), ptr(buf), p.numel(), lr, momentum, weight_decay, grad_scale,
