@@ -42,6 +42,9 @@
  *   nbdt_stem_wgrad        output pixels B*Ho*Wo < 2^31 - 2^22;  nbdt_stem_conv_pad / nbdt_stem_wgrad_pad: < 2^25
  *   nbdt_seg_*             blocks N*ceil(HW/64) < 2^31; nbdt_seg_soft_tree_loss and nbdt_seg_stats_accumulate also pixels
  *                          N*HW < 2^31 (the loss counts the valid pixels, the statistics count per block, in 32 bits)
+ *   nbdt_upsampled_xent    pixels N*H*W < 2^31 (one forward block per 64 of them); H, W <= 2^22 (the source index is an
+ *                          fp32: dst + 0.5f stays exact); C <= 262,140 (class chunks in grid.y); no limit on N*C*h*w
+ *                          (64-bit offsets)
  *   no limit below the launch grid (64-bit offsets throughout): nbdt_stem_conv, nbdt_stem_patches, nbdt_maxpool3x3s2_*,
  *   nbdt_dropout_*, nbdt_linear_*, nbdt_se_*, nbdt_mix_batch, nbdt_augment_batch*, nbdt_policy_*batch*,
  *   nbdt_resized_crop_*batch* (datasets and batches past 4 GiB are fine; one image has H, W <= 4096),
@@ -368,6 +371,42 @@ int nbdt_seg_stats_accumulate(const nbdt_tree* t, const void* z, int ztype, int6
                               int64_t* pred_hard, int64_t* pred_soft, void* stream);
 int nbdt_set_seg_stats_max_blocks(int blocks);
 int nbdt_get_seg_stats_max_blocks(void);
+
+/* ---- cross-entropy on bilinearly upsampled logits (nbdt_version() >= 133; csrc/upsampled_xent.hip, upsample_taps.h):
+ *   F.cross_entropy(F.interpolate(x, size=(H, W), mode="bilinear", align_corners), y, weight, ignore_index,
+ *                   reduction="mean", label_smoothing = smoothing)
+ * and its gradient from the LOW-resolution x and the FULL-resolution labels -- the criterion of backbones whose logits
+ * come at 1/4 of the label size.  No tensor of N*C*H*W elements is formed and no floating-point atomic is used: two
+ * calls on the same input give the same bits (torch's bilinear backward scatters with atomics).
+ *   x: [N, C, h, w] of type xtype (NBDT_F32 / _BF16 / _F16); the h*w elements of a plane are contiguous, image n /
+ *   channel c starts at element n*xi + c*xc (so a channel-sliced view works; xc >= h*w, xi >= (C-1)*xc + h*w).
+ *   y: [N, H, W] int64.  weight: [C] fp32 class weights or NULL.  gx: [N, C, h, w] dense fp32 = grad_scale * dloss/dx.
+ *   workspace: nbdt_upsampled_xent_workspace_floats(N, H, W) fp32 (lse and label per pixel, per-wave partials); loss: 1 fp32.
+ * Interpolation contract, per axis with `in` source and `out` destination samples, in fp32, every multiply and add a
+ * single rounding (torch's, ATen UpSample.h):
+ *   align_corners = 0: scale = (float)in / out,  src = max(scale * (dst + 0.5f) - 0.5f, 0)
+ *   align_corners = 1: scale = out > 1 ? (float)(in - 1) / (out - 1) : 0,  src = scale * dst
+ *   i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0, l0 = 1 - l1;  value = ly0*(lx0*a + lx1*b) + ly1*(lx0*c + lx1*d)
+ * nbdt_upsample_taps returns exactly what the kernels use for one destination index; nbdt_upsample_footprint the
+ * inclusive range of destinations whose taps can touch source index i (out >= in; never short, possibly holding a
+ * destination of weight 0).  Neither touches a device.
+ * Criterion: without weight, t'_c = (1 - smoothing) * 1[c == y] + smoothing / C, row = lse - sum_c t'_c v_c, mean over
+ * the pixels with y != ignore_index; with weight (smoothing must be 0), row = weight[y] * (lse - v_y) and the divisor is
+ * the sum of weight[y] over those pixels, in a fixed order.  A label outside [0, C) other than ignore_index gives a NaN
+ * loss; no valid pixel gives a NaN loss and a zero gradient.
+ * Three launches, no host read-back: forward (one lane per full-resolution pixel), a one-block fold of the per-wave
+ * partials in block order, and the gather-form backward (one lane per low-resolution pixel: the ordered sum over the
+ * pixels whose taps touch it, v recomputed from its 3 x 3 neighbourhood by the forward's own function).
+ * Refused with NBDT_EINVAL before any HIP call: null or aliased buffers, an unknown xtype, empty tensors, H < h or
+ * W < w (downsampling), H or W > 2^22, N*H*W >= 2^31, C > 262,140, overlapping planes, smoothing outside [0, 1), weight
+ * together with smoothing > 0, a NaN grad_scale. */
+int nbdt_upsample_taps(int in, int out, int align_corners, int dst, int* i0, int* i1, float* l0, float* l1);
+int nbdt_upsample_footprint(int in, int out, int align_corners, int i, int* lo, int* hi);
+int64_t nbdt_upsampled_xent_workspace_floats(int64_t N, int64_t H, int64_t W);
+int nbdt_upsampled_xent(const void* x, int xtype, int64_t N, int64_t C, int64_t h, int64_t w, int64_t xi, int64_t xc,
+                        const int64_t* y, int64_t H, int64_t W, int align_corners, int64_t ignore_index,
+                        const float* weight, float smoothing, float grad_scale, float* workspace, float* loss, float* gx,
+                        void* stream);
 
 /* ------------------------------------------------------------------ superclass evaluation (nbdt_version() >= 131)
  * Zero-shot evaluation on superclasses (reference nbdt/analysis.py:430-559, Superclass / SuperclassNBDT) and

@@ -1461,7 +1461,7 @@ __global__ __launch_bounds__(block_of(TPS)) void tree_stats_kernel(TreeView t, c
 // host side
 
 extern "C" const char* nbdt_last_error(void) { return nbdt::g_err; }
-extern "C" int nbdt_version(void) { return 132; }     // 132: nbdt_seg_stats_accumulate, nbdt_seg_stats_fits, nbdt_set / nbdt_get_seg_stats_max_blocks (segmentation evaluation: confusion matrices, totals, per-node counters and the first-error histogram of NCHW logits in one launch: csrc/seg_stats.h); 131: nbdt_groups_create / _destroy, nbdt_group_logits / _backward, nbdt_superclass_accumulate (zero-shot superclass evaluation and get_node_logits over an ad-hoc class grouping: csrc/superclass.hip); 130: every tensor entry point refuses a tensor at its 32-bit offset limit with NBDT_EINVAL before any HIP call (include/nbdt_hip.h "Size limits": new refusals in nbdt_conv_igemm* / _plan, nbdt_conv_wgrad, nbdt_conv_seg_create, nbdt_bn_apply_s2d, nbdt_stem_wgrad, nbdt_stem_conv, nbdt_seg_soft_tree_loss); 129: nbdt_seg_soft_forward / _soft_backward / _soft_tree_loss / _hard_forward, nbdt_seg_pixel_fits, nbdt_seg_loss_workspace_floats (the rules and the fused soft loss on NCHW logits, one lane per pixel: csrc/rules_pixel.h), "pixel" from nbdt_debug_last_rules_path; 128: nbdt_linkage / nbdt_linkage_workspace_bytes (agglomerative clustering for induced hierarchies: csrc/linkage.hip); 127: nbdt_set_rules_path / nbdt_get_rules_path / nbdt_debug_last_rules_path (the rules kernels with the sample row in global memory, for hierarchies too large for LDS: csrc/rules_global.h); 125: nbdt_conv_group_weight_prep[_batched], nbdt_conv_group_fwd / _dgrad / _wgrad and their nbdt_ref_conv_group_* twins (the grouped 3x3 convolution of ResNeXt as block-diagonal 32 x 32 blocks: csrc/conv_group.hip); 124: nbdt_resized_crop_policy_batch[_sharded] (policy chains and random erasing on the resized-crop path: csrc/resample.hip, csrc/policy_ops.h); 123: nbdt_policy_chain_batch[_sharded] (RandAugment / AutoAugment chains: csrc/policy.hip); 122: nbdt_bn_act_apply_rows, nbdt_bn_act_bwd_rows, their nbdt_ref_* twins, nbdt_stochastic_depth_draw (stochastic depth inside the MBConv residual passes: csrc/effnet.hip); 120: nbdt_arena_opt_create / _destroy, nbdt_adamw_step, nbdt_rmsprop_step (AdamW and RMSprop over the flat arena: csrc/adaptive.hip); 119: nbdt_policy_batch[_sharded] (TrivialAugmentWide + random erasing on device-resident datasets: csrc/policy.hip); 118: nbdt_ema_update / _swap and their _multi forms (weight EMA: the fused shadow update and the in-place exchange for evaluation: csrc/ema.hip); 117: nbdt_lars_create / _destroy / _step / _ratios (LARS over the flat parameter arena: csrc/lars.hip); 116: nbdt_soft_tree_loss_ex, nbdt_hard_tree_loss_ex (label smoothing in both fused tree losses, probability targets in the soft one), nbdt_mix_batch (MixUp / CutMix and their targets in one launch: csrc/mix.hip); 115: nbdt_stem_patches, nbdt_maxpool3x3s2_fwd / _bwd (the 7x7 / 2 stem as a patch gather in front of the 1x1 convolution, and MaxPool2d(3, 2, 1), for torchvision-shaped ResNets: csrc/stem_pool.hip); 114: nbdt_augment_batch_sharded, nbdt_resized_crop_batch_sharded (a rank keeps its contiguous shard of a device-resident dataset: the draw from the dataset index, the gather from index - index_base); 113: nbdt_conv_pw (stride-1 1x1 convolutions as a GEMM: the Bottleneck ResNets); 112: nbdt_tree_stats_accumulate (tree diagnostics: per-node counters, confusion matrices, entropy sums, scores in one launch); 111: nbdt_resized_crop_batch, nbdt_resized_crop_band_rows (RandomResizedCrop / Resize + CenterCrop datasets); 110: nbdt_augment_batch (device-resident datasets: gather + crop + flip + normalise), NBDT_U8; 109: nbdt_set/get_stream_nt_min_bytes, nbdt_debug_last_stream_nt, nbdt_conv_seg_create refuses ntensors > 2; 108: nbdt_se_param_grad, nbdt_se_gate_bwd without parameter gradients; 107: nbdt_bn_act_se_sums / _se_bwd_apply; 106: nbdt_conv_desc.ksplit is live (was reserved), nbdt_conv_seg_*
+extern "C" int nbdt_version(void) { return 133; }     // 133: nbdt_upsampled_xent, nbdt_upsampled_xent_workspace_floats, nbdt_upsample_taps, nbdt_upsample_footprint (cross-entropy on bilinearly upsampled logits from the low-resolution tensor, gather-form backward: csrc/upsampled_xent.hip); 132: nbdt_seg_stats_accumulate, nbdt_seg_stats_fits, nbdt_set / nbdt_get_seg_stats_max_blocks (segmentation evaluation: confusion matrices, totals, per-node counters and the first-error histogram of NCHW logits in one launch: csrc/seg_stats.h); 131: nbdt_groups_create / _destroy, nbdt_group_logits / _backward, nbdt_superclass_accumulate (zero-shot superclass evaluation and get_node_logits over an ad-hoc class grouping: csrc/superclass.hip); 130: every tensor entry point refuses a tensor at its 32-bit offset limit with NBDT_EINVAL before any HIP call (include/nbdt_hip.h "Size limits": new refusals in nbdt_conv_igemm* / _plan, nbdt_conv_wgrad, nbdt_conv_seg_create, nbdt_bn_apply_s2d, nbdt_stem_wgrad, nbdt_stem_conv, nbdt_seg_soft_tree_loss); 129: nbdt_seg_soft_forward / _soft_backward / _soft_tree_loss / _hard_forward, nbdt_seg_pixel_fits, nbdt_seg_loss_workspace_floats (the rules and the fused soft loss on NCHW logits, one lane per pixel: csrc/rules_pixel.h), "pixel" from nbdt_debug_last_rules_path; 128: nbdt_linkage / nbdt_linkage_workspace_bytes (agglomerative clustering for induced hierarchies: csrc/linkage.hip); 127: nbdt_set_rules_path / nbdt_get_rules_path / nbdt_debug_last_rules_path (the rules kernels with the sample row in global memory, for hierarchies too large for LDS: csrc/rules_global.h); 125: nbdt_conv_group_weight_prep[_batched], nbdt_conv_group_fwd / _dgrad / _wgrad and their nbdt_ref_conv_group_* twins (the grouped 3x3 convolution of ResNeXt as block-diagonal 32 x 32 blocks: csrc/conv_group.hip); 124: nbdt_resized_crop_policy_batch[_sharded] (policy chains and random erasing on the resized-crop path: csrc/resample.hip, csrc/policy_ops.h); 123: nbdt_policy_chain_batch[_sharded] (RandAugment / AutoAugment chains: csrc/policy.hip); 122: nbdt_bn_act_apply_rows, nbdt_bn_act_bwd_rows, their nbdt_ref_* twins, nbdt_stochastic_depth_draw (stochastic depth inside the MBConv residual passes: csrc/effnet.hip); 120: nbdt_arena_opt_create / _destroy, nbdt_adamw_step, nbdt_rmsprop_step (AdamW and RMSprop over the flat arena: csrc/adaptive.hip); 119: nbdt_policy_batch[_sharded] (TrivialAugmentWide + random erasing on device-resident datasets: csrc/policy.hip); 118: nbdt_ema_update / _swap and their _multi forms (weight EMA: the fused shadow update and the in-place exchange for evaluation: csrc/ema.hip); 117: nbdt_lars_create / _destroy / _step / _ratios (LARS over the flat parameter arena: csrc/lars.hip); 116: nbdt_soft_tree_loss_ex, nbdt_hard_tree_loss_ex (label smoothing in both fused tree losses, probability targets in the soft one), nbdt_mix_batch (MixUp / CutMix and their targets in one launch: csrc/mix.hip); 115: nbdt_stem_patches, nbdt_maxpool3x3s2_fwd / _bwd (the 7x7 / 2 stem as a patch gather in front of the 1x1 convolution, and MaxPool2d(3, 2, 1), for torchvision-shaped ResNets: csrc/stem_pool.hip); 114: nbdt_augment_batch_sharded, nbdt_resized_crop_batch_sharded (a rank keeps its contiguous shard of a device-resident dataset: the draw from the dataset index, the gather from index - index_base); 113: nbdt_conv_pw (stride-1 1x1 convolutions as a GEMM: the Bottleneck ResNets); 112: nbdt_tree_stats_accumulate (tree diagnostics: per-node counters, confusion matrices, entropy sums, scores in one launch); 111: nbdt_resized_crop_batch, nbdt_resized_crop_band_rows (RandomResizedCrop / Resize + CenterCrop datasets); 110: nbdt_augment_batch (device-resident datasets: gather + crop + flip + normalise), NBDT_U8; 109: nbdt_set/get_stream_nt_min_bytes, nbdt_debug_last_stream_nt, nbdt_conv_seg_create refuses ntensors > 2; 108: nbdt_se_param_grad, nbdt_se_gate_bwd without parameter gradients; 107: nbdt_bn_act_se_sums / _se_bwd_apply; 106: nbdt_conv_desc.ksplit is live (was reserved), nbdt_conv_seg_*
 extern "C" int nbdt_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

@@ -339,6 +339,14 @@ SIGNATURES = {
     "nbdt_group_logits_backward": (c_int, [c_void_p, _P, c_int64, _P, _P]),
     "nbdt_superclass_accumulate": (c_int, [c_void_p, _P, c_int, c_int64, c_int64, _P, _P, c_int32, _P, c_int32, _P, _P,
                                            _P, _P]),
+    # cross-entropy on upsampled logits (nbdt_version() >= 133): (x, xtype, N, C, h, w, xi, xc, y, H, W, align_corners,
+    # ignore_index, weight, smoothing, grad_scale, workspace, loss, gx, stream)
+    "nbdt_upsample_taps": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_float),
+                                   POINTER(c_float)]),
+    "nbdt_upsample_footprint": (c_int, [c_int, c_int, c_int, c_int, POINTER(c_int), POINTER(c_int)]),
+    "nbdt_upsampled_xent_workspace_floats": (c_int64, [c_int64, c_int64, c_int64]),
+    "nbdt_upsampled_xent": (c_int, [_P, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, _P, c_int64, c_int64,
+                                    c_int, c_int64, _P, c_float, c_float, _P, _P, _P, _P]),
 }
 
 
@@ -942,3 +950,81 @@ def seg_hard_forward(handle, z, want_onehot=True):
     check(lib().nbdt_seg_hard_forward(handle.h, ptr(zz), ztype_of(zz), N, HW, zi, zc, ptr(pred), ptr(onehot),
                                       stream_of(zz)))
     return pred, onehot
+
+
+# ---- cross-entropy on bilinearly upsampled logits (nbdt_upsampled_xent, csrc/upsampled_xent.hip)
+
+UPSAMPLE_MAX_EXTENT = 1 << 22       # kUpMaxExtent: H, W (the source index is an fp32)
+UPSAMPLE_MAX_CLASSES = 4 * 65535    # kUpBwdC classes per grid.y block of the backward
+
+
+def upsample_taps(n_in, n_out, align_corners, dst):
+    """(i0, i1, l0, l1) of destination index dst on an axis of n_in source and n_out destination samples: what the
+    kernels use, from their own function (no device involved)."""
+    i0, i1, l0, l1 = c_int(), c_int(), c_float(), c_float()
+    check(lib().nbdt_upsample_taps(int(n_in), int(n_out), int(bool(align_corners)), int(dst), ctypes.byref(i0),
+                                   ctypes.byref(i1), ctypes.byref(l0), ctypes.byref(l1)))
+    return i0.value, i1.value, l0.value, l1.value
+
+
+def upsample_footprint(n_in, n_out, align_corners, i):
+    """(lo, hi): the inclusive range of destinations whose taps can touch source index i (no device involved)."""
+    lo, hi = c_int(), c_int()
+    check(lib().nbdt_upsample_footprint(int(n_in), int(n_out), int(bool(align_corners)), int(i), ctypes.byref(lo),
+                                        ctypes.byref(hi)))
+    return lo.value, hi.value
+
+
+def upsampled_xent_refusal(shape, dtype, target_shape, target_dtype, has_weight, smoothing):
+    """Why nbdt_upsampled_xent does not take this call, or None -- a pure host function of shapes, dtypes and the
+    criterion's settings (the entry's own refusals, ahead of any allocation)."""
+    if len(shape) != 4 or len(target_shape) != 3:
+        return f"logits {tuple(shape)} / targets {tuple(target_shape)} are not [N, C, h, w] / [N, H, W]"
+    if dtype not in _ZTYPE:
+        return f"unsupported logits dtype {dtype}"
+    if target_dtype.is_floating_point or target_dtype in (torch.bool, torch.complex64, torch.complex128):
+        return f"targets of type {target_dtype} are not class indices"
+    (N, C, h, w), (Ny, H, W) = shape, target_shape
+    if Ny != N:
+        return f"{Ny} target images for {N} logit images"
+    if min(N, C, h, w) <= 0:
+        return "empty tensor"
+    if H < h or W < w:
+        return f"downsampling ({h} x {w} -> {H} x {W})"
+    if H > UPSAMPLE_MAX_EXTENT or W > UPSAMPLE_MAX_EXTENT:
+        return f"H or W beyond {UPSAMPLE_MAX_EXTENT}"
+    if N * H * W >= 2 ** 31:
+        return "N * H * W reaches 2^31"
+    if C > UPSAMPLE_MAX_CLASSES:
+        return f"more than {UPSAMPLE_MAX_CLASSES} classes"
+    if not 0.0 <= smoothing < 1.0:
+        return f"label_smoothing {smoothing} outside [0, 1)"
+    if has_weight and smoothing != 0.0:
+        return "class weights together with label smoothing"
+    return None
+
+
+def upsampled_xent(x, y, align_corners=False, ignore_index=-100, weight=None, smoothing=0.0, grad_scale=1.0):
+    """CE(up(x), y) for x [N, C, h, w] and class-index y [N, H, W]: (loss, gx [N, C, h, w] fp32 = grad_scale * dloss/dx),
+    without a full-resolution [N, C, H, W] tensor.  A layout whose planes are not dense takes one .contiguous() of x."""
+    require_gpu(x, "upsampled_xent")
+    why = upsampled_xent_refusal(tuple(x.shape), x.dtype, tuple(y.shape), y.dtype, weight is not None, float(smoothing))
+    if why is not None:
+        raise NBDTHipError(f"upsampled_xent: {why}")
+    if not _dense_planes(tuple(x.shape), tuple(x.stride())):
+        x = x.contiguous()
+    y = y.to(device=x.device, dtype=torch.int64).contiguous()
+    if weight is not None:
+        if weight.dim() != 1 or weight.shape[0] != x.shape[1]:
+            raise NBDTHipError(f"upsampled_xent: {tuple(weight.shape)} class weights for {x.shape[1]} classes")
+        weight = weight.detach().to(device=x.device, dtype=torch.float32).contiguous()
+    N, C, h, w = x.shape
+    H, W = y.shape[1:]
+    _, hw, xi, xc = _seg_geom(x)
+    ws = torch.empty((int(lib().nbdt_upsampled_xent_workspace_floats(N, H, W)),), dtype=torch.float32, device=x.device)
+    loss = torch.empty((), dtype=torch.float32, device=x.device)
+    gx = torch.empty((N, C, h, w), dtype=torch.float32, device=x.device)
+    check(lib().nbdt_upsampled_xent(ptr(x), ztype_of(x), N, C, h, w, xi, xc, ptr(y), H, W, int(bool(align_corners)),
+                                    int(ignore_index), ptr(weight), float(smoothing), float(grad_scale), ptr(ws),
+                                    ptr(loss), ptr(gx), stream_of(x)))
+    return loss, gx

@@ -49,6 +49,8 @@ FLAGS = {
     "linkage.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     # group means and their gradient terms: ordered fp32 sums and one IEEE division each, the contract of rules.hip
     "superclass.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # torch's bilinear taps and lerp as separate multiplies and adds (csrc/upsample_taps.h), shared by forward and backward
+    "upsampled_xent.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "ema.hip": ["-ffp-contract=off"],        # e + omd * (p - e): a subtract, a multiply and an add, never a fused multiply-add
 }
 

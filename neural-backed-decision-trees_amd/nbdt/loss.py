@@ -16,16 +16,22 @@ criterion composes the fused rules kernel (autograd-enabled) with the user's cri
 
 ``SoftSegTreeSupLoss`` (:318-327) is the soft loss on ``[N, C, H, W]`` logits and ``[N, H, W]`` targets; with a
 cross-entropy criterion of any ``ignore_index`` it is one fused launch on the pixel kernels (csrc/rules_pixel.h).
+
+``UpsampledCrossEntropyLoss`` is the criterion of backbones whose logits come at a fraction of the label size:
+bilinear ``F.interpolate`` to the targets' size, then cross-entropy -- computed from the low-resolution tensor by
+csrc/upsampled_xent.hip, for itself and for both terms of ``SoftSegTreeSupLoss``.
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from nbdt import _C
 from nbdt.model import HardEmbeddedDecisionRules, SoftEmbeddedDecisionRules
 from nbdt.tree import Tree
 from nbdt.utils import dataset_to_default_path_graph, dataset_to_default_path_wnids, hierarchy_to_path_graph
 
-__all__ = names = ("HardTreeSupLoss", "SoftTreeSupLoss", "SoftTreeLoss", "SoftSegTreeSupLoss", "CrossEntropyLoss")
+__all__ = names = ("HardTreeSupLoss", "SoftTreeSupLoss", "SoftTreeLoss", "SoftSegTreeSupLoss", "CrossEntropyLoss",
+                   "UpsampledCrossEntropyLoss")
 
 CrossEntropyLoss = nn.CrossEntropyLoss
 
@@ -441,6 +447,131 @@ class _FusedSoftSegTreeLossFn(torch.autograd.Function):
         return (gz * gloss).to(ctx.z_dtype), None, None, None, None, None, None
 
 
+def upsampled_xent_route(is_cuda, shape, dtype, target_shape, target_dtype, has_weight, smoothing):
+    """Which way UpsampledCrossEntropyLoss takes -- a pure host function of device kind, shapes, dtypes and settings:
+      "fused"     nbdt_upsampled_xent: GPU NCHW logits, class-index [N, H, W] targets, nothing the entry refuses
+      "plain"     targets already at the logits' size and no class weights: torch's cross-entropy, as it is
+      "composed"  everything else (CPU tensors, downsampling, weights with smoothing, ...): interpolate + cross-entropy
+    """
+    if len(shape) == 4 and len(target_shape) == 3 and tuple(shape[2:]) == tuple(target_shape[1:]) and not has_weight:
+        return "plain"
+    if not is_cuda:
+        return "composed"
+    refusal = _C.upsampled_xent_refusal(tuple(shape), dtype, tuple(target_shape), target_dtype, has_weight, smoothing)
+    return "fused" if refusal is None else "composed"
+
+
+class _UpsampledXentFn(torch.autograd.Function):
+    """loss, and dloss/dx [N, C, h, w] computed in the same call (saved for backward)."""
+
+    @staticmethod
+    def forward(ctx, x, y, weight, align_corners, ignore_index, smoothing):
+        loss, gx = _C.upsampled_xent(x, y, align_corners, ignore_index, weight, smoothing)
+        ctx.save_for_backward(gx)
+        ctx.x_dtype = x.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        (gx,) = ctx.saved_tensors
+        return (gx * gloss).to(ctx.x_dtype), None, None, None, None, None
+
+
+class UpsampledCrossEntropyLoss(nn.Module):
+    """The criterion of segmentation backbones that emit logits at a fraction of the label size (HRNet and its like):
+
+        F.cross_entropy(F.interpolate(score, size=target.shape[1:], mode="bilinear", align_corners=align_corners),
+                        target, weight, ignore_index=ignore_index, label_smoothing=label_smoothing)
+
+    On GPU NCHW logits with class-index ``[N, H, W]`` targets the loss and its gradient come from the low-resolution
+    tensor (``nbdt_upsampled_xent``): no ``[N, C, H, W]`` tensor is formed and two runs give the same bits, which
+    torch's bilinear backward (floating-point atomics) does not.  On any other input -- CPU tensors, downsampling, class
+    weights together with label smoothing -- it is exactly the composition above; with targets at the logits' size and
+    no weights it is torch's cross-entropy.  ``weight`` does not receive a gradient on the fused path.
+
+    ``SoftSegTreeSupLoss`` recognises this exact type and applies the same kernels to both of its terms."""
+
+    def __init__(self, weight=None, ignore_index=-100, label_smoothing=0.0, align_corners=False):
+        super().__init__()
+        self.register_buffer("weight", None if weight is None else torch.as_tensor(weight, dtype=torch.float32))
+        self.ignore_index = int(ignore_index)
+        self.label_smoothing = float(label_smoothing)
+        self.align_corners = bool(align_corners)
+
+    def route(self, score, target):
+        return upsampled_xent_route(score.is_cuda, tuple(score.shape), score.dtype, tuple(target.shape), target.dtype,
+                                    self.weight is not None, self.label_smoothing)
+
+    def composed(self, score, target):
+        if score.dim() == 4 and tuple(score.shape[2:]) != tuple(target.shape[-2:]):
+            score = F.interpolate(score, size=tuple(target.shape[-2:]), mode="bilinear", align_corners=self.align_corners)
+        weight = None if self.weight is None else self.weight.to(device=score.device, dtype=score.dtype)
+        return F.cross_entropy(score, target, weight, ignore_index=self.ignore_index,
+                               label_smoothing=self.label_smoothing)
+
+    def forward(self, score, target):
+        if self.route(score, target) == "fused":
+            return _UpsampledXentFn.apply(score, target, self.weight, self.align_corners, self.ignore_index,
+                                          self.label_smoothing)
+        return self.composed(score, target)
+
+    def extra_repr(self):
+        return (f"ignore_index={self.ignore_index}, label_smoothing={self.label_smoothing}, "
+                f"align_corners={self.align_corners}, weight={'yes' if self.weight is not None else None}")
+
+
+def seg_criterion_route(criterion, shape, dtype, target_shape, target_dtype):
+    """How SoftSegTreeSupLoss applies its criterion to GPU logits -- a pure host function of the criterion's type and
+    settings, shapes and dtypes:
+      ("pixel", ignore_index, smoothing)   nbdt_seg_soft_tree_loss, one fused call: an nn.CrossEntropyLoss it implements
+                                            (_seg_fusable), or an UpsampledCrossEntropyLoss without class weights whose
+                                            targets are already at the logits' size -- the same call, the same bits
+      ("upsampled",)                        an UpsampledCrossEntropyLoss (this exact type) that nbdt_upsampled_xent takes:
+                                            that kernel pair for both terms, the rules on the low-resolution grid
+      ("composed",)                         anything else, subclasses included: torch applies the criterion
+    """
+    index_targets = len(target_shape) == 3 and not target_dtype.is_floating_point
+    fusable = _seg_fusable(criterion)
+    if fusable is not None:
+        return ("pixel",) + fusable if index_targets else ("composed",)
+    if type(criterion) is not UpsampledCrossEntropyLoss:
+        return ("composed",)
+    how = upsampled_xent_route(True, tuple(shape), dtype, tuple(target_shape), target_dtype,
+                               criterion.weight is not None, criterion.label_smoothing)
+    if how == "plain" and index_targets and 0.0 <= criterion.label_smoothing < 1.0:
+        return ("pixel", criterion.ignore_index, criterion.label_smoothing)
+    return ("upsampled",) if how == "fused" else ("composed",)
+
+
+def _upsampled_seg_tree_loss(tree, criterion, z, y, w_tree, grad_scale=1.0):
+    """loss = CE(up(z), y) + w_tree * CE(up(rules(z)), y) and grad_scale * dloss/dz [N, C, h, w] fp32: the rules run on the
+    low-resolution grid (their usual routes), both cross-entropies at label resolution from low-resolution tensors."""
+    handle = tree.device_handle(z.device.index)
+    args = (criterion.align_corners, criterion.ignore_index, criterion.weight, criterion.label_smoothing)
+    loss_x, gz = _C.upsampled_xent(z, y, *args, grad_scale=grad_scale)
+    P = _C.seg_soft_forward(handle, z)
+    loss_t, gP = _C.upsampled_xent(P, y, *args, grad_scale=grad_scale * w_tree)
+    del P
+    gz += _C.seg_soft_backward(handle, z, gP)
+    return loss_x + loss_t * w_tree, gz
+
+
+class _FusedUpsampledSegTreeLossFn(torch.autograd.Function):
+    """loss, and dloss/dz [N, C, h, w] computed in the same call (saved for backward)."""
+
+    @staticmethod
+    def forward(ctx, z, y, tree, criterion, w_tree):
+        loss, gz = _upsampled_seg_tree_loss(tree, criterion, z, y, w_tree)
+        ctx.save_for_backward(gz)
+        ctx.z_dtype = z.dtype
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        (gz,) = ctx.saved_tensors
+        return (gz * gloss).to(ctx.z_dtype), None, None, None, None
+
+
 class SoftSegTreeSupLoss(SoftTreeSupLoss):
     """reference nbdt/loss.py:318-327, on ``[N, C, H, W]`` logits and ``[N, H, W]`` targets:
 
@@ -451,8 +582,11 @@ class SoftSegTreeSupLoss(SoftTreeSupLoss):
     here -- the cross-entropy term always weighs 1 and the tree term the constructor's ``tree_supervision_weight``.
 
     With an ``nn.CrossEntropyLoss`` without class weights (mean reduction, any ``ignore_index``, ``label_smoothing`` in
-    [0, 1)) the whole loss and its gradient are one call of ``nbdt_seg_soft_tree_loss``.  Any other criterion (OHEM and
-    the like) is applied by torch to the output of the autograd-enabled pixel rules."""
+    [0, 1)) the whole loss and its gradient are one call of ``nbdt_seg_soft_tree_loss``.  With an
+    ``UpsampledCrossEntropyLoss`` (this exact type) the logits may come at a fraction of the targets' size: both terms are
+    ``nbdt_upsampled_xent`` on low-resolution tensors, the rules run on the low-resolution grid (``seg_criterion_route``).
+    Any other criterion (OHEM and the like, subclasses of the two) is applied by torch to the output of the
+    autograd-enabled pixel rules."""
 
     def weights(self):
         return 1.0, float(self.tree_supervision_weight)
@@ -462,9 +596,12 @@ class SoftSegTreeSupLoss(SoftTreeSupLoss):
         assert len(outputs.shape) == 4, "Input must be of shape (N,C,H,W) for segmentation"
         _C.require_gpu(outputs, "SoftSegTreeSupLoss")
         w_xent, w_tree = self.weights()
-        fusable = _seg_fusable(self.criterion)
-        if fusable is not None and targets.dim() == 3 and not targets.is_floating_point():
-            return _FusedSoftSegTreeLossFn.apply(outputs, targets, self.tree, w_xent, w_tree, *fusable)
+        route = seg_criterion_route(self.criterion, tuple(outputs.shape), outputs.dtype, tuple(targets.shape),
+                                    targets.dtype)
+        if route[0] == "pixel":
+            return _FusedSoftSegTreeLossFn.apply(outputs, targets, self.tree, w_xent, w_tree, *route[1:])
+        if route[0] == "upsampled":
+            return _FusedUpsampledSegTreeLossFn.apply(outputs, targets, self.tree, self.criterion, w_tree)
         loss = self.criterion(outputs, targets)
         return loss + self.criterion(self.rules.forward_pixels(outputs), targets) * w_tree
 
@@ -473,9 +610,18 @@ class SoftSegTreeSupLoss(SoftTreeSupLoss):
         implement)."""
         self.assert_output_not_nbdt(outputs)
         fusable = _seg_fusable(self.criterion)
+        w_xent, w_tree = self.weights()
+        if fusable is None and type(self.criterion) is UpsampledCrossEntropyLoss:
+            _C.require_gpu(outputs, "SoftSegTreeSupLoss.loss_and_grad")
+            route = seg_criterion_route(self.criterion, tuple(outputs.shape), outputs.dtype, tuple(targets.shape),
+                                        targets.dtype)
+            if route[0] == "upsampled":
+                return _upsampled_seg_tree_loss(self.tree, self.criterion, outputs, targets, w_tree, grad_scale)
+            if route[0] == "pixel":
+                fusable = route[1:]
         if fusable is None:
             raise _C.NBDTHipError("SoftSegTreeSupLoss.loss_and_grad: the fused loss takes an nn.CrossEntropyLoss without "
-                                  "class weights and with mean reduction; call the module itself for any other criterion")
-        w_xent, w_tree = self.weights()
+                                  "class weights and with mean reduction, or an UpsampledCrossEntropyLoss on inputs its "
+                                  "kernels take; call the module itself for any other criterion")
         handle = self.tree.device_handle(outputs.device.index)
         return _C.seg_soft_tree_loss(handle, outputs, targets, fusable[0], w_xent, w_tree, grad_scale, fusable[1])
